@@ -13,7 +13,9 @@ Started without torchrun and with --gpus N > 1, it launches the N ranks itself (
 ``torch.distributed.run`` process, before anything touches the GPU) and relays rank 0's line.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): whole-job volumes/s over the
-timed K steps, plus
+timed K steps and ``ms_per_step``. A plain run does only that: set-up, W warm-up steps, the K timed
+steps (every launch on its usual streams, nothing instrumented) and the line. ``--dump-outputs DIR``
+also writes what the last timed step handed its caller (``dump_outputs``). ``--full`` adds
 
 * ``roofline``: the dominant MFMA kernel family (per-launch HIP-event timing inside the timed
   region, on every ``--event-every``-th step: an event pair idles the stream ~6 us, so timing
@@ -27,7 +29,9 @@ timed K steps, plus
 * ``secondary``: north_star's other workloads on the same module -- batch-1 128^3 and 256 x 256 x 128
   volumes (3 warm-up + 5 timed steps each, with their own ``roofline.frac``);
 * ``median_ms_per_step``: median of per-step HIP-event times; ``value`` keeps
-  the contract's definition (all K steps between two barriers).
+  the contract's definition (all K steps between two barriers);
+* ``streams`` (the same step with every launch on one stream) and, for N > 1,
+  ``gradient_exchange`` (the exchange profiled on 3 steps after the timed region).
 """
 import argparse
 import gc
@@ -66,8 +70,15 @@ def parse_args():
                     help="volumes per GPU per step (default: batch_size of the YAML = 2; "
                          "SURVEY.md 8(d): B per GPU in {1, 2})")
     ap.add_argument("--config", type=str, default=CONFIG)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss, parameters and "
+                         "gradients to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: roofline, one-stream "
+                         "step, fp32-MFMA step, the other workloads and BASELINE configs, CPU "
+                         "baseline, gradient-exchange profile (the --no-* switches below trim it)")
     ap.add_argument("--event-every", type=int, default=20,
-                    help="event-time the dominant kernel family on every M-th timed step "
+                    help="--full: event-time the dominant kernel family on every M-th timed step "
                          "(1: every step; each event pair idles the stream ~6 us)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32-MFMA secondary figure")
@@ -183,6 +194,35 @@ def synthetic_batch(batch, size, device, seed):
     x = torch.rand((batch, 2, *_shape(size)), generator=g)
     y = (torch.rand((batch, 1, *_shape(size)), generator=g) > 0.9).float()
     return {"image": x.to(device), "mask": y.to(device)}
+
+
+# --dump-outputs: at most this many values per array (16 MiB of float32; the headline U-Net has
+# 8.3 M parameters, so parameters + gradients in full would pass the 64 MB the dump may take)
+DUMP_MAX_VALUES = 4 << 20
+
+
+def dump_outputs(out_dir, net, loss):
+    """What the last timed step handed its caller, as float32 arrays in ``out_dir``: ``loss.npy``
+    (the step's loss), ``parameters.npy`` (the parameters after its optimiser step) and
+    ``gradients.npy`` (its gradients; zeros where a parameter has none), both flattened in
+    ``named_parameters()`` order. Longer than DUMP_MAX_VALUES, both keep the same fixed sample of
+    positions (seed 0, ascending), so that two builds compare entry for entry."""
+    import numpy as np
+    import torch
+
+    params = [p for _, p in net.named_parameters()]
+    flat = {"parameters": torch.cat([p.detach().reshape(-1) for p in params]),
+            "gradients": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p))
+                                    .detach().reshape(-1) for p in params])}
+    n = flat["parameters"].numel()
+    if n > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_VALUES, replace=False))
+        idx = torch.from_numpy(idx).to(flat["parameters"].device)
+        flat = {k: v[idx] for k, v in flat.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    for k, v in flat.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.float().cpu().numpy())
 
 
 def pmc_traffic(kernel, workload):
@@ -552,19 +592,20 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # warm-up (untimed): every instrumented kernel family is event-timed to find the dominant
-    # MFMA one; the timed region then carries events for that family and the HBM-bound
+    # warm-up (untimed). --full: every instrumented kernel family is event-timed to find the
+    # dominant MFMA one; the timed region then carries events for that family and the HBM-bound
     # norm/activation family only (fewer markers in the stream)
     # (instrumented steps keep every launch on one stream, see timed_steps; a few plain steps
     # after them warm the weight-gradient stream and its memory pool)
-    ops.KERNEL_TIMER = ops.KernelTimer()
+    ops.KERNEL_TIMER = ops.KernelTimer() if args.full else None
     overlap = HF.FLAGS["wgrad_stream"]
-    HF.FLAGS["wgrad_stream"] = False
+    HF.FLAGS["wgrad_stream"] = overlap and not args.full
     for _ in range(args.warmup):
         runner.train_step(batch)
     barrier()
     warm, ops.KERNEL_TIMER = ops.KERNEL_TIMER, None
     HF.FLAGS["wgrad_stream"] = overlap
+    # (a plain run takes these steps as well: the timed steps start from the same state either way)
     warm_extra = min(3, args.warmup) if overlap else 0
     for _ in range(warm_extra):
         runner.train_step(batch)
@@ -572,20 +613,23 @@ def main():
     # no device allocation inside a timed region: the pools get their head-room now (round 3's
     # driver record had a 64 ms and a 112 ms step where the pools grew by 4.3 / 7 GB)
     reserved_extra = runner.reserve_memory() if args.warmup > 0 else (0, 0)
-    dom_warm = warm.dominant() if args.warmup > 0 else None
-    warm_summary = warm.summary() if args.warmup > 0 else {}
-    ops.KERNEL_TIMER = ops.KernelTimer(only=None if dom_warm is None else {dom_warm[0]})
+    dom_warm = warm.dominant() if args.full and args.warmup > 0 else None
+    warm_summary = warm.summary() if args.full and args.warmup > 0 else {}
+    if args.full:
+        ops.KERNEL_TIMER = ops.KernelTimer(only=None if dom_warm is None else {dom_warm[0]})
     every = max(1, args.event_every)
     sampled = len(range(0, args.steps, every))
     barrier()
-    dt, loss, per_step = timed_steps(runner, batch, args.steps, barrier, timer=ops.KERNEL_TIMER,
-                                     event_every=every)
+    dt, loss, per_step = timed_steps(runner, batch, args.steps, barrier, per_step_events=args.full,
+                                     timer=ops.KERNEL_TIMER, event_every=every)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, loss)
     main_record = step_record(per_step, list(LAST_DIAG))
     timer, ops.KERNEL_TIMER = ops.KERNEL_TIMER, None
     # the HBM-bound norm / dropout / activation family: its own instrumented steps right after the
     # timed region (clocks still in their loaded state), so that its ~140 event pairs per step do
     # not sit inside the region `value` is measured over
-    hbm_steps = 2 if args.warmup > 0 else 0
+    hbm_steps = 2 if args.full and args.warmup > 0 else 0
     ops.KERNEL_TIMER = ops.KernelTimer(only={ops.NORM_ACT_FAMILY})
     overlap = HF.FLAGS["wgrad_stream"]
     HF.FLAGS["wgrad_stream"] = False          # (instrumented steps: one stream, see timed_steps)
@@ -595,7 +639,7 @@ def main():
     hbm_timer, ops.KERNEL_TIMER = ops.KERNEL_TIMER, None
     # the same step with every launch on one stream, for the record (a few steps)
     serial_ms = None
-    if overlap and args.warmup > 0:
+    if args.full and overlap and args.warmup > 0:
         nser = max(3, min(args.steps, 8))
         dts, _, _ = timed_steps(runner, batch, nser, barrier, per_step_events=False)
         serial_ms = 1e3 * reduce_max(dts, device) / nser
@@ -604,7 +648,7 @@ def main():
     # region (GradSync.exchange_stats: exposed wait of the main stream, bucket sizes, how long before
     # the end of backward each bucket went out) -- the line that explains a scaling curve
     exchange = None
-    if world > 1 and args.warmup > 0:
+    if args.full and world > 1 and args.warmup > 0:
         sync.profile = True
         timed_steps(runner, batch, 3, barrier, per_step_events=False)
         sync.profile = False
@@ -615,7 +659,7 @@ def main():
 
     f16 = HF.CONV_PRECISION != "fp32"
     fp32_line = None
-    if not args.no_fp32 and f16:
+    if args.full and not args.no_fp32 and f16:
         # secondary figure: the same step on the bit-exact fp32-MFMA conv kernels
         HF.set_conv_precision("fp32")
         for _ in range(2):
@@ -633,7 +677,8 @@ def main():
     # exchange inside a step is collective): 256 x 256 x 128 volumes and batch-1 128^3, 3 warm-up +
     # 5 timed steps each, then two instrumented steps for the dominant kernel family's roofline
     secondary = {}
-    if not args.no_secondary and args.shape is None and args.size == 128 and args.batch is None:
+    if (args.full and not args.no_secondary and args.shape is None and args.size == 128
+            and args.batch is None):
         # (the smaller workload first: it reuses the main run's memory pool; 3 warm-up steps, a new
         # shape's first steps grow the pool and repack nothing else)
         for key, sshape, sbatch in (("128^3_batch1", (128, 128, 128), 1),
@@ -664,7 +709,7 @@ def main():
             del sb
         torch.cuda.empty_cache()
     other = {}
-    if (not args.no_secondary and not args.no_other_configs and args.shape is None
+    if (args.full and not args.no_secondary and not args.no_other_configs and args.shape is None
             and args.size == 128 and args.batch is None and os.path.abspath(args.config) == CONFIG):
         # release the headline model's pools first: cfg 5 alone reserves ~45 GB
         del batch
@@ -702,12 +747,14 @@ def main():
         out["median_ms_per_step"] = med
         out["value_median"] = per_gpu_batch * world / (med * 1e-3)
         out["step_record"] = main_record
-    out["streams"] = {"weight_gradient_stream": bool(overlap),
-                      "ms_per_step_one_stream": serial_ms,
-                      "untimed_steps_after_warmup": warm_extra,
-                      "pool_headroom_bytes": list(reserved_extra),
-                      "note": "the weight-gradient kernels run on a second HIP stream beside the "
-                              "backward-data chain; the event-timed steps (roofline) keep one stream"}
+    if args.full:
+        out["streams"] = {"weight_gradient_stream": bool(overlap),
+                          "ms_per_step_one_stream": serial_ms,
+                          "untimed_steps_after_warmup": warm_extra,
+                          "pool_headroom_bytes": list(reserved_extra),
+                          "note": "the weight-gradient kernels run on a second HIP stream beside the "
+                                  "backward-data chain; the event-timed steps (roofline) keep one "
+                                  "stream"}
     if exchange is not None:
         exchange["gradient_mb"] = round(sum(exchange["bucket_mb"]), 3)
         exchange["exposed_share_of_step"] = (
@@ -720,7 +767,7 @@ def main():
         out["fp32_mfma"] = fp32_line
     if secondary:
         out["secondary"] = secondary
-    dom = timer.dominant()
+    dom = timer.dominant() if timer is not None else None
     if dom is not None:
         name, flops, ms, launches = dom
         kf16 = "f16" in name
@@ -759,7 +806,7 @@ def main():
                                        f"region"}
         roof["all_kernels_warmup"] = warm_summary
         out["roofline"] = roof
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from adell_mri_amd.modules.config_parsing import parse_config_unet
 
         cfg, _ = parse_config_unet(args.config, len(KEYS), 2)

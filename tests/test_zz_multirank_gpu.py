@@ -23,7 +23,7 @@ def test_two_rank_bench_prints_one_contract_line(cuda):
     cmd = ["timeout", "-k", "10", "240", sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "1", "--size", "32"]
+           "--batch", "1", "--size", "32", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -30,9 +30,9 @@ python3 tools/trace_stats.py $O/stats > $O/kernel_stats.txt 2>&1 || true
 python3 tools/trace_stats.py $O/stats2 > $O/kernel_stats_two_streams.txt 2>&1 || true
 python3 tools/pmc_traffic.py $O/pmcF $O/pmcW $O/pmc_traffic.json $O/bench_line.json > /dev/null 2>&1 || true
 python3 tools/pmc_mfma.py $O/pmcM > $O/pmc_mfma_utilisation.txt 2>&1 || true
-python3 bench.py > $O/bench_plain.json 2> $O/bench_plain.err
-# the driver's exact command as well (20 timed steps)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+python3 bench.py --full > $O/bench_plain.json 2> $O/bench_plain.err
+# the driver's step counts as well (20 timed steps), with the figures DESIGN.md section 4 quotes
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 # BASELINE configs 3 / 4 / 5: kernel summaries of their own step (one stream), program directly after `--`
 cd /tmp
 export ADELL_WGRAD_STREAM=0
