@@ -209,6 +209,11 @@ SIGNATURES = {
     "adell_conv_cin_small_fwd": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 5 + [_i, _vp]),
     "adell_conv_cin_small_bwd_data": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 4),
     "adell_multi_copy": (_i, [_vp, _i, _vp, _vp]),
+    "adell_grad_norm_workspace": (_l, [_i]),
+    "adell_grad_norm_partials": (_i, [_vp, _l, _i, _vp, _i, _vp]),
+    "adell_grad_norm_finalize": (_i, [_vp, _i, _i, _f, _f, _vp, _vp]),
+    "adell_grad_scale_by": (_i, [_vp, _l, _vp, _vp]),
+    "adell_multi_accumulate": (_i, [_vp, _i, _vp, _vp]),
     "adell_item_stats_workspace": (_l, [_i, _l]),
     "adell_item_stats": (_i, [_vp, _i, _l, _vp, _vp, ctypes.c_size_t, _vp]),
     "adell_aug_intensity": (_i, [_vp, _vp, _i, _l, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp]),

@@ -1594,6 +1594,52 @@ def multi_copy(table, rows, dst):
     check(_lib.lib().adell_multi_copy(_ptr(table), int(rows), _ptr(dst), _stream()))
 
 
+def multi_accumulate(table, rows, dst):
+    """``multi_copy`` with ``dst += src`` (the accumulate_grad_batches fold)."""
+    _require_cuda(dst)
+    if not table.is_cuda or table.dtype != torch.int64:
+        raise _lib.AdellHipError("multi_accumulate: the table must be an int64 CUDA tensor")
+    check(_lib.lib().adell_multi_accumulate(_ptr(table), int(rows), _ptr(dst), _stream()))
+
+
+# ---- gradient-norm clipping (csrc/grad_clip.hip) ------------------------------------------------
+def grad_norm_workspace_bytes(runs):
+    return int(_lib.lib().adell_grad_norm_workspace(int(runs)))
+
+
+def grad_norm_workspace(runs, device):
+    """The fp64 partials of ``runs`` runs: allocate once, outside any graph capture."""
+    return torch.empty(grad_norm_workspace_bytes(runs) // 8, dtype=torch.float64, device=device)
+
+
+def grad_norm_partials(g, norm_inf, workspace, run):
+    """Partial norm of the 1-D fp32 slice ``g`` (16-byte aligned) into slot ``run`` of ``workspace``."""
+    _require_cuda(g)
+    if workspace.dtype != torch.float64 or (run + 1) * grad_norm_workspace_bytes(1) > 8 * workspace.numel():
+        raise _lib.AdellHipError("grad_norm_partials: the workspace has no slot for this run")
+    check(_lib.lib().adell_grad_norm_partials(_ptr(g), g.numel(), int(bool(norm_inf)), _ptr(workspace),
+                                              int(run), _stream()))
+
+
+def grad_norm_finalize(workspace, runs, norm_inf, scale, max_norm, out):
+    """out[0] = ||scale * g|| over the ``runs`` partials, out[1] = min(max_norm / (out[0] + 1e-6), 1)."""
+    _require_cuda(out)
+    if workspace.dtype != torch.float64 or grad_norm_workspace_bytes(runs) > 8 * workspace.numel():
+        raise _lib.AdellHipError("grad_norm_finalize: the workspace holds fewer runs")
+    if out.numel() < 2:
+        raise _lib.AdellHipError("grad_norm_finalize: out needs two elements (norm, coefficient)")
+    check(_lib.lib().adell_grad_norm_finalize(_ptr(workspace), int(runs), int(bool(norm_inf)),
+                                              float(scale), float(max_norm), _ptr(out), _stream()))
+
+
+def grad_scale_by(g, coef):
+    """g *= coef[0] in place (``coef``: a device scalar; nothing happens when it is 1)."""
+    _require_cuda(g, coef)
+    if coef.numel() < 1:
+        raise _lib.AdellHipError("grad_scale_by: empty coefficient")
+    check(_lib.lib().adell_grad_scale_by(_ptr(g), g.numel(), _ptr(coef), _stream()))
+
+
 # ---- shifted-window (SWIN) token path -----------------------------------------------------
 def gather_nd(x, dims, axes, out=None):
     """Flat contiguous gather of ``x`` (csrc/window.hip). ``dims``: [(size, axis, mult)] of the

@@ -54,6 +54,11 @@ class FlatParameters:
                        for p, o in zip(self.params, self.offsets)]
         self._slot_ptr = [self.grad.data_ptr() + 4 * o for o in self.offsets]
         self._has = None
+        # accumulation mode (fold(), trainer.StepRunner(accumulate_grad_batches > 1)): collect()
+        # adds into the slots instead of copying, until zero_grad(); ``_handback`` marks the
+        # parameters whose gradient so far lives only in their slot (p.grad detached by fold())
+        self._accum = False
+        self._handback = None
         with torch.no_grad():
             for i, (p, o) in enumerate(zip(self.params, self.offsets)):
                 view = self.data[o:o + p.numel()].view(p.shape)
@@ -77,6 +82,7 @@ class FlatParameters:
         from . import functional as HF
         self.grad.zero_()
         self._has = None
+        self._accum, self._handback = False, None
         if set_to_none:
             for p in self.params:
                 p.grad = None
@@ -104,7 +110,7 @@ class FlatParameters:
             host[:n] = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
             dev[:n].copy_(host[:n], non_blocking=True)
             self._graph_tables = getattr(self, "_graph_tables", []) + [(host, dev)]
-            ops.multi_copy(dev, n, self.grad)
+            (ops.multi_accumulate if self._accum else ops.multi_copy)(dev, n, self.grad)
             return
         ring = getattr(self, "_ring", None)
         if ring is None or ring[0][0].shape[0] < n:
@@ -119,7 +125,7 @@ class FlatParameters:
         host[:n] = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
         dev[:n].copy_(host[:n], non_blocking=True)
         ev.record()
-        ops.multi_copy(dev, n, self.grad)
+        (ops.multi_accumulate if self._accum else ops.multi_copy)(dev, n, self.grad)
 
     def collect(self, indices=None, on_side_stream=False):
         """Copy every parameter gradient (of ``indices``, default all) that is not already a
@@ -127,7 +133,9 @@ class FlatParameters:
         the slots. Returns nothing; parameters without a gradient keep ``grad is None`` and a
         zero slot. ``on_side_stream``: the caller runs this on the weight-gradient stream itself
         (GradSync's buckets: in order behind the gradients, without stalling the main stream);
-        otherwise the current stream first waits for that stream."""
+        otherwise the current stream first waits for that stream. In accumulation mode (``fold``)
+        the gradients are ADDED to the slots, and a parameter whose gradient came only from earlier
+        micro-batches gets ``p.grad`` pointed at its slot as well."""
         from . import functional as HF
         if not on_side_stream:
             HF.join_side_stream()     # weight gradients still running on the side stream
@@ -166,11 +174,36 @@ class FlatParameters:
             rows = np.stack([ptr[ix] + 4 * start, off[ix] + start,
                              np.minimum(self.CHUNK, num[ix] - start)], 1)
             self._upload_and_copy(rows)
+        back = self._handback
         for i in idx:
             p = params[i]
             if p.grad is not None:
                 p.grad = slots[i]
+            elif back is not None and back[i]:
+                p.grad = slots[i]
+                if has is not None:
+                    has[i] = True
+            if back is not None:
+                back[i] = False
         self._has = has
+
+    def fold(self):
+        """End of a micro-batch under gradient accumulation (accumulation mode until
+        ``zero_grad``): add the fresh per-parameter gradients into their slots (one multi-accumulate
+        launch), then detach the parameters from the slots again -- the next micro-batch's weight
+        gradients are fresh tensors (the side stream of functional.side_run stays open to them) and
+        the next ``collect()`` adds them in turn. The "has a gradient" mask is the union over the
+        micro-batches."""
+        from . import functional as HF
+        self._accum = True
+        self.collect()
+        back = np.zeros(len(self.params), dtype=bool) if self._handback is None else self._handback
+        for i, p in enumerate(self.params):
+            if p.grad is not None:
+                back[i] = True
+                p.grad = None
+        self._handback = back
+        HF.reset_uses(self.params)
 
     def has_grad(self):
         """Which parameters hold a gradient. After a full ``collect()`` its mask is the starting
@@ -245,6 +278,61 @@ class _FusedBase(torch.optim.Optimizer):
         """Gather the parameters' gradients into the flat buffers (idempotent)."""
         for flat in self.flat_groups:
             flat.collect()
+
+    def fold_grads(self):
+        """Add this micro-batch's gradients into the flat buffers (FlatParameters.fold)."""
+        for flat in self.flat_groups:
+            flat.fold()
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, norm_type=2.0, error_if_nonfinite=False):
+        """``torch.nn.utils.clip_grad_norm_`` over the parameters ``step()`` would update (those
+        with a gradient; a stale slot stays out), as Lightning's ``Trainer(gradient_clip_val)``
+        calls it. The norm is that of the gradient the optimiser applies: the flat buffers scaled
+        by ``grad_scale``. 2 x (runs) + 1 launches, no host synchronisation -- the coefficient stays
+        on the device -- unless ``error_if_nonfinite`` (which reads the norm back to raise as torch
+        does). Returns the total norm as a 0-d fp32 device tensor."""
+        import math
+        nt = float(norm_type)
+        if nt != 2.0 and not (math.isinf(nt) and nt > 0):
+            raise ValueError(f"clip_grad_norm_: norm_type must be 2 or inf, got {norm_type}")
+        norm_inf = math.isinf(nt)
+        self.collect_grads()
+        slices, scales, dev = [], set(), None
+        for gi, g in enumerate(self.param_groups):
+            flat = self._flat(gi)
+            if not flat.params:           # frozen group
+                continue
+            dev = flat.grad.device
+            runs = flat.runs(flat.has_grad())
+            slices += [flat.grad[lo:hi] for _, lo, hi in runs]
+            if runs:
+                scales.add(float(g.get("grad_scale", 1.0)))
+        if not slices:
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        if len(scales) != 1:
+            raise ValueError("clip_grad_norm_: the parameter groups have different grad_scale")
+        ws = getattr(self, "_norm_ws", None)
+        need = ops.grad_norm_workspace_bytes(len(slices)) // 8
+        if ws is None or ws.numel() < need or ws.device != dev:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("clip_grad_norm_ inside a graph capture: run it eagerly first "
+                                   "(it sizes its workspace)")
+            ws = self._norm_ws = ops.grad_norm_workspace(len(slices), dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        for r, g in enumerate(slices):
+            ops.grad_norm_partials(g, norm_inf, ws, r)
+        ops.grad_norm_finalize(ws, len(slices), norm_inf, scales.pop(), max_norm, out)
+        total = out[0]
+        if error_if_nonfinite and not math.isfinite(float(total)):
+            raise RuntimeError(
+                f"The total norm of order {float(norm_type)} for gradients from `parameters` is "
+                "non-finite, so it cannot be clipped. To disable this error and scale the gradients "
+                "by the non-finite norm anyway, set `error_if_nonfinite=False`")
+        coef = out[1:]
+        for g in slices:
+            ops.grad_scale_by(g, coef)
+        return total
 
     def _buffer(self, gi, name):
         st = self._flat_state[gi]

@@ -1,7 +1,9 @@
 """Minimal optimisation loop for the HIP path when Lightning is not installed:
 the part of ``lightning.Trainer.fit`` the reference's training step relies on
 (adell_mri/entrypoints/segmentation/train.py:799-819): zero_grad ->
-training_step -> backward -> gradient exchange -> optimizer.step."""
+training_step -> backward -> gradient exchange -> optimizer.step, with the
+Trainer's ``gradient_clip_val`` and ``accumulate_grad_batches`` (train.py:807,811,
+ssl/train_3d.py:354-355)."""
 import itertools
 import os
 
@@ -21,14 +23,49 @@ def _offsets_drawn():
 
 
 class StepRunner:
-    def __init__(self, module, optimizer=None, sync=None):
+    """One training step per ``train_step(batch)``, with Lightning's meaning of
+
+    * ``gradient_clip_val`` (None / 0: off): ``clip_grad_norm_(gradient_clip_val, 2.0)`` of the fused
+      optimiser between the gradient exchange and ``optimizer.step()``; the norm is that of the
+      gradient the optimiser applies. ``gradient_clip_algorithm="value"`` is not supported (the
+      reference never sets it);
+    * ``accumulate_grad_batches`` N: ``train_step`` runs ONE micro-batch. Micro-batches 1..N-1 run
+      backward without exchanging anything (``GradSync.no_sync``) and fold their gradients into
+      the flat buffers; the N-th runs backward, the exchange, clipping and the step with 1/N folded
+      into the optimiser's ``grad_scale`` (Lightning divides the loss instead: same update).
+      ``flush()`` steps a partial window (end of an epoch) with the same 1/N.
+
+    ``step_idx`` counts micro-batches (the ``batch_idx`` of ``training_step``), ``optimizer_steps``
+    the optimiser steps, ``last_grad_norm`` is the device tensor of the last clip."""
+
+    def __init__(self, module, optimizer=None, sync=None, gradient_clip_val=None,
+                 gradient_clip_algorithm="norm", accumulate_grad_batches=1):
+        if gradient_clip_val is not None and float(gradient_clip_val) < 0:
+            raise ValueError(f"gradient_clip_val should be >= 0, got {gradient_clip_val}")
+        if gradient_clip_algorithm == "value":
+            raise NotImplementedError("StepRunner: gradient_clip_algorithm='value' is not supported "
+                                      "(the reference clips by norm)")
+        if gradient_clip_algorithm != "norm":
+            raise ValueError(f"gradient_clip_algorithm must be 'norm', got {gradient_clip_algorithm!r}")
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches should be an integer >= 1, got "
+                             f"{accumulate_grad_batches}")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
         self.module = module
         if optimizer is None:
             optimizer = module.configure_optimizers()["optimizer"]
         self.optimizer = optimizer
+        if (self.gradient_clip_val or self.accumulate_grad_batches > 1) and not (
+                hasattr(optimizer, "clip_grad_norm_") and hasattr(optimizer, "fold_grads")):
+            raise TypeError("StepRunner: gradient clipping / accumulation need a fused optimiser "
+                            "(adell_mri_amd.optim)")
         self.sync = sync if sync is not None else GradSync(optimizer)
         self.sync.broadcast_parameters(module=module)
         self.step_idx = 0
+        self.optimizer_steps = 0
+        self.last_grad_norm = None
+        self._micro = 0                  # micro-batches of the current accumulation window so far
         self._graph = None
 
     def reserve_memory(self, main_bytes=None, side_bytes=None):
@@ -93,6 +130,10 @@ class StepRunner:
         from . import functional as HF
         from . import ops
 
+        if self.accumulate_grad_batches > 1:
+            raise RuntimeError("StepRunner.enable_graph: one graph is one whole step; with "
+                               "accumulate_grad_batches > 1 a step is several micro-batches -- "
+                               "run them eagerly")
         if self.sync.overlap:
             raise RuntimeError("StepRunner.enable_graph: gradient buckets are sent from backward hooks "
                                "(GradSync(overlap=True)); build GradSync(optimizer, overlap=False)")
@@ -139,13 +180,58 @@ class StepRunner:
         self._graph = None
 
     def _eager_step(self, batch):
+        if self.accumulate_grad_batches > 1:
+            return self._micro_step(batch)
         self.optimizer.zero_grad(set_to_none=_SET_TO_NONE)
         loss = self.module.training_step(batch, self.step_idx)
         loss.backward()
-        self.sync.all_reduce()
-        self.optimizer.step()
+        self._exchange_and_step()
         self.step_idx += 1
         return loss
+
+    def _micro_step(self, batch):
+        if self._micro == 0:
+            self.optimizer.zero_grad(set_to_none=_SET_TO_NONE)
+        loss = self.module.training_step(batch, self.step_idx)
+        self._micro += 1
+        if self._micro < self.accumulate_grad_batches:
+            with self.sync.no_sync():
+                loss.backward()
+            self.optimizer.fold_grads()
+        else:
+            loss.backward()
+            self._exchange_and_step()
+        self.step_idx += 1
+        return loss
+
+    def _exchange_and_step(self):
+        """all-reduce -> clip -> step of the current window (1/N folded into grad_scale)."""
+        self.sync.all_reduce()
+        n = self.accumulate_grad_batches
+        if n == 1 and not self.gradient_clip_val:
+            self.optimizer.step()
+        else:
+            groups = self.optimizer.param_groups
+            kept = [g.get("grad_scale", 1.0) for g in groups]
+            try:
+                for g, s in zip(groups, kept):
+                    g["grad_scale"] = s / n
+                if self.gradient_clip_val:
+                    self.last_grad_norm = self.optimizer.clip_grad_norm_(self.gradient_clip_val, 2.0)
+                self.optimizer.step()
+            finally:
+                for g, s in zip(groups, kept):    # world-size state (optim.load_state_dict)
+                    g["grad_scale"] = s
+        self.optimizer_steps += 1
+        self._micro = 0
+
+    def flush(self):
+        """Step the micro-batches of an unfinished accumulation window (Lightning does at the end
+        of an epoch), with the same 1/accumulate_grad_batches. Returns whether it stepped."""
+        if self._micro == 0:
+            return False
+        self._exchange_and_step()
+        return True
 
     def train_step(self, batch):
         if getattr(self, "_graph", None) is None:
@@ -162,13 +248,15 @@ class StepRunner:
         if self._graph_draws:
             # the host counter stays where an eager loop would be (disable_graph continues there)
             HF._dropout_counter = itertools.count(_offsets_drawn() + self._graph_draws)
-        self.sync.all_reduce()
-        self.optimizer.step()
+        self._exchange_and_step()
         self.step_idx += 1
         return self._graph_loss
 
 
-def fit_steps(module, batches, optimizer=None):
-    runner = StepRunner(module, optimizer)
+def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulate_grad_batches=1):
+    runner = StepRunner(module, optimizer, gradient_clip_val=gradient_clip_val,
+                        accumulate_grad_batches=accumulate_grad_batches)
     module.train()
-    return [runner.train_step(b).detach() for b in batches]
+    losses = [runner.train_step(b).detach() for b in batches]
+    runner.flush()
+    return losses

@@ -754,6 +754,27 @@ int adell_conv_cin_small_bwd_data(const adell_conv3d_desc* d, const float* dy, c
  * gradients autograd produced into the flat gradient buffer of the fused optimisers. */
 int adell_multi_copy(const long* table, int rows, float* dst, void* stream);
 
+/* Gradient-norm clipping over the flat gradient buffers, torch.nn.utils.clip_grad_norm_ (norm 2 or
+ * inf) as Lightning's Trainer(gradient_clip_val) calls it (entrypoints/segmentation/train.py:807,
+ * ssl/train_3d.py:354; flag: assemble_args.py:386-392). No host synchronisation, no allocation:
+ *   adell_grad_norm_workspace(runs): bytes of the fp64 partials of `runs` runs (one per contiguous
+ *     run of parameters that have a gradient, over every parameter group);
+ *   adell_grad_norm_partials: run `run` (16-byte aligned, any length) -> its slots of `partials`;
+ *   adell_grad_norm_finalize: out[0] = ||scale g|| over every run, out[1] = the clip coefficient
+ *     min(max_norm / (out[0] + 1e-6), 1) (fp32; NaN stays NaN). `scale` is the factor between the
+ *     buffer and the gradient the optimiser applies (grad_scale / accumulate_grad_batches);
+ *   adell_grad_scale_by: g *= *coef_dev (returns at once, no traffic, when it is 1).
+ * Fixed grids and fixed-order fp64 sums: the same buffer gives the same bits. */
+long adell_grad_norm_workspace(int runs);
+int adell_grad_norm_partials(const float* g, long n, int norm_inf, double* partials, int run,
+                             void* stream);
+int adell_grad_norm_finalize(const double* partials, int runs, int norm_inf, float scale,
+                             float max_norm, float* out, void* stream);
+int adell_grad_scale_by(float* g, long n, const float* coef_dev, void* stream);
+/* adell_multi_copy with dst += src: folds a micro-batch's parameter gradients into the flat buffer
+ * under Trainer(accumulate_grad_batches) (train.py:811, ssl/train_3d.py:355). */
+int adell_multi_accumulate(const long* table, int rows, float* dst, void* stream);
+
 /* ---- shifted-window (SWIN) token path: vit.py:33-45,95-129,1005-1256; linear_blocks.py:358-417 */
 /* out (contiguous over sizes[0..nd)) = gather of `in`: out dim d adds coord*mult[d] to input
  * axis axis[d]; input axis a has extent / stride (elements) / cyclic shift:
