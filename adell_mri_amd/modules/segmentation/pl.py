@@ -8,7 +8,9 @@ otherwise the same methods live on a plain ``torch.nn.Module`` and
 arithmetic of ``step`` / ``training_step`` / ``calculate_loss`` /
 ``configure_optimizers`` (pl.py:218-222, 284-317, 382-421, 529-595) and the
 ``UNetPL`` constructor (pl.py:680-700). The optimiser is the fused flat-buffer
-HIP one (``adell_mri_amd.optim``) instead of ``torch.optim``.
+HIP one (``adell_mri_amd.optim``) instead of ``torch.optim``. The metric dicts
+(``get_metric_dict`` / ``update_metrics`` / ``setup_metrics``, pl.py:100-187,
+655-671) hold the on-device metrics of ``adell_mri_amd.metrics``.
 """
 from typing import Callable
 
@@ -16,6 +18,9 @@ import torch
 import torch.nn.functional as F
 
 from ... import functional as HF
+from ...metrics import (BinaryFBetaScore, BinaryJaccardIndex, BinaryPrecision, Dice,
+                        MulticlassDice, MulticlassFBetaScore, MulticlassJaccardIndex,
+                        MulticlassPrecision, update_many)
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from .unet import BrUNet, UNet
 from .unetpp import UNetPlusPlus
@@ -35,7 +40,55 @@ from ...utils.optimizer_factory import (OPTIMIZER_MATCH, get_optimizer,  # noqa:
                                         optimizer_eps_from_precision)
 
 
+def update_metrics(cls, metrics, pred, y, pred_class, y_class, **kwargs) -> None:
+    """Update every metric of ``metrics`` with the prediction ``pred`` and the ground truth ``y``
+    (pl.py:100-145): ONE fused update for the whole dict (two launches, no host synchronisation).
+    The target is rounded on the device. Bottleneck-classification metrics ("cl:" keys) are never
+    built here (see ``get_metric_dict``); Lightning's ``cls.log`` of each metric is not part of
+    the path (a no-op without Lightning)."""
+    seg = [m for k, m in metrics.items() if "cl:" not in k]
+    if seg:
+        update_many(seg, pred.detach(), y)
+
+
+def get_metric_dict(nc: int, bottleneck_classification: bool, metric_keys: list = None,
+                    prefix: str = "", dev: str = None):
+    """The metric dict of pl.py:148-187: binary metrics for ``nc`` <= 2 (one prediction channel),
+    macro-averaged multi-class ones for ``nc`` > 2.
+
+    ``AUC_bn`` is left out even with ``bottleneck_classification``: the reference builds it as
+    ``torchmetrics.AUROC`` without a ``task`` (pl.py:186), which its pinned torchmetrics cannot
+    construct; a requested ``AUC_bn`` key is skipped like any unknown key."""
+    if nc <= 2:
+        md = {
+            "IoU": lambda: BinaryJaccardIndex(),
+            "Pr": lambda: BinaryPrecision(),
+            "F1": lambda: BinaryFBetaScore(1.0),
+            "Dice": lambda: Dice(num_classes=1, multiclass=False),
+        }
+    else:
+        md = {
+            "IoU": lambda: MulticlassJaccardIndex(nc, average="macro"),
+            "Pr": lambda: MulticlassPrecision(nc, average="macro"),
+            "F1": lambda: MulticlassFBetaScore(nc, average="macro"),
+            "Dice": lambda: MulticlassDice(nc, average="macro"),
+        }
+    if metric_keys is None:
+        metric_keys = list(md.keys())
+    metric_dict = torch.nn.ModuleDict({})
+    for k in metric_keys:
+        if k in md:
+            metric_dict[prefix + k] = md[k]()
+    if dev is not None:
+        metric_dict = {k: metric_dict[k].to(dev) for k in metric_dict}
+    return metric_dict
+
+
 class UNetBasePL(_Base):
+    # training_step also updates train_metrics (pl.py:403) when True; off by default, so that a
+    # training step issues exactly the launches it issues without metrics
+    compute_train_metrics = False
+
     def __init__(self):
         super().__init__()
         self.train_batch_size = None
@@ -122,29 +175,51 @@ class UNetBasePL(_Base):
             output = output[0]
         return output[0] if single else output
 
-    def _evaluation_loss(self, batch):
+    def _evaluation_loss(self, batch, metrics=None, crop=False):
         """What validation_step / test_step return (pl.py:423-524): the step loss over micro-batches
-        of the training batch size, averaged. (Metric objects and PI-CAI lists are Lightning /
-        torchmetrics bookkeeping outside the path.)"""
+        of the training batch size, averaged. Each micro-batch's prediction also updates
+        ``metrics`` (pl.py:467, 513), against the ground truth cropped to it first when ``crop``
+        (test_step, pl.py:511). (PI-CAI lists are outside the path.)"""
         x, x_cond, x_fc, y, y_class = self.unpack_batch(batch)
         total = torch.zeros((), device=x.device, dtype=x.dtype)
         bs = x.shape[0]
         mbs = self.batch_size if self.train_batch_size is None else self.train_batch_size
         for m in range(0, bs, mbs):
             part = slice(m, m + mbs)
-            _, _, loss, class_loss = self.step(
+            pred_final, pred_class, loss, class_loss = self.step(
                 x[part], y[part], None if y_class is None else y_class[part],
                 None if x_cond is None else x_cond[part],
                 x_fc[part] if x_cond is not None else None)   # sic: keyed on x_cond, pl.py:440
             total = total + (loss.mean() if class_loss is None
                              else loss.mean() + class_loss) / (bs // mbs)
+            if metrics:
+                y_part = y[part]
+                if crop:
+                    y_part, _ = self.crop_if_necessary(y_part, pred_final)
+                update_metrics(self, metrics, pred_final, y_part, pred_class,
+                               None if y_class is None else y_class[part])
         return total
 
     def validation_step(self, batch, batch_idx):
-        return self._evaluation_loss(batch)
+        return self._evaluation_loss(batch, getattr(self, "val_metrics", None))
 
     def test_step(self, batch, batch_idx):
-        return self._evaluation_loss(batch)
+        return self._evaluation_loss(batch, getattr(self, "test_metrics", None), crop=True)
+
+    def setup_metrics(self):
+        """The three metric dicts of pl.py:655-671. They are submodules (ModuleDicts), so they move
+        with the module; their counts are plain tensor attributes, so they add no parameter,
+        buffer or state_dict entry."""
+        self.train_metrics = get_metric_dict(self.n_classes, self.bottleneck_classification,
+                                             ["IoU", "Dice"], prefix="")
+        self.val_metrics = get_metric_dict(self.n_classes, self.bottleneck_classification,
+                                           ["IoU", "Dice", "AUC_bn"], prefix="V_")
+        self.test_metrics = get_metric_dict(self.n_classes, self.bottleneck_classification, None,
+                                            prefix="T_")
+
+    def _update_train_metrics(self, pred_final, y, pred_class, y_class):
+        if self.compute_train_metrics and getattr(self, "train_metrics", None):
+            update_metrics(self, self.train_metrics, pred_final, y, pred_class, y_class)
 
     def log_loss(self, key, loss, **kwargs):
         for i in range(loss.nelement()):
@@ -156,6 +231,7 @@ class UNetBasePL(_Base):
         pred_final, pred_class, loss, class_loss = self.step(x, y, y_class, x_cond, x_fc)
         if _Base is not torch.nn.Module:
             self.log_loss("train_loss", loss, batch_size=y.shape[0])
+        self._update_train_metrics(pred_final, y, pred_class, y_class)
         self.train_batch_size = x.shape[0]
         return loss.mean() if class_loss is None else loss.mean() + class_loss
 
@@ -219,6 +295,7 @@ class UNetPL(UNet, UNetBasePL):
         self.loss_fn = loss_fn
         self.picai_eval = picai_eval
         self.loss_fn_class = torch.nn.BCEWithLogitsLoss()
+        self.setup_metrics()
 
 
 class BrUNetPL(BrUNet, UNetBasePL):
@@ -256,6 +333,7 @@ class BrUNetPL(BrUNet, UNetBasePL):
         self.all_pred = []
         self.all_true = []
         self.bn_mult = 0.1
+        self.setup_metrics()
 
     def step(self, x, x_weights, y, y_class, x_cond, x_fc):
         y = torch.round(y)
@@ -294,6 +372,7 @@ class BrUNetPL(BrUNet, UNetBasePL):
         pred_final, pred_class, loss, class_loss = self.step(x, x_weights, y, y_class, x_cond, x_fc)
         if _Base is not torch.nn.Module:
             self.log_loss("train_loss", loss, batch_size=y.shape[0])
+        self._update_train_metrics(pred_final, y, pred_class, y_class)
         self.train_batch_size = y.shape[0]
         return loss.mean() if class_loss is None else loss.mean() + class_loss
 
@@ -328,6 +407,7 @@ class UNETRPL(UNETR, UNetBasePL):
         hp = {k: v for k, v in locals().items() if k not in ("self", "args", "kwargs", "__class__")}
         super().__init__(*args, **kwargs)
         _training_attributes(self, hp)
+        self.setup_metrics()
 
 
 class SWINUNetPL(SWINUNet, UNetBasePL):
@@ -345,6 +425,7 @@ class SWINUNetPL(SWINUNet, UNetBasePL):
         hp = {k: v for k, v in locals().items() if k not in ("self", "args", "kwargs", "__class__")}
         super().__init__(*args, **kwargs)
         _training_attributes(self, hp)
+        self.setup_metrics()
 
 
 class UNetPlusPlusPL(UNetPlusPlus, UNetBasePL):
@@ -365,4 +446,5 @@ class UNetPlusPlusPL(UNetPlusPlus, UNetBasePL):
         hp = {k: v for k, v in locals().items() if k not in ("self", "args", "kwargs", "__class__")}
         super().__init__(*args, **kwargs)
         _training_attributes(self, hp)
+        self.setup_metrics()
         self.deep_supervision = True

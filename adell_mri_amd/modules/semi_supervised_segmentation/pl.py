@@ -3,13 +3,14 @@ the supervised U-Net step plus a local contrastive term between the decoder feat
 un-annotated views -- the student's features of view 1 against the EMA teacher's (or the
 stop-gradient student's) linearly transformed features of view 2, weighted by ``ssl_weight`` = 0.01.
 Method names, batch layout ({"supervised": ..., "self_supervised": ...}) and arithmetic follow the
-reference; Lightning logging and the torchmetrics bookkeeping are not part of the path."""
+reference; Lightning logging is not part of the path. The metric dicts are those of
+``UNetBasePL.setup_metrics`` (reference pl.py:127)."""
 from typing import Callable
 
 import numpy as np
 import torch
 
-from ..segmentation.pl import UNetBasePL, _Base
+from ..segmentation.pl import UNetBasePL, _Base, update_metrics
 from .losses import LocalContrastiveLoss
 from .unet import UNetSemiSL
 
@@ -62,6 +63,7 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
         self.ssl_weight = 0.01
         self.semi_supervised = (self.semi_sl_image_key_1 is not None
                                 and self.semi_sl_image_key_2 is not None)
+        self.setup_metrics()
 
     # ---- batches (pl.py:148-198) ---------------------------------------------------------------
     def unpack_batch(self, batch):
@@ -132,6 +134,7 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
             output_loss = loss.mean() if class_loss is None else loss.mean() + class_loss
             if _Base is not torch.nn.Module:
                 self.log_loss("train_loss", loss, batch_size=y.shape[0])
+            self._update_train_metrics(pred_final, y, pred_class, y_class)
             self.train_batch_size = x.shape[0]
         if self.semi_sl_image_key_1 is not None and self.semi_sl_image_key_2 is not None:
             x_1, x_2, x_cond, x_fc = self.unpack_batch_semi_sl(batch)
@@ -153,12 +156,14 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
             mbs = self.batch_size if self.train_batch_size is None else self.train_batch_size
             for i in range(0, bs, mbs):
                 m, M = i, i + mbs
-                _, _, loss, class_loss = self.step(
+                pred_final, pred_class, loss, class_loss = self.step(
                     x[m:M], y[m:M], y_class[m:M] if y_class is not None else None,
                     x_cond[m:M] if x_cond is not None else None,
                     x_fc[m:M] if x_cond is not None else None)   # sic: x_cond, as pl.py:485
                 output_loss = output_loss + (
                     loss.mean() if class_loss is None else loss.mean() + class_loss) / (bs // mbs)
+                update_metrics(self, self.val_metrics, pred_final, y[m:M], pred_class,
+                               y_class[m:M] if y_class is not None else None)   # pl.py:506
         if self.semi_sl_image_key_1 is not None and self.semi_sl_image_key_2 is not None:
             x_1, x_2, x_cond, x_fc = self.unpack_batch_semi_sl(batch)
             output_loss = output_loss + self.step_semi_sl(None, x_1, x_2, x_cond, x_fc)

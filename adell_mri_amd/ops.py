@@ -1640,6 +1640,75 @@ def grad_scale_by(g, coef):
     check(_lib.lib().adell_grad_scale_by(_ptr(g), g.numel(), _ptr(coef), _stream()))
 
 
+# ---- segmentation metrics (csrc/seg_metrics.hip) ------------------------------------------------
+SEG_METRIC_KINDS = {"iou": 0, "precision": 1, "fbeta": 2, "dice": 3}
+SEG_MAX_CLASSES = 32
+_SEG_TARGET_TYPES = {torch.float32: 0, torch.uint8: 1, torch.bool: 1, torch.int64: 2}
+
+
+def seg_confusion_update(pred, target, states):
+    """Add the confusion counts of one update into every state of ``states`` (at most 8 int64 CUDA
+    tensors of 3 C + 1 elements). ``pred``: fp32 [B, C, *spatial] (C = 1: binary), NCDHW or
+    channels-last memory; ``target``: [B, *spatial] or [B, 1, *spatial] of fp32, uint8, bool or int64
+    (other dtypes are converted). Two launches, no host synchronisation."""
+    if pred.dim() < 3:
+        raise AdellHipError(f"seg_confusion_update: pred must be [B, C, *spatial], got {tuple(pred.shape)}")
+    B, C = int(pred.shape[0]), int(pred.shape[1])
+    spatial = tuple(pred.shape[2:])
+    if C > SEG_MAX_CLASSES:
+        raise AdellHipError(f"seg_confusion_update: {C} classes; at most {SEG_MAX_CLASSES} are supported")
+    if tuple(target.shape) not in ((B,) + spatial, (B, 1) + spatial):
+        raise AdellHipError(f"seg_confusion_update: target of shape {tuple(target.shape)} does not match "
+                            f"pred {tuple(pred.shape)} (expected {(B,) + spatial} or {(B, 1) + spatial})")
+    if not 1 <= len(states) <= 8:
+        raise AdellHipError(f"seg_confusion_update: {len(states)} states (1..8 per update)")
+    for s in states:
+        if s.dtype != torch.int64 or s.numel() != 3 * C + 1 or not s.is_contiguous():
+            raise AdellHipError(f"seg_confusion_update: a state must be a contiguous int64 tensor of "
+                                f"{3 * C + 1} elements for {C} classes")
+        if s.device != pred.device:
+            raise AdellHipError(f"seg_confusion_update: state on {s.device}, pred on {pred.device}")
+    _require_cuda(pred)
+    if not target.is_cuda or target.device != pred.device:
+        raise AdellHipError("seg_confusion_update: the target must be on the device of pred")
+    S = 1
+    for d in spatial:
+        S *= int(d)
+    channels_last = 0
+    if C > 1 and not pred.is_contiguous():
+        cl = {5: torch.channels_last_3d, 4: torch.channels_last}.get(pred.dim())
+        channels_last = int(cl is not None and pred.is_contiguous(memory_format=cl))
+    if not (pred.is_contiguous() or channels_last):
+        pred = pred.contiguous()
+    if target.dtype not in _SEG_TARGET_TYPES:
+        target = target.to(torch.float32 if target.is_floating_point() else torch.int64)
+    if not target.is_contiguous():
+        target = target.contiguous()      # a cropped ground truth (crop_if_necessary)
+    n = B * S
+    ws_bytes = int(_lib.lib().adell_seg_confusion_workspace(n, C))
+    ws = _workspace(ws_bytes, pred.device)
+    ptrs = (ctypes.c_void_p * len(states))(*[s.data_ptr() for s in states])
+    check(_lib.lib().adell_seg_confusion_update(
+        _ptr(pred), _ptr(target), _SEG_TARGET_TYPES[target.dtype], B, C, S, channels_last, _ptr(ws),
+        ws_bytes, ptrs, len(states), _stream()))
+
+
+def seg_metric_compute(state, kind, beta=1.0, num_classes=None):
+    """The metric ``kind`` ('iou', 'precision', 'fbeta', 'dice') of an int64 state as a 0-dim fp32
+    device tensor (fp64 arithmetic on the counts; macro mean over the classes that occur)."""
+    if kind not in SEG_METRIC_KINDS:
+        raise AdellHipError(f"seg_metric_compute: unknown metric {kind!r} (one of {sorted(SEG_METRIC_KINDS)})")
+    C = (state.numel() - 1) // 3 if num_classes is None else int(num_classes)
+    if state.dtype != torch.int64 or state.numel() != 3 * C + 1 or not 1 <= C <= SEG_MAX_CLASSES:
+        raise AdellHipError("seg_metric_compute: the state must be int64 [3 C + 1], 1 <= C <= 32")
+    if not state.is_cuda:
+        raise AdellHipError("adell_mri_amd kernels run on MI355X only: got a CPU tensor (no CPU fallback)")
+    out = torch.empty((), dtype=torch.float32, device=state.device)
+    check(_lib.lib().adell_seg_metric_compute(_ptr(state), C, SEG_METRIC_KINDS[kind], float(beta),
+                                              _ptr(out), _stream()))
+    return out
+
+
 # ---- shifted-window (SWIN) token path -----------------------------------------------------
 def gather_nd(x, dims, axes, out=None):
     """Flat contiguous gather of ``x`` (csrc/window.hip). ``dims``: [(size, axis, mult)] of the

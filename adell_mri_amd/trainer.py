@@ -3,7 +3,8 @@ the part of ``lightning.Trainer.fit`` the reference's training step relies on
 (adell_mri/entrypoints/segmentation/train.py:799-819): zero_grad ->
 training_step -> backward -> gradient exchange -> optimizer.step, with the
 Trainer's ``gradient_clip_val`` and ``accumulate_grad_batches`` (train.py:807,811,
-ssl/train_3d.py:354-355)."""
+ssl/train_3d.py:354-355); ``validate_steps`` / ``test_steps`` are the part of
+``Trainer.validate`` / ``Trainer.test`` the reference uses (train.py:819-830)."""
 import itertools
 import os
 
@@ -140,6 +141,10 @@ class StepRunner:
         if getattr(self.module, "ema", None) is not None:
             raise RuntimeError("StepRunner.enable_graph: the module's EMA update takes its decay from a "
                                "host-side schedule inside training_step; a replay would freeze it")
+        if getattr(self.module, "compute_train_metrics", False):
+            raise RuntimeError("StepRunner.enable_graph: compute_train_metrics is on; metrics are not "
+                               "captured in a HIP graph -- set module.compute_train_metrics = False "
+                               "or run eager steps")
         if warmup < 1:
             raise ValueError("StepRunner.enable_graph: at least one warm-up step (it leaves the packed "
                              "weight tables, staging rings and launch plans the capture may not build)")
@@ -260,3 +265,83 @@ def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulat
     losses = [runner.train_step(b).detach() for b in batches]
     runner.flush()
     return losses
+
+
+def _batch_size(module, batch):
+    """Items in a batch: those of the image (``image_key`` / the first ``image_keys`` entry, inside
+    a semi-supervised batch's "supervised" part), else of its first tensor."""
+    import torch
+
+    if isinstance(batch, dict) and "supervised" in batch:
+        batch = batch["supervised"]
+    key = getattr(module, "image_key", None) or (getattr(module, "image_keys", None) or [None])[0]
+    if isinstance(batch, dict) and key in batch and torch.is_tensor(batch[key]):
+        return int(batch[key].shape[0])
+    stack = [batch]
+    while stack:
+        b = stack.pop(0)
+        if torch.is_tensor(b):
+            return int(b.shape[0])
+        if isinstance(b, dict):
+            stack.extend(b.values())
+        elif isinstance(b, (list, tuple)):
+            stack.extend(b)
+    return 1
+
+
+def _evaluate(module, batches, step_name, loss_key, metrics_attr):
+    import torch
+    import torch.distributed as dist
+
+    from .metrics import bad_target_message
+
+    metrics = getattr(module, metrics_attr, None) or {}
+    was_training = module.training
+    module.eval()
+    try:
+        with torch.no_grad():
+            total, count = None, 0
+            for i, batch in enumerate(batches):
+                loss = getattr(module, step_name)(batch, i).detach().double().reshape(())
+                bs = _batch_size(module, batch)
+                total = loss * bs if total is None else total + loss * bs
+                count += bs
+            if total is None:
+                raise ValueError(f"{step_name}s: no batches")
+            mean = total / count
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                dist.all_reduce(mean)             # Lightning's sync_dist: the mean over ranks
+                mean = mean / dist.get_world_size()
+            values, flags = [mean], []
+            for m in metrics.values():
+                v, bad = m.compute_async()
+                values.append(v.double())
+                flags.append(bad.double())
+            host = torch.stack(values + flags).cpu().tolist()    # the one host synchronisation
+        keys = list(metrics.keys())
+        for k, bad in zip(keys, host[1 + len(keys):]):
+            if bad > 0:
+                raise RuntimeError(f"{k}: " + bad_target_message(metrics[k].num_classes))
+        out = {loss_key: host[0]}
+        out.update(zip(keys, host[1:1 + len(keys)]))
+        return out
+    finally:
+        for m in metrics.values():
+            m.reset()
+        module.train(was_training)
+
+
+def validate_steps(module, batches):
+    """``validation_step`` over ``batches`` in eval mode without autograd, then
+    ``{"val_loss": batch-size-weighted mean of the step losses (averaged over ranks), "V_IoU": ...,
+    ...}`` from ``module.val_metrics``, which are reset. One host synchronisation, at the end."""
+    return _evaluate(module, batches, "validation_step", "val_loss", "val_metrics")
+
+
+def test_steps(module, batches):
+    """``test_step`` over ``batches``: ``{"test_loss": ..., "T_IoU": ..., ...}`` from
+    ``module.test_metrics``, as ``validate_steps``."""
+    return _evaluate(module, batches, "test_step", "test_loss", "test_metrics")
+
+
+test_steps.__test__ = False     # a loop, not a pytest test, wherever it is imported

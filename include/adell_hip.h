@@ -775,6 +775,28 @@ int adell_grad_scale_by(float* g, long n, const float* coef_dev, void* stream);
  * under Trainer(accumulate_grad_batches) (train.py:811, ssl/train_3d.py:355). */
 int adell_multi_accumulate(const long* table, int rows, float* dst, void* stream);
 
+/* Segmentation metrics (csrc/seg_metrics.hip): the confusion counts behind the reference's
+ * torchmetrics dicts (modules/segmentation/pl.py:100-187, setup_metrics :655-671; updated from
+ * training_step / validation_step / test_step :403, :467, :513; reported by
+ * entrypoints/segmentation/test.py:337-392). A metric state is int64 [3 C + 1]: (tp, fp, fn) per
+ * class, then the bad-target flag.
+ *   adell_seg_confusion_workspace(n, C): bytes of the int32 partial rows for n = B * S voxels;
+ *   adell_seg_confusion_update: pred fp32 [B][C][S] (channels_last: [B][S][C]; C <= 32), target
+ *     [B][S] of target_type 0 fp32 (rounded half-to-even), 1 uint8 / bool, 2 int64. Two launches
+ *     (partial rows, one-block finalize) that ADD the counts of this update into each of the
+ *     nstates <= 8 states (host array of device pointers). C = 1: mask p > 0.5, or sigmoid(p) > 0.5
+ *     when any p of this update lies outside [0, 1] (NaN included). C > 1: argmax over the
+ *     channels. A target outside {0, 1} / [0, C) sets the flag. No host synchronisation;
+ *   adell_seg_metric_compute: out[0] (fp32) = kind of the state, fp64 arithmetic, averaged over the
+ *     classes with tp + fp + fn > 0 (0 when none; a zero denominator gives 0). */
+enum { ADELL_SEG_IOU = 0, ADELL_SEG_PRECISION = 1, ADELL_SEG_FBETA = 2, ADELL_SEG_DICE = 3 };
+long adell_seg_confusion_workspace(long n, int C);
+int adell_seg_confusion_update(const float* pred, const void* target, int target_type, long B, int C,
+                               long S, int channels_last, int* workspace, long workspace_bytes,
+                               long long* const* states, int nstates, void* stream);
+int adell_seg_metric_compute(const long long* state, int C, int kind, float beta, float* out,
+                             void* stream);
+
 /* ---- shifted-window (SWIN) token path: vit.py:33-45,95-129,1005-1256; linear_blocks.py:358-417 */
 /* out (contiguous over sizes[0..nd)) = gather of `in`: out dim d adds coord*mult[d] to input
  * axis axis[d]; input axis a has extent / stride (elements) / cyclic shift:
