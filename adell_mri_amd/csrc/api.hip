@@ -14,6 +14,17 @@ void adell_set_error(const char* fmt, ...) {
 extern "C" const char* adell_last_error(void) { return g_err; }
 extern "C" int adell_abi_version(void) { return ADELL_ABI_VERSION; }
 
+int adell_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 0;
+    return n > 0 ? n : 256;
+  }();
+  return cus;
+}
+
 // ---- launch-plan switches -------------------------------------------------------------------
 #include <stdlib.h>
 #include <string.h>

@@ -506,15 +506,9 @@ extern "C" int adell_gibbs_lowpass(const float* x, float* out, int N, int D, int
     hipLaunchKernelGGL(adell_kspace_kernel, dim3((unsigned)b, N), dim3(256), 0, st, x, buf, out, D, H,
                        W, C, radius, phase);
   };
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dft_axis_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  auto dft = [&](int axis, int inverse) {
+  auto dft = [&](int axis, int inverse) -> int {
     const int L = axis == 0 ? D : (axis == 1 ? H : W);
-    if (L == 1) return;
+    if (L == 1) return ADELL_OK;
     const long S = (axis == 0 ? (long)H * W : (axis == 1 ? (long)W : 1L)) * C;
     const long total = (long)N * D * H * W * C;
     const long lines = total / L;        // outer * S with outer = N * (dims before the axis)
@@ -522,13 +516,17 @@ extern "C" int adell_gibbs_lowpass(const float* x, float* out, int N, int D, int
     while (G > 1 && (S % G != 0 || (size_t)(G + 1) * L * 8 > 96 * 1024)) G >>= 1;
     long groups = (lines + G - 1) / G;
     if (groups > 65535 * 4) groups = 65535 * 4;
-    hipLaunchKernelGGL(adell_dft_axis_kernel, dim3((unsigned)groups), dim3(256),
-                       (size_t)(G + 1) * L * sizeof(float2), st, buf, lines, L, S, G, inverse);
+    return adell_launch<adell_dft_axis_kernel>(dim3((unsigned)groups), dim3(256),
+                                               (size_t)(G + 1) * L * sizeof(float2), st, buf, lines,
+                                               L, S, G, inverse);
   };
+  int rc = ADELL_OK;
   pass(0);
-  for (int a = 0; a < 3; ++a) dft(a, 0);
+  for (int a = 0; a < 3 && rc == ADELL_OK; ++a) rc = dft(a, 0);
+  if (rc != ADELL_OK) return rc;
   pass(1);
-  for (int a = 0; a < 3; ++a) dft(a, 1);
+  for (int a = 0; a < 3 && rc == ADELL_OK; ++a) rc = dft(a, 1);
+  if (rc != ADELL_OK) return rc;
   pass(2);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;

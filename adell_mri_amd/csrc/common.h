@@ -71,6 +71,41 @@ extern long g_adell_plan_epoch;
     }                                                                          \
   } while (0)
 
+// LDS per CU on gfx950 (MI355X): the most LDS one block may take.
+constexpr int kAdellLdsPerCu = 160 * 1024;
+
+// Launch of a kernel whose dynamic LDS may exceed the runtime's 64 KiB default. The first call for
+// each Kern raises its limit, once per process (a thread-safe function-local static), to the CU's
+// LDS less the kernel's static LDS; every call launches and checks the launch. Errors name Kern
+// through __PRETTY_FUNCTION__.
+template <auto Kern, typename... Args>
+static int adell_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static const hipError_t attr = [] {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kern));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(Kern),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               kAdellLdsPerCu - (int)fa.sharedSizeBytes);
+  }();
+  if (attr != hipSuccess) {
+    adell_set_error("%s: raising the dynamic LDS limit -> %s", __PRETTY_FUNCTION__,
+                    hipGetErrorString(attr));
+    return ADELL_E_HIP;
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    adell_set_error("%s: launch -> %s", __PRETTY_FUNCTION__, hipGetErrorString(e));
+    return ADELL_E_HIP;
+  }
+  return ADELL_OK;
+}
+
+// Number of CUs of the current device (256 if the runtime cannot say); queried once (api.hip).
+// It sizes persistent grids, and with them the *_ntiles / workspace plans callers allocate against.
+int adell_cu_count();
+
 static inline int adell_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int adell_ilog2(int v) {
   int r = 0;

@@ -81,17 +81,7 @@ extern "C" void adell_debug_force_conv_cfg(int cfg) {
 template <int MT, int NT, int WM, int WN>
 static int adell_launch_conv(const ConvArgs& a, dim3 grid, size_t lds,
                              hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = adell_conv_igemm_kernel<MT, NT, WM, WN>;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(kern),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_conv_igemm_kernel<MT, NT, WM, WN>>(grid, dim3(256), lds, st, a);
 }
 
 // Generic launcher. `a` must have everything but the tile fields filled in.
@@ -358,28 +348,8 @@ extern "C" int adell_pack_weight(const float* w, float* out, int mode, int dim0,
 template <int MT, int NT, int WM, int WN, int SPEC, int EPI = 0, int ROWS = 0>
 static int adell_launch_conv_f16(const ConvArgs& a, const ConvF16Extra& e, dim3 grid, size_t lds,
                                  hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = adell_conv_igemm_f16_kernel<MT, NT, WM, WN, SPEC, EPI, ROWS>;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, st, a, e);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
-}
-
-static int adell_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
+  return adell_launch<adell_conv_igemm_f16_kernel<MT, NT, WM, WN, SPEC, EPI, ROWS>>(
+      grid, dim3(WM * WN * 64), lds, st, a, e);
 }
 
 // 16 -> 16 channel layers: the z-marching 16-column kernel (conv_zring16.hip)

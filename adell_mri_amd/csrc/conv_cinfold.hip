@@ -1304,50 +1304,25 @@ extern "C" int adell_conv_cinfold_dx_applicable(const adell_conv3d_desc* d) {
 }
 
 template <int CIN, int CO>
-static void adell_cinfold_dx_f16_launch(const CinFoldDxArgs& a, dim3 grid, hipStream_t st) {
+static int adell_cinfold_dx_f16_launch(const CinFoldDxArgs& a, dim3 grid, hipStream_t st) {
   constexpr int KP = ((27 * CIN + 31) / 32) * 32;
   const size_t lds = (size_t)((CO / 16) * 128 * 16 + 128 * (KP + 1) + 8) * sizeof(float);
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adell_cinfold_dx_f16_kernel<CIN, CO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    done = true;
-  }
-  hipLaunchKernelGGL((adell_cinfold_dx_f16_kernel<CIN, CO>), grid, dim3(256), lds, st, a);
+  return adell_launch<adell_cinfold_dx_f16_kernel<CIN, CO>>(grid, dim3(256), lds, st, a);
 }
 
 template <int CIN>
-static void adell_cinfold_dx_launch(const CinFoldDxArgs& a, dim3 grid, hipStream_t st, int f16x3) {
+static int adell_cinfold_dx_launch(const CinFoldDxArgs& a, dim3 grid, hipStream_t st, int f16x3) {
   constexpr int KP = ((27 * CIN + 31) / 32) * 32;
-  if (f16x3 && a.Cout <= 32) {
-    adell_cinfold_dx_f16_launch<CIN, 32>(a, grid, st);
-    return;
-  }
+  if (f16x3 && a.Cout <= 32) return adell_cinfold_dx_f16_launch<CIN, 32>(a, grid, st);
   if constexpr (CIN < 4) {   // (4 channels x 64 columns: the split fragments do not fit 256 registers)
-    if (f16x3) {
-      adell_cinfold_dx_f16_launch<CIN, 64>(a, grid, st);
-      return;
-    }
+    if (f16x3) return adell_cinfold_dx_f16_launch<CIN, 64>(a, grid, st);
   }
   if (a.Cout <= 32) {
     const size_t lds = (size_t)(128 * 33 + 128 * (KP + 1)) * sizeof(float);
-    static bool done = false;
-    if (!done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adell_cinfold_dx_kernel<CIN, 32>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      done = true;
-    }
-    hipLaunchKernelGGL((adell_cinfold_dx_kernel<CIN, 32>), grid, dim3(256), lds, st, a);
-  } else {
-    const size_t lds = (size_t)(128 * 65 + 128 * (KP + 1)) * sizeof(float);
-    static bool done = false;
-    if (!done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adell_cinfold_dx_kernel<CIN, 64>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      done = true;
-    }
-    hipLaunchKernelGGL((adell_cinfold_dx_kernel<CIN, 64>), grid, dim3(256), lds, st, a);
+    return adell_launch<adell_cinfold_dx_kernel<CIN, 32>>(grid, dim3(256), lds, st, a);
   }
+  const size_t lds = (size_t)(128 * 65 + 128 * (KP + 1)) * sizeof(float);
+  return adell_launch<adell_cinfold_dx_kernel<CIN, 64>>(grid, dim3(256), lds, st, a);
 }
 
 static int adell_cinfold_bwd_data_impl(const adell_conv3d_desc* d, const float* dy, const float* w,
@@ -1388,11 +1363,9 @@ static int adell_cinfold_bwd_data_impl(const adell_conv3d_desc* d, const float* 
   dim3 grid((unsigned)(a.ntx * a.nty * a.nseg), (unsigned)d->N);
   hipStream_t st = (hipStream_t)stream;
   switch (d->C0) {
-    case 1: adell_cinfold_dx_launch<1>(a, grid, st, f16x3); break;
-    case 2: adell_cinfold_dx_launch<2>(a, grid, st, f16x3); break;
-    case 3: adell_cinfold_dx_launch<3>(a, grid, st, f16x3); break;
-    default: adell_cinfold_dx_launch<4>(a, grid, st, f16x3); break;
+    case 1: return adell_cinfold_dx_launch<1>(a, grid, st, f16x3);
+    case 2: return adell_cinfold_dx_launch<2>(a, grid, st, f16x3);
+    case 3: return adell_cinfold_dx_launch<3>(a, grid, st, f16x3);
+    default: return adell_cinfold_dx_launch<4>(a, grid, st, f16x3);
   }
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
 }

@@ -339,18 +339,6 @@ __global__ __launch_bounds__(256, 1) void adell_dgrad_s2_fused_kernel(DgradS2Arg
 
 namespace {
 
-int cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 bool dgrad_s2_fused_ok(const adell_conv3d_desc* d) {
   return d && d->C1 == 0 && d->C0 == 32 && d->Cout == 32 && d->KD == 3 && d->KH == 3 && d->KW == 3 &&
          d->SD == 2 && d->SH == 2 && d->SW == 2 && d->PD == 1 && d->PH == 1 && d->PW == 1 &&
@@ -391,30 +379,18 @@ extern "C" int adell_conv3d_bwd_data_s2_fused(const adell_conv3d_desc* d, const 
   const long nbricks = (long)d->N * a.ntx * a.nty * a.ntz;
   ADELL_REQUIRE(nbricks < 0x7fffffffL, "conv_bwd_data_s2_fused: too many bricks");
   a.nbricks = (int)nbricks;
-  const int grid = (int)(nbricks < cu_count() ? nbricks : cu_count());   // one block per CU
-  auto launch = [&](auto kern) -> int {
-    // (the attribute is per kernel symbol; set on every call: a cheap host-side table write)
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds, (hipStream_t)stream, a);
-    return ADELL_OK;
-  };
-  int rc = ADELL_OK;
+  const int grid = (int)(nbricks < adell_cu_count() ? nbricks : adell_cu_count());  // one block per CU
+  hipStream_t st = (hipStream_t)stream;
 #ifdef ADELL_DEBUG
   switch (g_adell_tune.igemm_dbg) {
-    case 1: rc = launch(adell_dgrad_s2_fused_kernel<1>); break;
-    case 2: rc = launch(adell_dgrad_s2_fused_kernel<2>); break;
-    case 3: rc = launch(adell_dgrad_s2_fused_kernel<3>); break;
-    case 4: rc = launch(adell_dgrad_s2_fused_kernel<4>); break;
-    case 8: rc = launch(adell_dgrad_s2_fused_kernel<8>); break;
-    case 16: rc = launch(adell_dgrad_s2_fused_kernel<16>); break;
-    case 27: rc = launch(adell_dgrad_s2_fused_kernel<27>); break;
-    default: rc = launch(adell_dgrad_s2_fused_kernel<0>); break;
+    case 1: return adell_launch<adell_dgrad_s2_fused_kernel<1>>(dim3(grid), dim3(256), kLds, st, a);
+    case 2: return adell_launch<adell_dgrad_s2_fused_kernel<2>>(dim3(grid), dim3(256), kLds, st, a);
+    case 3: return adell_launch<adell_dgrad_s2_fused_kernel<3>>(dim3(grid), dim3(256), kLds, st, a);
+    case 4: return adell_launch<adell_dgrad_s2_fused_kernel<4>>(dim3(grid), dim3(256), kLds, st, a);
+    case 8: return adell_launch<adell_dgrad_s2_fused_kernel<8>>(dim3(grid), dim3(256), kLds, st, a);
+    case 16: return adell_launch<adell_dgrad_s2_fused_kernel<16>>(dim3(grid), dim3(256), kLds, st, a);
+    case 27: return adell_launch<adell_dgrad_s2_fused_kernel<27>>(dim3(grid), dim3(256), kLds, st, a);
   }
-#else
-  rc = launch(adell_dgrad_s2_fused_kernel<0>);
 #endif
-  if (rc != ADELL_OK) return rc;
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dgrad_s2_fused_kernel<0>>(dim3(grid), dim3(256), kLds, st, a);
 }

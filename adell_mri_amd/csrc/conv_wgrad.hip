@@ -439,17 +439,7 @@ static size_t adell_wgrad_ws_bytes(const WgradPlan& p, int ntap, int Cin, int Co
 
 template <int MAXJ>
 static int adell_launch_wgrad(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = adell_conv_wgrad_kernel<MAXJ>;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_conv_wgrad_kernel<MAXJ>>(grid, dim3(256), lds, st, a);
 }
 
 // Core: X is the strided/haloed operand (its channels index dW's "Cin" axis), dY

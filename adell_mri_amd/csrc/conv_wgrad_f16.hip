@@ -521,16 +521,7 @@ static size_t adell_wgrad_f16_ws(const WgradF16Plan& p, int ntap, int Cin, int C
 
 template <int MAXJ, int PFX = 0, int PFY = 0, int MINB = 2>
 static int adell_launch_wgrad_f16(const WgradF16Args& a, dim3 grid, size_t lds, hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = adell_conv_wgrad_f16_kernel<MAXJ, PFX, PFY, MINB>;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_conv_wgrad_f16_kernel<MAXJ, PFX, PFY, MINB>>(grid, dim3(256), lds, st, a);
 }
 
 static int adell_wgrad_f16_core(int N, int D, int H, int W, int C0, int C1, const float* x0,

@@ -341,18 +341,6 @@ struct WgradS2Plan {
   int ntx, nty, ntz, nbricks, blocks, R;
 };
 
-static int wgrad_s2_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 // 1 + plan when the kernel takes the problem: 32 -> 32 channels, k = 3, stride 2, padding 1, even
 // input dims, one source
 extern "C" int adell_wgrad_s2_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
@@ -372,9 +360,9 @@ extern "C" int adell_wgrad_s2_plan(int N, int D, int H, int W, int C0, int C1, i
   if (nb >= 0x0fffffffL) return 0;
   // every (block, group) writes a 108 KB slab: below a few bricks per block the slab fold costs more
   // than the kernel saves (2 x 64^3: 0.087 ms here against 0.077 on the generic kernel)
-  if (nb < 8L * wgrad_s2_cus()) return 0;
+  if (nb < 8L * adell_cu_count()) return 0;
   p->nbricks = (int)nb;
-  const long want = 2L * wgrad_s2_cus();     // two resident blocks per CU
+  const long want = 2L * adell_cu_count();     // two resident blocks per CU
   p->blocks = (int)(nb < want ? nb : want);
   p->R = p->blocks;
   return 1;
@@ -388,25 +376,14 @@ extern "C" int adell_wgrad_s2_launch(const WgradS2Plan* p, int N, int D, int H, 
   a.x = x; a.dy = dy; a.ws = slabs; a.wsdb = wsdb; a.xmax = xmax; a.ymax = ymax;
   a.N = N; a.D = D; a.H = H; a.W = W; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
   a.ntx = p->ntx; a.nty = p->nty; a.ntz = p->ntz; a.nbricks = p->nbricks;
-  auto launch = [&](auto kern) -> int {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)p->blocks), dim3(kThreads), kLds, st, a);
-    return ADELL_OK;
-  };
-  int rc = ADELL_OK;
+  const dim3 grid((unsigned)p->blocks);
 #ifdef ADELL_DEBUG
   switch (g_adell_tune.zr_dbg) {
-    case 1: rc = launch(adell_conv_wgrad_s2_kernel<1>); break;
-    case 8: rc = launch(adell_conv_wgrad_s2_kernel<8>); break;
-    case 16: rc = launch(adell_conv_wgrad_s2_kernel<16>); break;
-    case 25: rc = launch(adell_conv_wgrad_s2_kernel<25>); break;
-    default: rc = launch(adell_conv_wgrad_s2_kernel<0>); break;
+    case 1: return adell_launch<adell_conv_wgrad_s2_kernel<1>>(grid, dim3(kThreads), kLds, st, a);
+    case 8: return adell_launch<adell_conv_wgrad_s2_kernel<8>>(grid, dim3(kThreads), kLds, st, a);
+    case 16: return adell_launch<adell_conv_wgrad_s2_kernel<16>>(grid, dim3(kThreads), kLds, st, a);
+    case 25: return adell_launch<adell_conv_wgrad_s2_kernel<25>>(grid, dim3(kThreads), kLds, st, a);
   }
-#else
-  rc = launch(adell_conv_wgrad_s2_kernel<0>);
 #endif
-  if (rc != ADELL_OK) return rc;
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_conv_wgrad_s2_kernel<0>>(grid, dim3(kThreads), kLds, st, a);
 }

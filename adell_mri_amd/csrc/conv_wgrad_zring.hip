@@ -693,14 +693,6 @@ extern "C" int adell_wgrad_zring_launch(const WgradZrPlan* p, int N, int D, int 
     return ADELL_OK;
   }
   const size_t lds = 2 * (ZR_SLOTS * (size_t)ZR_PLANE + 2 * 64 * 64);
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_conv_wgrad_zring_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(adell_conv_wgrad_zring_kernel, dim3((unsigned)p->R, (unsigned)(p->nci * p->nco)),
-                     dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_conv_wgrad_zring_kernel>(dim3((unsigned)p->R, (unsigned)(p->nci * p->nco)),
+                                                     dim3(256), lds, st, a);
 }

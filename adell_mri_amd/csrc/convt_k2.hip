@@ -494,16 +494,7 @@ extern "C" int adell_convt_k221_fwd(int N, int D, int H, int W, int Cin, int Cou
 
 template <int COUT, int FX>
 static int adell_ctk2_launch_dx(const ConvTK2Args& a, dim3 grid, size_t lds, hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = adell_convt_k2_dx_kernel<COUT, FX>;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_convt_k2_dx_kernel<COUT, FX>>(grid, dim3(256), lds, st, a);
 }
 
 static int adell_convt_k2_bwd_data_impl(int N, int D, int H, int W, int Cin, int Cout, int FX,

@@ -224,16 +224,8 @@ extern "C" int adell_dw_dense_ok(int N, int C, int D, int H, int W, int KD, int 
 
 template <int CG>
 static int adell_dw_dense_go(const DwDenseArgs& a, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dw_dense_kernel<CG>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(adell_dw_dense_kernel<CG>, dim3(a.C / CG, (a.N + DD_IT - 1) / DD_IT), dim3(64 * CG),
-                     dd_lds<CG>(), st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dw_dense_kernel<CG>>(dim3(a.C / CG, (a.N + DD_IT - 1) / DD_IT),
+                                                 dim3(64 * CG), dd_lds<CG>(), st, a);
 }
 
 extern "C" int adell_dw_dense_launch(const float* x, const float* w, const float* b, float* y, int N,

@@ -348,33 +348,15 @@ extern "C" int adell_dw_mfma_ok(int N, int C, int D, int H, int W, int KD, int K
 extern "C" int adell_dw_mfma_launch(const float* x, const float* w, const float* b, float* y, int N,
                                     int C, int D, int H, int W, int flip, void* stream) {
   ADELL_REQUIRE(adell_dw_mfma_ok(N, C, D, H, W, 7, 7, 7, x, y), "dw_mfma: shape not covered");
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dw_mfma_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dw_mfma_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
   const long total = (long)N * (C / DM_CG);
   ADELL_REQUIRE(total <= 0x7fffffffL - 4096, "dw_mfma: too many work items");
   DwMfmaArgs a = {x, w, b, y, N, C, D, H, W, flip, (int)total};
   if (D <= 16) {
     // one block per CU (LDS): persistent blocks, each prefetching its next column
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ADELL_CHECK_HIP(hipGetDevice(&dev));
-      ADELL_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-      cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    const int cus = adell_cu_count();
     const int grid = total < cus ? (int)total : cus;
-    hipLaunchKernelGGL(adell_dw_mfma_kernel<true>, dim3(grid), dim3(256), DM_LDS, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(adell_dw_mfma_kernel<false>, dim3((unsigned)total), dim3(256), DM_LDS,
-                       (hipStream_t)stream, a);
+    return adell_launch<adell_dw_mfma_kernel<true>>(dim3(grid), dim3(256), DM_LDS, (hipStream_t)stream, a);
   }
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dw_mfma_kernel<false>>(dim3((unsigned)total), dim3(256), DM_LDS,
+                                                   (hipStream_t)stream, a);
 }

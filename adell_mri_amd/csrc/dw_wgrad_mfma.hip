@@ -287,15 +287,8 @@ extern "C" int adell_dw_wgrad_mfma_launch(const float* x, const float* dy, float
   if (rc != ADELL_OK) return rc;
   rc = adell_absmax_f32(dy, total, words + 1, stream);
   if (rc != ADELL_OK) return rc;
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dw_wgrad_mfma_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
   DwWgMfmaArgs a = {x, dy, workspace, words, N, C, D, H, W, ipc};
-  hipLaunchKernelGGL(adell_dw_wgrad_mfma_kernel, dim3(C / WM_CG, chunks), dim3(256), WM_LDS, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  *chunks_out = chunks;
-  return ADELL_OK;
+  rc = adell_launch<adell_dw_wgrad_mfma_kernel>(dim3(C / WM_CG, chunks), dim3(256), WM_LDS, st, a);
+  if (rc == ADELL_OK) *chunks_out = chunks;
+  return rc;
 }

@@ -659,13 +659,7 @@ static int gemm_h_run(int M, int N, int K, const float* A, long lda, int a_kc,
   dim3 grid(adell_cdiv(M, BM), adell_cdiv(N, BN), p.splits);
   ADELL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm_f16x3: grid too large");
   constexpr size_t kLds = 2 * kTileBytes + 8 * sizeof(float);
-  auto launch = [&](auto kern) -> int {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    hipLaunchKernelGGL(kern, grid, dim3(256), kLds, st, a);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  };
+  const dim3 block(256);
   int rc;
   const bool wide = N % 4 == 0 && ldc % 4 == 0 && (!residual || ldr % 4 == 0) &&
                     ((((uintptr_t)C) | ((uintptr_t)bias) | ((uintptr_t)residual) |
@@ -673,21 +667,21 @@ static int gemm_h_run(int M, int N, int K, const float* A, long lda, int a_kc,
   ADELL_REQUIRE(wide || !epi, "gemm_f16x3_act: operands do not qualify for the wide epilogue");
   if (wide) {
     if (a_kc && b_kc)
-      rc = launch(adell_gemm_f16x3_kernel<true, true, true>);
+      rc = adell_launch<adell_gemm_f16x3_kernel<true, true, true>>(grid, block, kLds, st, a);
     else if (a_kc && !b_kc)
-      rc = launch(adell_gemm_f16x3_kernel<true, false, true>);
+      rc = adell_launch<adell_gemm_f16x3_kernel<true, false, true>>(grid, block, kLds, st, a);
     else if (!a_kc && !b_kc)
-      rc = launch(adell_gemm_f16x3_kernel<false, false, true>);
+      rc = adell_launch<adell_gemm_f16x3_kernel<false, false, true>>(grid, block, kLds, st, a);
     else
-      rc = launch(adell_gemm_f16x3_kernel<false, true, true>);
+      rc = adell_launch<adell_gemm_f16x3_kernel<false, true, true>>(grid, block, kLds, st, a);
   } else if (a_kc && b_kc)
-    rc = launch(adell_gemm_f16x3_kernel<true, true>);
+    rc = adell_launch<adell_gemm_f16x3_kernel<true, true>>(grid, block, kLds, st, a);
   else if (a_kc && !b_kc)
-    rc = launch(adell_gemm_f16x3_kernel<true, false>);
+    rc = adell_launch<adell_gemm_f16x3_kernel<true, false>>(grid, block, kLds, st, a);
   else if (!a_kc && !b_kc)
-    rc = launch(adell_gemm_f16x3_kernel<false, false>);
+    rc = adell_launch<adell_gemm_f16x3_kernel<false, false>>(grid, block, kLds, st, a);
   else
-    rc = launch(adell_gemm_f16x3_kernel<false, true>);
+    rc = adell_launch<adell_gemm_f16x3_kernel<false, true>>(grid, block, kLds, st, a);
   if (rc != ADELL_OK) return rc;
   if (p.splits > 1) {
     if (N % 4 == 0 && (((uintptr_t)a.slab) & 15) == 0)

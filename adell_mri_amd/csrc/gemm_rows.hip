@@ -410,22 +410,6 @@ __global__ __launch_bounds__(64 * (RB_CW + 4), (RB_CW + 4) / 4) void adell_gemm_
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-namespace {
-
-int rb_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-}  // namespace
-
 // Whether the streaming kernel takes this problem (gemm_f16x3.hip asks before it plans its tiles):
 // A K-contiguous, K a multiple of 32, many rows, a weight small enough to pack per call, and an
 // epilogue it has an instance of (no activation, or GELU for the activation pair).
@@ -442,7 +426,7 @@ bool adell_gemm_rows_ok(int M, int N, int K, const float* A, long lda, int a_kc,
   if (dact) return false;
   // enough tiles for the persistent grid: at least one per CU
   const long tiles = (long)adell_cdiv(M, RB_M) * adell_cdiv(N, RB_N);
-  return tiles >= (long)rb_cu_count();
+  return tiles >= (long)adell_cu_count();
 }
 
 // floats of workspace: the packed image + the column scales
@@ -466,10 +450,9 @@ int adell_gemm_rows_run(int M, int N, int K, const float* A, long lda, const flo
   int R = b_kc ? 8 : 32;
   while (R > 1 && (size_t)R * (K + 4) * 4 > 64 * 1024) R >>= 1;
   const size_t plds = (size_t)R * (K + 4) * 4 + 32 * sizeof(unsigned);
-  ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_gemm_rows_pack_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-  hipLaunchKernelGGL(adell_gemm_rows_pack_kernel, dim3((unsigned)(slices * RB_N / R)), dim3(256), plds, st,
-                     B, ldb, b_kc, N, K, R, img, bscale);
+  const int rc = adell_launch<adell_gemm_rows_pack_kernel>(dim3((unsigned)(slices * RB_N / R)), dim3(256),
+                                                           plds, st, B, ldb, b_kc, N, K, R, img, bscale);
+  if (rc != ADELL_OK) return rc;
   a.A = A; a.Bimg = img; a.bscale = bscale; a.C = C; a.bias = bias; a.residual = residual;
   a.act_out = act_out; a.dact_in = dact_in;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr;
@@ -477,20 +460,16 @@ int adell_gemm_rows_run(int M, int N, int K, const float* A, long lda, const flo
   const long tiles = (long)adell_cdiv(M, RB_M) * slices;
   ADELL_REQUIRE(tiles < 0x7fffffffL, "gemm_rows: too many tiles");
   a.tiles = (int)tiles;
-  int blocks = rb_cu_count();
+  int blocks = adell_cu_count();
   if (blocks > tiles) blocks = (int)tiles;
   a.tiles_per_block = (int)((tiles + blocks - 1) / blocks);
   blocks = (int)((tiles + a.tiles_per_block - 1) / a.tiles_per_block);
   a.act_p = act_p;
-  auto launch = [&](auto kern) -> int {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, RB_LDS));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * (RB_CW + 4)), RB_LDS, st, a);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  };
+  const dim3 grid((unsigned)blocks), block(64 * (RB_CW + 4));
   (void)act;
-  if (act_out) return launch(adell_gemm_rows_f16x3_kernel<1, ADELL_ACT_GELU>);
-  if (dact_in) return launch(adell_gemm_rows_f16x3_kernel<2, ADELL_ACT_GELU>);
-  return launch(adell_gemm_rows_f16x3_kernel<0, ADELL_ACT_IDENTITY>);
+  if (act_out)
+    return adell_launch<adell_gemm_rows_f16x3_kernel<1, ADELL_ACT_GELU>>(grid, block, RB_LDS, st, a);
+  if (dact_in)
+    return adell_launch<adell_gemm_rows_f16x3_kernel<2, ADELL_ACT_GELU>>(grid, block, RB_LDS, st, a);
+  return adell_launch<adell_gemm_rows_f16x3_kernel<0, ADELL_ACT_IDENTITY>>(grid, block, RB_LDS, st, a);
 }

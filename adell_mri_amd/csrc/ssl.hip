@@ -523,17 +523,9 @@ static int adell_dw_zring_plan(int N, int C, int D, int H, int W, int KD, int KH
 }
 
 static int adell_dw_zring_launch(DwZrArgs z, hipStream_t st) {
-  static bool attr_done = false;
   const size_t lds = (size_t)(DZ_SLOTS * DZ_PLANE + 16 * DZ_K3) * sizeof(float);
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_dw_zring_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
   const long blocks = (long)z.N * z.tilesY * z.chanBlocks * z.nseg;
-  hipLaunchKernelGGL(adell_dw_zring_kernel, dim3((unsigned)blocks), dim3(256), lds, st, z);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dw_zring_kernel>(dim3((unsigned)blocks), dim3(256), lds, st, z);
 }
 
 // tiled path: cubic K in {3,5,7}. Returns the x-row width WT (4 / 8 / 16) or 0.
@@ -558,19 +550,10 @@ static int adell_dw_plan(int N, int C, int D, int H, int W, int KD, int KH, int 
 template <int K, int WT>
 static int adell_dw_tile_launch(const DwTileArgs& a, hipStream_t st) {
   using Cf = DwCfg<K, WT>;
-  static bool attr_done = false;
-  auto kern = adell_dw_tile_kernel<K, WT>;
   const size_t lds = (size_t)(Cf::XT_FLOATS + Cf::WT_FLOATS) * sizeof(float);
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
   const DwTile& t = a.t;
   const long blocks = (long)t.N * t.tilesZ * t.tilesY * t.tilesX * t.chanBlocks;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dw_tile_kernel<K, WT>>(dim3((unsigned)blocks), dim3(256), lds, st, a);
 }
 
 #define ADELL_DW_DISPATCH(FN, K, WT, ...)                                  \
@@ -702,18 +685,9 @@ static int adell_dw_wgrad_splits(const DwTile& t, long* items_out, int* ips_out)
 template <int K, int WT>
 static int adell_dw_wgrad_tile_launch(DwWgradArgs a, int splits, hipStream_t st) {
   using Cf = DwCfg<K, WT>;
-  static bool attr_done = false;
-  auto kern = adell_dw_wgrad_tile_kernel<K, WT>;
   const size_t lds = (size_t)(Cf::XT_FLOATS + Cf::DY_FLOATS) * sizeof(float);
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(splits * a.t.chanBlocks)), dim3(Cf::WG_THREADS), lds, st,
-                     a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_dw_wgrad_tile_kernel<K, WT>>(dim3((unsigned)(splits * a.t.chanBlocks)),
+                                                         dim3(Cf::WG_THREADS), lds, st, a);
 }
 
 static int adell_dw_wgrad_dispatch(int K, int WT, const DwWgradArgs& a, int splits,
@@ -1481,14 +1455,6 @@ extern "C" int adell_pair_loss_bwd(const float* x1, const float* x2, int B, int 
   a.W = const_cast<float*>(scratch) + (size_t)R * R; a.g = g; a.dx1 = dx1; a.dx2 = dx2;
   a.B = B; a.D = D; a.kind = kind; a.relu = (kind == 2 && apply_relu) ? 1 : 0;
   a.invT = kind == 2 ? 1.f / temperature : 1.f;
-  static bool attr_done = false;
-  if (!attr_done) {
-    ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(adell_pair_bwd_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(adell_pair_bwd_kernel, dim3(R), dim3(256), (size_t)D * sizeof(float),
-                     (hipStream_t)stream, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<adell_pair_bwd_kernel>(dim3(R), dim3(256), (size_t)D * sizeof(float),
+                                             (hipStream_t)stream, a);
 }

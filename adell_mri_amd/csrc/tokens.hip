@@ -1002,19 +1002,9 @@ static bool adell_att_mfma_ok(int T, int A, int Dv) {
 // which: 0 forward, 1 backward dQ, 2 backward dK/dV
 template <int AT, int DT, bool RES>
 static int adell_att_mfma_launch3(int which, const AttArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  const void* fn = which == 0 ? reinterpret_cast<const void*>(adell_attn_mfma_fwd_kernel<AT, DT, RES>)
-                   : which == 1 ? reinterpret_cast<const void*>(adell_attn_mfma_bwd_q_kernel<AT, DT, RES>)
-                                : reinterpret_cast<const void*>(adell_attn_mfma_bwd_kv_kernel<AT, DT, RES>);
-  if (lds > 48 * 1024)
-    ADELL_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  if (which == 0)
-    hipLaunchKernelGGL((adell_attn_mfma_fwd_kernel<AT, DT, RES>), grid, dim3(256), lds, st, a);
-  else if (which == 1)
-    hipLaunchKernelGGL((adell_attn_mfma_bwd_q_kernel<AT, DT, RES>), grid, dim3(256), lds, st, a);
-  else
-    hipLaunchKernelGGL((adell_attn_mfma_bwd_kv_kernel<AT, DT, RES>), grid, dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  if (which == 0) return adell_launch<adell_attn_mfma_fwd_kernel<AT, DT, RES>>(grid, dim3(256), lds, st, a);
+  if (which == 1) return adell_launch<adell_attn_mfma_bwd_q_kernel<AT, DT, RES>>(grid, dim3(256), lds, st, a);
+  return adell_launch<adell_attn_mfma_bwd_kv_kernel<AT, DT, RES>>(grid, dim3(256), lds, st, a);
 }
 template <int AT, int DT>
 static int adell_att_mfma_launch2(int which, const AttArgs& a, int BH, hipStream_t st) {
@@ -1049,14 +1039,10 @@ static int adell_att_check(int BH, int T, int A, int Dv, int nbias, const float*
   return ADELL_OK;
 }
 
-template <typename K>
-static int adell_att_launch(K kern, const AttArgs& a, int BH, size_t lds, hipStream_t st) {
+template <auto Kern>
+static int adell_att_launch(const AttArgs& a, int BH, size_t lds, hipStream_t st) {
   ADELL_REQUIRE(lds <= 160 * 1024, "attention: head dims need %zu B of LDS (> 160 KiB)", lds);
-  ADELL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL(kern, dim3(adell_cdiv(a.T, ATT_ROWS), BH), dim3(256), lds, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
-  return ADELL_OK;
+  return adell_launch<Kern>(dim3(adell_cdiv(a.T, ATT_ROWS), BH), dim3(256), lds, st, a);
 }
 
 // contiguous [BH][T][A | Dv] operands as strides
@@ -1096,7 +1082,7 @@ extern "C" int adell_attention_fwd(const float* q, const float* k, const float* 
   }
   const size_t lds = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * Dv +
                                       (size_t)ATT_ROWS * A + 4 * ATT_TK);
-  return adell_att_launch(adell_attention_fwd_kernel, a, BH, lds, (hipStream_t)stream);
+  return adell_att_launch<adell_attention_fwd_kernel>(a, BH, lds, (hipStream_t)stream);
 }
 
 extern "C" int adell_attention_bwd(const float* q, const float* k, const float* v,
@@ -1123,12 +1109,12 @@ extern "C" int adell_attention_bwd(const float* q, const float* k, const float* 
   }
   const size_t lds_q = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * (Dv + 1) +
                                         (size_t)ATT_ROWS * A + (size_t)ATT_ROWS * Dv + 4 * ATT_TK);
-  rc = adell_att_launch(adell_attention_bwd_q_kernel, a, BH, lds_q, (hipStream_t)stream);
+  rc = adell_att_launch<adell_attention_bwd_q_kernel>(a, BH, lds_q, (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
   const size_t lds_kv = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * (Dv + 1) +
                                          (size_t)ATT_ROWS * A + (size_t)ATT_ROWS * Dv +
                                          8 * ATT_TK + 2 * ATT_TK);
-  return adell_att_launch(adell_attention_bwd_kv_kernel, a, BH, lds_kv, (hipStream_t)stream);
+  return adell_att_launch<adell_attention_bwd_kv_kernel>(a, BH, lds_kv, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -41,6 +41,29 @@ def test_library_exports_nothing_but_the_declared_symbols():
     assert exported == _declared_symbols(), sorted(set(exported) ^ set(_declared_symbols()))
 
 
+def test_launch_setup_lives_in_common_h():
+    """Raising a kernel's dynamic-LDS limit is adell_launch's job (csrc/common.h) and the CU count is
+    adell_cu_count's (csrc/api.hip): no source repeats either with a flag or a device-properties query."""
+    import glob
+
+    csrc = os.path.join(ROOT, "adell_mri_amd", "csrc")
+    srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(srcs) >= 20
+    set_attr, props, flags = [], [], []
+    for path in srcs:
+        name = os.path.basename(path)
+        text = open(path).read()
+        if "hipFuncSetAttribute" in text and name != "common.h":
+            set_attr.append(name)
+        if "hipGetDeviceProperties" in text:
+            props.append(name)
+        if re.search(r"\bstatic\s+bool\s+\w*done\b", text):
+            flags.append(name)
+    assert not set_attr, f"hipFuncSetAttribute outside common.h: {set_attr}"
+    assert not props, f"hipGetDeviceProperties in: {props}"
+    assert not flags, f"static 'done' flags in: {flags}"
+
+
 def test_binding_table_matches_header():
     assert sorted(_lib.SIGNATURES) == _declared_symbols()
 
