@@ -217,6 +217,11 @@ SIGNATURES = {
     "adell_seg_confusion_workspace": (_l, [_l, _i]),
     "adell_seg_confusion_update": (_i, [_vp, _vp, _i, _l, _i, _l, _i, _vp, _l, _vp, _i, _vp]),
     "adell_seg_metric_compute": (_i, [_vp, _i, _i, _f, _vp, _vp]),
+    "adell_cc_workspace": (_l, [_l, _i, _i, _i]),
+    "adell_cc_label": (_i, [_vp, _l, _i, _i, _i, _i, _f, _vp, _vp, _vp, _l, _vp]),
+    "adell_picai_tables_workspace": (_l, [_l, _i, _i, _i]),
+    "adell_picai_tables_capacity": (_l, [_l, _i, _i, _i]),
+    "adell_picai_tables": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _f, _vp, _vp, _l, _vp, _l, _vp]),
     "adell_item_stats_workspace": (_l, [_i, _l]),
     "adell_item_stats": (_i, [_vp, _i, _l, _vp, _vp, ctypes.c_size_t, _vp]),
     "adell_aug_intensity": (_i, [_vp, _vp, _i, _l, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp]),

@@ -22,6 +22,7 @@ from ...metrics import (BinaryFBetaScore, BinaryJaccardIndex, BinaryPrecision, D
                         MulticlassDice, MulticlassFBetaScore, MulticlassJaccardIndex,
                         MulticlassPrecision, update_many)
 from ..learning_rate import CosineAnnealingWithWarmupLR
+from .picai_eval import PicaiEval
 from .unet import BrUNet, UNet
 from .unetpp import UNetPlusPlus
 from .unetr import SWINUNet, UNETR
@@ -88,6 +89,10 @@ class UNetBasePL(_Base):
     # training_step also updates train_metrics (pl.py:403) when True; off by default, so that a
     # training step issues exactly the launches it issues without metrics
     compute_train_metrics = False
+    # test_step's PI-CAI lists pair each micro-batch's predictions with the WHOLE batch's targets
+    # (sic: pl.py:503-509 zips pred_final with y, not y[m:M]); the semi-supervised wrapper pairs
+    # them correctly (semi_supervised_segmentation/pl.py:572-577)
+    picai_test_pairs_whole_batch = True
 
     def __init__(self):
         super().__init__()
@@ -175,15 +180,41 @@ class UNetBasePL(_Base):
             output = output[0]
         return output[0] if single else output
 
+    def picai_accumulator(self):
+        """The module's ``PicaiEval`` (created on first use) when ``picai_eval`` is set, else None. A
+        plain attribute: no submodule, parameter or buffer. The reference's own route fails for 2-D
+        networks and for more than one prediction channel (scipy: "structure and input must have
+        equal rank"); those raise NotImplementedError here."""
+        if not getattr(self, "picai_eval", False):
+            return None
+        if getattr(self, "spatial_dimensions", 3) != 3:
+            raise NotImplementedError(
+                "picai_eval needs a 3-D network: the reference labels lesions with a 3x3x3 structure, "
+                "which scipy rejects on 2-D cases ('structure and input must have equal rank')")
+        if getattr(self, "n_classes", 2) > 2:
+            raise NotImplementedError(
+                "picai_eval needs one prediction channel (n_classes <= 2): the reference's detection "
+                "maps of several channels are 4-D, which scipy rejects ('structure and input must "
+                "have equal rank')")
+        acc = self.__dict__.get("_picai")
+        if acc is None:
+            acc = PicaiEval()
+            self.__dict__["_picai"] = acc
+        return acc
+
     def _evaluation_loss(self, batch, metrics=None, crop=False):
         """What validation_step / test_step return (pl.py:423-524): the step loss over micro-batches
         of the training batch size, averaged. Each micro-batch's prediction also updates
         ``metrics`` (pl.py:467, 513), against the ground truth cropped to it first when ``crop``
-        (test_step, pl.py:511). (PI-CAI lists are outside the path.)"""
+        (test_step, pl.py:511), and, with ``picai_eval``, the PI-CAI accumulator with the raw
+        prediction and target (pl.py:446-452, 503-509; the test step's pairing is the reference's,
+        ``picai_test_pairs_whole_batch``)."""
         x, x_cond, x_fc, y, y_class = self.unpack_batch(batch)
+        picai = self.picai_accumulator()
         total = torch.zeros((), device=x.device, dtype=x.dtype)
         bs = x.shape[0]
         mbs = self.batch_size if self.train_batch_size is None else self.train_batch_size
+        y_cur = y        # the reference's test_step rebinds y to its cropped form (pl.py:511)
         for m in range(0, bs, mbs):
             part = slice(m, m + mbs)
             pred_final, pred_class, loss, class_loss = self.step(
@@ -192,6 +223,15 @@ class UNetBasePL(_Base):
                 x_fc[part] if x_cond is not None else None)   # sic: keyed on x_cond, pl.py:440
             total = total + (loss.mean() if class_loss is None
                              else loss.mean() + class_loss) / (bs // mbs)
+            if picai is not None:
+                if not crop:
+                    picai.update(pred_final, y[part])
+                elif self.picai_test_pairs_whole_batch:
+                    picai.update(pred_final, y_cur[:pred_final.shape[0]])    # sic: pl.py:505-506
+                else:
+                    picai.update(pred_final, y_cur[part])
+                if crop:
+                    y_cur, _ = self.crop_if_necessary(y_cur, pred_final)
             if metrics:
                 y_part = y[part]
                 if crop:
@@ -374,6 +414,20 @@ class BrUNetPL(BrUNet, UNetBasePL):
             self.log_loss("train_loss", loss, batch_size=y.shape[0])
         self._update_train_metrics(pred_final, y, pred_class, y_class)
         self.train_batch_size = y.shape[0]
+        return loss.mean() if class_loss is None else loss.mean() + class_loss
+
+    def _evaluation_loss(self, batch, metrics=None, crop=False):
+        """validation_step / test_step of pl.py:1510-1575: one step over the whole batch (no
+        micro-batching, no crop), the metrics and, with ``picai_eval``, the PI-CAI accumulator fed
+        with the raw prediction and target (pl.py:1517-1523, 1557-1563). The reference's steps
+        return nothing; the step loss is returned here, as for the other wrappers."""
+        x, x_weights, y, x_cond, x_fc, y_class = self.unpack_batch(batch)
+        picai = self.picai_accumulator()
+        pred_final, pred_class, loss, class_loss = self.step(x, x_weights, y, y_class, x_cond, x_fc)
+        if picai is not None:
+            picai.update(pred_final, y)
+        if metrics:
+            update_metrics(self, metrics, pred_final, y, pred_class, y_class)
         return loss.mean() if class_loss is None else loss.mean() + class_loss
 
 

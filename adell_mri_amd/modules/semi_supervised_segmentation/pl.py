@@ -18,6 +18,8 @@ OPTIMIZER_EPS_DEFAULT = 1e-8
 
 
 class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
+    picai_test_pairs_whole_batch = False     # its test_step zips y[m:M] (pl.py:572-577)
+
     def __init__(self, image_key: str = "image", semi_sl_image_key_1: str = "semi_sl_image_1",
                  semi_sl_image_key_2: str = "semi_sl_image_2", label_key: str = "label",
                  skip_conditioning_key: str | None = None,
@@ -152,6 +154,7 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
         y = None
         if self.label_key is not None:
             x, x_cond, x_fc, y, y_class = self.unpack_batch(batch)
+            picai = self.picai_accumulator()
             bs = x.shape[0]
             mbs = self.batch_size if self.train_batch_size is None else self.train_batch_size
             for i in range(0, bs, mbs):
@@ -162,6 +165,8 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
                     x_fc[m:M] if x_cond is not None else None)   # sic: x_cond, as pl.py:485
                 output_loss = output_loss + (
                     loss.mean() if class_loss is None else loss.mean() + class_loss) / (bs // mbs)
+                if picai is not None:
+                    picai.update(pred_final, y[m:M])                         # pl.py:491-497
                 update_metrics(self, self.val_metrics, pred_final, y[m:M], pred_class,
                                y_class[m:M] if y_class is not None else None)   # pl.py:506
         if self.semi_sl_image_key_1 is not None and self.semi_sl_image_key_2 is not None:

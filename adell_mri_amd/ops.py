@@ -1709,6 +1709,81 @@ def seg_metric_compute(state, kind, beta=1.0, num_classes=None):
     return out
 
 
+# ---- connected components and PI-CAI lesion tables (csrc/components.hip) -----------------------
+def _volumes(x, name):
+    """``x`` as a contiguous fp32 [NV, D, H, W] device tensor: a 3-D volume, or a batch of them with
+    any number of leading dimensions. Masks of other dtypes are converted (non-zero is foreground)."""
+    if x.dim() < 3:
+        raise AdellHipError(f"{name}: expected a 3-D volume or a batch of them, got shape {tuple(x.shape)} "
+                            f"(the reference's 3x3x3 structure needs 3-D input)")
+    if not x.is_cuda:
+        raise AdellHipError("adell_mri_amd kernels run on MI355X only: got a CPU tensor (no CPU fallback)")
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    D, H, W = (int(v) for v in x.shape[-3:])
+    return x.contiguous().view(-1, D, H, W)
+
+
+def label_components(x, threshold=None):
+    """``scipy.ndimage.label(x, structure=np.ones((3, 3, 3)))`` on the device: 26-connected components
+    of a 3-D volume [D, H, W] or of every volume of a batch [..., D, H, W], numbered 1..N in the raster
+    order of their first voxel, bit-identical to scipy. Foreground is ``x > threshold`` when a
+    threshold is given, else ``x != 0``. Returns (labels int32 of x's shape, counts int32 of x's
+    leading shape, 0-dim for one volume), both on the device; no host synchronisation."""
+    lead = tuple(x.shape[:-3])
+    if x.dtype != torch.float32 and x.is_cuda:
+        # foreground decided in x's own dtype (an fp32 copy could round 0.1000000001 down to the
+        # threshold or a tiny float64 value to 0); the kernel then labels the exact 0 / 1 mask
+        x = ((x > threshold) if threshold is not None else (x != 0)).to(torch.float32)
+        threshold = None
+    v = _volumes(x, "label_components")
+    NV, D, H, W = (int(s) for s in v.shape)
+    labels = torch.empty(v.shape, dtype=torch.int32, device=v.device)
+    counts = torch.empty(NV, dtype=torch.int32, device=v.device)
+    if NV == 0:
+        return labels.view(x.shape), counts.view(lead)
+    ws_bytes = int(_lib.lib().adell_cc_workspace(NV, D, H, W))
+    if ws_bytes <= 0:
+        raise AdellHipError(f"label_components: unsupported shape {tuple(x.shape)}")
+    ws = _workspace(ws_bytes, v.device)
+    check(_lib.lib().adell_cc_label(_ptr(v), NV, D, H, W, int(threshold is not None),
+                                    float(threshold if threshold is not None else 0.0), _ptr(labels),
+                                    _ptr(counts), _ptr(ws), ws_bytes, _stream()))
+    return labels.view(x.shape), counts.view(lead)
+
+
+def picai_tables(pred, target, threshold=0.1):
+    """The lesion tables of B cases (csrc/components.hip, adell_picai_tables): ``pred`` and ``target``
+    are [B, D, H, W] (any dtype; converted to fp32). Candidates are the 26-connected components of
+    ``pred > threshold`` (confidence 1, the reference's ``get_lesions``) or, with ``threshold=None``,
+    of ``pred != 0`` (confidence = the maximum of pred over the component); GT lesions those of
+    ``target.astype(int32) != 0``. The prediction is taken in fp32, as the reference's
+    ``y_det.astype("float32")`` does (eval.py:128); a target of another dtype is truncated in its own
+    dtype first (a float64 0.9999999999 is a 0, as astype(int32) makes it). Returns (hdr, out)
+    device int32 tensors without synchronising: ``hdr`` [B, 3] = (N_cand, N_gt, n_pairs), ``out``
+    the packed records (include/adell_hip.h)."""
+    if target.dtype != torch.float32 and target.is_cuda:
+        target = (torch.trunc(target) if target.is_floating_point() else target) != 0
+    p = _volumes(pred, "picai_tables")
+    t = _volumes(target, "picai_tables")
+    if p.shape != t.shape or p.device != t.device:
+        raise AdellHipError(f"picai_tables: prediction {tuple(pred.shape)} and target {tuple(target.shape)} "
+                            "must have the same shape and device")
+    B, D, H, W = (int(s) for s in p.shape)
+    lib = _lib.lib()
+    ws_bytes = int(lib.adell_picai_tables_workspace(B, D, H, W))
+    cap = int(lib.adell_picai_tables_capacity(B, D, H, W))
+    if ws_bytes <= 0 or cap <= 0:
+        raise AdellHipError(f"picai_tables: unsupported shape {tuple(pred.shape)}")
+    ws = _workspace(ws_bytes, p.device)
+    hdr = torch.empty((B, 3), dtype=torch.int32, device=p.device)
+    out = torch.empty(cap, dtype=torch.int32, device=p.device)
+    check(lib.adell_picai_tables(_ptr(p), _ptr(t), B, D, H, W, int(threshold is not None),
+                                 float(threshold if threshold is not None else 0.0), _ptr(hdr), _ptr(out),
+                                 cap, _ptr(ws), ws_bytes, _stream()))
+    return hdr, out
+
+
 # ---- shifted-window (SWIN) token path -----------------------------------------------------
 def gather_nd(x, dims, axes, out=None):
     """Flat contiguous gather of ``x`` (csrc/window.hip). ``dims``: [(size, axis, mult)] of the

@@ -296,6 +296,9 @@ def _evaluate(module, batches, step_name, loss_key, metrics_attr):
     from .metrics import bad_target_message
 
     metrics = getattr(module, metrics_attr, None) or {}
+    picai = module.picai_accumulator() if hasattr(module, "picai_accumulator") else None
+    if picai is not None:
+        picai.reset()
     was_training = module.training
     module.eval()
     try:
@@ -324,17 +327,25 @@ def _evaluate(module, batches, step_name, loss_key, metrics_attr):
                 raise RuntimeError(f"{k}: " + bad_target_message(metrics[k].num_classes))
         out = {loss_key: host[0]}
         out.update(zip(keys, host[1:1 + len(keys)]))
+        if picai is not None and len(picai):
+            # pl.py:609-652: the test epoch logs the same V_ keys (sic); mean over ranks
+            lesion = picai.compute()
+            out.update({"V_AP": lesion["AP"], "V_R": lesion["R"], "V_AUC": lesion["AUC"]})
         return out
     finally:
         for m in metrics.values():
             m.reset()
+        if picai is not None:
+            picai.reset()
         module.train(was_training)
 
 
 def validate_steps(module, batches):
     """``validation_step`` over ``batches`` in eval mode without autograd, then
     ``{"val_loss": batch-size-weighted mean of the step losses (averaged over ranks), "V_IoU": ...,
-    ...}`` from ``module.val_metrics``, which are reset. One host synchronisation, at the end."""
+    ...}`` from ``module.val_metrics``, which are reset. One host synchronisation, at the end; with
+    ``picai_eval``, also one per micro-batch (the sizes of its lesion tables), and ``"V_AP"``,
+    ``"V_R"`` and ``"V_AUC"`` of the PI-CAI evaluation (averaged over ranks)."""
     return _evaluate(module, batches, "validation_step", "val_loss", "val_metrics")
 
 

@@ -797,6 +797,31 @@ int adell_seg_confusion_update(const float* pred, const void* target, int target
 int adell_seg_metric_compute(const long long* state, int C, int kind, float beta, float* out,
                              void* stream);
 
+/* Connected components and PI-CAI lesion tables (csrc/components.hip).
+ *   adell_cc_label: labels int32 [NV][D][H][W] and component counts [NV] of fp32 volumes x
+ *     [NV][D][H][W], bit-identical to scipy.ndimage.label(x_i, np.ones((3, 3, 3))) (26-connected,
+ *     components numbered in the raster order of their first voxel); foreground is x > threshold
+ *     (use_threshold) or x != 0. Replaces the labelling of the reference's picai_eval
+ *     (picai_eval/analysis_utils.py:38, eval.py:163; reached from modules/segmentation/pl.py:609-652).
+ *     adell_cc_workspace gives the workspace bytes. No host synchronisation;
+ *   adell_picai_tables: the lesion tables of picai_eval.evaluate_case (eval.py:51-251) for B cases,
+ *     fed by the reference's all_pred / all_true lists (pl.py:446-452, 503-509): candidates are the
+ *     components of pred > threshold (get_lesions, pl.py:75-97; or pred != 0 without use_threshold,
+ *     confidence = the maximum of pred over each), GT lesions those of target.astype(int32) != 0.
+ *     hdr int32 [B][3] = (N_cand, N_gt, n_pairs); out holds one record per case, back to back:
+ *     [N_cand, N_gt, n_pairs, gt voxel counts, candidate voxel counts, candidate confidences (fp32
+ *     bits), (gt, cand, intersection) x n_pairs], the pairs (any order) being those with
+ *     10 * intersection >= union. out_capacity >= adell_picai_tables_capacity words. No host
+ *     synchronisation. */
+long adell_cc_workspace(long NV, int D, int H, int W);
+int adell_cc_label(const float* x, long NV, int D, int H, int W, int use_threshold, float threshold,
+                   int* labels, int* counts, void* workspace, long workspace_bytes, void* stream);
+long adell_picai_tables_workspace(long B, int D, int H, int W);
+long adell_picai_tables_capacity(long B, int D, int H, int W);
+int adell_picai_tables(const float* pred, const float* target, long B, int D, int H, int W,
+                       int use_threshold, float threshold, int* hdr, int* out, long out_capacity,
+                       void* workspace, long workspace_bytes, void* stream);
+
 /* ---- shifted-window (SWIN) token path: vit.py:33-45,95-129,1005-1256; linear_blocks.py:358-417 */
 /* out (contiguous over sizes[0..nd)) = gather of `in`: out dim d adds coord*mult[d] to input
  * axis axis[d]; input axis a has extent / stride (elements) / cyclic shift:
