@@ -97,6 +97,8 @@ SIGNATURES = {
     "adell_stats_finalize_workspace": (_l, [_i, _i, _i]),
     "adell_stats_finalize": (_i, [_vp, _i, _i, _i, _l, _f, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "adell_bn_running_update": (_i, [_vp] * 5 + [_i, _l, _f, _f, _vp]),
+    "adell_bn_stats_sums": (_i, [_vp, _i, _i, _i, _l, _vp, _vp, ctypes.c_size_t, _vp]),
+    "adell_bn_stats_from_sums": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "adell_channel_partials_ntiles": (_i, [_l]),
     "adell_channel_partials": (_i, [_vp, _i, _l, _i, _vp, _vp]),
     "adell_norm_act_fwd": (_i, [ctypes.POINTER(NormActDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -117,6 +119,9 @@ SIGNATURES = {
                                         + [ctypes.POINTER(AdnSite), ctypes.POINTER(AdnSite), _vp, _i, _vp]),
     "adell_norm_act_bwd_workspace": (_l, [ctypes.POINTER(NormActDesc)]),
     "adell_norm_act_bwd": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 11 + [ctypes.c_size_t, _vp]),
+    "adell_norm_act_bwd_sums": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 11 + [ctypes.c_size_t, _vp]),
+    "adell_norm_act_bwd_apply_sums": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 10
+                                      + [ctypes.c_size_t, _vp]),
     "adell_norm_act_bwd_lowrank": (_i, [ctypes.POINTER(NormActDesc), _vp, _vp, _vp, _i, _vp, _vp, _vp,
                                         _vp, ctypes.c_size_t, _vp]),
     "adell_dice_focal_workspace": (_l, [_i, _l]),

@@ -980,6 +980,59 @@ extern "C" int adell_norm_act_bwd_lowrank(const adell_norm_act_desc* d, const fl
                                  nullptr, workspace, workspace_bytes, stream, g, w, co);
 }
 
+// Which kernels run: float4 (C % 4 == 0, aligned x / dout / dx), and the bandwidth-tuned ones
+// (power-of-two C <= 1024; C < 4 when a float4 spans voxels).
+static void adell_na_bwd_route(const NormActBwdArgs& a, const adell_norm_act_desc* d, bool* vec,
+                               bool* fast) {
+  const bool aligned = ((((uintptr_t)a.x | (uintptr_t)a.dout | (uintptr_t)a.dx) & 15) == 0);
+  *vec = (d->C % 4 == 0) && aligned;
+  const bool narrow = d->C < 4 && a.VC % 4 == 0 && !a.lr_g && aligned;
+  *fast = (*vec || narrow) && adell_is_pow2(d->C) && d->C <= 1024;
+}
+
+// Pass 1 of the backward: per-slab partials (sum dt, sum dt*hn) into a.part; the bandwidth-tuned
+// kernels have their own tile count, left in a.ntiles.
+static void adell_na_bwd_partials_launch(NormActBwdArgs& a, const adell_norm_act_desc* d, bool fast,
+                                         bool vec, hipStream_t st) {
+  dim3 grid(a.ntiles, (unsigned)d->N);
+  if (fast) {
+    a.ntiles = (int)adell_na_fast_blocks(d->V, d->C);
+    if (a.lr_g) {
+      ADELL_ACT_DISPATCH_LR(adell_na_bwd_partials_fast_kernel, d->act,
+                            dim3(a.ntiles, (unsigned)d->N), st, a);
+    } else {
+      ADELL_ACT_DISPATCH(adell_na_bwd_partials_fast_kernel, d->act,
+                         dim3(a.ntiles, (unsigned)d->N), st, a);
+    }
+  } else if (vec)
+    hipLaunchKernelGGL(adell_na_bwd_partials_kernel<true>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(adell_na_bwd_partials_kernel<false>, grid, dim3(256), 0, st, a);
+}
+
+// Pass 2: dx from a.c1 / a.c2.
+static void adell_na_bwd_apply_launch(const NormActBwdArgs& a, const adell_norm_act_desc* d,
+                                      bool fast, bool vec, hipStream_t st) {
+  const long nw = vec ? a.total / 4 : a.total;
+  if (fast) {
+    long bx = ((a.VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
+    if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
+    if (bx < 1) bx = 1;
+    if (a.lr_g) {
+      ADELL_ACT_DISPATCH_LR(adell_na_bwd_apply_fast_kernel, d->act,
+                            dim3((unsigned)bx, (unsigned)d->N), st, a);
+    } else {
+      ADELL_ACT_DISPATCH(adell_na_bwd_apply_fast_kernel, d->act,
+                         dim3((unsigned)bx, (unsigned)d->N), st, a);
+    }
+  } else if (vec)
+    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<true>, dim3(adell_ew_blocks(nw)), dim3(256), 0,
+                       st, a);
+  else
+    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<false>, dim3(adell_ew_blocks(nw)), dim3(256),
+                       0, st, a);
+}
+
 static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
                                    const float* dout, const float* mean, const float* rstd,
                                    const float* gamma, const float* beta, const float* act_w,
@@ -996,11 +1049,8 @@ static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
   hipStream_t st = (hipStream_t)stream;
   a.x = x; a.dout = dout; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta;
   a.act_w = act_w; a.dx = dx;
-  const bool vec = (d->C % 4 == 0) && (((uintptr_t)x & 15) == 0) &&
-                   (((uintptr_t)dout & 15) == 0) && (((uintptr_t)dx & 15) == 0);
-  const bool narrow = d->C < 4 && a.VC % 4 == 0 && !lr_g && (((uintptr_t)x & 15) == 0) &&
-                      (((uintptr_t)dout & 15) == 0) && (((uintptr_t)dx & 15) == 0);
-  const bool fast = (vec || narrow) && adell_is_pow2(d->C) && d->C <= 1024;
+  bool vec, fast;
+  adell_na_bwd_route(a, d, &vec, &fast);
   if (mean || dgamma || dbeta) {
     ADELL_REQUIRE(workspace && (long)workspace_bytes >= adell_norm_act_bwd_workspace(d),
                   "norm_act_bwd: workspace too small");
@@ -1010,20 +1060,7 @@ static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
     float* c1 = part + (size_t)d->N * ntmax * d->C * 2;
     float* c2 = c1 + (size_t)d->N * d->C;
     a.part = part; a.c1 = c1; a.c2 = c2;
-    dim3 grid(a.ntiles, (unsigned)d->N);
-    if (fast) {
-      a.ntiles = (int)adell_na_fast_blocks(d->V, d->C);
-      if (lr_g) {
-        ADELL_ACT_DISPATCH_LR(adell_na_bwd_partials_fast_kernel, d->act,
-                              dim3(a.ntiles, (unsigned)d->N), st, a);
-      } else {
-        ADELL_ACT_DISPATCH(adell_na_bwd_partials_fast_kernel, d->act,
-                           dim3(a.ntiles, (unsigned)d->N), st, a);
-      }
-    } else if (vec)
-      hipLaunchKernelGGL(adell_na_bwd_partials_kernel<true>, grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(adell_na_bwd_partials_kernel<false>, grid, dim3(256), 0, st, a);
+    adell_na_bwd_partials_launch(a, d, fast, vec, st);
     if (d->stats_per_item && !dgamma && !dbeta && d->N <= 65535)
       hipLaunchKernelGGL(adell_na_bwd_finalize_item_kernel,
                          dim3(adell_cdiv(d->C, 8), (unsigned)d->N), dim3(256), 0, st,
@@ -1033,24 +1070,7 @@ static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
                          st, (const float*)part, (int)d->N, a.ntiles, d->C, (double)d->V,
                          d->stats_per_item, gamma, c1, c2, dgamma, dbeta);
   }
-  const long nw = vec ? a.total / 4 : a.total;
-  if (fast) {
-    long bx = ((a.VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
-    if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
-    if (bx < 1) bx = 1;
-    if (lr_g) {
-      ADELL_ACT_DISPATCH_LR(adell_na_bwd_apply_fast_kernel, d->act,
-                            dim3((unsigned)bx, (unsigned)d->N), st, a);
-    } else {
-      ADELL_ACT_DISPATCH(adell_na_bwd_apply_fast_kernel, d->act,
-                         dim3((unsigned)bx, (unsigned)d->N), st, a);
-    }
-  } else if (vec)
-    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<true>, dim3(adell_ew_blocks(nw)), dim3(256), 0,
-                       st, a);
-  else
-    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<false>, dim3(adell_ew_blocks(nw)), dim3(256),
-                       0, st, a);
+  adell_na_bwd_apply_launch(a, d, fast, vec, st);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -1509,6 +1529,243 @@ extern "C" int adell_prelu_wgrad(const adell_norm_act_desc* d, const float* x, c
                      st, a, chunk);
   hipLaunchKernelGGL(adell_prelu_wgrad_final_kernel, dim3(1), dim3(1024), 0, st,
                      (const float*)workspace, nb, d->C, d->act_w_n == 1 ? 1 : 0, dact_w);
+  ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Synchronised batch norm (torch.nn.SyncBatchNorm): the statistics and the backward reductions of
+// a batch-norm site, split where the sum over data-parallel ranks goes. A site exchanges ONE
+// record per direction: 2C + 1 doubles [sum_0 .. sum_{C-1} | sum2_0 .. sum2_{C-1} | count]
+// (forward: sum x, sum x^2; backward: sum dt, sum dt * hn). The folds are the fixed-order fp64 ones
+// of adell_stats_finalize_kernel / adell_na_bwd_finalize_kernel, so one rank's record turns into
+// exactly the statistics and c1 / c2 of the unsplit path.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void adell_bn_sums_kernel(const float* __restrict__ part, int N,
+                                                            int ntiles, int C, double count,
+                                                            double* __restrict__ rec) {
+  __shared__ double sh[8][32][2];
+  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + cl;
+  double s1 = 0.0, s2 = 0.0;
+  if (c < C) {
+    for (int n = 0; n < N; ++n) {
+      // (the loop of adell_stats_finalize_kernel: eight rows in flight, added in row order)
+      const float* p = part + ((size_t)n * ntiles * C + c) * 2;
+      int t = sl;
+      for (; t + 56 < ntiles; t += 64) {
+        float2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          v[u] = *reinterpret_cast<const float2*>(p + (size_t)(t + 8 * u) * C * 2);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          s1 += (double)v[u].x;
+          s2 += (double)v[u].y;
+        }
+      }
+      for (; t < ntiles; t += 8) {
+        const float2 v = *reinterpret_cast<const float2*>(p + (size_t)t * C * 2);
+        s1 += (double)v.x;
+        s2 += (double)v.y;
+      }
+    }
+  }
+  sh[sl][cl][0] = s1;
+  sh[sl][cl][1] = s2;
+  __syncthreads();
+  if (sl == 0 && c < C) {
+    double a = 0.0, b = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      a += sh[k][cl][0];
+      b += sh[k][cl][1];
+    }
+    rec[c] = a;
+    rec[C + c] = b;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rec[2 * C] = count * N;
+}
+
+extern "C" int adell_bn_stats_sums(const float* partials, int N, int ntiles, int C, long count,
+                                   double* sums, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  ADELL_REQUIRE(partials && sums, "bn_stats_sums: null pointer");
+  ADELL_REQUIRE(N > 0 && ntiles > 0 && C > 0 && count > 0, "bn_stats_sums: bad dims");
+  hipStream_t st = (hipStream_t)stream;
+  const long need = adell_stats_finalize_workspace(N, ntiles, C);
+  if (need > 0) {
+    ADELL_REQUIRE(workspace && (long)workspace_bytes >= need, "bn_stats_sums: workspace too small");
+    const int Z = (ntiles + 255) / 256;
+    hipLaunchKernelGGL(adell_stats_fold_kernel, dim3(adell_cdiv(C, 32), N, Z), dim3(256), 0, st,
+                       partials, ntiles, C, Z, (float*)workspace, C, 0);
+    partials = (const float*)workspace;
+    ntiles = Z;
+  }
+  hipLaunchKernelGGL(adell_bn_sums_kernel, dim3(adell_cdiv(C, 32)), dim3(256), 0, st, partials, N,
+                     ntiles, C, (double)count, sums);
+  ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+// mean / rstd (the formula of adell_stats_finalize_kernel) and, with running buffers, the update of
+// adell_bn_running_update_kernel with the record's count. One block (the counter is read by every
+// thread before thread 0 writes it back).
+__global__ __launch_bounds__(256) void adell_bn_stats_from_sums_kernel(
+    const double* __restrict__ rec, int C, float eps, float* __restrict__ mean,
+    float* __restrict__ rstd, float* __restrict__ rmean, float* __restrict__ rvar,
+    long long* __restrict__ nbt, float momentum) {
+  const double cnt = rec[2 * C];
+  long long t = nbt != nullptr ? nbt[0] + 1 : 0;
+  const float mom = momentum >= 0.f ? momentum : 1.f / (float)t;
+  const float unbias = (float)(cnt / (cnt > 1.0 ? cnt - 1.0 : 1.0));
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const double m = rec[c] / cnt;
+    double var = rec[C + c] / cnt - m * m;
+    if (var < 0.0) var = 0.0;
+    const float mf = (float)m, r = (float)(1.0 / sqrt(var + (double)eps));
+    mean[c] = mf;
+    rstd[c] = r;
+    if (rmean != nullptr) {
+      const float v = (1.f / (r * r) - eps) * unbias;
+      rmean[c] = rmean[c] * (1.f - mom) + mom * mf;
+      rvar[c] = rvar[c] * (1.f - mom) + mom * v;
+    }
+  }
+  if (threadIdx.x == 0 && rmean != nullptr && nbt != nullptr) nbt[0] = t;
+}
+
+extern "C" int adell_bn_stats_from_sums(const double* sums, int C, float eps, float* mean,
+                                        float* rstd, float* running_mean, float* running_var,
+                                        long long* num_batches_tracked, float momentum,
+                                        void* stream) {
+  ADELL_REQUIRE(sums && mean && rstd && C > 0, "bn_stats_from_sums: bad arguments");
+  ADELL_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
+                "bn_stats_from_sums: running mean / variance mismatch");
+  ADELL_REQUIRE(running_mean == nullptr || momentum >= 0.f || num_batches_tracked != nullptr,
+                "bn_stats_from_sums: the cumulative average needs num_batches_tracked");
+  hipLaunchKernelGGL(adell_bn_stats_from_sums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                     sums, C, eps, mean, rstd, running_mean, running_var,
+                     running_mean != nullptr ? num_batches_tracked : nullptr, momentum);
+  ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+// Backward record from the partials of adell_na_bwd_partials(_fast)_kernel: the batch fold of
+// adell_na_bwd_finalize_kernel (per item: tile lanes, a tree over the 32 lanes; then items in
+// order), plus the local dgamma / dbeta.
+__global__ __launch_bounds__(1024) void adell_na_bwd_sums_kernel(
+    const float* __restrict__ part, int N, int ntiles, int C, double count, double* __restrict__ rec,
+    float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  __shared__ double sh[32][32][2];
+  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + cl;
+  double accA = 0.0, accB = 0.0;
+  for (int n = 0; n < N; ++n) {
+    double s1 = 0.0, s2 = 0.0;
+    if (c < C)
+      for (int t = sl; t < ntiles; t += 32) {
+        const float2 v =
+            *reinterpret_cast<const float2*>(part + (((size_t)n * ntiles + t) * C + c) * 2);
+        s1 += (double)v.x;
+        s2 += (double)v.y;
+      }
+    sh[sl][cl][0] = s1;
+    sh[sl][cl][1] = s2;
+    __syncthreads();
+    if (sl == 0 && c < C) {
+      double A = 0.0, B = 0.0;
+#pragma unroll
+      for (int k = 0; k < 32; ++k) {
+        A += sh[k][cl][0];
+        B += sh[k][cl][1];
+      }
+      accA += A;
+      accB += B;
+    }
+    __syncthreads();
+  }
+  if (sl == 0 && c < C) {
+    rec[c] = accA;
+    rec[C + c] = accB;
+    if (dgamma) dgamma[c] = (float)accB;
+    if (dbeta) dbeta[c] = (float)accA;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rec[2 * C] = count * N;
+}
+
+// c1 = gamma sum(dt) / count, c2 = gamma sum(dt hn) / count (adell_na_bwd_finalize_kernel's formula)
+__global__ __launch_bounds__(256) void adell_na_bwd_c12_kernel(const double* __restrict__ rec, int C,
+                                                               const float* __restrict__ gamma,
+                                                               float* __restrict__ c1,
+                                                               float* __restrict__ c2) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double cnt = rec[2 * C];
+  const double g = gamma ? (double)gamma[c] : 1.0;
+  c1[c] = (float)(g * rec[c] / cnt);
+  c2[c] = (float)(g * rec[C + c] / cnt);
+}
+
+static int adell_na_sync_fill(NormActBwdArgs* a, const adell_norm_act_desc* d, const float* x,
+                              const float* dout, const float* mean, const float* rstd,
+                              const float* gamma, const float* beta, const float* act_w,
+                              const char* what) {
+  int rc = adell_nab_fill(a, d);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(x && dout && mean && rstd, "%s: null pointer", what);
+  ADELL_REQUIRE(d->stats_per_item == 0, "%s: batch statistics only (stats_per_item = 0)", what);
+  a->x = x; a->dout = dout; a->mean = mean; a->rstd = rstd; a->gamma = gamma; a->beta = beta;
+  a->act_w = act_w;
+  return ADELL_OK;
+}
+
+extern "C" int adell_norm_act_bwd_sums(const adell_norm_act_desc* d, const float* x,
+                                       const float* dout, const float* mean, const float* rstd,
+                                       const float* gamma, const float* beta, const float* act_w,
+                                       double* sums, float* dgamma, float* dbeta, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  NormActBwdArgs a = {};
+  int rc = adell_na_sync_fill(&a, d, x, dout, mean, rstd, gamma, beta, act_w, "norm_act_bwd_sums");
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(sums, "norm_act_bwd_sums: null record");
+  ADELL_REQUIRE(workspace && (long)workspace_bytes >= adell_norm_act_bwd_workspace(d),
+                "norm_act_bwd_sums: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  bool vec, fast;
+  adell_na_bwd_route(a, d, &vec, &fast);   // (a.dx is null: dx is the apply's business)
+  a.part = (float*)workspace;
+  adell_na_bwd_partials_launch(a, d, fast, vec, st);
+  hipLaunchKernelGGL(adell_na_bwd_sums_kernel, dim3(adell_cdiv(d->C, 32)), dim3(1024), 0, st,
+                     (const float*)a.part, (int)d->N, a.ntiles, d->C, (double)d->V, sums, dgamma,
+                     dbeta);
+  ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+extern "C" int adell_norm_act_bwd_apply_sums(const adell_norm_act_desc* d, const float* x,
+                                             const float* dout, const float* mean,
+                                             const float* rstd, const float* gamma,
+                                             const float* beta, const float* act_w,
+                                             const double* sums, float* dx, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  NormActBwdArgs a = {};
+  int rc = adell_na_sync_fill(&a, d, x, dout, mean, rstd, gamma, beta, act_w,
+                              "norm_act_bwd_apply_sums");
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(sums && dx, "norm_act_bwd_apply_sums: null pointer");
+  ADELL_REQUIRE(workspace && workspace_bytes >= 2 * sizeof(float) * (size_t)d->C,
+                "norm_act_bwd_apply_sums: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  a.dx = dx;
+  a.c1 = (float*)workspace;
+  a.c2 = a.c1 + d->C;
+  hipLaunchKernelGGL(adell_na_bwd_c12_kernel, dim3(adell_cdiv(d->C, 256)), dim3(256), 0, st, sums,
+                     d->C, gamma, (float*)a.c1, (float*)a.c2);
+  bool vec, fast;
+  adell_na_bwd_route(a, d, &vec, &fast);
+  adell_na_bwd_apply_launch(a, d, fast, vec, st);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }

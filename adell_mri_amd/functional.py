@@ -17,6 +17,7 @@ import weakref
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib, ops
 
@@ -988,7 +989,7 @@ conv_transpose3d_k2s2 = conv_transpose3d
 class _NormDropActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mean, rstd, gamma, beta, act_w, conf):
-        act, act_p, per_item, drop_p, seed, offset, site, split_exp = conf
+        act, act_p, per_item, drop_p, seed, offset, site, split_exp, _group = conf
         if site is not None:
             out, mask = ops.norm_act_fwd(x, mean, rstd, act, gamma=gamma, beta=beta, act_w=act_w,
                                          act_p=act_p, stats_per_item=per_item, drop_p=drop_p,
@@ -1006,7 +1007,7 @@ class _NormDropActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, mean, rstd, gamma, beta, act_w = ctx.saved_tensors
-        act, act_p, per_item, drop_p, seed, offset, site, _split_exp = ctx.conf
+        act, act_p, per_item, drop_p, seed, offset, site, _split_exp, group = ctx.conf
         if site is not None:
             fused, part, poff = site.fused, site.part, site.poff
             site.fused, site.part = False, None
@@ -1029,6 +1030,19 @@ class _NormDropActFn(torch.autograd.Function):
                                      stats_per_item=per_item, drop_p=drop_p, seed=seed,
                                      rng_offset=offset)
         want_affine = gamma is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if group is not None:
+            # synchronised batch norm: sum dt and sum dt * xhat over the ranks before dx is formed;
+            # dgamma / dbeta stay local (the gradient exchange averages them)
+            rec, dgamma, dbeta = ops.norm_act_bwd_sums(
+                x, dout, mean, rstd, act, gamma=gamma, beta=beta, act_w=act_w, act_p=act_p,
+                drop_p=drop_p, seed=seed, rng_offset=offset, want_affine_grads=want_affine)
+            dist.all_reduce(rec, op=dist.ReduceOp.SUM, group=group)
+            dx = ops.norm_act_bwd_apply_sums(x, dout, mean, rstd, rec, act, gamma=gamma, beta=beta,
+                                             act_w=act_w, act_p=act_p, drop_p=drop_p, seed=seed,
+                                             rng_offset=offset)
+            if beta is None:
+                dbeta = None
+            return dx, None, None, dgamma, dbeta, dact_w, None
         dx, dgamma, dbeta = ops.norm_act_bwd(
             x, dout, mean, rstd, act, gamma=gamma, beta=beta, act_w=act_w, act_p=act_p,
             stats_per_item=per_item, drop_p=drop_p, seed=seed, rng_offset=offset,
@@ -1040,17 +1054,21 @@ class _NormDropActFn(torch.autograd.Function):
 
 def norm_drop_act(x, *, norm="none", eps=1e-5, gamma=None, beta=None, running=None,
                   momentum=0.1, act="identity", act_p=0.0, act_w=None, drop_p=0.0,
-                  training=False, rows_reader=None):
+                  training=False, rows_reader=None, sync_group=None):
     """Fused Norm -> Dropout -> Activation.
 
     norm: "none" | "instance" | "batch". ``running`` = (running_mean, running_var,
     num_batches_tracked) buffers of a BatchNorm module (updated in training).
+    ``sync_group``: a process group of more than one rank makes a batch norm in training
+    synchronised (torch.nn.SyncBatchNorm): statistics over the items of every rank of the group,
+    and the backward's two per-channel sums too -- one all-reduce of 2C + 1 doubles each way, ordered
+    on the current stream. A group of one (or None) is the unsynchronised path.
     """
     part = getattr(x, "_adell_partials", None)
     x = ops.ndhwc(x)
     N, C = x.shape[:2]
     V = x.shape[2] * x.shape[3] * x.shape[4]
-    mean = rstd = None
+    mean = rstd = group = None
     per_item = 1
     if norm == "instance":
         if part is None:
@@ -1058,7 +1076,15 @@ def norm_drop_act(x, *, norm="none", eps=1e-5, gamma=None, beta=None, running=No
         mean, rstd = ops.stats_finalize(part, V, eps, per_item=True)
     elif norm == "batch":
         per_item = 0
-        if training or running is None or running[0] is None:
+        if (training and sync_group is not None
+                and dist.get_world_size(group=sync_group) > 1):
+            if part is None:
+                part = ops.channel_partials(x.detach())
+            rec = ops.bn_stats_sums(part, V)
+            dist.all_reduce(rec, op=dist.ReduceOp.SUM, group=sync_group)
+            mean, rstd = ops.bn_stats_from_sums(rec, eps, running, momentum)
+            group = sync_group
+        elif training or running is None or running[0] is None:
             if part is None:
                 part = ops.channel_partials(x.detach())
             mean, rstd = ops.stats_finalize(part, V, eps, per_item=False)
@@ -1093,7 +1119,7 @@ def norm_drop_act(x, *, norm="none", eps=1e-5, gamma=None, beta=None, running=No
         site = AdnSite(None, None, None, None, p, act, float(act_p))
     # (rows_reader: the conv that is the ONLY reader of the output, take_rows_reader)
     split_exp = _rows_exponent(x, rows_reader, norm, gamma, beta, act, float(act_p), act_w, p)
-    conf = (act, float(act_p), per_item, p, seed, offset, site, split_exp)
+    conf = (act, float(act_p), per_item, p, seed, offset, site, split_exp, group)
     out = _NormDropActFn.apply(x, mean, rstd, gamma, beta, act_w, conf)
     if site is not None:
         out._adell_site = site

@@ -14,6 +14,7 @@ from functools import partial
 import torch
 
 from ... import functional as HF
+from ...parallel import sync_bn_group
 from ..activations import act_spec, activation_factory
 from .regularization import LayerNormChannelsFirst, UOut
 
@@ -88,10 +89,17 @@ class ActDropNorm(torch.nn.Module):
             self._stages[-1][k] = self.name_dict[k]
             last = _RANK[k]
 
+    def _get(self, name):
+        """The module of a stage: the registered child of ``op`` -- a converter (torch's
+        ``SyncBatchNorm.convert_sync_batchnorm``, ``parallel.convert_sync_batchnorm``) replaces
+        those, not the construction-time ``op_list``."""
+        op = self._modules.get("op")
+        return op._modules[name] if op is not None else self.op_list[name]
+
     def _run_stage(self, X, stage, reader=None):
         kw = {"training": self.training}
         if "N" in stage:
-            m = self.op_list[stage["N"]]
+            m = self._get(stage["N"])
             if isinstance(m, torch.nn.modules.instancenorm._InstanceNorm):
                 if m.track_running_stats:
                     raise NotImplementedError("InstanceNorm with running stats: no HIP kernel")
@@ -100,6 +108,9 @@ class ActDropNorm(torch.nn.Module):
                 kw.update(norm="batch", eps=m.eps, gamma=m.weight, beta=m.bias,
                           momentum=m.momentum,
                           running=(m.running_mean, m.running_var, m.num_batches_tracked))
+                if isinstance(m, torch.nn.SyncBatchNorm) and self.training:
+                    # statistics over the items of every rank of the module's group
+                    kw["sync_group"] = sync_bn_group(m.process_group)
             elif isinstance(m, LayerNormChannelsFirst):
                 X = m(X)
             elif isinstance(m, torch.nn.LayerNorm):
@@ -112,7 +123,7 @@ class ActDropNorm(torch.nn.Module):
                 raise NotImplementedError(
                     f"normalisation {type(m).__name__} has no HIP kernel on the adell_mri_amd path")
         if "D" in stage:
-            m = self.op_list[stage["D"]]
+            m = self._get(stage["D"])
             if isinstance(m, torch.nn.Dropout):
                 kw["drop_p"] = m.p
             elif isinstance(m, UOut):
@@ -130,7 +141,7 @@ class ActDropNorm(torch.nn.Module):
                 raise NotImplementedError(
                     f"dropout {type(m).__name__} has no HIP kernel on the adell_mri_amd path")
         if "A" in stage:
-            name, p, w = act_spec(self.op_list[stage["A"]])
+            name, p, w = act_spec(self._get(stage["A"]))
             kw.update(act=name, act_p=p, act_w=w)
         if (kw.get("norm", "none") == "none" and kw.get("act", "identity") == "identity"
                 and not (self.training and kw.get("drop_p", 0.0) > 0.0)):
@@ -153,7 +164,7 @@ class ActDropNorm(torch.nn.Module):
         ``functional.mlp`` can carry in a GEMM epilogue -- else None."""
         name = None
         for k in self.ordering:
-            m = self.op_list[self.name_dict[k]]
+            m = self._get(self.name_dict[k])
             if k == "N" and not isinstance(m, torch.nn.Identity):
                 return None
             if k == "D" and not isinstance(m, torch.nn.Identity):
@@ -173,6 +184,27 @@ class ActDropNorm(torch.nn.Module):
         for i, stage in enumerate(self._stages):
             X = self._run_stage(X, stage, reader if i == last else None)
         return X
+
+
+def norm_forward(m, X):
+    """A normalisation module on its own (a projection head's closing norm, a bare BatchNorm) run
+    as a one-stage ADN: the HIP kernels, not the torch class's forward."""
+    adn = ActDropNorm.__new__(ActDropNorm)
+    torch.nn.Module.__init__(adn)
+    adn.training = m.training
+    adn.op_list = {"normalization": m}
+    adn._stages = [{"N": "normalization"}]
+    return adn._run_stage(X, adn._stages[0])
+
+
+class SyncBatchNorm(torch.nn.SyncBatchNorm):
+    """torch.nn.SyncBatchNorm on the HIP path (``parallel.convert_sync_batchnorm`` makes these):
+    in training, mean and variance over the items of every rank of ``process_group`` (None: the
+    dedicated batch-norm group of ``parallel.sync_bn_group``), and the backward's per-channel sums
+    too; eval and a group of one are the plain batch norm. Inputs [N, C] or [N, C, *spatial]."""
+
+    def forward(self, X):
+        return norm_forward(self, X)
 
 
 class ActDropNormBuilder:

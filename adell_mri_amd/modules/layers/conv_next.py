@@ -11,7 +11,7 @@ import torch
 from .conv import Conv2d, Conv3d, MaxPool2d, MaxPool3d
 from .regularization import LayerNorm
 from .res_blocks import ConvNeXtBlock2d, ConvNeXtBlock3d
-from .res_net import ProjectionHead, _NormLeaf
+from .res_net import HeadSequential, ProjectionHead, _NormLeaf
 
 
 def _stage(block, width_in: int, width: int, inner: int, kernel: int, n_blocks: int):
@@ -110,7 +110,7 @@ class ConvNeXt(torch.nn.Module):
             norm_fn = head_args["adn_fn"](width).norm_fn
         except Exception:  # noqa: BLE001
             norm_fn = torch.nn.LayerNorm
-        return torch.nn.Sequential(ProjectionHead(**head_args), _NormLeaf(norm_fn, width))
+        return HeadSequential(ProjectionHead(**head_args), _NormLeaf(norm_fn, width))
 
     def forward_representation(self, X, *args, **kwargs):
         return self.backbone(X, *args, **kwargs)

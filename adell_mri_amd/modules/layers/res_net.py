@@ -144,8 +144,8 @@ class ResNet(torch.nn.Module):
             norm_fn = head_args.pop("last_layer_norm", None)
             if norm_fn is None:
                 norm_fn = getattr(head_args["adn_fn"](width), "norm_fn", LayerNorm)
-            self.projection_head = torch.nn.Sequential(ProjectionHead(**head_args),
-                                                       _NormLeaf(norm_fn, width))
+            self.projection_head = HeadSequential(ProjectionHead(**head_args),
+                                                  _NormLeaf(norm_fn, width))
         if prediction_head_args is not None:
             self.prediction_head = ProjectionHead(**prediction_head_args)
 
@@ -170,10 +170,23 @@ class ResNet(torch.nn.Module):
         return out
 
 
+class HeadSequential(torch.nn.Sequential):
+    """torch.nn.Sequential (same state_dict keys) that keeps a closing norm on the HIP path after
+    torch's ``SyncBatchNorm.convert_sync_batchnorm`` (what Lightning's ``sync_batchnorm=True``
+    runs) has swapped it for a plain ``torch.nn.SyncBatchNorm``."""
+
+    def forward(self, X):
+        from .adn_fn import norm_forward
+
+        for m in self:
+            X = norm_forward(m, X) if isinstance(m, torch.nn.SyncBatchNorm) else m(X)
+        return X
+
+
 def _NormLeaf(norm_fn, d):
     """The normalisation closing a projection head, as a HIP leaf with the state_dict
     layout of the torch class it stands for."""
-    from .adn_fn import ActDropNorm
+    from .adn_fn import norm_forward
 
     if norm_fn in (torch.nn.LayerNorm, LayerNorm):
         return LayerNorm(d)
@@ -182,11 +195,6 @@ def _NormLeaf(norm_fn, d):
 
     class _Norm(norm_fn):  # BatchNorm1d / InstanceNorm1d...: parameters of the torch class
         def forward(self, X):
-            adn = ActDropNorm.__new__(ActDropNorm)
-            torch.nn.Module.__init__(adn)
-            adn.training = self.training
-            adn.op_list = {"normalization": self}
-            adn._stages = [{"N": "normalization"}]
-            return adn._run_stage(X, adn._stages[0])
+            return norm_forward(self, X)
 
     return _Norm(d)

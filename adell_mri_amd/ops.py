@@ -971,6 +971,97 @@ def stats_finalize(partials, count, eps, per_item=True):
     return mean, rstd
 
 
+# ---- synchronised batch norm: a site's reductions split around one all-reduce per direction ----
+def _record(C, device):
+    """The 2C + 1 fp64 record a synchronised batch-norm site all-reduces (csrc/norm_act.hip)."""
+    return torch.empty((2 * C + 1,), device=device, dtype=torch.float64)
+
+
+def _record_check(rec, C):
+    if not rec.is_cuda or rec.dtype != torch.float64 or rec.numel() != 2 * C + 1 or not rec.is_contiguous():
+        raise _lib.AdellHipError(f"a batch-norm record is a dense fp64 device tensor of 2C + 1 = "
+                                 f"{2 * C + 1} values; got {rec.dtype} {tuple(rec.shape)}")
+
+
+def bn_stats_sums(partials, count):
+    """The forward record [sum x (C) | sum x^2 (C) | count] of a batch-norm site from partials
+    [N, ntiles, C, 2] (channel_partials or a conv epilogue's), ``count`` elements per item: what
+    the ranks of a synchronised batch norm sum. Same fold as stats_finalize(per_item=False)."""
+    _require_cuda(partials)
+    N, nt, C, _ = partials.shape
+    rec = _record(C, partials.device)
+    nbytes = _lib.lib().adell_stats_finalize_workspace(N, nt, C)
+    ws = _workspace(nbytes, partials.device) if nbytes > 0 else None
+    check(_lib.lib().adell_bn_stats_sums(_ptr(partials), N, nt, C, int(count), _ptr(rec), _ptr(ws),
+                                         0 if ws is None else ws.numel() * 4, _stream()))
+    return rec
+
+
+def bn_stats_from_sums(rec, eps, running=None, momentum=0.1):
+    """(mean, rstd) [C] of a (reduced) forward record, stats_finalize's formula; with ``running`` =
+    (running_mean, running_var, num_batches_tracked) also bn_running_update with the record's
+    count, in the same launch."""
+    C = (rec.numel() - 1) // 2
+    _record_check(rec, C)
+    mean = torch.empty((C,), device=rec.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    rm = rv = nbt = None
+    if running is not None and running[0] is not None:
+        rm, rv, nbt = running
+        _require_cuda(rm, rv)
+        if nbt is not None and (not nbt.is_cuda or nbt.dtype != torch.int64):
+            raise _lib.AdellHipError("num_batches_tracked must be an int64 device tensor")
+        if nbt is None and momentum is None:
+            raise ValueError("BatchNorm with momentum=None needs num_batches_tracked")
+    check(_lib.lib().adell_bn_stats_from_sums(
+        _ptr(rec), C, float(eps), _ptr(mean), _ptr(rstd), _ptr(rm), _ptr(rv),
+        None if nbt is None else ctypes.c_void_p(nbt.data_ptr()),
+        -1.0 if momentum is None else float(momentum), _stream()))
+    return mean, rstd
+
+
+def norm_act_bwd_sums(x, dout, mean, rstd, act, gamma=None, beta=None, act_w=None, act_p=0.0,
+                      drop_p=0.0, seed=0, rng_offset=0, want_affine_grads=False):
+    """First half of norm_act_bwd at a batch-norm site: the record [sum dt (C) | sum dt * xhat (C) |
+    count] the ranks sum, and the local (dgamma, dbeta) when want_affine_grads."""
+    _require_cuda(x, dout, mean, rstd, gamma, beta, act_w)
+    x, dout = ndhwc(x), ndhwc(dout)
+    C = x.shape[1]
+    d = make_na_desc(x, act, 0, act_p, 0 if act_w is None else act_w.numel(), drop_p, seed,
+                     rng_offset)
+    rec = _record(C, x.device)
+    dgamma = dbeta = None
+    if want_affine_grads:
+        dgamma = torch.empty((C,), device=x.device, dtype=torch.float32)
+        dbeta = torch.empty_like(dgamma)
+    ws = _workspace(_lib.lib().adell_norm_act_bwd_workspace(ctypes.byref(d)), x.device)
+    # algorithmic bytes: read x and dout once
+    check(_timed(NORM_ACT_FAMILY, 0.0, lambda: _lib.lib().adell_norm_act_bwd_sums(
+        ctypes.byref(d), _ptr(x), _ptr(dout), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+        _ptr(act_w), _ptr(rec), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel() * 4, _stream()),
+        "bwd_sums", 8.0 * x.numel()))
+    return rec, dgamma, dbeta
+
+
+def norm_act_bwd_apply_sums(x, dout, mean, rstd, rec, act, gamma=None, beta=None, act_w=None,
+                            act_p=0.0, drop_p=0.0, seed=0, rng_offset=0):
+    """Second half: dx of a batch-norm site from a (reduced) backward record."""
+    _require_cuda(x, dout, mean, rstd, gamma, beta, act_w)
+    x, dout = ndhwc(x), ndhwc(dout)
+    C = x.shape[1]
+    _record_check(rec, C)
+    d = make_na_desc(x, act, 0, act_p, 0 if act_w is None else act_w.numel(), drop_p, seed,
+                     rng_offset)
+    dx = new_act(*x.shape, x.device)
+    ws = _workspace(8 * C, x.device)
+    # algorithmic bytes: read x and dout once, write dx once
+    check(_timed(NORM_ACT_FAMILY, 0.0, lambda: _lib.lib().adell_norm_act_bwd_apply_sums(
+        ctypes.byref(d), _ptr(x), _ptr(dout), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+        _ptr(act_w), _ptr(rec), _ptr(dx), _ptr(ws), ws.numel() * 4, _stream()),
+        "bwd_apply", 12.0 * x.numel()))
+    return dx
+
+
 def channel_partials(x):
     _require_cuda(x)
     x = ndhwc(x)

@@ -432,3 +432,74 @@ def reduce_max(value, device):
     t = torch.tensor([float(value)], device=device, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+# ---- synchronised batch norm (Lightning's Trainer(sync_batchnorm=True)) ---------------------------
+_SYNC_BN = {}     # default process group -> the dedicated batch-norm group spanning its world
+
+
+def sync_bn_group(process_group=None):
+    """The group a synchronised batch norm all-reduces on, or None when it has nothing to exchange
+    (no process group, or a group of one). ``process_group`` None means a group of its own spanning
+    the world, NOT the default group: GradSync's bucket all-reduces go out asynchronously on the
+    default group while backward runs, and a batch-norm collective must never interleave with them.
+    ``dist.new_group`` is collective, so every rank creates it at the same point, once:
+    ``convert_sync_batchnorm`` and ``StepRunner`` do (the first synchronised forward would
+    otherwise, on every rank alike)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    if process_group is not None:
+        return process_group if dist.get_world_size(group=process_group) > 1 else None
+    world = dist.group.WORLD
+    if dist.get_world_size() == 1:
+        return None
+    g = _SYNC_BN.get(world)
+    if g is None:
+        g = _SYNC_BN[world] = dist.new_group(list(range(dist.get_world_size())))
+    return g
+
+
+def _has_sync_bn(module):
+    return any(isinstance(m, torch.nn.SyncBatchNorm) for m in module.modules())
+
+
+def sync_bn_communicates(module):
+    """Whether a training step of ``module`` runs batch-norm collectives (a SyncBatchNorm whose
+    group has more than one rank)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return False
+    return any(isinstance(m, torch.nn.SyncBatchNorm) and dist.get_world_size(group=m.process_group) > 1
+               for m in module.modules())
+
+
+def convert_sync_batchnorm(module, process_group=None):
+    """Counterpart of ``torch.nn.SyncBatchNorm.convert_sync_batchnorm``: every ``_BatchNorm`` of
+    ``module`` (ADN-held ones, the closing norm of a projection head, bare ``BatchNorm{1,2,3}d``;
+    a ``torch.nn.SyncBatchNorm`` keeps its group) becomes a ``torch.nn.SyncBatchNorm`` that runs the
+    HIP kernels (``modules.layers.adn_fn.SyncBatchNorm``). The Parameter and buffer OBJECTS are kept
+    (a fused optimiser built before holds views of them), so are the state_dict keys and the
+    train / eval mode. Returns the converted module (``module`` itself unless it is a batch norm)."""
+    from .modules.layers.adn_fn import SyncBatchNorm
+
+    if process_group is None:
+        sync_bn_group()          # collective: every rank creates the dedicated group here
+
+    def convert(m):
+        out = m
+        if (isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+                and not isinstance(m, SyncBatchNorm)):
+            pg = process_group
+            if pg is None and isinstance(m, torch.nn.SyncBatchNorm):
+                pg = m.process_group
+            out = SyncBatchNorm(m.num_features, m.eps, m.momentum, m.affine, m.track_running_stats,
+                                pg)
+            if m.affine:
+                out.weight, out.bias = m.weight, m.bias
+            out.running_mean, out.running_var = m.running_mean, m.running_var
+            out.num_batches_tracked = m.num_batches_tracked
+            out.training = m.training
+        for name, child in m.named_children():
+            out.add_module(name, convert(child))
+        return out
+
+    return convert(module)

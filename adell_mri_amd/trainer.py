@@ -8,7 +8,8 @@ ssl/train_3d.py:354-355); ``validate_steps`` / ``test_steps`` are the part of
 import itertools
 import os
 
-from .parallel import GradSync
+from .parallel import (GradSync, _has_sync_bn, convert_sync_batchnorm, sync_bn_communicates,
+                       sync_bn_group)
 
 # ADELL_GRAD_COLLECT=0: keep p.grad as views of the flat buffer (autograd accumulates into them)
 _SET_TO_NONE = os.environ.get("ADELL_GRAD_COLLECT", "1") != "0"
@@ -34,13 +35,18 @@ class StepRunner:
       backward without exchanging anything (``GradSync.no_sync``) and fold their gradients into
       the flat buffers; the N-th runs backward, the exchange, clipping and the step with 1/N folded
       into the optimiser's ``grad_scale`` (Lightning divides the loss instead: same update).
-      ``flush()`` steps a partial window (end of an epoch) with the same 1/N.
+      ``flush()`` steps a partial window (end of an epoch) with the same 1/N;
+    * ``sync_batchnorm``: ``parallel.convert_sync_batchnorm(module)`` before the parameters are
+      broadcast -- batch statistics over the items of all ranks (one all-reduce per batch-norm site
+      and direction, on a process group of their own). A no-op in effect at world size 1. A module
+      that already holds ``torch.nn.SyncBatchNorm`` modules (torch's converter) is synchronised either
+      way; its batch-norm group is created here.
 
     ``step_idx`` counts micro-batches (the ``batch_idx`` of ``training_step``), ``optimizer_steps``
     the optimiser steps, ``last_grad_norm`` is the device tensor of the last clip."""
 
     def __init__(self, module, optimizer=None, sync=None, gradient_clip_val=None,
-                 gradient_clip_algorithm="norm", accumulate_grad_batches=1):
+                 gradient_clip_algorithm="norm", accumulate_grad_batches=1, sync_batchnorm=False):
         if gradient_clip_val is not None and float(gradient_clip_val) < 0:
             raise ValueError(f"gradient_clip_val should be >= 0, got {gradient_clip_val}")
         if gradient_clip_algorithm == "value":
@@ -51,8 +57,19 @@ class StepRunner:
         if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
             raise ValueError(f"accumulate_grad_batches should be an integer >= 1, got "
                              f"{accumulate_grad_batches}")
+        if not isinstance(sync_batchnorm, bool):
+            raise TypeError(f"sync_batchnorm must be a bool, got {sync_batchnorm!r}")
         self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
         self.accumulate_grad_batches = int(accumulate_grad_batches)
+        if sync_batchnorm:
+            # (in place below the root: every batch norm of these modules is a child of something)
+            converted = convert_sync_batchnorm(module)
+            if converted is not module:
+                raise TypeError("StepRunner(sync_batchnorm=True): the module itself is a batch norm; "
+                                "convert it with parallel.convert_sync_batchnorm and pass the result")
+        elif _has_sync_bn(module):
+            sync_bn_group()      # collective: the dedicated batch-norm group, on every rank here
+        self.sync_batchnorm = sync_batchnorm
         self.module = module
         if optimizer is None:
             optimizer = module.configure_optimizers()["optimizer"]
@@ -138,6 +155,10 @@ class StepRunner:
         if self.sync.overlap:
             raise RuntimeError("StepRunner.enable_graph: gradient buckets are sent from backward hooks "
                                "(GradSync(overlap=True)); build GradSync(optimizer, overlap=False)")
+        if sync_bn_communicates(self.module):
+            raise RuntimeError("StepRunner.enable_graph: synchronised batch norm all-reduces its "
+                               "statistics inside the step (world size > 1); collectives are not "
+                               "captured in a HIP graph -- run eager steps")
         if getattr(self.module, "ema", None) is not None:
             raise RuntimeError("StepRunner.enable_graph: the module's EMA update takes its decay from a "
                                "host-side schedule inside training_step; a replay would freeze it")
@@ -258,9 +279,11 @@ class StepRunner:
         return self._graph_loss
 
 
-def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulate_grad_batches=1):
+def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulate_grad_batches=1,
+              sync_batchnorm=False):
     runner = StepRunner(module, optimizer, gradient_clip_val=gradient_clip_val,
-                        accumulate_grad_batches=accumulate_grad_batches)
+                        accumulate_grad_batches=accumulate_grad_batches,
+                        sync_batchnorm=sync_batchnorm)
     module.train()
     losses = [runner.train_step(b).detach() for b in batches]
     runner.flush()

@@ -330,6 +330,20 @@ int adell_stats_finalize(const float* partials, int N, int ntiles, int C,
 int adell_bn_running_update(const float* mean, const float* rstd, float* running_mean,
                             float* running_var, long long* num_batches_tracked, int C, long count,
                             float eps, float momentum, void* stream);
+/* Synchronised batch norm (torch.nn.SyncBatchNorm): the statistics split where the sum over
+ * data-parallel ranks goes. A site's record is 2C + 1 doubles [sum_c (C) | sum2_c (C) | count]:
+ * one all-reduce (SUM) per site and direction between the two halves.
+ * adell_bn_stats_sums: the record (sum x, sum x^2 over all N items, count = N * count) of partials
+ *   [N][ntiles][C][2] (conv epilogue or adell_channel_partials), in the fixed-order fp64 fold of
+ *   adell_stats_finalize; workspace as adell_stats_finalize_workspace.
+ * adell_bn_stats_from_sums: mean / rstd [C] from a (reduced) record with adell_stats_finalize's
+ *   formula; with running buffers (may be NULL) also adell_bn_running_update with the record's
+ *   count. One launch. */
+int adell_bn_stats_sums(const float* partials, int N, int ntiles, int C, long count, double* sums,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int adell_bn_stats_from_sums(const double* sums, int C, float eps, float* mean, float* rstd,
+                             float* running_mean, float* running_var,
+                             long long* num_batches_tracked, float momentum, void* stream);
 /* Partials of an arbitrary tensor x [N][V][C] (same buffer format). */
 int adell_channel_partials_ntiles(long V);
 int adell_channel_partials(const float* x, int N, long V, int C, float* partials,
@@ -403,6 +417,20 @@ int adell_norm_act_bwd(const adell_norm_act_desc* d, const float* x, const float
                        const float* beta, const float* act_w, float* dx, float* dgamma,
                        float* dbeta, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* adell_norm_act_bwd of a synchronised batch-norm site (stats_per_item = 0), in two halves around
+ * the all-reduce of a 2C + 1 double record [sum dt (C) | sum dt * xhat (C) | count]:
+ * adell_norm_act_bwd_sums: the partials kernels of adell_norm_act_bwd, folded into the record;
+ *   the local dgamma / dbeta (may be NULL). Workspace: adell_norm_act_bwd_workspace(d) bytes.
+ * adell_norm_act_bwd_apply_sums: c1 / c2 from a (reduced) record, then dx with the apply kernels
+ *   of adell_norm_act_bwd. Workspace: 2 C floats. */
+int adell_norm_act_bwd_sums(const adell_norm_act_desc* d, const float* x, const float* dout,
+                            const float* mean, const float* rstd, const float* gamma,
+                            const float* beta, const float* act_w, double* sums, float* dgamma,
+                            float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+int adell_norm_act_bwd_apply_sums(const adell_norm_act_desc* d, const float* x, const float* dout,
+                                  const float* mean, const float* rstd, const float* gamma,
+                                  const float* beta, const float* act_w, const double* sums,
+                                  float* dx, void* workspace, size_t workspace_bytes, void* stream);
 /* adell_norm_act_bwd with a LOW-RANK upstream gradient dout[v][c] = sum_o g[v][o] * w[o][c]
  * (g: [N][V][co] channels-last, w: [co][C], 1 <= co <= 4): the site in front of a 1x1x1 conv with
  * few output channels -- the logits head Conv3d -> ADN -> Conv3d(C -> n_classes, k = 1) of
