@@ -75,6 +75,7 @@ SIGNATURES = {
     "adell_conv3d_bwd_data_s2_fused_applicable": (_i, [ctypes.POINTER(ConvDesc)]),
     "adell_conv3d_bwd_data_s2_fused": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 7),
     "adell_conv3d_splitk_workspace": (_l, [ctypes.POINTER(ConvDesc), _i]),
+    "adell_conv3d_f16x3_plan": (_i, [ctypes.POINTER(ConvDesc), _i, _vp]),
     "adell_conv3d_fwd_f16x3_ws": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 8 + [_i, _vp, _vp,
                                                                          ctypes.c_size_t, _vp]),
     "adell_conv3d_bwd_data_f16x3_ws": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 7 + [ctypes.c_size_t, _vp]),
@@ -204,6 +205,7 @@ SIGNATURES = {
     "adell_prelu_wgrad": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 8 + [ctypes.c_size_t, _vp]),
     "adell_convtranspose3d_fwd_f16x3": (_i, [_i] * 9 + [_vp] * 7),
     "adell_convtranspose3d_bwd_data_f16x3": (_i, [_i] * 9 + [_vp] * 6),
+    "adell_convtranspose3d_f16x3_plan": (_i, [_i] * 9 + [_vp]),
     "adell_conv1_small_applicable": (_i, [ctypes.POINTER(ConvDesc)]),
     "adell_conv1_small_fwd": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 6),
     "adell_conv1_small_bwd_data": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 5),

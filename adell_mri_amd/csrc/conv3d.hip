@@ -439,7 +439,11 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
     }
   }
   size_t lds = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
+  // (when the halo + weight slice does not fit: 256 x 64 bricks step down to 64 x 64, 256 x 32 to
+  // 128 x 32, and those to the two-wave 64 x 32 brick, the smallest. A 7^3 stride-2 layer with 64
+  // outputs takes 64 x 64 -> 64 x 32, or 256 x 64 -> 64 x 64 -> 64 x 32 from 65 536 output voxels x
+  // 64-column tiles on)
+  for (int attempt = 0; attempt < 3; ++attempt) {
     a.lTX = t.lTX; a.lTY = t.lTY; a.lTZ = t.lTZ;
     const int TX = 1 << t.lTX, TY = 1 << t.lTY, TZ = 1 << t.lTZ;
     a.ntx = adell_cdiv(a.Wo, TX);
@@ -455,7 +459,7 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
     const size_t red = (size_t)8 * t.BN * 2 * sizeof(float);
     if (lds < red) lds = red;
     if (lds <= 160 * 1024) break;
-    const int next = t.BN == 64 ? 2 : (t.cfg == 3 ? 6 : 3);
+    const int next = t.cfg == 0 ? 2 : t.cfg == 1 ? 3 : 6;
     if (t.cfg == next || g_conv_force_cfg >= 0) break;
     t = adell_pick_tile(N, a.Do, a.Ho, a.Wo, a.Cout, next);
   }
@@ -829,6 +833,31 @@ extern "C" long adell_conv3d_splitk_workspace(const adell_conv3d_desc* d, int ba
   return (long)sizeof(float) * shares * d->N * a.Do * a.Ho * a.Wo * a.Cout;
 }
 
+// out[8] of the plan queries below: {cfg, BM, BN, lTX, lTY, lTZ, K shares, LDS bytes}
+static void adell_plan_report(const ConvTile& t, int shares, size_t lds, int* out) {
+  out[0] = t.cfg; out[1] = t.BM; out[2] = t.BN;
+  out[3] = t.lTX; out[4] = t.lTY; out[5] = t.lTZ;
+  out[6] = shares; out[7] = (int)lds;
+}
+
+// Launch plan of adell_conv3d_fwd_f16x3_ws (backward_data = 0) / adell_conv3d_bwd_data_f16x3_ws (1)
+// called with the workspace adell_conv3d_splitk_workspace asks for. Host only: launches nothing and
+// reads no pointer.
+extern "C" int adell_conv3d_f16x3_plan(const adell_conv3d_desc* d, int backward_data, int* out) {
+  ADELL_REQUIRE(d && out, "conv3d_f16x3_plan: null pointer");
+  ConvArgs a;
+  float dummy;
+  int rc = backward_data ? adell_fill_bwd_data(a, d, &dummy, &dummy, d->C1 > 0 ? &dummy : nullptr)
+                         : adell_fill_fwd(a, d, &dummy, d->C1 > 0 ? &dummy : nullptr, nullptr,
+                                          nullptr, &dummy, nullptr);
+  if (rc != ADELL_OK) return rc;
+  ConvTile t;
+  size_t lds;
+  if (adell_plan_f16(a, d->N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
+  adell_plan_report(t, adell_splitk_shares(a, t, d->N), lds, out);
+  return ADELL_OK;
+}
+
 extern "C" int adell_conv3d_fwd_f16x3_ws(const adell_conv3d_desc* d, const float* x0,
                                          const float* x1, const void* w_split,
                                          const float* wscale, const float* bias,
@@ -1005,16 +1034,11 @@ extern "C" int adell_conv3d_bwd_data_s2_f16x3_add(const adell_conv3d_desc* d, co
 // VIRTUAL 1x1x1 conv weight V[(f, co)][ci] = w[ci][co][f] packed with mode 0 (wscale has
 // F*Cout entries); backward-data: the torch weight [Cin][Cout][taps] read as a conv weight with
 // Cin outputs and Cout inputs, packed with mode 0 as well.
-extern "C" int adell_convtranspose3d_fwd_f16x3(int N, int D, int H, int W, int Cin, int Cout,
-                                               int FD, int FH, int FW, const float* x,
-                                               const void* w_split, const float* wscale,
-                                               const float* bias, float* y, uint32_t* in_absmax,
-                                               void* stream) {
+static int adell_fill_convt_fwd(ConvArgs& a, int N, int D, int H, int W, int Cin, int Cout, int FD,
+                                int FH, int FW) {
   ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "convT_fwd: bad dims");
   ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_fwd: kernel=stride must be 1 or 2 per dim");
-  ADELL_REQUIRE(x && w_split && wscale && y, "convT_fwd_f16x3: null pointer");
-  ConvArgs a = {};
-  a.x0 = x; a.bias = bias; a.y0 = y;
+  a = ConvArgs{};
   a.D = D; a.H = H; a.W = W;
   a.C0 = Cin; a.C1 = 0; a.Cin = Cin; a.Cout = FD * FH * FW * Cout;
   a.KD = a.KH = a.KW = 1;
@@ -1023,8 +1047,36 @@ extern "C" int adell_convtranspose3d_fwd_f16x3(int N, int D, int H, int W, int C
   a.Do = D; a.Ho = H; a.Wo = W;
   a.ysplit = a.Cout; a.Cs = Cout;
   a.shuffle = 8 | (FW - 1) | ((FH - 1) << 1) | ((FD - 1) << 2);
+  return ADELL_OK;
+}
+
+extern "C" int adell_convtranspose3d_fwd_f16x3(int N, int D, int H, int W, int Cin, int Cout,
+                                               int FD, int FH, int FW, const float* x,
+                                               const void* w_split, const float* wscale,
+                                               const float* bias, float* y, uint32_t* in_absmax,
+                                               void* stream) {
+  ConvArgs a;
+  int rc = adell_fill_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(x && w_split && wscale && y, "convT_fwd_f16x3: null pointer");
+  a.x0 = x; a.bias = bias; a.y0 = y;
   ConvF16Extra e = {(const _Float16*)w_split, wscale, in_absmax, nullptr, nullptr, nullptr};
   return adell_conv_dispatch_f16(a, e, N, (hipStream_t)stream);
+}
+
+// Launch plan of adell_convtranspose3d_fwd_f16x3 (out[8] as adell_conv3d_f16x3_plan; host only).
+// Its backward-data is the kernel = stride conv of adell_conv3d_f16x3_plan.
+extern "C" int adell_convtranspose3d_f16x3_plan(int N, int D, int H, int W, int Cin, int Cout,
+                                                int FD, int FH, int FW, int* out) {
+  ADELL_REQUIRE(out, "convtranspose3d_f16x3_plan: null pointer");
+  ConvArgs a;
+  int rc = adell_fill_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc != ADELL_OK) return rc;
+  ConvTile t;
+  size_t lds;
+  if (adell_plan_f16(a, N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
+  adell_plan_report(t, adell_splitk_shares(a, t, N), lds, out);
+  return ADELL_OK;
 }
 
 extern "C" int adell_convtranspose3d_bwd_data_f16x3(int N, int D, int H, int W, int Cin, int Cout,

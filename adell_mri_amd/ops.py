@@ -5,6 +5,7 @@ memory is dense NDHWC (``torch.channels_last_3d``); ``ndhwc()`` / ``new_act()``
 are the only places that care about strides. Everything is enqueued on
 ``torch.cuda.current_stream()``; PyTorch only provides memory and streams.
 """
+import collections
 import ctypes
 import math
 import os
@@ -303,6 +304,34 @@ def _splitk_workspace(d, backward, device):
     if nbytes <= 0:
         return None, 0
     return _workspace(nbytes, device), nbytes
+
+
+# launch plan of an f16x3 conv (adell_conv3d_f16x3_plan): config (8 = the 16-channel z-ring kernel),
+# brick voxels, columns per tile, log2 brick extents, K shares (1 = no split-K), LDS bytes
+ConvPlan = collections.namedtuple("ConvPlan", "cfg BM BN lTX lTY lTZ shares lds")
+
+
+def conv3d_plan(N, in_size, C0, C1, Cout, kernel, stride, padding, backward_data=False):
+    """The launch plan conv3d_fwd (or conv3d_bwd_data) would run on the f16x3 kernel; None when
+    that kernel refuses the problem. Host only: no GPU needed."""
+    d = make_conv_desc(N, tuple(in_size), C0, C1, Cout, kernel, stride, padding)
+    out = (ctypes.c_int * 8)()
+    rc = _lib.lib().adell_conv3d_f16x3_plan(ctypes.byref(d), int(bool(backward_data)), out)
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    check(rc)
+    return ConvPlan(*out)
+
+
+def convtranspose3d_plan(N, in_size, Cin, Cout, factors=(2, 2, 2)):
+    """The same for convtranspose3d_fwd on the f16x3 kernel (its backward-data is the
+    kernel = stride conv3d_plan)."""
+    out = (ctypes.c_int * 8)()
+    rc = _lib.lib().adell_convtranspose3d_f16x3_plan(N, *in_size, Cin, Cout, *factors, out)
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    check(rc)
+    return ConvPlan(*out)
 
 
 def conv3d_fwd(x0, w_packed, bias, Cout, kernel, stride, padding, x1=None, residual=None,

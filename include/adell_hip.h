@@ -191,6 +191,12 @@ int adell_conv3d_bwd_data_s2_fused(const adell_conv3d_desc* d, const float* dy,
  * outputs in fixed order -- bit-reproducible, bias / residual / statistics as in the plain call.
  * Without a workspace (or with one that is too small) they behave like the plain calls. */
 long adell_conv3d_splitk_workspace(const adell_conv3d_desc* d, int backward_data);
+/* Launch plan of the two _ws calls below (forward: backward_data = 0; backward-data: 1) given the
+ * workspace adell_conv3d_splitk_workspace asks for: out[8] = {config (8: the 16-channel z-ring
+ * kernel), brick voxels, columns per tile, log2 of the brick's x / y / z extents, K shares (1 = no
+ * split), LDS bytes}. ADELL_E_UNSUPPORTED when the f16x3 kernel cannot take the problem. Host
+ * only: launches nothing, reads no tensor, needs no GPU. */
+int adell_conv3d_f16x3_plan(const adell_conv3d_desc* d, int backward_data, int* out);
 int adell_conv3d_fwd_f16x3_ws(const adell_conv3d_desc* d, const float* x0, const float* x1,
                               const void* w_split, const float* wscale, const float* bias,
                               const float* residual, float* y, float* stat_partials,
@@ -290,6 +296,10 @@ int adell_convtranspose3d_bwd_data_f16x3(int N, int D, int H, int W, int Cin, in
                                          int FH, int FW, const float* dy, const void* w_split_bwd,
                                          const float* wscale, float* dx, uint32_t* dy_absmax,
                                          void* stream);
+/* Launch plan of adell_convtranspose3d_fwd_f16x3 (out[8] as adell_conv3d_f16x3_plan, host only).
+ * Its backward-data is the kernel = stride convolution that adell_conv3d_f16x3_plan describes. */
+int adell_convtranspose3d_f16x3_plan(int N, int D, int H, int W, int Cin, int Cout, int FD, int FH,
+                                     int FW, int* out);
 long adell_convtranspose3d_bwd_weight_workspace(int N, int D, int H, int W, int Cin, int Cout,
                                                 int FD, int FH, int FW);
 int adell_convtranspose3d_bwd_weight(int N, int D, int H, int W, int Cin, int Cout, int FD,
