@@ -239,6 +239,7 @@ SIGNATURES = {
     "adell_dw_mfma_ok": (_i, [_i] * 8 + [_vp, _vp]),
     "adell_dw_dense_ok": (_i, [_i] * 8 + [_vp, _vp]),
     "adell_dw_wgrad_mfma_ok": (_i, [_i] * 8 + [_vp, _vp]),
+    "adell_dwconv3d_plan": (_i, [_i] * 11 + [_vp]),
     "adell_wgrad_zring_plan": (_i, [_i] * 16 + [_vp]),
     "adell_rowscale_fwd": (_i, [_vp] * 5 + [_i, _i, _vp]),
     "adell_rowscale_bwd": (_i, [_vp] * 8 + [_i, _i, _vp]),

@@ -106,6 +106,23 @@ static int adell_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const
 // It sizes persistent grids, and with them the *_ntiles / workspace plans callers allocate against.
 int adell_cu_count();
 
+// Launch plan of a depthwise convolution (adell_dwconv3d_plan, include/adell_hip.h: the ADELL_DW_*
+// forms and the out[] layout). Each form's own translation unit decides whether it takes a problem and
+// fills its geometry (the *_plan functions below; xa / ya: the launch's two tensors are 16-byte
+// aligned); the launchers and the query both walk them in adell_dw_plan_fwd / adell_dw_plan_wgrad
+// (csrc/ssl.hip), so a condition is written once.
+struct AdellDwPlan {
+  int form, K, WT, nseg, seg, vec;
+  long blocks, loop, parts, workspace;
+};
+int adell_dw_dense_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa, int ya,
+                        AdellDwPlan* p);
+int adell_dw_mfma_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa, int ya,
+                       AdellDwPlan* p);
+int adell_dw_wgrad_mfma_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa,
+                             int ya, AdellDwPlan* p);
+static inline int adell_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 static inline int adell_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int adell_ilog2(int v) {
   int r = 0;

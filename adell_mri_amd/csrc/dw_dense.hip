@@ -214,25 +214,39 @@ __global__ __launch_bounds__(64 * CG) void adell_dw_dense_kernel(DwDenseArgs a) 
   }
 }
 
-// 7^3 taps on volumes of at most 4 x 4 x 4 voxels (more than 16 of them), channels in fours
+// 7^3 taps on volumes of at most 4 x 4 x 4 voxels (more than 16 of them), channels in fours. One block
+// per 4 channels x DD_IT items (one M tile).
+constexpr int DD_CG = 4;
+int adell_dw_dense_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa, int ya,
+                        AdellDwPlan* p) {
+  const int itemBlocks = (N + DD_IT - 1) / DD_IT;
+  if (!(KD == 7 && KH == 7 && KW == 7 && D <= 4 && H <= 4 && W <= 4 && D * H * W > 16 &&
+        C % 4 == 0 && itemBlocks <= 65535 && xa && ya && !g_adell_tune.dw_nomfma))
+    return 0;
+  *p = AdellDwPlan{};
+  p->form = ADELL_DW_DENSE;
+  p->vec = 1;
+  p->parts = itemBlocks;                       // grid (C / 4, item blocks)
+  p->blocks = (long)(C / DD_CG) * itemBlocks;
+  p->loop = N < DD_IT ? N : DD_IT;
+  return 1;
+}
+
 extern "C" int adell_dw_dense_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
                                  const float* x, const float* y) {
-  return KD == 7 && KH == 7 && KW == 7 && D <= 4 && H <= 4 && W <= 4 && D * H * W > 16 &&
-         C % 4 == 0 && (N + DD_IT - 1) / DD_IT <= 65535 &&
-         ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0 && !g_adell_tune.dw_nomfma;
+  AdellDwPlan p;
+  return adell_dw_dense_plan(N, C, D, H, W, KD, KH, KW, adell_aligned16(x), adell_aligned16(y), &p);
 }
 
-template <int CG>
-static int adell_dw_dense_go(const DwDenseArgs& a, hipStream_t st) {
-  return adell_launch<adell_dw_dense_kernel<CG>>(dim3(a.C / CG, (a.N + DD_IT - 1) / DD_IT),
-                                                 dim3(64 * CG), dd_lds<CG>(), st, a);
-}
-
-extern "C" int adell_dw_dense_launch(const float* x, const float* w, const float* b, float* y, int N,
+int adell_dw_dense_launch(const float* x, const float* w, const float* b, float* y, int N,
                                      int C, int D, int H, int W, int flip, void* stream) {
-  ADELL_REQUIRE(adell_dw_dense_ok(N, C, D, H, W, 7, 7, 7, x, y), "dw_dense: shape not covered");
+  AdellDwPlan p;
+  ADELL_REQUIRE(adell_dw_dense_plan(N, C, D, H, W, 7, 7, 7, adell_aligned16(x), adell_aligned16(y), &p),
+                "dw_dense: shape not covered");
   DwDenseArgs a = {x, w, b, y, N, C, D, H, W, flip};
   // (16 channels per block quarter the line requests but leave 96 blocks of 1 024 threads for 256 CUs at
   // ConvNeXt's 64 crops x 384 channels: 30.4 us against 24.4 -- A/B switch only)
-  return adell_dw_dense_go<4>(a, (hipStream_t)stream);
+  return adell_launch<adell_dw_dense_kernel<DD_CG>>(dim3((unsigned)(p.blocks / p.parts), (unsigned)p.parts),
+                                                    dim3(64 * DD_CG), dd_lds<DD_CG>(),
+                                                    (hipStream_t)stream, a);
 }

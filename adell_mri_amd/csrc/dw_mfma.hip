@@ -338,25 +338,46 @@ __global__ __launch_bounds__(256, 1) void adell_dw_mfma_kernel(DwMfmaArgs a) {
 }
 
 // K = 7 cubic, rows of 9 .. 16 voxels in x and y, channels in fours, 16-byte aligned tensors
-extern "C" int adell_dw_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
-                                const float* x, const float* y) {
-  return KD == 7 && KH == 7 && KW == 7 && W > 8 && W <= 16 && H > 8 && H <= 16 && D >= 1 &&
-         C % DM_CG == 0 && N <= 65535 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0 &&
-         !g_adell_tune.dw_nomfma;
+// resident (D <= 16): one block per CU (LDS), persistent blocks, each prefetching its next column;
+// streamed: one block per work item
+int adell_dw_mfma_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa, int ya,
+                       AdellDwPlan* p) {
+  if (!(KD == 7 && KH == 7 && KW == 7 && W > 8 && W <= 16 && H > 8 && H <= 16 && D >= 1 &&
+        C % DM_CG == 0 && N <= 65535 && xa && ya && !g_adell_tune.dw_nomfma))
+    return 0;
+  *p = AdellDwPlan{};
+  const long total = (long)N * (C / DM_CG);
+  p->vec = 1;
+  p->parts = total;                            // work items
+  if (D <= 16) {
+    const int cus = adell_cu_count();
+    p->form = ADELL_DW_MFMA;
+    p->blocks = total < cus ? total : cus;
+  } else {
+    p->form = ADELL_DW_MFMA_STREAM;
+    p->blocks = total;
+  }
+  p->loop = (total + p->blocks - 1) / p->blocks;
+  return 1;
 }
 
-extern "C" int adell_dw_mfma_launch(const float* x, const float* w, const float* b, float* y, int N,
+extern "C" int adell_dw_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
+                                const float* x, const float* y) {
+  AdellDwPlan p;
+  return adell_dw_mfma_plan(N, C, D, H, W, KD, KH, KW, adell_aligned16(x), adell_aligned16(y), &p);
+}
+
+int adell_dw_mfma_launch(const float* x, const float* w, const float* b, float* y, int N,
                                     int C, int D, int H, int W, int flip, void* stream) {
-  ADELL_REQUIRE(adell_dw_mfma_ok(N, C, D, H, W, 7, 7, 7, x, y), "dw_mfma: shape not covered");
-  const long total = (long)N * (C / DM_CG);
+  AdellDwPlan p;
+  ADELL_REQUIRE(adell_dw_mfma_plan(N, C, D, H, W, 7, 7, 7, adell_aligned16(x), adell_aligned16(y), &p),
+                "dw_mfma: shape not covered");
+  const long total = p.parts;
   ADELL_REQUIRE(total <= 0x7fffffffL - 4096, "dw_mfma: too many work items");
   DwMfmaArgs a = {x, w, b, y, N, C, D, H, W, flip, (int)total};
-  if (D <= 16) {
-    // one block per CU (LDS): persistent blocks, each prefetching its next column
-    const int cus = adell_cu_count();
-    const int grid = total < cus ? (int)total : cus;
-    return adell_launch<adell_dw_mfma_kernel<true>>(dim3(grid), dim3(256), DM_LDS, (hipStream_t)stream, a);
-  }
-  return adell_launch<adell_dw_mfma_kernel<false>>(dim3((unsigned)total), dim3(256), DM_LDS,
+  if (p.form == ADELL_DW_MFMA)
+    return adell_launch<adell_dw_mfma_kernel<true>>(dim3((unsigned)p.blocks), dim3(256), DM_LDS,
+                                                    (hipStream_t)stream, a);
+  return adell_launch<adell_dw_mfma_kernel<false>>(dim3((unsigned)p.blocks), dim3(256), DM_LDS,
                                                    (hipStream_t)stream, a);
 }

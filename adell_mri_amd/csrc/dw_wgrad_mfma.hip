@@ -251,44 +251,47 @@ __global__ __launch_bounds__(256, 1) void adell_dw_wgrad_mfma_kernel(DwWgMfmaArg
 
 extern "C" int adell_absmax_f32(const float* x, long n, uint32_t* out, void* stream);
 
-static int adell_dw_wgrad_mfma_chunks(int N, int C, int* items_per_chunk) {
+// grid (C / 4, chunks): ~256 blocks; a chunk is p->loop consecutive items (the last may be short),
+// its partial sums one [C][344] slab of the workspace (+ 4 words for the two absmax)
+int adell_dw_wgrad_mfma_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa,
+                             int ya, AdellDwPlan* p) {
+  if (!(KD == 7 && KH == 7 && KW == 7 && W > 8 && W <= 16 && H > 8 && H <= 16 && D >= 1 &&
+        C % WM_CG == 0 && xa && ya && !g_adell_tune.dw_nomfma && !g_adell_tune.dw_wgrad_nomfma))
+    return 0;
+  *p = AdellDwPlan{};
   const int groups = C / WM_CG;
   int chunks = 256 / groups;
   chunks = chunks < 1 ? 1 : (chunks > N ? N : chunks);
   const int ipc = (N + chunks - 1) / chunks;
-  *items_per_chunk = ipc;
-  return (N + ipc - 1) / ipc;
+  p->form = ADELL_DW_WGRAD_MFMA;
+  p->vec = 1;
+  p->loop = ipc;
+  p->parts = (N + ipc - 1) / ipc;
+  p->blocks = (long)groups * p->parts;
+  p->workspace = p->parts * C * 344 + 4;
+  return 1;
 }
 
 extern "C" int adell_dw_wgrad_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
                                       const float* x, const float* dy) {
-  return KD == 7 && KH == 7 && KW == 7 && W > 8 && W <= 16 && H > 8 && H <= 16 && D >= 1 &&
-         C % WM_CG == 0 && ((((uintptr_t)x) | ((uintptr_t)dy)) & 15) == 0 &&
-         !g_adell_tune.dw_nomfma && !g_adell_tune.dw_wgrad_nomfma;
+  AdellDwPlan p;
+  return adell_dw_wgrad_mfma_plan(N, C, D, H, W, KD, KH, KW, adell_aligned16(x), adell_aligned16(dy),
+                                  &p);
 }
 
-extern "C" long adell_dw_wgrad_mfma_workspace_floats(int N, int C) {
-  int ipc;
-  const int chunks = adell_dw_wgrad_mfma_chunks(N, C, &ipc);
-  return (long)chunks * C * 344 + 4;
-}
-
-// dw [C][343], db [C] or null; workspace: adell_dw_wgrad_mfma_workspace_floats floats
-extern "C" int adell_dw_wgrad_mfma_launch(const float* x, const float* dy, float* workspace, int N,
-                                          int C, int D, int H, int W, int* chunks_out, void* stream) {
-  ADELL_REQUIRE(workspace, "dw_wgrad_mfma: workspace required");
+// partial sums [p.parts][C][344] (column 343: db) into workspace (p.workspace floats)
+int adell_dw_wgrad_mfma_launch(const float* x, const float* dy, float* workspace, const AdellDwPlan& p,
+                               int N, int C, int D, int H, int W, void* stream) {
+  ADELL_REQUIRE(workspace && p.form == ADELL_DW_WGRAD_MFMA, "dw_wgrad_mfma: workspace required");
   hipStream_t st = (hipStream_t)stream;
-  int ipc;
-  const int chunks = adell_dw_wgrad_mfma_chunks(N, C, &ipc);
-  uint32_t* words = reinterpret_cast<uint32_t*>(workspace + (long)chunks * C * 344);
+  uint32_t* words = reinterpret_cast<uint32_t*>(workspace + p.parts * C * 344);
   ADELL_CHECK_HIP(hipMemsetAsync(words, 0, 8, st));
   const long total = (long)N * C * D * H * W;
   int rc = adell_absmax_f32(x, total, words, stream);
   if (rc != ADELL_OK) return rc;
   rc = adell_absmax_f32(dy, total, words + 1, stream);
   if (rc != ADELL_OK) return rc;
-  DwWgMfmaArgs a = {x, dy, workspace, words, N, C, D, H, W, ipc};
-  rc = adell_launch<adell_dw_wgrad_mfma_kernel>(dim3(C / WM_CG, chunks), dim3(256), WM_LDS, st, a);
-  if (rc == ADELL_OK) *chunks_out = chunks;
-  return rc;
+  DwWgMfmaArgs a = {x, dy, workspace, words, N, C, D, H, W, (int)p.loop};
+  return adell_launch<adell_dw_wgrad_mfma_kernel>(dim3(C / WM_CG, (unsigned)p.parts), dim3(256), WM_LDS,
+                                                  st, a);
 }

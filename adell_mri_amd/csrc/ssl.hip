@@ -16,13 +16,14 @@ struct DwArgs {
   const float* b;   // [C] or null
   float* y;
   int N, C, D, H, W, KD, KH, KW, PD, PH, PW, flip;
+  int vec;          // one float4 of 4 channels per thread (C % 4 == 0, 16-byte aligned x and y)
 };
 
 // y[v][c] = sum_tap x[v + tap - p][c] * w[c][tap (flipped when a.flip)] (+ b[c])
 __global__ __launch_bounds__(256) void adell_dwconv3d_kernel(DwArgs a) {
   const int taps = a.KD * a.KH * a.KW;
   const int C4 = a.C >> 2;
-  const bool vec = (a.C & 3) == 0;
+  const bool vec = a.vec != 0;
   const int CW = vec ? C4 : a.C;
   const long total = (long)a.N * a.D * a.H * a.W * CW;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
@@ -506,8 +507,9 @@ __global__ __launch_bounds__(256) void adell_dw_zring_kernel(DwZrArgs a) {
   }
 }
 
-// 1 when the z-marching kernel takes the problem; fills the launch geometry
-static int adell_dw_zring_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, DwZrArgs* z) {
+// 1 when the z-marching kernel takes the problem; fills the launch geometry (xa: x is 16-byte aligned)
+static int adell_dw_zring_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa,
+                               DwZrArgs* z, AdellDwPlan* p) {
   if (KD != 7 || KH != 7 || KW != 7 || W > DZ_WT || W <= 8 || D < 4) return 0;
   z->N = N; z->C = C; z->D = D; z->H = H; z->W = W;
   z->tilesY = adell_cdiv(H, DZ_TY);
@@ -519,22 +521,30 @@ static int adell_dw_zring_plan(int N, int C, int D, int H, int W, int KD, int KH
   z->seglen = adell_cdiv(D, (int)nseg);
   z->nseg = adell_cdiv(D, z->seglen);
   if (base * z->nseg > 0x7fffffffL) return 0;
+  z->vec = (C % 4 == 0) && xa;
+  *p = AdellDwPlan{};
+  p->form = ADELL_DW_ZRING; p->K = DZ_K; p->WT = DZ_WT;
+  p->nseg = z->nseg; p->seg = z->seglen; p->vec = z->vec;
+  p->blocks = base * z->nseg;
+  p->loop = 1;
   return 1;
 }
 
-static int adell_dw_zring_launch(DwZrArgs z, hipStream_t st) {
+static int adell_dw_zring_launch(DwZrArgs z, long blocks, hipStream_t st) {
   const size_t lds = (size_t)(DZ_SLOTS * DZ_PLANE + 16 * DZ_K3) * sizeof(float);
-  const long blocks = (long)z.N * z.tilesY * z.chanBlocks * z.nseg;
   return adell_launch<adell_dw_zring_kernel>(dim3((unsigned)blocks), dim3(256), lds, st, z);
 }
 
-// tiled path: cubic K in {3,5,7}. Returns the x-row width WT (4 / 8 / 16) or 0.
-static int adell_dw_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, DwTile* t) {
+// tiled path: cubic K in {3,5,7}. Returns the x-row width WT (4 / 8 / 16) or 0. aligned: every tensor
+// the kernel stages is 16-byte aligned. Fills what the forward and the weight gradient share of the
+// plan (blocks / loop / parts: the forward's, one tile per block).
+static int adell_dw_plan(int N, int C, int D, int H, int W, int KD, int KH, int KW, int aligned,
+                         DwTile* t, AdellDwPlan* p) {
   if (KD != KH || KH != KW || (KD != 3 && KD != 5 && KD != 7)) return 0;
   const int K = KD, P = K / 2;
   int WT = W <= 4 ? 4 : (W <= 8 ? 8 : 16);
   t->N = N; t->C = C; t->D = D; t->H = H; t->W = W;
-  t->vec = (C % 4) == 0;
+  t->vec = (C % 4) == 0 && aligned;
   t->single = W <= WT;
   if (!t->single && WT - 2 * P < 4) return 0;
   t->seg = t->single ? W : WT - 2 * P;
@@ -544,15 +554,18 @@ static int adell_dw_plan(int N, int C, int D, int H, int W, int KD, int KH, int 
   t->chanBlocks = adell_cdiv(C, 16);
   const long blocks = (long)N * t->tilesZ * t->tilesY * t->tilesX * t->chanBlocks;
   if (blocks > 0x7fffffffL) return 0;
+  *p = AdellDwPlan{};
+  p->form = ADELL_DW_TILE; p->K = K; p->WT = WT;
+  p->nseg = t->tilesX; p->seg = t->seg; p->vec = t->vec;
+  p->blocks = blocks;
+  p->loop = 1;
   return WT;
 }
 
 template <int K, int WT>
-static int adell_dw_tile_launch(const DwTileArgs& a, hipStream_t st) {
+static int adell_dw_tile_launch(const DwTileArgs& a, long blocks, hipStream_t st) {
   using Cf = DwCfg<K, WT>;
   const size_t lds = (size_t)(Cf::XT_FLOATS + Cf::WT_FLOATS) * sizeof(float);
-  const DwTile& t = a.t;
-  const long blocks = (long)t.N * t.tilesZ * t.tilesY * t.tilesX * t.chanBlocks;
   return adell_launch<adell_dw_tile_kernel<K, WT>>(dim3((unsigned)blocks), dim3(256), lds, st, a);
 }
 
@@ -573,40 +586,54 @@ static int adell_dw_tile_launch(const DwTileArgs& a, hipStream_t st) {
     return FN<7, 16>(__VA_ARGS__);                                         \
   } while (0)
 
-extern "C" int adell_dw_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
-                                const float* x, const float* y);
-extern "C" int adell_dw_mfma_launch(const float* x, const float* w, const float* b, float* y, int N,
-                                    int C, int D, int H, int W, int flip, void* stream);
+int adell_dw_mfma_launch(const float* x, const float* w, const float* b, float* y, int N, int C, int D,
+                         int H, int W, int flip, void* stream);
+int adell_dw_dense_launch(const float* x, const float* w, const float* b, float* y, int N, int C, int D,
+                          int H, int W, int flip, void* stream);
 
-extern "C" int adell_dw_dense_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
-                                 const float* x, const float* y);
-extern "C" int adell_dw_dense_launch(const float* x, const float* w, const float* b, float* y, int N,
-                                     int C, int D, int H, int W, int flip, void* stream);
+// The dispatch of forward and backward-data, in this order: dense small volumes (csrc/dw_dense.hip),
+// the Toeplitz MFMA form (csrc/dw_mfma.hip), the z-marching ring, the tiles, the generic kernel.
+// xa / ya: the input / output tensor of the launch is 16-byte aligned.
+static void adell_dw_plan_fwd(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa, int ya,
+                              AdellDwPlan* p, DwZrArgs* zr, DwTile* t) {
+  // 7^3 taps on volumes of at most 4^3 voxels: a dense per-channel matrix
+  if (adell_dw_dense_plan(N, C, D, H, W, KD, KH, KW, xa, ya, p)) return;
+  // 7^3 taps on rows of 9 .. 16 voxels: the Toeplitz form on the f16x3 MFMA
+  if (adell_dw_mfma_plan(N, C, D, H, W, KD, KH, KW, xa, ya, p)) return;
+  if (adell_dw_zring_plan(N, C, D, H, W, KD, KH, KW, xa, zr, p)) return;
+  if (adell_dw_plan(N, C, D, H, W, KD, KH, KW, xa, t, p)) return;
+  *p = AdellDwPlan{};
+  p->form = ADELL_DW_GENERIC;
+  p->vec = (C % 4 == 0) && xa && ya;
+  const long total = (long)N * D * H * W * (p->vec ? C / 4 : C);
+  p->blocks = (total + 255) / 256;
+  if (p->blocks > 16384) p->blocks = 16384;
+  p->loop = (total + p->blocks * 256 - 1) / (p->blocks * 256);   // grid-stride rounds
+}
 
 static int adell_dw_launch(DwArgs a, hipStream_t st) {
-  // 7^3 taps on volumes of at most 4^3 voxels: a dense per-channel matrix (csrc/dw_dense.hip)
-  if (adell_dw_dense_ok(a.N, a.C, a.D, a.H, a.W, a.KD, a.KH, a.KW, a.x, a.y))
-    return adell_dw_dense_launch(a.x, a.w, a.b, a.y, a.N, a.C, a.D, a.H, a.W, a.flip, st);
-  // 7^3 taps on rows of 9 .. 16 voxels: the Toeplitz form on the f16x3 MFMA (csrc/dw_mfma.hip)
-  if (adell_dw_mfma_ok(a.N, a.C, a.D, a.H, a.W, a.KD, a.KH, a.KW, a.x, a.y))
-    return adell_dw_mfma_launch(a.x, a.w, a.b, a.y, a.N, a.C, a.D, a.H, a.W, a.flip, st);
+  AdellDwPlan p;
   DwZrArgs zr = {};
-  if (adell_dw_zring_plan(a.N, a.C, a.D, a.H, a.W, a.KD, a.KH, a.KW, &zr)) {
-    zr.x = a.x; zr.w = a.w; zr.b = a.b; zr.y = a.y; zr.flip = a.flip;
-    zr.vec = (a.C % 4 == 0) && ((uintptr_t)a.x % 16 == 0);
-    return adell_dw_zring_launch(zr, st);
-  }
   DwTileArgs ta;
-  const int WT = adell_dw_plan(a.N, a.C, a.D, a.H, a.W, a.KD, a.KH, a.KW, &ta.t);
-  if (WT) {
-    ta.x = a.x; ta.w = a.w; ta.b = a.b; ta.y = a.y; ta.flip = a.flip;
-    ta.t.vec = ta.t.vec && ((uintptr_t)a.x % 16 == 0);
-    ADELL_DW_DISPATCH(adell_dw_tile_launch, a.KD, WT, ta, st);
+  adell_dw_plan_fwd(a.N, a.C, a.D, a.H, a.W, a.KD, a.KH, a.KW, adell_aligned16(a.x),
+                    adell_aligned16(a.y), &p, &zr, &ta.t);
+  switch (p.form) {
+    case ADELL_DW_DENSE:
+      return adell_dw_dense_launch(a.x, a.w, a.b, a.y, a.N, a.C, a.D, a.H, a.W, a.flip, st);
+    case ADELL_DW_MFMA:
+    case ADELL_DW_MFMA_STREAM:
+      return adell_dw_mfma_launch(a.x, a.w, a.b, a.y, a.N, a.C, a.D, a.H, a.W, a.flip, st);
+    case ADELL_DW_ZRING:
+      zr.x = a.x; zr.w = a.w; zr.b = a.b; zr.y = a.y; zr.flip = a.flip;
+      return adell_dw_zring_launch(zr, p.blocks, st);
+    case ADELL_DW_TILE:
+      ta.x = a.x; ta.w = a.w; ta.b = a.b; ta.y = a.y; ta.flip = a.flip;
+      ADELL_DW_DISPATCH(adell_dw_tile_launch, p.K, p.WT, ta, p.blocks, st);
+    default:
+      break;
   }
-  const long total = (long)a.N * a.D * a.H * a.W * (((a.C & 3) == 0) ? a.C / 4 : a.C);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(adell_dwconv3d_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  a.vec = p.vec;
+  hipLaunchKernelGGL(adell_dwconv3d_kernel, dim3((unsigned)p.blocks), dim3(256), 0, st, a);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -634,18 +661,20 @@ extern "C" int adell_dwconv3d_bwd_data(int N, int C, int D, int H, int W, int KD
 
 // dw[c][tap] = sum_v x[v + tap - p][c] * dy[v][c];  db[c] = sum_v dy[v][c] (tap == centre
 // block also reduces db). grid (taps, channel groups of 64); block = 64 channels x 4 lanes.
-// Generic fallback (non-cubic kernels).
+// Generic fallback (non-cubic kernels). A lane walks a quarter of ALL voxels in turn, so its two
+// sums are kept in fp64 (as the finalize kernels fold): in fp32 the rounding of that serial sum
+// grows with the voxel count (1.1 M voxels of a 2-D batch: 1e-5 of the largest dW entry).
 __global__ __launch_bounds__(256) void adell_dwconv3d_wgrad_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dw,
     float* __restrict__ db, int N, int C, int D, int H, int W, int KD, int KH, int KW) {
-  __shared__ float sh[4][64][2];
+  __shared__ double sh[4][64][2];
   const int taps = KD * KH * KW;
   const int tap = blockIdx.x;
   const int kx = tap % KW, ky = (tap / KW) % KH, kz = tap / (KW * KH);
   const int cl = threadIdx.x & 63, vl = threadIdx.x >> 6;
   const int c = blockIdx.y * 64 + cl;
   const int dz = kz - KD / 2, dyy = ky - KH / 2, dx = kx - KW / 2;
-  float s = 0.f, sb = 0.f;
+  double s = 0.0, sb = 0.0;
   if (c < C) {
     const long V = (long)N * D * H * W;
     for (long v = vl; v < V; v += 4) {
@@ -658,18 +687,21 @@ __global__ __launch_bounds__(256) void adell_dwconv3d_wgrad_kernel(
       sb += g;
       const int xx = x0 + dx, yy = y0 + dyy, zz = z0 + dz;
       if (xx < 0 || xx >= W || yy < 0 || yy >= H || zz < 0 || zz >= D) continue;
-      s += g * x[((((size_t)nb * D + zz) * H + yy) * W + xx) * C + c];
+      s += (double)g * x[((((size_t)nb * D + zz) * H + yy) * W + xx) * C + c];
     }
   }
   sh[vl][cl][0] = s;
   sh[vl][cl][1] = sb;
   __syncthreads();
   if (vl == 0 && c < C) {
-    dw[(size_t)c * taps + tap] = (sh[0][cl][0] + sh[1][cl][0]) + (sh[2][cl][0] + sh[3][cl][0]);
-    if (db && tap == 0) db[c] = (sh[0][cl][1] + sh[1][cl][1]) + (sh[2][cl][1] + sh[3][cl][1]);
+    dw[(size_t)c * taps + tap] =
+        (float)((sh[0][cl][0] + sh[1][cl][0]) + (sh[2][cl][0] + sh[3][cl][0]));
+    if (db && tap == 0)
+      db[c] = (float)((sh[0][cl][1] + sh[1][cl][1]) + (sh[2][cl][1] + sh[3][cl][1]));
   }
 }
 
+// splits of the tile weight gradient: ~512 blocks, each over ips consecutive tiles (the last may be short)
 static int adell_dw_wgrad_splits(const DwTile& t, long* items_out, int* ips_out) {
   const long items = (long)t.N * t.tilesZ * t.tilesY * t.tilesX;
   long splits = adell_cdiv(512, t.chanBlocks);
@@ -683,38 +715,55 @@ static int adell_dw_wgrad_splits(const DwTile& t, long* items_out, int* ips_out)
 }
 
 template <int K, int WT>
-static int adell_dw_wgrad_tile_launch(DwWgradArgs a, int splits, hipStream_t st) {
+static int adell_dw_wgrad_tile_launch(DwWgradArgs a, long blocks, hipStream_t st) {
   using Cf = DwCfg<K, WT>;
   const size_t lds = (size_t)(Cf::XT_FLOATS + Cf::DY_FLOATS) * sizeof(float);
-  return adell_launch<adell_dw_wgrad_tile_kernel<K, WT>>(dim3((unsigned)(splits * a.t.chanBlocks)),
-                                                         dim3(Cf::WG_THREADS), lds, st, a);
+  return adell_launch<adell_dw_wgrad_tile_kernel<K, WT>>(dim3((unsigned)blocks), dim3(Cf::WG_THREADS),
+                                                         lds, st, a);
 }
 
-static int adell_dw_wgrad_dispatch(int K, int WT, const DwWgradArgs& a, int splits,
-                                   hipStream_t st) {
-  ADELL_DW_DISPATCH(adell_dw_wgrad_tile_launch, K, WT, a, splits, st);
+static int adell_dw_wgrad_dispatch(int K, int WT, const DwWgradArgs& a, long blocks, hipStream_t st) {
+  ADELL_DW_DISPATCH(adell_dw_wgrad_tile_launch, K, WT, a, blocks, st);
 }
 
-extern "C" int adell_dw_wgrad_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
-                                      const float* x, const float* dy);
-extern "C" long adell_dw_wgrad_mfma_workspace_floats(int N, int C);
-extern "C" int adell_dw_wgrad_mfma_launch(const float* x, const float* dy, float* workspace, int N,
-                                          int C, int D, int H, int W, int* chunks_out, void* stream);
+int adell_dw_wgrad_mfma_launch(const float* x, const float* dy, float* workspace, const AdellDwPlan& p,
+                               int N, int C, int D, int H, int W, void* stream);
+
+// The dispatch of the weight gradient, in this order: the MFMA form (csrc/dw_wgrad_mfma.hip), the tiles
+// behind a split plan, the generic kernel. xa / ya: x / dy is 16-byte aligned. a: the tile kernel's
+// geometry (t, items, itemsPerSplit).
+static void adell_dw_plan_wgrad(int N, int C, int D, int H, int W, int KD, int KH, int KW, int xa,
+                                int ya, AdellDwPlan* p, DwWgradArgs* a) {
+  // 7^3 taps on rows of 9 .. 16 voxels: rows as the reduction dimension of f16x3 MFMA products
+  if (adell_dw_wgrad_mfma_plan(N, C, D, H, W, KD, KH, KW, xa, ya, p)) return;
+  if (adell_dw_plan(N, C, D, H, W, KD, KH, KW, xa && ya, &a->t, p)) {
+    p->parts = adell_dw_wgrad_splits(a->t, &a->items, &a->itemsPerSplit);
+    p->loop = a->itemsPerSplit;
+    p->blocks = p->parts * a->t.chanBlocks;
+    p->workspace = p->blocks * 16 * ((long)KD * KH * KW + 1);
+    return;
+  }
+  // one block per (tap, 64 channels); its four lanes per channel each walk a quarter of the voxels
+  *p = AdellDwPlan{};
+  p->form = ADELL_DW_GENERIC;
+  p->parts = adell_cdiv(C, 64);
+  p->blocks = (long)KD * KH * KW * p->parts;
+  p->loop = ((long)N * D * H * W + 3) / 4;
+}
 
 // floats of workspace adell_dwconv3d_bwd_weight needs (0: none)
 extern "C" long adell_dwconv3d_bwd_weight_workspace_floats(int N, int C, int D, int H, int W,
                                                            int KD, int KH, int KW) {
-  DwTile t;
   if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  // (the form is chosen per call from the operands' alignment: size for either)
   long need = 0;
-  // (the MFMA form is chosen per call from the operands' alignment: size for either)
-  if (KD == 7 && KH == 7 && KW == 7 && C % 4 == 0) need = adell_dw_wgrad_mfma_workspace_floats(N, C);
-  if (!adell_dw_plan(N, C, D, H, W, KD, KH, KW, &t)) return need;
-  long items;
-  int ips;
-  const int splits = adell_dw_wgrad_splits(t, &items, &ips);
-  const long tile = (long)splits * t.chanBlocks * 16 * ((long)KD * KH * KW + 1);
-  return tile > need ? tile : need;
+  for (int aligned = 0; aligned < 2; ++aligned) {
+    AdellDwPlan p;
+    DwWgradArgs a;
+    adell_dw_plan_wgrad(N, C, D, H, W, KD, KH, KW, aligned, aligned, &p, &a);
+    if (p.workspace > need) need = p.workspace;
+  }
+  return need;
 }
 
 extern "C" int adell_dwconv3d_bwd_weight(int N, int C, int D, int H, int W, int KD, int KH,
@@ -724,42 +773,54 @@ extern "C" int adell_dwconv3d_bwd_weight(int N, int C, int D, int H, int W, int 
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(x && dy && dw, "dwconv_bwd_weight: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  // 7^3 taps on rows of 9 .. 16 voxels: rows as the reduction dimension of f16x3 MFMA products
-  // (csrc/dw_wgrad_mfma.hip), per-chunk partial sums folded by the reduce kernel below
-  if (adell_dw_wgrad_mfma_ok(N, C, D, H, W, KD, KH, KW, x, dy)) {
-    ADELL_REQUIRE(workspace, "dwconv_bwd_weight: workspace of "
-                             "adell_dwconv3d_bwd_weight_workspace_floats() floats required");
-    int chunks = 0;
-    rc = adell_dw_wgrad_mfma_launch(x, dy, workspace, N, C, D, H, W, &chunks, stream);
-    if (rc != ADELL_OK) return rc;
-    long blocks = ((long)C * 344 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adell_dw_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                       workspace, chunks, C, C, 343, dw, db);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  }
+  AdellDwPlan p;
   DwWgradArgs a;
-  const int WT = adell_dw_plan(N, C, D, H, W, KD, KH, KW, &a.t);
-  if (WT) {
-    ADELL_REQUIRE(workspace, "dwconv_bwd_weight: workspace of "
-                             "adell_dwconv3d_bwd_weight_workspace_floats() floats required");
-    a.x = x; a.dy = dy; a.part = workspace;
-    a.t.vec = a.t.vec && (((uintptr_t)x | (uintptr_t)dy) % 16 == 0);
-    const int splits = adell_dw_wgrad_splits(a.t, &a.items, &a.itemsPerSplit);
-    rc = adell_dw_wgrad_dispatch(KD, WT, a, splits, st);
-    if (rc != ADELL_OK) return rc;
-    const int K3 = KD * KH * KW;
-    long blocks = ((long)C * (K3 + 1) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adell_dw_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                       workspace, splits, a.t.chanBlocks * 16, C, K3, dw, db);
+  adell_dw_plan_wgrad(N, C, D, H, W, KD, KH, KW, adell_aligned16(x), adell_aligned16(dy), &p, &a);
+  if (p.form == ADELL_DW_GENERIC) {
+    hipLaunchKernelGGL(adell_dwconv3d_wgrad_kernel, dim3(KD * KH * KW, (unsigned)p.parts), dim3(256),
+                       0, st, x, dy, dw, db, N, C, D, H, W, KD, KH, KW);
     ADELL_CHECK_HIP(hipGetLastError());
     return ADELL_OK;
   }
-  hipLaunchKernelGGL(adell_dwconv3d_wgrad_kernel, dim3(KD * KH * KW, adell_cdiv(C, 64)), dim3(256),
-                     0, st, x, dy, dw, db, N, C, D, H, W, KD, KH, KW);
+  // both other forms: per-chunk / per-split partial sums, folded in a fixed order by the reduce kernel
+  ADELL_REQUIRE(workspace, "dwconv_bwd_weight: workspace of "
+                           "adell_dwconv3d_bwd_weight_workspace_floats() floats required");
+  const int K3 = KD * KH * KW;
+  int cpad = C;
+  if (p.form == ADELL_DW_WGRAD_MFMA) {
+    rc = adell_dw_wgrad_mfma_launch(x, dy, workspace, p, N, C, D, H, W, stream);
+  } else {
+    a.x = x; a.dy = dy; a.part = workspace;
+    cpad = a.t.chanBlocks * 16;
+    rc = adell_dw_wgrad_dispatch(p.K, p.WT, a, p.blocks, st);
+  }
+  if (rc != ADELL_OK) return rc;
+  long blocks = ((long)C * (K3 + 1) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(adell_dw_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
+                     workspace, (int)p.parts, cpad, C, K3, dw, db);
   ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+// Host-only launch plan of adell_dwconv3d_fwd / _bwd_data (pass 0) or _bwd_weight (pass 1): the same
+// adell_dw_plan_fwd / adell_dw_plan_wgrad call the launch makes (include/adell_hip.h: out[10]).
+extern "C" int adell_dwconv3d_plan(int pass, int N, int C, int D, int H, int W, int KD, int KH, int KW,
+                                   int a_aligned, int b_aligned, long* out) {
+  int rc = adell_dw_check(N, C, D, H, W, KD, KH, KW);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(out && (pass == 0 || pass == 1), "dwconv3d_plan: bad arguments");
+  AdellDwPlan p;
+  if (pass == 0) {
+    DwZrArgs zr = {};
+    DwTile t;
+    adell_dw_plan_fwd(N, C, D, H, W, KD, KH, KW, a_aligned != 0, b_aligned != 0, &p, &zr, &t);
+  } else {
+    DwWgradArgs a;
+    adell_dw_plan_wgrad(N, C, D, H, W, KD, KH, KW, a_aligned != 0, b_aligned != 0, &p, &a);
+  }
+  out[0] = p.form; out[1] = p.K; out[2] = p.WT; out[3] = p.nseg; out[4] = p.seg; out[5] = p.vec;
+  out[6] = p.blocks; out[7] = p.loop; out[8] = p.parts; out[9] = p.workspace;
   return ADELL_OK;
 }
 

@@ -1706,6 +1706,27 @@ def dwconv3d_bwd_weight(x, dy, kshape, want_db):
     return dw, db
 
 
+# launch plan of a depthwise conv (adell_dwconv3d_plan). form: one of DW_FORMS; K, WT: the tile
+# instantiation (ring: 7, 16); nseg / seg: x segments of a tile row and outputs per segment, or z
+# segments of the ring and planes per segment; vec: 16-byte channel loads; blocks of the main kernel;
+# loop: the most work items one block loops over (rounds of the resident MFMA kernel, items per chunk,
+# tiles per split, grid-stride rounds ...); parts: chunks / splits; workspace floats
+DwPlan = collections.namedtuple("DwPlan", "form K WT nseg seg vec blocks loop parts workspace")
+DW_FORMS = ("generic", "dense", "mfma", "mfma_stream", "zring", "tile", "wgrad_mfma")
+
+
+def dwconv3d_plan(N, C, size, kernel, backward_weight=False, aligned=(True, True)):
+    """What dwconv3d_fwd / dwconv3d_bwd_data (one dispatch) or, with ``backward_weight``,
+    dwconv3d_bwd_weight would launch for these extents under the current tuning switches and conv
+    precision. ``aligned``: the launch's two tensors are 16-byte aligned (always, from torch). Host
+    only: no GPU needed."""
+    kernel = (kernel,) * 3 if isinstance(kernel, int) else tuple(kernel)
+    out = (ctypes.c_long * 10)()
+    check(_lib.lib().adell_dwconv3d_plan(int(bool(backward_weight)), N, C, *size, *kernel,
+                                         int(bool(aligned[0])), int(bool(aligned[1])), out))
+    return DwPlan(DW_FORMS[out[0]], *list(out)[1:])
+
+
 def multi_copy(table, rows, dst):
     """table: int64 device tensor [rows, 3] of (src pointer, dst offset, numel <= 16384)."""
     _require_cuda(dst)

@@ -1038,6 +1038,29 @@ int adell_dw_dense_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW,
 int adell_dw_wgrad_mfma_ok(int N, int C, int D, int H, int W, int KD, int KH, int KW, const float* x,
                            const float* dy);
 
+/* Launch plan of a depthwise convolution, host only (no launch, no tensor read, no device needed):
+ * what adell_dwconv3d_fwd / adell_dwconv3d_bwd_data (pass 0: one dispatch for both) or
+ * adell_dwconv3d_bwd_weight (pass 1) would run under the current tuning switches, decided by the same
+ * functions the launch calls. a_aligned / b_aligned: the launch's two tensors (x, y / dy, dx / x, dy)
+ * are 16-byte aligned. out[10]:
+ *   [0] form (ADELL_DW_*); [1] K, [2] WT of a tile instantiation <K, WT> (ring: 7, 16; else 0);
+ *   [3] x segments of a tile row / z segments of the ring; [4] outputs per x segment / planes per z
+ *   segment; [5] 1 when 16-byte channel loads are used; [6] blocks of the main kernel;
+ *   [7] the most work items one block loops over: rounds of the resident MFMA kernel, items per chunk
+ *   (MFMA weight gradient), tiles per split (tile weight gradient), items of a dense block's M tile,
+ *   grid-stride rounds (generic), voxels per lane (generic weight gradient), 1 otherwise;
+ *   [8] chunks / splits of the weight gradient (generic: rows of 64 channels; forward MFMA: work
+ *   items; dense: item blocks); [9] workspace floats this form needs. */
+#define ADELL_DW_GENERIC 0
+#define ADELL_DW_DENSE 1
+#define ADELL_DW_MFMA 2         /* resident: persistent blocks, D <= 16 */
+#define ADELL_DW_MFMA_STREAM 3  /* streamed column, D > 16 */
+#define ADELL_DW_ZRING 4
+#define ADELL_DW_TILE 5
+#define ADELL_DW_WGRAD_MFMA 6
+int adell_dwconv3d_plan(int pass, int N, int C, int D, int H, int W, int KD, int KH, int KW,
+                        int a_aligned, int b_aligned, long* out);
+
 /* Launch plan of the z-ring weight-gradient kernel (csrc/conv_wgrad_zring.hip) for a conv of these
  * extents: returns 1 and fills plan[8] = {column tiles x, y, z segments, planes per segment, input /
  * output channel tiles, resident blocks, 1 when the 16 x 16 tile form (16-channel layers) runs}, or 0

@@ -95,7 +95,7 @@ def test_dispatch_limits_and_the_fp32_mode(cuda):
         HF.set_conv_precision(old)
 
 
-@pytest.mark.parametrize("N,C,size", CASES + [(9, 8, (6, 16, 16))])   # several items per chunk, D < 7
+@pytest.mark.parametrize("N,C,size", CASES + [(9, 8, (6, 16, 16))])   # 9 chunks of one item, D < 7 (several items per chunk: test_dw_plans.py)
 @pytest.mark.parametrize("scale", [1.0, 2e4, 3e-5])
 def test_weight_and_bias_gradient_against_fp64(cuda, N, C, size, scale):
     """csrc/dw_wgrad_mfma.hip: rows as the reduction dimension of f16x3 MFMA products, one power-of-two
