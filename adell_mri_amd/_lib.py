@@ -229,6 +229,10 @@ SIGNATURES = {
     "adell_picai_tables_workspace": (_l, [_l, _i, _i, _i]),
     "adell_picai_tables_capacity": (_l, [_l, _i, _i, _i]),
     "adell_picai_tables": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _f, _vp, _vp, _l, _vp, _l, _vp]),
+    "adell_lesion_candidates_workspace": (_l, [_l, _i, _i, _i, _i]),
+    "adell_lesion_candidates_capacity": (_l, [_i] * 6),
+    "adell_lesion_candidates": (_i, [_vp, _l, _i, _i, _i, _i, _f, _f] + [_i] * 5 + [_vp] * 6
+                                + [_l, ctypes.POINTER(ctypes.c_int), _vp, _l, _vp]),
     "adell_item_stats_workspace": (_l, [_i, _l]),
     "adell_item_stats": (_i, [_vp, _i, _l, _vp, _vp, ctypes.c_size_t, _vp]),
     "adell_aug_intensity": (_i, [_vp, _vp, _i, _l, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp]),

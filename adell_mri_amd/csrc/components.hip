@@ -25,7 +25,14 @@
 // truncated target (volume B + b) in one labelling launch sequence; a global hash of the
 // (GT lesion, candidate) intersections; the pairs with 10 * inter >= union (every pair whose IoU can
 // reach min_overlap >= 0.1; at most 10 * min(N_gt, N_cand)); and one packed int32 record per case.
+//
+// Lesion candidates (the reference's extract_lesion_candidates.py, at the end of this file): the same
+// labelling sequence with a fourth foreground predicate, x >= thr and x != 0 with a threshold per
+// volume in device memory, and an optional per-volume flag that makes the blocks of a finished
+// volume exit at once (the rounds of the dynamic mode).
 #include "common.h"
+
+#include <vector>
 
 #define CC_THREADS 256
 #define CC_TZ 8
@@ -36,7 +43,7 @@
 #define CC_CHUNK (CC_THREADS * CC_PER)      // voxels per block in the linear passes
 #define CC_HS 4096                          // LDS hash slots of the aggregating passes
 
-enum { CC_MODE_GT = 0, CC_MODE_NONZERO = 1, CC_MODE_TRUNC = 2 };
+enum { CC_MODE_GT = 0, CC_MODE_NONZERO = 1, CC_MODE_TRUNC = 2, CC_MODE_GE = 3 };
 
 struct CcSrc {
   const float* x0;
@@ -44,11 +51,14 @@ struct CcSrc {
   long n0;             // volumes from x0; the rest from x1
   int mode0, mode1;
   float thr;
+  const float* thr_v;  // CC_MODE_GE: the threshold of every volume (device memory); null: thr
+  const int* act;      // null, or [NV]: the blocks of a volume with act[vol] == 0 exit at once
 };
 
 __device__ __forceinline__ bool cc_fg(float v, int mode, float thr) {
   if (mode == CC_MODE_GT) return v > thr;
   if (mode == CC_MODE_NONZERO) return v != 0.0f;     // NaN is foreground, as for numpy
+  if (mode == CC_MODE_GE) return !(v < thr) && v != 0.0f;   // x[x < thr] = 0, then x != 0
   return !(v > -1.0f && v < 1.0f);                   // astype(int32) != 0 (NaN, +-inf included)
 }
 
@@ -122,16 +132,18 @@ struct CcGeom {
 __global__ __launch_bounds__(CC_THREADS) void adell_cc_local_kernel(CcSrc src, CcGeom g, int* P) {
   __shared__ int par[CC_TILE];
   const long vol = blockIdx.y;
+  if (src.act && !src.act[vol]) return;
   const int tz = blockIdx.x / (g.ty * g.tx), rem = blockIdx.x % (g.ty * g.tx);
   const int z0 = tz * CC_TZ, y0 = (rem / g.tx) * CC_TY, x0 = (rem % g.tx) * CC_TX;
   const float* x = vol < src.n0 ? src.x0 + vol * g.V : src.x1 + (vol - src.n0) * g.V;
   const int mode = vol < src.n0 ? src.mode0 : src.mode1;
+  const float thr = src.thr_v ? src.thr_v[vol] : src.thr;
   for (int t = threadIdx.x; t < CC_TILE; t += CC_THREADS) {
     const int lx = t % CC_TX, ly = (t / CC_TX) % CC_TY, lz = t / (CC_TX * CC_TY);
     const int zz = z0 + lz, yy = y0 + ly, xx = x0 + lx;
     bool fg = false;
     if (zz < g.D && yy < g.H && xx < g.W)
-      fg = cc_fg(x[((long)zz * g.H + yy) * g.W + xx], mode, src.thr);
+      fg = cc_fg(x[((long)zz * g.H + yy) * g.W + xx], mode, thr);
     par[t] = fg ? t : -1;
   }
   __syncthreads();
@@ -163,8 +175,10 @@ __global__ __launch_bounds__(CC_THREADS) void adell_cc_local_kernel(CcSrc src, C
 
 // 2. unions across tile boundaries: only voxels on a tile face have a backward neighbour in
 // another tile (z = 0; y = 0 or TY - 1; x = 0 or TX - 1, the high faces through +1 offsets)
-__global__ __launch_bounds__(CC_THREADS) void adell_cc_merge_kernel(CcGeom g, int* P) {
+__global__ __launch_bounds__(CC_THREADS) void adell_cc_merge_kernel(CcGeom g, int* P,
+                                                                   const int* act) {
   const long vol = blockIdx.y;
+  if (act && !act[vol]) return;
   const int tz = blockIdx.x / (g.ty * g.tx), rem = blockIdx.x % (g.ty * g.tx);
   const int z0 = tz * CC_TZ, y0 = (rem / g.tx) * CC_TY, x0 = (rem % g.tx) * CC_TX;
   int* Pv = P + vol * g.V;
@@ -214,8 +228,9 @@ __device__ __forceinline__ int cc_block_excl_scan(int v, int* total) {
 
 // 3. flatten + roots per chunk (thread: CC_PER consecutive voxels)
 __global__ __launch_bounds__(CC_THREADS) void adell_cc_flatten_kernel(CcGeom g, int* P, int* blk,
-                                                                     int nb) {
+                                                                     int nb, const int* act) {
   const long vol = blockIdx.y;
+  if (act && !act[vol]) return;
   int* Pv = P + vol * g.V;
   const long v0 = (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
   int roots = 0;
@@ -236,7 +251,9 @@ __global__ __launch_bounds__(CC_THREADS) void adell_cc_flatten_kernel(CcGeom g, 
 }
 
 // 4. exclusive scan of the chunk counts of each volume; n[vol] = its component count
-__global__ __launch_bounds__(CC_THREADS) void adell_cc_scan_kernel(int* blk, int nb, int* n) {
+__global__ __launch_bounds__(CC_THREADS) void adell_cc_scan_kernel(int* blk, int nb, int* n,
+                                                                  const int* act) {
+  if (act && !act[blockIdx.x]) return;
   int* b = blk + (long)blockIdx.x * nb;
   int carry = 0;
   for (int base = 0; base < nb; base += CC_THREADS) {
@@ -252,8 +269,10 @@ __global__ __launch_bounds__(CC_THREADS) void adell_cc_scan_kernel(int* blk, int
 
 // 5. roots: label = 1 + rank in raster order
 __global__ __launch_bounds__(CC_THREADS) void adell_cc_roots_kernel(CcGeom g, const int* P,
-                                                                   const int* blk, int nb, int* L) {
+                                                                   const int* blk, int nb, int* L,
+                                                                   const int* act) {
   const long vol = blockIdx.y;
+  if (act && !act[vol]) return;
   const int* Pv = P + vol * g.V;
   int* Lv = L + vol * g.V;
   const long v0 = (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
@@ -300,6 +319,7 @@ __global__ __launch_bounds__(CC_THREADS) void adell_cc_relabel_kernel(CcSrc src,
   __shared__ int hcnt[CC_HS];
   __shared__ unsigned hmax[CC_HS];
   const long vol = blockIdx.y;
+  if (src.act && !src.act[vol]) return;
   const int* Pv = P + vol * g.V;
   int* Lv = L + vol * g.V;
   const bool stats = st.cnt != nullptr;
@@ -392,17 +412,17 @@ static int cc_run(const CcSrc& src, long NV, const CcGeom& g, int* L, int* n, ch
   ADELL_CHECK_HIP(hipGetLastError());
   if (tiles > 1) {
     hipLaunchKernelGGL(adell_cc_merge_kernel, dim3((unsigned)tiles, (unsigned)NV), dim3(CC_THREADS),
-                       0, s, g, P);
+                       0, s, g, P, src.act);
     ADELL_CHECK_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(adell_cc_flatten_kernel, dim3((unsigned)nb, (unsigned)NV), dim3(CC_THREADS), 0,
-                     s, g, P, blk, (int)nb);
+                     s, g, P, blk, (int)nb, src.act);
   ADELL_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(adell_cc_scan_kernel, dim3((unsigned)NV), dim3(CC_THREADS), 0, s, blk, (int)nb,
-                     n);
+                     n, src.act);
   ADELL_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(adell_cc_roots_kernel, dim3((unsigned)nb, (unsigned)NV), dim3(CC_THREADS), 0, s,
-                     g, P, blk, (int)nb, L);
+                     g, P, blk, (int)nb, L, src.act);
   ADELL_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(adell_cc_relabel_kernel, dim3((unsigned)nb, (unsigned)NV), dim3(CC_THREADS), 0,
                      s, src, g, P, L, st);
@@ -428,7 +448,7 @@ extern "C" int adell_cc_label(const float* x, long NV, int D, int H, int W, int 
   ADELL_REQUIRE(workspace_bytes >= adell_cc_workspace(NV, D, H, W),
                 "cc_label: workspace of %ld bytes, %ld needed", workspace_bytes,
                 adell_cc_workspace(NV, D, H, W));
-  CcSrc src = {x, x, NV, use_threshold ? CC_MODE_GT : CC_MODE_NONZERO, 0, threshold};
+  CcSrc src = {x, x, NV, use_threshold ? CC_MODE_GT : CC_MODE_NONZERO, 0, threshold, nullptr, nullptr};
   CcStats st = {nullptr, nullptr, 0};
   return cc_run(src, NV, cc_geom(D, H, W), labels, counts, (char*)workspace, st,
                 (hipStream_t)stream);
@@ -612,7 +632,8 @@ extern "C" int adell_picai_tables(const float* pred, const float* target, long B
   int* lab = reinterpret_cast<int*>(ws + l.off_lab);
   int* n = reinterpret_cast<int*>(ws + l.off_n);
   ADELL_CHECK_HIP(hipMemsetAsync(ws, 0, l.zero_end, s));
-  CcSrc src = {pred, target, B, use_threshold ? CC_MODE_GT : CC_MODE_NONZERO, CC_MODE_TRUNC, threshold};
+  CcSrc src = {pred, target, B, use_threshold ? CC_MODE_GT : CC_MODE_NONZERO, CC_MODE_TRUNC, threshold,
+               nullptr, nullptr};
   CcStats st = {cnt, cmax, l.L};
   const CcGeom g = cc_geom(D, H, W);
   const int rc = cc_run(src, 2 * B, g, lab, n, ws + l.off_cc, st, s);
@@ -631,5 +652,400 @@ extern "C" int adell_picai_tables(const float* pred, const float* target, long B
   hipLaunchKernelGGL(adell_picai_pack_kernel, dim3((unsigned)pb, (unsigned)B), dim3(CC_THREADS), 0, s,
                      B, n, cnt, cmax, l.L, np, pairs, hdr, out);
   ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
+// ---- lesion candidates -------------------------------------------------------------------------
+// The Report-Guided-Annotation post-processing of the reference
+// (adell_mri/modules/extract_lesion_candidates.py): a probability map becomes a detection map whose
+// components carry their peak probability. Static (:19-55): label x >= thr (and != 0) with the
+// sequence above, drop the components of <= min_voxels voxels, paint the others with their
+// (optionally rounded) maximum. Dynamic-fast (:198-211): the same with thr = max(x) / factor, taken
+// on the device. Dynamic (:58-134): rounds of [label the working copy at max / factor, choose the
+// kept component of the largest painted value (ties: the lowest label), reject it if it touches a
+// stored one, store it otherwise, remove it from the working copy], all volumes in lockstep; the
+// kernels of a finished volume exit at once (act). Per round the host reads back act [NV] and
+// nothing else.
+enum { LC_STATIC = 0, LC_DYNAMIC_FAST = 1, LC_DYNAMIC = 2 };
+
+// np.round(float64(max), d) as numpy computes it (multiply, rint, divide; for d < 0 divide, rint,
+// multiply), then the float32 the reference's `all_hard_blobs += hard_blob` stores
+struct LcRound {
+  double scale;        // 10^|d|
+  int how;             // 0: no rounding; 1: d >= 0; 2: d < 0
+};
+__device__ __forceinline__ float lc_paint(float m, LcRound r) {
+  if (r.how == 0) return m;
+  const double d = (double)m;
+  return (float)(r.how == 1 ? rint(d * r.scale) / r.scale : rint(d / r.scale) * r.scale);
+}
+
+struct LcState {       // per volume, [NV] each
+  unsigned* mx;        // ordered maximum of the working copy (0: not taken yet)
+  float* thr;
+  int* act;
+  int* sel;            // the chosen component's label of this round; -1: the whole volume
+  float* selconf;
+  int* adj;            // the chosen component touches a stored one
+  int* pend;           // a choice waits for lc_decide to count it
+};
+
+__device__ __forceinline__ unsigned lc_wave_max(unsigned m) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned u = __shfl_xor(m, o, 64);
+    m = u > m ? u : m;
+  }
+  return m;
+}
+
+// mx[vol] = max over x[vol] (ordered bits; the caller zeroes mx)
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_max_kernel(const float* x, long V,
+                                                                 unsigned* mx) {
+  const long vol = blockIdx.y;
+  const float* xv = x + vol * V;
+  const long v0 = (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
+  unsigned m = 0;
+  for (int k = 0; k < CC_PER; ++k) {
+    const long v = v0 + k;
+    if (v >= V) break;
+    const unsigned o = cc_ord(xv[v]);
+    m = o > m ? o : m;
+  }
+  m = lc_wave_max(m);
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(mx + vol, m);
+}
+
+// dynamic-fast: thr = max / float32(factor), correctly rounded (:200-201)
+__global__ void adell_lc_thr_kernel(long NV, const unsigned* mx, float factor, float* thr) {
+  const long vol = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vol < NV) thr[vol] = __fdiv_rn(cc_unord(mx[vol]), factor);
+}
+
+// static: the kept components (more than minvox voxels) of every volume in ascending label, and
+// cnt / cmax rewritten in place as (kept, painted value bits) for lc_paint_kernel
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_table_kernel(
+    const int* n, int* cnt, unsigned* cmax, long L, int minvox, LcRound r, int* nout, int* ids,
+    float* conf, float* peak, long cap) {
+  const long vol = blockIdx.x;
+  const int nc = n[vol];
+  int* c = cnt + vol * L;
+  unsigned* cm = cmax + vol * L;
+  int carry = 0;
+  for (int base = 0; base < nc; base += CC_THREADS) {
+    const int i = base + threadIdx.x;
+    const int kept = i < nc && c[i] > minvox;
+    int total;
+    const int pos = carry + cc_block_excl_scan(kept, &total);
+    if (i < nc) {
+      const float m = cc_unord(cm[i]);
+      const float p = lc_paint(m, r);
+      if (kept && pos < cap) {
+        ids[vol * cap + pos] = i + 1;
+        conf[vol * cap + pos] = p;
+        peak[vol * cap + pos] = m;
+      }
+      c[i] = kept;
+      cm[i] = __float_as_uint(p);
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) nout[vol] = carry < cap ? carry : (int)cap;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_paint_kernel(const int* lab, long V,
+                                                                   const int* cnt,
+                                                                   const unsigned* cmax, long L,
+                                                                   float* hard, int* indexed) {
+  const long vol = blockIdx.y;
+  const long v0 = (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
+  for (int k = 0; k < CC_PER; ++k) {
+    const long v = v0 + k;
+    if (v >= V) break;
+    const int id = lab[vol * V + v];
+    const bool kept = id && cnt[vol * L + id - 1];
+    hard[vol * V + v] = kept ? __uint_as_float(cmax[vol * L + id - 1]) : 0.0f;
+    indexed[vol * V + v] = kept ? id : 0;
+  }
+}
+
+// dynamic, between the rounds: count the choice of the round before (unless it was rejected), then
+// open the next round (:77-87) or finish the volume
+__global__ void adell_lc_decide_kernel(long NV, LcState st, float factor, int num, int remove_adj,
+                                       int* nout, int* ids, float* conf, float* peak, long cap) {
+  const long vol = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vol >= NV) return;
+  if (st.pend[vol]) {
+    if (!(remove_adj && st.adj[vol])) {
+      const int k = nout[vol];
+      if (k < cap) {
+        ids[vol * cap + k] = k + 1;
+        conf[vol * cap + k] = st.selconf[vol];
+        peak[vol * cap + k] = st.selconf[vol];
+        nout[vol] = k + 1;
+      }
+    }
+    st.pend[vol] = 0;
+    st.adj[vol] = 0;
+  }
+  if (!st.act[vol]) return;
+  const float m = cc_unord(st.mx[vol]);
+  st.mx[vol] = 0;
+  if (nout[vol] >= num || m < 0.01f) st.act[vol] = 0;      // max_prob_failsafe_stopping_threshold
+  else st.thr[vol] = __fdiv_rn(m, factor);
+}
+
+// dynamic: the kept component with the largest painted value, ties to the lowest label (:101-108:
+// the second labelling numbers the components of one first labelling in the same raster order).
+// sic: when no component survives the size filter (or the best one is painted 0), all_hard_blobs is
+// all zero, `all_hard_blobs == max` is the whole volume, and the reference goes on with that as the
+// "lesion", confidence 0. Reproduced: sel = -1.
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_select_kernel(const int* n, const int* cnt,
+                                                                    const unsigned* cmax, long L,
+                                                                    int minvox, LcRound r,
+                                                                    LcState st) {
+  __shared__ unsigned long long sbest;
+  const long vol = blockIdx.x;
+  if (!st.act[vol]) return;
+  if (threadIdx.x == 0) sbest = 0;
+  __syncthreads();
+  const int nc = n[vol];
+  unsigned long long best = 0;
+  for (int i = threadIdx.x; i < nc; i += CC_THREADS) {
+    if (cnt[vol * L + i] <= minvox) continue;
+    const float p = lc_paint(cc_unord(cmax[vol * L + i]), r);
+    const unsigned long long key =
+        ((unsigned long long)cc_ord(p) << 32) | (0xffffffffu - (unsigned)(i + 1));
+    best = key > best ? key : best;
+  }
+  if (best) atomicMax(&sbest, best);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float p = sbest ? cc_unord((unsigned)(sbest >> 32)) : 0.0f;
+    const bool whole = !(p > 0.0f);
+    st.sel[vol] = whole ? -1 : (int)(0xffffffffu - (unsigned)(sbest & 0xffffffffu));
+    st.selconf[vol] = whole ? 0.0f : p;
+    st.pend[vol] = 1;
+  }
+}
+
+// dynamic: does the chosen component touch a stored voxel (hard > 0 in its 3x3x3 neighbourhood;
+// outside the volume is background) (:114-119)
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_adjacent_kernel(const int* lab, CcGeom g,
+                                                                      const float* hard,
+                                                                      const int* nout, LcState st) {
+  const long vol = blockIdx.y;
+  if (!st.act[vol] || nout[vol] == 0) return;     // nothing stored: nothing to touch
+  const int sel = st.sel[vol];
+  const int* lv = lab + vol * g.V;
+  const float* hv = hard + vol * g.V;
+  const long v0 = (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
+  bool found = false;
+  for (int k = 0; k < CC_PER && !found; ++k) {
+    const long v = v0 + k;
+    if (v >= g.V) break;
+    if (sel >= 0 && lv[v] != sel) continue;
+    const int x = (int)(v % g.W), y = (int)((v / g.W) % g.H), z = (int)(v / ((long)g.W * g.H));
+    for (int dz = -1; dz <= 1 && !found; ++dz) {
+      const int zz = z + dz;
+      if (zz < 0 || zz >= g.D) continue;
+      for (int dy = -1; dy <= 1 && !found; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= g.H) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int xx = x + dx;
+          if (xx < 0 || xx >= g.W) continue;
+          if (hv[((long)zz * g.H + yy) * g.W + xx] > 0.0f) {
+            found = true;
+            break;
+          }
+        }
+      }
+    }
+  }
+  if (found) atomicOr(st.adj + vol, 1);
+}
+
+// dynamic: store the chosen component unless it was rejected (:122-129), remove it from the working
+// copy either way (:132) and take the maximum of what is left for the next round
+__global__ __launch_bounds__(CC_THREADS) void adell_lc_apply_kernel(const int* lab, long V,
+                                                                   float* work, float* hard,
+                                                                   int* indexed, const int* nout,
+                                                                   int remove_adj, LcState st) {
+  const long vol = blockIdx.y;
+  if (!st.act[vol]) return;
+  const int sel = st.sel[vol];
+  const bool store = !(remove_adj && st.adj[vol]);
+  const float c = st.selconf[vol];
+  const int index = nout[vol] + 1;
+  const long v0 = vol * V + (long)blockIdx.x * CC_CHUNK + (long)threadIdx.x * CC_PER;
+  const long vend = (vol + 1) * V;
+  unsigned m = 0;
+  for (int k = 0; k < CC_PER; ++k) {
+    const long v = v0 + k;
+    if (v >= vend) break;
+    if (sel < 0 || lab[v] == sel) {
+      if (store) {
+        hard[v] += c;
+        indexed[v] += index;
+      }
+      work[v] = 0.0f;
+      m = m > 0x80000000u ? m : 0x80000000u;      // cc_ord(0.0f)
+    } else {
+      const unsigned o = cc_ord(work[v]);
+      m = o > m ? o : m;
+    }
+  }
+  m = lc_wave_max(m);
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(st.mx + vol, m);
+}
+
+struct LcLayout {
+  long L;
+  long off_cnt, off_max, stats_end, off_lab, off_n, off_state, off_work, off_cc, total;
+};
+static LcLayout lc_layout(long NV, int D, int H, int W, int mode) {
+  LcLayout l;
+  const long V = (long)D * H * W;
+  l.L = pc_lattice(D, H, W);
+  long o = 0;
+  l.off_cnt = o;   o += cc_align(NV * l.L * 4);
+  l.off_max = o;   o += cc_align(NV * l.L * 4);
+  l.stats_end = o;
+  l.off_lab = o;   o += cc_align(NV * V * 4);
+  l.off_n = o;     o += cc_align(NV * 4);
+  l.off_state = o; o += 7 * cc_align(NV * 4);
+  l.off_work = o;  o += mode == LC_DYNAMIC ? cc_align(NV * V * 4) : 0;
+  l.off_cc = o;    o += cc_label_ws(NV, V);
+  l.total = o;
+  return l;
+}
+
+static bool lc_mode_ok(int mode) { return mode >= LC_STATIC && mode <= LC_DYNAMIC; }
+
+extern "C" long adell_lesion_candidates_workspace(long NV, int D, int H, int W, int mode) {
+  if (!cc_shape_ok(NV, D, H, W) || !lc_mode_ok(mode)) return 0;
+  return lc_layout(NV, D, H, W, mode).total;
+}
+
+extern "C" long adell_lesion_candidates_capacity(int D, int H, int W, int mode, int min_voxels,
+                                                 int num_lesions) {
+  if (!cc_shape_ok(1, D, H, W) || !lc_mode_ok(mode)) return 0;
+  if (mode == LC_DYNAMIC) return num_lesions > 1 ? num_lesions : 1;
+  // a kept component has more than min_voxels voxels, and no mask holds more than the lattice bound
+  const long V = (long)D * H * W, lat = pc_lattice(D, H, W);
+  const long by_size = V / ((min_voxels > 0 ? (long)min_voxels : 0) + 1);
+  const long c = by_size < lat ? by_size : lat;
+  return c > 1 ? c : 1;
+}
+
+extern "C" int adell_lesion_candidates(const float* x, long NV, int D, int H, int W, int mode,
+                                       float threshold, float factor, int min_voxels,
+                                       int num_lesions, int round_decimals, int use_round,
+                                       int remove_adjacent, float* hard, int* indexed, int* n_out,
+                                       int* ids, float* conf, float* peak, long cap, int* rounds,
+                                       void* workspace, long workspace_bytes, void* stream) {
+  ADELL_REQUIRE(x && hard && indexed && n_out && ids && conf && peak && workspace,
+                "lesion_candidates: bad arguments");
+  ADELL_REQUIRE(lc_mode_ok(mode), "lesion_candidates: mode %d (0 static, 1 dynamic-fast, 2 dynamic)",
+                mode);
+  ADELL_REQUIRE(cc_shape_ok(NV, D, H, W), "lesion_candidates: bad shape %ld x %d x %d x %d", NV, D, H,
+                W);
+  ADELL_REQUIRE(!use_round || (round_decimals >= -300 && round_decimals <= 300),
+                "lesion_candidates: max_prob_round_decimals %d", round_decimals);
+  ADELL_REQUIRE(cap >= adell_lesion_candidates_capacity(D, H, W, mode, min_voxels, num_lesions),
+                "lesion_candidates: table of %ld entries per volume, %ld needed", cap,
+                adell_lesion_candidates_capacity(D, H, W, mode, min_voxels, num_lesions));
+  const LcLayout l = lc_layout(NV, D, H, W, mode);
+  ADELL_REQUIRE(workspace_bytes >= l.total, "lesion_candidates: workspace of %ld bytes, %ld needed",
+                workspace_bytes, l.total);
+  const hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  int* cnt = reinterpret_cast<int*>(ws + l.off_cnt);
+  unsigned* cmax = reinterpret_cast<unsigned*>(ws + l.off_max);
+  int* lab = reinterpret_cast<int*>(ws + l.off_lab);
+  int* n = reinterpret_cast<int*>(ws + l.off_n);
+  const long sw = cc_align(NV * 4);
+  LcState st;
+  st.mx = reinterpret_cast<unsigned*>(ws + l.off_state);
+  st.thr = reinterpret_cast<float*>(ws + l.off_state + sw);
+  st.act = reinterpret_cast<int*>(ws + l.off_state + 2 * sw);
+  st.sel = reinterpret_cast<int*>(ws + l.off_state + 3 * sw);
+  st.selconf = reinterpret_cast<float*>(ws + l.off_state + 4 * sw);
+  st.adj = reinterpret_cast<int*>(ws + l.off_state + 5 * sw);
+  st.pend = reinterpret_cast<int*>(ws + l.off_state + 6 * sw);
+  LcRound r = {1.0, 0};
+  if (use_round) {
+    r.how = round_decimals >= 0 ? 1 : 2;
+    for (int k = 0; k < (round_decimals >= 0 ? round_decimals : -round_decimals); ++k) r.scale *= 10.0;
+  }
+  const CcGeom g = cc_geom(D, H, W);
+  const CcStats stats = {cnt, cmax, l.L};
+  const long nb = cc_nb(g.V);
+  ADELL_REQUIRE(nb < (1L << 31) && NV < 65536, "lesion_candidates: %ld volumes are too many to grid",
+                NV);
+  const dim3 lin((unsigned)nb, (unsigned)NV), per_vol((unsigned)((NV + 63) / 64));
+  if (rounds) *rounds = 0;
+  ADELL_CHECK_HIP(hipMemsetAsync(ws + l.off_state, 0, 7 * sw, s));
+
+  if (mode != LC_DYNAMIC) {
+    if (mode == LC_DYNAMIC_FAST) {
+      hipLaunchKernelGGL(adell_lc_max_kernel, lin, dim3(CC_THREADS), 0, s, x, g.V, st.mx);
+      ADELL_CHECK_HIP(hipGetLastError());
+      hipLaunchKernelGGL(adell_lc_thr_kernel, per_vol, dim3(64), 0, s, NV, st.mx, factor, st.thr);
+      ADELL_CHECK_HIP(hipGetLastError());
+    }
+    ADELL_CHECK_HIP(hipMemsetAsync(ws, 0, l.stats_end, s));
+    const CcSrc src = {x, x, NV, CC_MODE_GE, CC_MODE_GE, threshold,
+                       mode == LC_DYNAMIC_FAST ? st.thr : nullptr, nullptr};
+    const int rc = cc_run(src, NV, g, lab, n, ws + l.off_cc, stats, s);
+    if (rc != ADELL_OK) return rc;
+    hipLaunchKernelGGL(adell_lc_table_kernel, dim3((unsigned)NV), dim3(CC_THREADS), 0, s, n, cnt, cmax,
+                       l.L, min_voxels, r, n_out, ids, conf, peak, cap);
+    ADELL_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(adell_lc_paint_kernel, lin, dim3(CC_THREADS), 0, s, lab, g.V, cnt, cmax, l.L,
+                       hard, indexed);
+    ADELL_CHECK_HIP(hipGetLastError());
+    return ADELL_OK;
+  }
+
+  float* work = reinterpret_cast<float*>(ws + l.off_work);
+  ADELL_CHECK_HIP(hipMemcpyAsync(work, x, NV * g.V * 4, hipMemcpyDeviceToDevice, s));
+  ADELL_CHECK_HIP(hipMemsetAsync(hard, 0, NV * g.V * 4, s));
+  ADELL_CHECK_HIP(hipMemsetAsync(indexed, 0, NV * g.V * 4, s));
+  ADELL_CHECK_HIP(hipMemsetAsync(n_out, 0, NV * 4, s));
+  ADELL_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)st.act, 1, NV, s));
+  hipLaunchKernelGGL(adell_lc_max_kernel, lin, dim3(CC_THREADS), 0, s, work, g.V, st.mx);
+  ADELL_CHECK_HIP(hipGetLastError());
+  std::vector<int> act(NV);
+  // a round removes more than min_voxels voxels of a volume, or all of them
+  const long max_rounds = g.V / ((min_voxels > 0 ? (long)min_voxels : 0) + 1) + 2;
+  for (long round = 0;; ++round) {
+    hipLaunchKernelGGL(adell_lc_decide_kernel, per_vol, dim3(64), 0, s, NV, st, factor, num_lesions,
+                       remove_adjacent, n_out, ids, conf, peak, cap);
+    ADELL_CHECK_HIP(hipGetLastError());
+    // the one read-back of the round: which volumes go on
+    ADELL_CHECK_HIP(hipMemcpyAsync(act.data(), st.act, NV * 4, hipMemcpyDeviceToHost, s));
+    ADELL_CHECK_HIP(hipStreamSynchronize(s));
+    bool any = false;
+    for (long v = 0; v < NV; ++v) any = any || act[v];
+    if (!any) break;
+    ADELL_REQUIRE(round < max_rounds, "lesion_candidates: no end after %ld rounds", round);
+    if (rounds) *rounds = (int)(round + 1);
+    ADELL_CHECK_HIP(hipMemsetAsync(ws, 0, l.stats_end, s));
+    const CcSrc src = {work, work, NV, CC_MODE_GE, CC_MODE_GE, 0.0f, st.thr, st.act};
+    const int rc = cc_run(src, NV, g, lab, n, ws + l.off_cc, stats, s);
+    if (rc != ADELL_OK) return rc;
+    hipLaunchKernelGGL(adell_lc_select_kernel, dim3((unsigned)NV), dim3(CC_THREADS), 0, s, n, cnt, cmax,
+                       l.L, min_voxels, r, st);
+    ADELL_CHECK_HIP(hipGetLastError());
+    if (remove_adjacent) {
+      hipLaunchKernelGGL(adell_lc_adjacent_kernel, lin, dim3(CC_THREADS), 0, s, lab, g, hard, n_out, st);
+      ADELL_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(adell_lc_apply_kernel, lin, dim3(CC_THREADS), 0, s, lab, g.V, work, hard,
+                       indexed, n_out, remove_adjacent, st);
+    ADELL_CHECK_HIP(hipGetLastError());
+  }
   return ADELL_OK;
 }

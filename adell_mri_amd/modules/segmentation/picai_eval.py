@@ -237,14 +237,31 @@ class PicaiEval:
     [B, D, H, W] device tensors, raw (the prediction is thresholded at ``threshold`` on the device;
     ``threshold=None`` takes it as a detection map). Each update is one launch sequence and ONE host
     synchronisation (the record sizes); the records themselves are copied asynchronously into pinned
-    host memory, and ``compute`` waits for them. State: plain attributes (no buffers)."""
+    host memory, and ``compute`` waits for them. State: plain attributes (no buffers).
 
-    def __init__(self, min_overlap=0.1, threshold=0.1):
+    ``extract_lesions=True`` is the reference's other route (``get_lesions(x, threshold,
+    extract_lesions=True)``, pl.py:76-97, and entrypoints/segmentation/test.py:361-399): every
+    prediction goes through ``ops.lesion_candidates`` first (``threshold`` a number, ``"dynamic"`` or
+    ``"dynamic-fast"``; the other keywords are those of ``extract_lesion_candidates``) and the
+    resulting detection map, whose components carry their peak probability, is evaluated as it is.
+    The dynamic mode adds its own synchronisations (one per round plus one)."""
+
+    def __init__(self, min_overlap=0.1, threshold=0.1, extract_lesions=False,
+                 min_voxels_detection=10, num_lesions_to_extract=5, dynamic_threshold_factor=2.5,
+                 max_prob_round_decimals=None, remove_adjacent_lesion_candidates=True):
         if not 0.1 <= float(min_overlap) <= 1.0:
             raise ValueError(f"PicaiEval: min_overlap must lie in [0.1, 1], got {min_overlap}: the "
                              "device keeps only the (lesion, candidate) pairs with IoU >= 0.1")
         self.min_overlap = float(min_overlap)
         self.threshold = threshold
+        self.extract_lesions = bool(extract_lesions)
+        self.extract_kwargs = dict(
+            min_voxels_detection=min_voxels_detection, num_lesions_to_extract=num_lesions_to_extract,
+            dynamic_threshold_factor=dynamic_threshold_factor,
+            max_prob_round_decimals=max_prob_round_decimals,
+            remove_adjacent_lesion_candidates=remove_adjacent_lesion_candidates)
+        if isinstance(threshold, str) and not self.extract_lesions:
+            raise ValueError(f"PicaiEval: threshold {threshold!r} needs extract_lesions=True")
         self.reset()
 
     def reset(self):
@@ -266,7 +283,11 @@ class PicaiEval:
         if pred.shape != y.shape:
             raise ValueError(f"PicaiEval.update: prediction {tuple(pred.shape)} and target "
                              f"{tuple(y.shape)} differ")
-        hdr, out = ops.picai_tables(pred, y, self.threshold)
+        if self.extract_lesions:
+            hard_blobs = ops.lesion_candidates(pred, self.threshold, **self.extract_kwargs)[0]
+            hdr, out = ops.picai_tables(hard_blobs, y, threshold=None)
+        else:
+            hdr, out = ops.picai_tables(pred, y, self.threshold)
         h = hdr.cpu().numpy().astype(np.int64)       # the one host synchronisation
         sizes = 3 + h[:, 1] + 2 * h[:, 0] + 3 * h[:, 2]
         total = int(sizes.sum())
@@ -316,11 +337,15 @@ class PicaiEval:
         return {"AP": float(vals[0]), "R": float(vals[1]), "AUC": float(vals[2])}
 
 
-def evaluate(y_det, y_true, min_overlap=0.1, threshold=0.1):
+def evaluate(y_det, y_true, min_overlap=0.1, threshold=0.1, extract_lesions=False,
+             **extract_kwargs):
     """``picai_eval.evaluate(y_det, y_true, y_det_postprocess_func=get_lesions)`` over lists or
     batches of device tensors (one 3-D volume per case; the cases of a list may differ in shape).
-    Returns a ``Metrics``; ValueError for ``min_overlap`` below 0.1."""
-    acc = PicaiEval(min_overlap=min_overlap, threshold=threshold)
+    Returns a ``Metrics``; ValueError for ``min_overlap`` below 0.1. With ``extract_lesions`` it is
+    ``evaluate(y_det=[extract_lesion_candidates(p, threshold, ...)[0] for p in y_det], y_true,
+    y_det_postprocess_func=None)`` (``extract_kwargs``: see ``PicaiEval``)."""
+    acc = PicaiEval(min_overlap=min_overlap, threshold=threshold, extract_lesions=extract_lesions,
+                    **extract_kwargs)
     if isinstance(y_det, (list, tuple)) or isinstance(y_true, (list, tuple)):
         dets, trues = list(y_det), list(y_true)
         if len(dets) != len(trues):

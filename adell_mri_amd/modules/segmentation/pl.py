@@ -41,6 +41,17 @@ from ...utils.optimizer_factory import (OPTIMIZER_MATCH, get_optimizer,  # noqa:
                                         optimizer_eps_from_precision)
 
 
+def get_lesions(x, threshold=0.1, extract_lesions=False):
+    """The detection map of a prediction (pl.py:76-97): ``x > threshold``, or with ``extract_lesions``
+    the ``hard_blobs`` of ``extract_lesion_candidates(x, threshold=threshold)`` (``threshold`` may
+    then be ``"dynamic"`` or ``"dynamic-fast"``), computed on the device."""
+    if extract_lesions is True:
+        from ..extract_lesion_candidates import extract_lesion_candidates
+
+        return extract_lesion_candidates(x, threshold=threshold)[0]
+    return x > threshold
+
+
 def update_metrics(cls, metrics, pred, y, pred_class, y_class, **kwargs) -> None:
     """Update every metric of ``metrics`` with the prediction ``pred`` and the ground truth ``y``
     (pl.py:100-145): ONE fused update for the whole dict (two launches, no host synchronisation).
@@ -93,6 +104,12 @@ class UNetBasePL(_Base):
     # (sic: pl.py:503-509 zips pred_final with y, not y[m:M]); the semi-supervised wrapper pairs
     # them correctly (semi_supervised_segmentation/pl.py:572-577)
     picai_test_pairs_whole_batch = True
+    # how the PI-CAI accumulator turns a prediction into a detection map: get_lesions' arguments
+    # (pl.py:76-97). The reference's constructors do not take them; set them on the module.
+    # picai_extract_lesions = True runs extract_lesion_candidates (picai_threshold may then be
+    # "dynamic" or "dynamic-fast"), so that candidates carry their peak probability.
+    picai_threshold = 0.1
+    picai_extract_lesions = False
 
     def __init__(self):
         super().__init__()
@@ -198,7 +215,8 @@ class UNetBasePL(_Base):
                 "have equal rank')")
         acc = self.__dict__.get("_picai")
         if acc is None:
-            acc = PicaiEval()
+            acc = PicaiEval(threshold=self.picai_threshold,
+                            extract_lesions=self.picai_extract_lesions)
             self.__dict__["_picai"] = acc
         return acc
 

@@ -1925,6 +1925,94 @@ def picai_tables(pred, target, threshold=0.1):
     return hdr, out
 
 
+_LC_MODES = {"dynamic-fast": 1, "dynamic": 2}
+
+
+def _lesion_candidates(x, threshold, min_voxels_detection, num_lesions_to_extract,
+                       dynamic_threshold_factor, max_prob_round_decimals,
+                       remove_adjacent_lesion_candidates):
+    """``lesion_candidates`` plus the unrounded peak of every kept component and the number of
+    rounds the dynamic mode ran (None for the static modes)."""
+    import math
+
+    if not torch.is_tensor(x):
+        raise TypeError(f"lesion_candidates: expected a device tensor, got {type(x).__name__}")
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(
+            f"lesion_candidates: {x.dtype} input: the device path is fp32 (float16 / bfloat16 are "
+            "converted, as the reference converts float16); float64 maxima cannot be kept, and integer "
+            "or complex maps are not probabilities")
+    if isinstance(threshold, str):
+        if threshold not in _LC_MODES:
+            raise ValueError(f"lesion_candidates: threshold {threshold!r}: 'dynamic', 'dynamic-fast' "
+                             "or a number")
+        mode, thr = _LC_MODES[threshold], 0.0
+    else:
+        mode, thr = 0, float(threshold)
+    lead = tuple(x.shape[:-3])
+    v = _volumes(x, "lesion_candidates")
+    NV, D, H, W = (int(s) for s in v.shape)
+    minvox = max(-1, min(int(math.floor(min_voxels_detection)), 2 ** 31 - 1))
+    num = max(0, min(int(num_lesions_to_extract), 2 ** 31 - 1))
+    use_round = max_prob_round_decimals is not None
+    lib = _lib.lib()
+    cap = int(lib.adell_lesion_candidates_capacity(D, H, W, mode, minvox, num))
+    ws_bytes = int(lib.adell_lesion_candidates_workspace(max(NV, 1), D, H, W, mode))
+    if cap <= 0 or ws_bytes <= 0:
+        raise AdellHipError(f"lesion_candidates: unsupported shape {tuple(x.shape)}")
+    dev = v.device
+    hard = torch.empty(v.shape, dtype=torch.float32, device=dev)
+    indexed = torch.empty(v.shape, dtype=torch.int32, device=dev)
+    n = torch.zeros(NV, dtype=torch.int32, device=dev)
+    ids = torch.zeros((NV, cap), dtype=torch.int32, device=dev)
+    conf = torch.zeros((NV, cap), dtype=torch.float32, device=dev)
+    peak = torch.zeros((NV, cap), dtype=torch.float32, device=dev)
+    rounds = ctypes.c_int(0)
+    if NV:
+        ws = _workspace(ws_bytes, dev)
+        check(lib.adell_lesion_candidates(
+            _ptr(v), NV, D, H, W, mode, thr, float(dynamic_threshold_factor), minvox, num,
+            int(max_prob_round_decimals) if use_round else 0, int(use_round),
+            int(bool(remove_adjacent_lesion_candidates)), _ptr(hard), _ptr(indexed), _ptr(n), _ptr(ids),
+            _ptr(conf), _ptr(peak), cap, ctypes.byref(rounds), _ptr(ws), ws_bytes, _stream()))
+    return (hard.view(x.shape), indexed.view(x.shape), n.view(lead), ids.view(lead + (cap,)),
+            conf.view(lead + (cap,)), peak.view(lead + (cap,)), rounds.value if mode == 2 else None)
+
+
+def lesion_candidates(x, threshold="dynamic-fast", min_voxels_detection=10, num_lesions_to_extract=5,
+                      dynamic_threshold_factor=2.5, max_prob_round_decimals=None,
+                      remove_adjacent_lesion_candidates=True):
+    """The reference's ``extract_lesion_candidates`` (adell_mri/modules/extract_lesion_candidates.py,
+    Report-Guided-Annotation) on the device (csrc/components.hip, adell_lesion_candidates): a
+    probability map [D, H, W], or every volume of a batch [..., D, H, W], becomes a detection map whose
+    26-connected components carry their peak probability. ``threshold``: a number (static, :19-55:
+    foreground ``x >= threshold``, components of ``<= min_voxels_detection`` voxels dropped),
+    ``"dynamic-fast"`` (:198-211: static at ``max(x) / dynamic_threshold_factor`` per volume) or
+    ``"dynamic"`` (:58-134: up to ``num_lesions_to_extract`` rounds per volume, each at the remaining
+    maximum over the factor, taking the component of the largest confidence and rejecting it when it
+    touches a stored one and ``remove_adjacent_lesion_candidates``). Bit-identical to the reference
+    run on every volume, its whole-volume candidate of confidence 0 included (the dynamic mode on a
+    map whose components are all too small).
+
+    Input: float32; float16 and bfloat16 are converted to float32; anything else raises TypeError.
+    Values are assumed finite and non-negative (probabilities).
+
+    Returns device tensors ``(hard_blobs, indexed, n, ids, confidences)``: ``hard_blobs`` float32 and
+    ``indexed`` int32 of x's shape; ``n`` int32 of x's leading shape, the number of candidates;
+    ``ids`` int32 and ``confidences`` float32 [..., K], of which the first ``n`` entries per volume
+    are the candidates in ascending index (the scipy label in the static modes, 1..n in the dynamic
+    one) with the value they are painted with (rounded to ``max_prob_round_decimals`` as
+    ``float32(np.round(float64(peak), d))``), the rest 0.
+
+    Host synchronisations: none in the static and dynamic-fast modes. The dynamic mode synchronises
+    once per round plus once (rounds + 1; the rounds of a batch are those of its slowest volume, at
+    most ``num_lesions_to_extract`` plus the rejected candidates), each time reading back one int32
+    per volume."""
+    return _lesion_candidates(x, threshold, min_voxels_detection, num_lesions_to_extract,
+                              dynamic_threshold_factor, max_prob_round_decimals,
+                              remove_adjacent_lesion_candidates)[:5]
+
+
 # ---- shifted-window (SWIN) token path -----------------------------------------------------
 def gather_nd(x, dims, axes, out=None):
     """Flat contiguous gather of ``x`` (csrc/window.hip). ``dims``: [(size, axis, mult)] of the

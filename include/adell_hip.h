@@ -860,6 +860,33 @@ int adell_picai_tables(const float* pred, const float* target, long B, int D, in
                        int use_threshold, float threshold, int* hdr, int* out, long out_capacity,
                        void* workspace, long workspace_bytes, void* stream);
 
+/* Lesion-candidate extraction (csrc/components.hip): the reference's
+ * adell_mri/modules/extract_lesion_candidates.py (Report-Guided-Annotation), reached from
+ * get_lesions(extract_lesions=True) (modules/segmentation/pl.py:76-97) and from the test entry point
+ * (entrypoints/segmentation/test.py:361-399), on fp32 volumes x [NV][D][H][W] of finite,
+ * non-negative values. mode 0, static (:19-55): foreground x >= threshold and x != 0, 26-connected
+ * labelling as adell_cc_label, components of <= min_voxels voxels dropped, every other one painted
+ * with its maximum in hard [NV][D][H][W] and with its scipy label in indexed (int32). use_round:
+ * the painted value is float32(np.round(float64(max), round_decimals)). mode 1, dynamic-fast
+ * (:198-211): static with threshold = max(x_i) / factor per volume, a correctly rounded fp32
+ * division on the device. mode 2, dynamic (:58-134): up to num_lesions rounds per volume of
+ * [threshold = max(working) / factor, stop below 0.01; static extraction; choose the kept component
+ * of the largest painted value, ties to the lowest label; reject it when remove_adjacent and a stored
+ * voxel > 0 lies in the 3x3x3 neighbourhood of one of its voxels, else store it with index 1 + the
+ * number stored; remove it from the working copy], including the reference's whole-volume
+ * "candidate" of confidence 0 when no component survives the size filter.
+ * n_out [NV], ids / conf / peak [NV][cap]: the kept components in ascending index, their painted
+ * value and their unrounded maximum; cap >= adell_lesion_candidates_capacity. rounds (host, may be
+ * null): the rounds the dynamic mode ran. Modes 0 and 1 never synchronise with the host; mode 2
+ * synchronises rounds + 1 times, reading back one int per volume each time. */
+long adell_lesion_candidates_workspace(long NV, int D, int H, int W, int mode);
+long adell_lesion_candidates_capacity(int D, int H, int W, int mode, int min_voxels, int num_lesions);
+int adell_lesion_candidates(const float* x, long NV, int D, int H, int W, int mode, float threshold,
+                            float factor, int min_voxels, int num_lesions, int round_decimals,
+                            int use_round, int remove_adjacent, float* hard, int* indexed, int* n_out,
+                            int* ids, float* conf, float* peak, long cap, int* rounds,
+                            void* workspace, long workspace_bytes, void* stream);
+
 /* ---- shifted-window (SWIN) token path: vit.py:33-45,95-129,1005-1256; linear_blocks.py:358-417 */
 /* out (contiguous over sizes[0..nd)) = gather of `in`: out dim d adds coord*mult[d] to input
  * axis axis[d]; input axis a has extent / stride (elements) / cyclic shift:
