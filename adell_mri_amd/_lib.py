@@ -146,6 +146,7 @@ SIGNATURES = {
     "adell_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f,
                                  ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp]),
     "adell_attention_strided_ok": (_i, [_i, _i, _i]),
+    "adell_attention_plan": (_i, [_i] * 5 + [_vp]),
     "adell_attention_fwd_strided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _f,
                                          ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp]),
     "adell_attention_bwd_strided": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i,

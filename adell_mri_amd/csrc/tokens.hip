@@ -8,6 +8,8 @@
 // the token axis). Sequences are short (216 tokens at config 3): these kernels
 // are latency/HBM-bound fp32 VALU code, one wave per row, wavefront-shuffle
 // reductions, fixed summation order.
+#include <initializer_list>
+
 #include "common.h"
 
 ADELL_RNG_STEP_DEFINE(tokens)
@@ -379,33 +381,35 @@ __global__ __launch_bounds__(256) void adell_attention_fwd_kernel(AttArgs a) {
   }
 }
 
-// dQ: one wave per query row (same structure as forward).
+// dQ: one wave per query row (same structure as forward). ROWS: query rows per block (ATT_ROWS, or
+// half of it for head dims whose 16-row block would not fit the LDS: adell_att_plan).
+template <int ROWS>
 __global__ __launch_bounds__(256) void adell_attention_bwd_q_kernel(AttArgs a) {
   extern __shared__ float sh[];
   const int AP = a.A + 1, DP = a.Dv + 1;
   float* sK = sh;                        // [ATT_TK][AP]
   float* sV = sK + ATT_TK * AP;          // [ATT_TK][DP]
-  float* sQ = sV + ATT_TK * DP;          // [ATT_ROWS][A]
-  float* sdO = sQ + ATT_ROWS * a.A;      // [ATT_ROWS][Dv]
-  float* sP = sdO + ATT_ROWS * a.Dv;     // [4][ATT_TK]  (holds dS)
+  float* sQ = sV + ATT_TK * DP;          // [ROWS][A]
+  float* sdO = sQ + ROWS * a.A;      // [ROWS][Dv]
+  float* sP = sdO + ROWS * a.Dv;     // [4][ATT_TK]  (holds dS)
   const int bh = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row0 = blockIdx.x * ATT_ROWS;
+  const int row0 = blockIdx.x * ROWS;
   const float* qb = a.q + (size_t)bh * a.T * a.A;
   const float* kb = a.k + (size_t)bh * a.T * a.A;
   const float* vb = a.v + (size_t)bh * a.T * a.Dv;
   const float* ob = a.o + (size_t)bh * a.T * a.Dv;
   const float* gb = a.dout + (size_t)bh * a.T * a.Dv;
-  for (int i = threadIdx.x; i < ATT_ROWS * a.A; i += 256) {
+  for (int i = threadIdx.x; i < ROWS * a.A; i += 256) {
     const int r = i / a.A, c = i - r * a.A;
     sQ[i] = (row0 + r < a.T) ? qb[(size_t)(row0 + r) * a.A + c] : 0.f;
   }
-  for (int i = threadIdx.x; i < ATT_ROWS * a.Dv; i += 256) {
+  for (int i = threadIdx.x; i < ROWS * a.Dv; i += 256) {
     const int r = i / a.Dv, c = i - r * a.Dv;
     sdO[i] = (row0 + r < a.T) ? gb[(size_t)(row0 + r) * a.Dv + c] : 0.f;
   }
   __syncthreads();
-  constexpr int RPW = ATT_ROWS / 4;
+  constexpr int RPW = ROWS / 4;
   constexpr int MAXA = 4;  // A <= 256
   float Dr[RPW], lse[RPW], acc[RPW][MAXA];
 #pragma unroll
@@ -477,32 +481,33 @@ __global__ __launch_bounds__(256) void adell_attention_bwd_q_kernel(AttArgs a) {
 }
 
 // dK, dV: one wave per key row; queries streamed through LDS in tiles of 64.
+template <int ROWS>
 __global__ __launch_bounds__(256) void adell_attention_bwd_kv_kernel(AttArgs a) {
   extern __shared__ float sh[];
   const int AP = a.A + 1, DP = a.Dv + 1;
   float* sQ = sh;                        // [ATT_TK][AP]   query tile
   float* sdO = sQ + ATT_TK * AP;         // [ATT_TK][DP]
-  float* sK = sdO + ATT_TK * DP;         // [ATT_ROWS][A]  this block's keys
-  float* sV = sK + ATT_ROWS * a.A;       // [ATT_ROWS][Dv]
-  float* sP = sV + ATT_ROWS * a.Dv;      // [4][2][ATT_TK] (p, dS)
+  float* sK = sdO + ATT_TK * DP;         // [ROWS][A]  this block's keys
+  float* sV = sK + ROWS * a.A;       // [ROWS][Dv]
+  float* sP = sV + ROWS * a.Dv;      // [4][2][ATT_TK] (p, dS)
   float* sL = sP + 4 * 2 * ATT_TK;       // [ATT_TK][2] lse, D of the query tile
   const int bh = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row0 = blockIdx.x * ATT_ROWS;
+  const int row0 = blockIdx.x * ROWS;
   const float* qb = a.q + (size_t)bh * a.T * a.A;
   const float* kb = a.k + (size_t)bh * a.T * a.A;
   const float* vb = a.v + (size_t)bh * a.T * a.Dv;
   const float* ob = a.o + (size_t)bh * a.T * a.Dv;
   const float* gb = a.dout + (size_t)bh * a.T * a.Dv;
-  for (int i = threadIdx.x; i < ATT_ROWS * a.A; i += 256) {
+  for (int i = threadIdx.x; i < ROWS * a.A; i += 256) {
     const int r = i / a.A, c = i - r * a.A;
     sK[i] = (row0 + r < a.T) ? kb[(size_t)(row0 + r) * a.A + c] : 0.f;
   }
-  for (int i = threadIdx.x; i < ATT_ROWS * a.Dv; i += 256) {
+  for (int i = threadIdx.x; i < ROWS * a.Dv; i += 256) {
     const int r = i / a.Dv, c = i - r * a.Dv;
     sV[i] = (row0 + r < a.T) ? vb[(size_t)(row0 + r) * a.Dv + c] : 0.f;
   }
-  constexpr int RPW = ATT_ROWS / 4;
+  constexpr int RPW = ROWS / 4;
   constexpr int MAXC = 4;
   float dk[RPW][MAXC], dv[RPW][MAXC];
 #pragma unroll
@@ -995,11 +1000,60 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_kv_kernel(AttArgs a) 
     }
 }
 
-static bool adell_att_mfma_ok(int T, int A, int Dv) {
-  return T >= 16 && (A == 32 || A == 64 || A == 128) && (Dv == 32 || Dv == 64 || Dv == 128);
+// ---------------------------------------------------------------------------------------------
+// Launch plan of one attention pass (which: 0 forward, 1 backward dQ, 2 backward dK/dV): every
+// decision the launchers below take, and what adell_attention_plan reports. Host only.
+//   MFMA kernels: A, Dv in {32, 64, 128}, T >= 16, 16-byte aligned operands; resident while the
+//   padded sequence fits ADELL_ATT_RES_BYTES of LDS (dK/dV rows carry D and lse: 2 floats more).
+//   Vector-ALU kernels: everything else up to head dims of 256; the two backward kernels halve
+//   their query / key row block when 16 rows would not fit the LDS budget (A + Dv > 502 / 507).
+// ---------------------------------------------------------------------------------------------
+#define ADELL_ATT_RES_BYTES (150 * 1024)
+#define ADELL_ATT_LDS_MAX (160 * 1024)
+
+struct AdellAttPlan {
+  int path;     // ADELL_ATT_*
+  size_t lds;   // dynamic LDS bytes
+  int grid_x;   // blocks per sequence (grid y = BH)
+  int rows;     // query (dK/dV: key) rows per block
+};
+
+static size_t adell_att_valu_lds(int which, int A, int Dv, int rows) {
+  size_t fl = (size_t)ATT_TK * (A + 1) + (size_t)rows * A;
+  if (which == 0) fl += (size_t)ATT_TK * Dv + 4 * ATT_TK;
+  else fl += (size_t)ATT_TK * (Dv + 1) + (size_t)rows * Dv + (which == 1 ? 4 : 10) * ATT_TK;
+  return sizeof(float) * fl;
 }
 
-// which: 0 forward, 1 backward dQ, 2 backward dK/dV
+static AdellAttPlan adell_att_plan(int which, int T, int A, int Dv, bool aligned) {
+  AdellAttPlan p = {ADELL_ATT_REFUSED, 0, 0, 0};
+  if (T <= 0 || A <= 0 || Dv <= 0 || A > 256 || Dv > 256) return p;
+  const bool mfma = T >= 16 && (A == 32 || A == 64 || A == 128) && (Dv == 32 || Dv == 64 || Dv == 128) &&
+                    aligned && !g_adell_tune.attn_nomfma;
+  if (mfma) {
+    const size_t tpad = (size_t)((T + 31) & ~31);
+    const size_t per_row = (size_t)(A + 1) + (size_t)(Dv + 1) + (which == 2 ? 2 : 0);
+    const size_t res = sizeof(float) * tpad * per_row;
+    p.rows = 128;
+    p.grid_x = adell_cdiv(T, 128);
+    if (res <= ADELL_ATT_RES_BYTES) {   // the whole sequence stays in LDS
+      p.path = ADELL_ATT_MFMA_RESIDENT;
+      p.lds = res;
+    } else {
+      p.path = ADELL_ATT_MFMA_STREAMED;
+      p.lds = sizeof(float) * 32 * per_row;
+    }
+    return p;
+  }
+  p.rows = ATT_ROWS;
+  if (which != 0 && adell_att_valu_lds(which, A, Dv, p.rows) > ADELL_ATT_LDS_MAX) p.rows = ATT_ROWS / 2;
+  p.lds = adell_att_valu_lds(which, A, Dv, p.rows);
+  if (p.lds > ADELL_ATT_LDS_MAX) return p;   // (not reached with head dims <= 256)
+  p.path = ADELL_ATT_VALU;
+  p.grid_x = adell_cdiv(T, p.rows);
+  return p;
+}
+
 template <int AT, int DT, bool RES>
 static int adell_att_mfma_launch3(int which, const AttArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   if (which == 0) return adell_launch<adell_attn_mfma_fwd_kernel<AT, DT, RES>>(grid, dim3(256), lds, st, a);
@@ -1007,29 +1061,44 @@ static int adell_att_mfma_launch3(int which, const AttArgs& a, dim3 grid, size_t
   return adell_launch<adell_attn_mfma_bwd_kv_kernel<AT, DT, RES>>(grid, dim3(256), lds, st, a);
 }
 template <int AT, int DT>
-static int adell_att_mfma_launch2(int which, const AttArgs& a, int BH, hipStream_t st) {
-  const dim3 grid((unsigned)adell_cdiv(a.T, 128), (unsigned)BH);
-  const size_t tpad = (size_t)((a.T + 31) & ~31);
-  const size_t per_row = (size_t)(AT * 32 + 1) + (size_t)(DT * 32 + 1) + (which == 2 ? 2 : 0);
-  const size_t res = sizeof(float) * tpad * per_row;
-  if (res <= 150 * 1024)   // the whole sequence stays in LDS
-    return adell_att_mfma_launch3<AT, DT, true>(which, a, grid, res, st);
-  return adell_att_mfma_launch3<AT, DT, false>(which, a, grid, sizeof(float) * 32 * per_row, st);
+static int adell_att_mfma_launch2(int which, const AttArgs& a, int BH, const AdellAttPlan& p, hipStream_t st) {
+  const dim3 grid((unsigned)p.grid_x, (unsigned)BH);
+  if (p.path == ADELL_ATT_MFMA_RESIDENT)
+    return adell_att_mfma_launch3<AT, DT, true>(which, a, grid, p.lds, st);
+  return adell_att_mfma_launch3<AT, DT, false>(which, a, grid, p.lds, st);
 }
 template <int AT>
-static int adell_att_mfma_launch1(int which, const AttArgs& a, int BH, hipStream_t st) {
+static int adell_att_mfma_launch1(int which, const AttArgs& a, int BH, const AdellAttPlan& p, hipStream_t st) {
   switch (a.Dv) {
-    case 32: return adell_att_mfma_launch2<AT, 1>(which, a, BH, st);
-    case 64: return adell_att_mfma_launch2<AT, 2>(which, a, BH, st);
-    default: return adell_att_mfma_launch2<AT, 4>(which, a, BH, st);
+    case 32: return adell_att_mfma_launch2<AT, 1>(which, a, BH, p, st);
+    case 64: return adell_att_mfma_launch2<AT, 2>(which, a, BH, p, st);
+    default: return adell_att_mfma_launch2<AT, 4>(which, a, BH, p, st);
   }
 }
-static int adell_att_mfma_launch(int which, const AttArgs& a, int BH, hipStream_t st) {
+static int adell_att_mfma_launch(int which, const AttArgs& a, int BH, const AdellAttPlan& p, hipStream_t st) {
   switch (a.A) {
-    case 32: return adell_att_mfma_launch1<1>(which, a, BH, st);
-    case 64: return adell_att_mfma_launch1<2>(which, a, BH, st);
-    default: return adell_att_mfma_launch1<4>(which, a, BH, st);
+    case 32: return adell_att_mfma_launch1<1>(which, a, BH, p, st);
+    case 64: return adell_att_mfma_launch1<2>(which, a, BH, p, st);
+    default: return adell_att_mfma_launch1<4>(which, a, BH, p, st);
   }
+}
+
+template <auto Kern>
+static int adell_att_valu_launch(const AttArgs& a, int BH, const AdellAttPlan& p, hipStream_t st) {
+  return adell_launch<Kern>(dim3((unsigned)p.grid_x, (unsigned)BH), dim3(256), p.lds, st, a);
+}
+
+// one pass of the contiguous or the strided entry, as planned
+static int adell_att_launch(int which, const AttArgs& a, int BH, const AdellAttPlan& p, hipStream_t st) {
+  if (p.path == ADELL_ATT_MFMA_RESIDENT || p.path == ADELL_ATT_MFMA_STREAMED)
+    return adell_att_mfma_launch(which, a, BH, p, st);
+  ADELL_REQUIRE(p.path == ADELL_ATT_VALU, "attention: no kernel for head dims (%d, %d)", a.A, a.Dv);
+  if (which == 0) return adell_att_valu_launch<adell_attention_fwd_kernel>(a, BH, p, st);
+  if (which == 1)
+    return p.rows == ATT_ROWS ? adell_att_valu_launch<adell_attention_bwd_q_kernel<ATT_ROWS>>(a, BH, p, st)
+                              : adell_att_valu_launch<adell_attention_bwd_q_kernel<ATT_ROWS / 2>>(a, BH, p, st);
+  return p.rows == ATT_ROWS ? adell_att_valu_launch<adell_attention_bwd_kv_kernel<ATT_ROWS>>(a, BH, p, st)
+                            : adell_att_valu_launch<adell_attention_bwd_kv_kernel<ATT_ROWS / 2>>(a, BH, p, st);
 }
 
 static int adell_att_check(int BH, int T, int A, int Dv, int nbias, const float* bias) {
@@ -1039,10 +1108,10 @@ static int adell_att_check(int BH, int T, int A, int Dv, int nbias, const float*
   return ADELL_OK;
 }
 
-template <auto Kern>
-static int adell_att_launch(const AttArgs& a, int BH, size_t lds, hipStream_t st) {
-  ADELL_REQUIRE(lds <= 160 * 1024, "attention: head dims need %zu B of LDS (> 160 KiB)", lds);
-  return adell_launch<Kern>(dim3(adell_cdiv(a.T, ATT_ROWS), BH), dim3(256), lds, st, a);
+static bool adell_att_aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (((uintptr_t)p) & 15) return false;
+  return true;
 }
 
 // contiguous [BH][T][A | Dv] operands as strides
@@ -1076,13 +1145,10 @@ extern "C" int adell_attention_fwd(const float* q, const float* k, const float* 
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
-  if (adell_att_mfma_ok(T, A, Dv) && !g_adell_tune.attn_nomfma) {
-    adell_att_contiguous(&a);
-    return adell_att_mfma_launch(0, a, BH, (hipStream_t)stream);
-  }
-  const size_t lds = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * Dv +
-                                      (size_t)ATT_ROWS * A + 4 * ATT_TK);
-  return adell_att_launch<adell_attention_fwd_kernel>(a, BH, lds, (hipStream_t)stream);
+  // the MFMA kernels stage with 16-byte loads: unaligned operands take the vector-ALU kernels
+  const AdellAttPlan p = adell_att_plan(0, T, A, Dv, adell_att_aligned16({q, k, v, out}));
+  adell_att_contiguous(&a);
+  return adell_att_launch(0, a, BH, p, (hipStream_t)stream);
 }
 
 extern "C" int adell_attention_bwd(const float* q, const float* k, const float* v,
@@ -1101,20 +1167,14 @@ extern "C" int adell_attention_bwd(const float* q, const float* k, const float* 
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
-  if (adell_att_mfma_ok(T, A, Dv) && !g_adell_tune.attn_nomfma) {
-    adell_att_contiguous(&a);
-    rc = adell_att_mfma_launch(1, a, BH, (hipStream_t)stream);
-    if (rc != ADELL_OK) return rc;
-    return adell_att_mfma_launch(2, a, BH, (hipStream_t)stream);
-  }
-  const size_t lds_q = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * (Dv + 1) +
-                                        (size_t)ATT_ROWS * A + (size_t)ATT_ROWS * Dv + 4 * ATT_TK);
-  rc = adell_att_launch<adell_attention_bwd_q_kernel>(a, BH, lds_q, (hipStream_t)stream);
+  const bool aligned = adell_att_aligned16({q, k, v, out, dout, dq, dk, dv});
+  const AdellAttPlan pq = adell_att_plan(1, T, A, Dv, aligned), pkv = adell_att_plan(2, T, A, Dv, aligned);
+  ADELL_REQUIRE(pq.path != ADELL_ATT_REFUSED && pkv.path != ADELL_ATT_REFUSED,
+                "attention_bwd: no kernel for head dims (%d, %d)", A, Dv);   // before the first launch
+  adell_att_contiguous(&a);
+  rc = adell_att_launch(1, a, BH, pq, (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
-  const size_t lds_kv = sizeof(float) * ((size_t)ATT_TK * (A + 1) + (size_t)ATT_TK * (Dv + 1) +
-                                         (size_t)ATT_ROWS * A + (size_t)ATT_ROWS * Dv +
-                                         8 * ATT_TK + 2 * ATT_TK);
-  return adell_att_launch<adell_attention_bwd_kv_kernel>(a, BH, lds_kv, (hipStream_t)stream);
+  return adell_att_launch(2, a, BH, pkv, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1125,7 +1185,8 @@ extern "C" int adell_attention_bwd(const float* q, const float* k, const float* 
 // linear_blocks.py:372-417 exist as launches. MFMA-shaped heads only (adell_attention_strided_ok).
 // ---------------------------------------------------------------------------------------------
 extern "C" int adell_attention_strided_ok(int T, int A, int Dv) {
-  return adell_att_mfma_ok(T, A, Dv) && !g_adell_tune.attn_nomfma ? 1 : 0;
+  const int path = adell_att_plan(0, T, A, Dv, true).path;
+  return path == ADELL_ATT_MFMA_RESIDENT || path == ADELL_ATT_MFMA_STREAMED ? 1 : 0;
 }
 
 extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const float* v,
@@ -1150,7 +1211,7 @@ extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const
   if ((rc = adell_att_stride("k", k, strides + 3, A, &a.sk)) != ADELL_OK) return rc;
   if ((rc = adell_att_stride("v", v, strides + 6, Dv, &a.sv)) != ADELL_OK) return rc;
   if ((rc = adell_att_stride("out", out, strides + 9, Dv, &a.so)) != ADELL_OK) return rc;
-  return adell_att_mfma_launch(0, a, B * H, (hipStream_t)stream);
+  return adell_att_launch(0, a, B * H, adell_att_plan(0, T, A, Dv, true), (hipStream_t)stream);
 }
 
 extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const float* v,
@@ -1181,7 +1242,16 @@ extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const
   if ((rc = adell_att_stride("dq", dq, strides + 15, A, &a.sdq)) != ADELL_OK) return rc;
   if ((rc = adell_att_stride("dk", dk, strides + 18, A, &a.sdk)) != ADELL_OK) return rc;
   if ((rc = adell_att_stride("dv", dv, strides + 21, Dv, &a.sdv)) != ADELL_OK) return rc;
-  rc = adell_att_mfma_launch(1, a, B * H, (hipStream_t)stream);
+  rc = adell_att_launch(1, a, B * H, adell_att_plan(1, T, A, Dv, true), (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
-  return adell_att_mfma_launch(2, a, B * H, (hipStream_t)stream);
+  return adell_att_launch(2, a, B * H, adell_att_plan(2, T, A, Dv, true), (hipStream_t)stream);
+}
+
+// Host-only launch plan of one pass of adell_attention_fwd / _bwd (and, with aligned = 1, of the
+// strided entries): the adell_att_plan call the launch makes (include/adell_hip.h: out[4]).
+extern "C" int adell_attention_plan(int pass, int T, int A, int Dv, int aligned, int* out) {
+  ADELL_REQUIRE(out && pass >= 0 && pass <= 2, "attention_plan: bad arguments");
+  const AdellAttPlan p = adell_att_plan(pass, T, A, Dv, aligned != 0);
+  out[0] = p.path; out[1] = (int)p.lds; out[2] = p.grid_x; out[3] = p.rows;
+  return ADELL_OK;
 }

@@ -1491,6 +1491,24 @@ def attention_bwd(q, k, v, bias, out, dout, lse, scale, drop_p=0.0, seed=0, offs
     return dq, dk, dv
 
 
+# launch plan of one attention pass (adell_attention_plan). path: one of ATT_PATHS; lds: dynamic LDS
+# bytes; blocks: grid x (blocks per sequence); rows: query (dK/dV: key) rows per block
+AttPlan = collections.namedtuple("AttPlan", "path lds blocks rows")
+ATT_PATHS = ("valu", "mfma_resident", "mfma_streamed", "refused")
+_ATT_PASSES = {"fwd": 0, "dq": 1, "dkv": 2}
+
+
+def attention_plan(T, A, Dv, which="fwd", aligned=True):
+    """What attention_fwd (``which`` "fwd") or the dQ / dK-dV kernel of attention_bwd ("dq", "dkv")
+    would launch for T tokens and head dims (A, Dv) under the current tuning switches. ``aligned``:
+    every tensor of the call is 16-byte aligned (always, from torch, unless a view starts inside a
+    storage). Host only: no GPU needed."""
+    out = (ctypes.c_int * 4)()
+    check(_lib.lib().adell_attention_plan(_ATT_PASSES[which], int(T), int(A), int(Dv),
+                                          int(bool(aligned)), out))
+    return AttPlan(ATT_PATHS[out[0]], *list(out)[1:])
+
+
 # ---- data movement (U-Net++ dense links) ----------------------------------------------------
 def cat_channels(tensors):
     """Channel concat of NDHWC tensors [N,Ci,D,H,W] -> [N,sum Ci,D,H,W]."""

@@ -544,7 +544,8 @@ int adell_add_bcast(const float* a, const float* b, float* out, long n, long per
                     void* stream);
 int adell_sum_bcast(const float* g, float* db, long n, long period, void* stream);
 /* softmax(q k^T * scale + bias) v per sequence: q,k [BH][T][A]; v,out [BH][T][Dv];
- * bias [nbias][T][T] or NULL (sequence bh uses bias[bh % nbias]); lse [BH][T].
+ * bias [nbias][T][T] or NULL (sequence bh uses bias[bh % nbias]); lse [BH][T]. Head dims A, Dv up
+ * to 256, in the forward and the backward alike (adell_attention_plan below).
  * drop_p > 0 drops attention probabilities (dropout_p of the same call): the mask of entry
  * (bh, query, key) is a Philox function of (seed, rng_offset), regenerated by the backward.
  * F.scaled_dot_product_attention as called at linear_blocks.py:407-414. */
@@ -557,6 +558,24 @@ int adell_attention_bwd(const float* q, const float* k, const float* v, const fl
                         int BH, int T, int A, int Dv, float scale, float drop_p,
                         unsigned long long seed, unsigned int rng_offset, float* dq, float* dk,
                         float* dv, void* stream);
+/* Launch plan of one attention pass, host only (no launch, no tensor read, no device needed): what
+ * adell_attention_fwd (pass 0) or the dQ (pass 1) and dK/dV (pass 2) kernels of adell_attention_bwd
+ * would run under the current tuning switches, decided by the same function the launches call.
+ * aligned: every tensor of the call (forward: q, k, v, out; backward: those and dout, dq, dk, dv) is
+ * 16-byte aligned -- the MFMA kernels stage with 16-byte loads, other operands take the vector-ALU
+ * kernels (the strided entries refuse them). out[4]:
+ *   [0] path (ADELL_ATT_*); [1] dynamic LDS bytes; [2] blocks per sequence (grid x; grid y = BH);
+ *   [3] query (pass 2: key) rows per block.
+ * MFMA paths: A, Dv in {32, 64, 128} and T >= 16; resident while the sequence, padded to a multiple
+ * of 32 rows of A + Dv + 2 (pass 2: + 4) floats, fits 150 KiB of LDS. Vector-ALU: head dims up to
+ * 256 in all three passes; the backward kernels work on 8 instead of 16 rows per block where 16
+ * would not fit 160 KiB (A + Dv > 507 for dQ, > 502 for dK/dV). Refused: head dims above 256
+ * (forward and backward alike, before any launch). */
+#define ADELL_ATT_VALU 0
+#define ADELL_ATT_MFMA_RESIDENT 1
+#define ADELL_ATT_MFMA_STREAMED 2
+#define ADELL_ATT_REFUSED 3
+int adell_attention_plan(int pass, int T, int A, int Dv, int aligned, int* out);
 /* The same attention with every operand addressed by element strides: sequence bh = b * H + h,
  * `strides` holds (item b, head h, token row) triples in the order q, k, v, out (forward: 12
  * values) and q, k, v, out, dout, dq, dk, dv (backward: 24). Q / K / V may stay inside the packed

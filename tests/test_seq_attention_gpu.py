@@ -18,7 +18,9 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("B,H,T,A,Dv", [(2, 3, 216, 64, 64), (1, 2, 50, 32, 64), (3, 1, 130, 64, 32),
-                                        (1, 4, 300, 128, 128)])
+                                        (1, 4, 300, 128, 128),
+                                        # forward / dQ resident with dK/dV streamed; a last block of one tile
+                                        (1, 2, 545, 32, 32), (2, 1, 129, 128, 32)])
 @pytest.mark.parametrize("drop", [0.0, 0.25])
 def test_strided_kernels_are_the_contiguous_ones(cuda, B, H, T, A, Dv, drop):
     g = torch.Generator().manual_seed(T + A)
