@@ -227,6 +227,7 @@ struct AttArgs {
   const float* k;
   const float* v;
   const float* bias;
+  const int* labels; // [nlab][T] region labels or null: -100 between tokens whose labels differ
   const float* o;    // bwd
   const float* dout; // bwd
   const float* lse;  // bwd: [BH][T] log-sum-exp of the scaled scores
@@ -236,6 +237,7 @@ struct AttArgs {
   float* dk;
   float* dv;
   int T, A, Dv, nbias;
+  int nlab, labH;    // item bh / labH reads label row (bh / labH) % nlab
   float scale;
   float drop_p;      // attention-probability dropout (0 = off)
   uint32_t seed_lo, seed_hi, rng_offset;
@@ -249,6 +251,12 @@ struct AttArgs {
 __device__ __forceinline__ size_t att_base(const AttArgs& a, const AttStride& s, int bh) {
   return (size_t)(bh / a.H) * s.b + (size_t)(bh % a.H) * s.h;
 }
+
+// label row of sequence bh (null without labels) and the additive term of one (query, key) pair
+__device__ __forceinline__ const int* att_labels(const AttArgs& a, int bh) {
+  return a.labels ? a.labels + (size_t)((bh / a.labH) % a.nlab) * a.T : nullptr;
+}
+__device__ __forceinline__ float att_label_term(int lq, int lk) { return lq != lk ? -100.f : 0.f; }
 
 // word `i` (0..3) of a Philox block by selects (indexing a local array with a run-time index puts the
 // array in scratch memory)
@@ -318,6 +326,7 @@ __global__ __launch_bounds__(256) void adell_attention_fwd_kernel(AttArgs a) {
     for (int d = 0; d < MAXD; ++d) acc[r][d] = 0.f;
   }
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
   const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
   for (int k0 = 0; k0 < a.T; k0 += ATT_TK) {
     __syncthreads();
@@ -340,6 +349,7 @@ __global__ __launch_bounds__(256) void adell_attention_fwd_kernel(AttArgs a) {
         for (int c = 0; c < a.A; ++c) t += qr[c] * sK[lane * AP + c];
         s = t * a.scale;
         if (biasb) s += biasb[(size_t)qrow * a.T + k0 + lane];
+        if (labb) s += att_label_term(labb[qrow], labb[k0 + lane]);
       }
       float mx = s;
 #pragma unroll
@@ -425,6 +435,7 @@ __global__ __launch_bounds__(256) void adell_attention_bwd_q_kernel(AttArgs a) {
     for (int d = 0; d < MAXA; ++d) acc[r][d] = 0.f;
   }
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
   const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
   for (int k0 = 0; k0 < a.T; k0 += ATT_TK) {
     __syncthreads();
@@ -448,6 +459,7 @@ __global__ __launch_bounds__(256) void adell_attention_bwd_q_kernel(AttArgs a) {
         for (int c = 0; c < a.A; ++c) t += qr[c] * sK[lane * AP + c];
         float s = t * a.scale;
         if (biasb) s += biasb[(size_t)qrow * a.T + k0 + lane];
+        if (labb) s += att_label_term(labb[qrow], labb[k0 + lane]);
         const float p = expf(s - lse[r]);
         float dp = 0.f;
         for (int c = 0; c < a.Dv; ++c) dp += gr[c] * sV[lane * DP + c];
@@ -515,6 +527,7 @@ __global__ __launch_bounds__(256) void adell_attention_bwd_kv_kernel(AttArgs a) 
 #pragma unroll
     for (int d = 0; d < MAXC; ++d) dk[r][d] = dv[r][d] = 0.f;
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
   const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
   for (int q0 = 0; q0 < a.T; q0 += ATT_TK) {
     __syncthreads();
@@ -550,6 +563,7 @@ __global__ __launch_bounds__(256) void adell_attention_bwd_kv_kernel(AttArgs a) 
         for (int c = 0; c < a.A; ++c) t += kr[c] * sQ[lane * AP + c];
         float s = t * a.scale;
         if (biasb) s += biasb[(size_t)(q0 + lane) * a.T + krow];
+        if (labb) s += att_label_term(labb[q0 + lane], labb[krow]);
         p = expf(s - sL[lane * 2 + 0]);
         float dp = 0.f;
         for (int c = 0; c < a.Dv; ++c) dp += vr[c] * sdO[lane * DP + c];
@@ -671,14 +685,15 @@ __device__ __forceinline__ void am_stage_all(float* dst, const float* src, long 
 // S^T tile: rows = keys k0 + am_row(r, h), column = this lane's query; -inf outside the sequence
 template <int A>
 __device__ __forceinline__ void am_scores_t(const AttArgs& a, const float* sK, const float* qreg,
-                                            const float* biasb, int qrow, bool qok, int k0, int li,
-                                            int h, float* val) {
+                                            const float* biasb, const int* labb, int qrow, bool qok,
+                                            int k0, int li, int h, float* val) {
   f32x16 s;
 #pragma unroll
   for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
   for (int ss = 0; ss < A / 2; ++ss)
     s = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[li * (A + 1) + 2 * ss + h], qreg[ss], s, 0, 0, 0);
+  const int qlab = labb && qok ? labb[qrow] : 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int key = k0 + am_row(r, h);
@@ -686,6 +701,7 @@ __device__ __forceinline__ void am_scores_t(const AttArgs& a, const float* sK, c
     if (qok && key < a.T) {
       v = s[r] * a.scale;
       if (biasb) v += biasb[(size_t)qrow * a.T + key];
+      if (labb) v += att_label_term(qlab, labb[key]);
     }
     val[r] = v;
   }
@@ -708,6 +724,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_fwd_kernel(AttArgs a) {
   const float* kb = a.k + att_base(a, a.sk, bh);
   const float* vb = a.v + att_base(a, a.sv, bh);
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
   float qreg[A / 2];
 #pragma unroll
   for (int ss = 0; ss < A / 2; ++ss) qreg[ss] = qok ? qb[(size_t)qrow * a.sq.r + 2 * ss + h] : 0.f;
@@ -726,7 +743,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_fwd_kernel(AttArgs a) {
     }
     if (!active) continue;
     float val[16];
-    am_scores_t<A>(a, sK + (size_t)(RES ? k0 : 0) * (A + 1), qreg, biasb, qrow, qok, k0, li, h, val);
+    am_scores_t<A>(a, sK + (size_t)(RES ? k0 : 0) * (A + 1), qreg, biasb, labb, qrow, qok, k0, li, h, val);
     float mt = val[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mt = fmaxf(mt, val[r]);
@@ -757,7 +774,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_fwd_kernel(AttArgs a) {
     if (!active) continue;
     const float* sVt = sV + (size_t)(RES ? k0 : 0) * (Dv + 1);
     float val[16];
-    am_scores_t<A>(a, sK + (size_t)(RES ? k0 : 0) * (A + 1), qreg, biasb, qrow, qok, k0, li, h, val);
+    am_scores_t<A>(a, sK + (size_t)(RES ? k0 : 0) * (A + 1), qreg, biasb, labb, qrow, qok, k0, li, h, val);
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
       bool keep[4];   // registers 4 r4 .. 4 r4 + 3 are four consecutive keys
@@ -804,6 +821,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_q_kernel(AttArgs a) {
   const float* ob = a.o + att_base(a, a.so, bh);
   const float* gb = a.dout + att_base(a, a.sg, bh);
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
   float qreg[A / 2], doreg[Dv / 2];
   float D = 0.f;
 #pragma unroll
@@ -837,7 +855,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_q_kernel(AttArgs a) {
     const float* sKt = sK + (size_t)(RES ? k0 : 0) * (A + 1);
     const float* sVt = sV + (size_t)(RES ? k0 : 0) * (Dv + 1);
     float val[16];
-    am_scores_t<A>(a, sKt, qreg, biasb, qrow, qok, k0, li, h, val);
+    am_scores_t<A>(a, sKt, qreg, biasb, labb, qrow, qok, k0, li, h, val);
     f32x16 dp;   // dP^T = V dO^T: rows = keys, column = query
 #pragma unroll
     for (int r = 0; r < 16; ++r) dp[r] = 0.f;
@@ -894,6 +912,8 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_kv_kernel(AttArgs a) 
   const float* ob = a.o + att_base(a, a.so, bh);
   const float* gb = a.dout + att_base(a, a.sg, bh);
   const float* biasb = a.bias ? a.bias + (size_t)(bh % a.nbias) * a.T * a.T : nullptr;
+  const int* labb = att_labels(a, bh);
+  const int klab = labb && kok ? labb[krow] : 0;
   float kreg[A / 2], vreg[Dv / 2];
 #pragma unroll
   for (int ss = 0; ss < A / 2; ++ss) kreg[ss] = kok ? kb[(size_t)krow * a.sk.r + 2 * ss + h] : 0.f;
@@ -964,6 +984,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_kv_kernel(AttArgs a) 
       if (kok && qr < a.T) {
         float v = s[r] * a.scale;
         if (biasb) v += biasb[(size_t)qr * a.T + krow];
+        if (labb) v += att_label_term(labb[qr], klab);
         p = expf(v - sL[base + row]);
       }
       const bool keep = adell_att_keep(a, bh, qr, krow);
@@ -998,6 +1019,195 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_kv_kernel(AttArgs a) 
       const int row = k0 + am_row(r, h);
       if (row < a.T) a.dk[att_base(a, a.sdk, bh) + (size_t)row * a.sdk.r + t * 32 + li] = dk[t][r] * a.scale;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradient of the additive bias, reduced over the sequences that share a bias slice and never
+// materialised per sequence: dbias[j] = sum over bh % nbias == j of dS[bh], dS = P o (keep dP /
+// (1 - p) - D) -- the gradient of the pre-softmax additive term, so without `scale`. S, P and dS are
+// rebuilt exactly as the dQ kernels build them (scale, bias, labels, the same keep mask).
+// A block owns slice j (grid y), one tile of the [T][T] result (grid x) and one contiguous chunk of
+// j's sequences (grid z), walks the chunk in ascending bh and accumulates in registers. With one
+// chunk the tile goes straight to dbias; otherwise to partial slice z of the workspace, and
+// adell_attn_dbias_fold_kernel adds the partial slices in chunk order: no atomics, the same bits on
+// every run. Operands by (item, head, row) strides as in adell_attention_bwd_strided.
+// ---------------------------------------------------------------------------------------------
+struct AttBiasGrad {
+  float* dst;    // dbias, or the workspace [chunks][nbias][T][T]
+  int BH, chunk; // sequences in all; sequences of one slice per block
+  int tiles_k;   // key tiles per row of tiles (grid x = query tiles * tiles_k)
+};
+
+// MFMA form: 4 waves = 4 query tiles of 32 rows sharing the staged 32-key K / V tiles, NK key tiles
+// per block (128 x 32 NK results, 16 NK accumulator registers per lane); dS^T tiles as in the dQ kernel
+template <int AT, int DT, int NK>
+__global__ __launch_bounds__(256) void adell_attn_mfma_dbias_kernel(AttArgs a, AttBiasGrad g) {
+  constexpr int A = AT * 32, Dv = DT * 32;
+  extern __shared__ float sh[];
+  float* sK = sh;
+  float* sV = sK + 32 * (A + 1);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
+  const int tq = blockIdx.x / g.tiles_k, tk = blockIdx.x - tq * g.tiles_k;
+  const int q0 = (tq * 4 + wave) * 32, qrow = q0 + li, kbase = tk * 32 * NK;
+  const bool qok = qrow < a.T, active = q0 < a.T;   // `active` is wave-uniform
+  const int j = blockIdx.y;
+  const int nj = (g.BH - j + a.nbias - 1) / a.nbias;   // sequences j, j + nbias, ...
+  const int i0 = blockIdx.z * g.chunk, i1 = min(i0 + g.chunk, nj);
+  const float* biasb = a.bias ? a.bias + (size_t)j * a.T * a.T : nullptr;
+  const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+  f32x16 acc[NK];
+#pragma unroll
+  for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[kt][r] = 0.f;
+  for (int i = i0; i < i1; ++i) {
+    const int bh = j + i * a.nbias;
+    const float* qb = a.q + att_base(a, a.sq, bh);
+    const float* kb = a.k + att_base(a, a.sk, bh);
+    const float* vb = a.v + att_base(a, a.sv, bh);
+    const float* ob = a.o + att_base(a, a.so, bh);
+    const float* gb = a.dout + att_base(a, a.sg, bh);
+    const int* labb = att_labels(a, bh);
+    float qreg[A / 2], doreg[Dv / 2];
+    float D = 0.f;
+#pragma unroll
+    for (int ss = 0; ss < A / 2; ++ss) qreg[ss] = qok ? qb[(size_t)qrow * a.sq.r + 2 * ss + h] : 0.f;
+#pragma unroll
+    for (int ss = 0; ss < Dv / 2; ++ss) {
+      doreg[ss] = qok ? gb[(size_t)qrow * a.sg.r + 2 * ss + h] : 0.f;
+      D += qok ? doreg[ss] * ob[(size_t)qrow * a.so.r + 2 * ss + h] : 0.f;
+    }
+    D += __shfl_xor(D, 32, 64);
+    const float lse = qok ? a.lse[(size_t)bh * a.T + qrow] : 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NK; ++kt) {
+      const int k0 = kbase + 32 * kt;
+      if (k0 >= a.T) continue;   // block-uniform
+      __syncthreads();
+      am_stage32<A>(sK, kb, a.sk.r, k0, a.T, tid);
+      am_stage32<Dv>(sV, vb, a.sv.r, k0, a.T, tid);
+      __syncthreads();
+      if (!active) continue;
+      float val[16];
+      am_scores_t<A>(a, sK, qreg, biasb, labb, qrow, qok, k0, li, h, val);
+      f32x16 dp;   // dP^T = V dO^T: rows = keys, column = query
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+      for (int ss = 0; ss < Dv / 2; ++ss)
+        dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[li * (Dv + 1) + 2 * ss + h], doreg[ss], dp, 0, 0, 0);
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        bool keep[4];
+        adell_att_keep4(a, bh, qrow, k0 + am_row(4 * r4, h), keep);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int r = 4 * r4 + jj;
+          const float p = (val[r] == -INFINITY) ? 0.f : expf(val[r] - lse);
+          const float gd = keep[jj] ? dp[r] * keep_scale : 0.f;
+          acc[kt][r] += p * (gd - D);
+        }
+      }
+    }
+  }
+  if (!qok) return;
+  float* dst = g.dst + ((size_t)blockIdx.z * a.nbias + j) * a.T * a.T + (size_t)qrow * a.T;
+#pragma unroll
+  for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = kbase + 32 * kt + am_row(r, h);
+      if (key < a.T) dst[key] = acc[kt][r];
+    }
+}
+
+// vector-ALU form (the structure of adell_attention_bwd_q_kernel): one wave per query row, lane =
+// key of the block's 64-key tile; block tile ROWS queries x 64 keys
+template <int ROWS>
+__global__ __launch_bounds__(256) void adell_attention_dbias_kernel(AttArgs a, AttBiasGrad g) {
+  extern __shared__ float sh[];
+  const int AP = a.A + 1, DP = a.Dv + 1;
+  float* sK = sh;                        // [ATT_TK][AP]
+  float* sV = sK + ATT_TK * AP;          // [ATT_TK][DP]
+  float* sQ = sV + ATT_TK * DP;          // [ROWS][A]
+  float* sdO = sQ + ROWS * a.A;          // [ROWS][Dv]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tq = blockIdx.x / g.tiles_k, tk = blockIdx.x - tq * g.tiles_k;
+  const int row0 = tq * ROWS, k0 = tk * ATT_TK;
+  const int j = blockIdx.y;
+  const int nj = (g.BH - j + a.nbias - 1) / a.nbias;
+  const int i0 = blockIdx.z * g.chunk, i1 = min(i0 + g.chunk, nj);
+  const float* biasb = a.bias ? a.bias + (size_t)j * a.T * a.T : nullptr;
+  const float keep_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+  constexpr int RPW = ROWS / 4;
+  float acc[RPW];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) acc[r] = 0.f;
+  for (int i = i0; i < i1; ++i) {
+    const int bh = j + i * a.nbias;
+    const float* qb = a.q + att_base(a, a.sq, bh);
+    const float* kb = a.k + att_base(a, a.sk, bh);
+    const float* vb = a.v + att_base(a, a.sv, bh);
+    const float* ob = a.o + att_base(a, a.so, bh);
+    const float* gb = a.dout + att_base(a, a.sg, bh);
+    const int* labb = att_labels(a, bh);
+    __syncthreads();
+    for (int e = threadIdx.x; e < ROWS * a.A; e += 256) {
+      const int r = e / a.A, c = e - r * a.A;
+      sQ[e] = (row0 + r < a.T) ? qb[(size_t)(row0 + r) * a.sq.r + c] : 0.f;
+    }
+    for (int e = threadIdx.x; e < ROWS * a.Dv; e += 256) {
+      const int r = e / a.Dv, c = e - r * a.Dv;
+      sdO[e] = (row0 + r < a.T) ? gb[(size_t)(row0 + r) * a.sg.r + c] : 0.f;
+    }
+    for (int e = threadIdx.x; e < ATT_TK * a.A; e += 256) {
+      const int r = e / a.A, c = e - r * a.A;
+      sK[r * AP + c] = (k0 + r < a.T) ? kb[(size_t)(k0 + r) * a.sk.r + c] : 0.f;
+    }
+    for (int e = threadIdx.x; e < ATT_TK * a.Dv; e += 256) {
+      const int r = e / a.Dv, c = e - r * a.Dv;
+      sV[r * DP + c] = (k0 + r < a.T) ? vb[(size_t)(k0 + r) * a.sv.r + c] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      const int qrow = row0 + wave * RPW + r;
+      const float* qr = sQ + (wave * RPW + r) * a.A;
+      const float* gr = sdO + (wave * RPW + r) * a.Dv;
+      float t = 0.f;
+      if (qrow < a.T)
+        for (int c = lane; c < a.Dv; c += 64) t += gr[c] * ob[(size_t)qrow * a.so.r + c];
+      const float Dr = adell_wave_sum(t);
+      if (k0 + lane < a.T && qrow < a.T) {
+        float d = 0.f;
+        for (int c = 0; c < a.A; ++c) d += qr[c] * sK[lane * AP + c];
+        float s = d * a.scale;
+        if (biasb) s += biasb[(size_t)qrow * a.T + k0 + lane];
+        if (labb) s += att_label_term(labb[qrow], labb[k0 + lane]);
+        const float p = expf(s - a.lse[(size_t)bh * a.T + qrow]);
+        float dp = 0.f;
+        for (int c = 0; c < a.Dv; ++c) dp += gr[c] * sV[lane * DP + c];
+        dp = adell_att_keep(a, bh, qrow, k0 + lane) ? dp * keep_scale : 0.f;
+        acc[r] += p * (dp - Dr);
+      }
+    }
+  }
+  float* dst = g.dst + ((size_t)blockIdx.z * a.nbias + j) * a.T * a.T;
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int qrow = row0 + wave * RPW + r;
+    if (qrow < a.T && k0 + lane < a.T) dst[(size_t)qrow * a.T + k0 + lane] = acc[r];
+  }
+}
+
+// dbias[e] = part[0][e] + part[1][e] + ... in chunk order
+__global__ __launch_bounds__(256) void adell_attn_dbias_fold_kernel(
+    const float* __restrict__ part, float* __restrict__ dbias, long n, int chunks) {
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    float s = part[e];
+    for (int z = 1; z < chunks; ++z) s += part[(size_t)z * n + e];
+    dbias[e] = s;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1108,6 +1318,15 @@ static int adell_att_check(int BH, int T, int A, int Dv, int nbias, const float*
   return ADELL_OK;
 }
 
+// region labels [nlab][T] of items of H sequences each (null: none)
+static int adell_att_set_labels(AttArgs* a, const int* labels, int nlab, int H) {
+  ADELL_REQUIRE(labels == nullptr || (nlab > 0 && H > 0), "attention: labels need nlab > 0 and H > 0");
+  a->labels = labels;
+  a->nlab = nlab > 0 ? nlab : 1;
+  a->labH = H > 0 ? H : 1;
+  return ADELL_OK;
+}
+
 static bool adell_att_aligned16(std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs)
     if (((uintptr_t)p) & 15) return false;
@@ -1131,17 +1350,19 @@ static int adell_att_stride(const char* what, const void* p, const long* s, int 
   return ADELL_OK;
 }
 
-extern "C" int adell_attention_fwd(const float* q, const float* k, const float* v,
-                                   const float* bias, int nbias, int BH, int T, int A, int Dv,
-                                   float scale, float drop_p, unsigned long long seed,
-                                   unsigned int rng_offset, float* out, float* lse,
-                                   void* stream) {
+extern "C" int adell_attention_fwd_labels(const float* q, const float* k, const float* v,
+                                          const float* bias, int nbias, const int* labels, int nlab,
+                                          int H, int BH, int T, int A, int Dv, float scale,
+                                          float drop_p, unsigned long long seed,
+                                          unsigned int rng_offset, float* out, float* lse,
+                                          void* stream) {
   int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(q && k && v && out && lse, "attention_fwd: null pointer");
   AttArgs a = {};
   a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out; a.lse_out = lse;
   a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale;
+  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
@@ -1151,12 +1372,22 @@ extern "C" int adell_attention_fwd(const float* q, const float* k, const float* 
   return adell_att_launch(0, a, BH, p, (hipStream_t)stream);
 }
 
-extern "C" int adell_attention_bwd(const float* q, const float* k, const float* v,
-                                   const float* bias, int nbias, const float* out,
-                                   const float* dout, const float* lse, int BH, int T, int A,
-                                   int Dv, float scale, float drop_p, unsigned long long seed,
-                                   unsigned int rng_offset, float* dq, float* dk, float* dv,
+extern "C" int adell_attention_fwd(const float* q, const float* k, const float* v,
+                                   const float* bias, int nbias, int BH, int T, int A, int Dv,
+                                   float scale, float drop_p, unsigned long long seed,
+                                   unsigned int rng_offset, float* out, float* lse,
                                    void* stream) {
+  return adell_attention_fwd_labels(q, k, v, bias, nbias, nullptr, 0, 1, BH, T, A, Dv, scale, drop_p,
+                                    seed, rng_offset, out, lse, stream);
+}
+
+extern "C" int adell_attention_bwd_labels(const float* q, const float* k, const float* v,
+                                          const float* bias, int nbias, const int* labels, int nlab,
+                                          int H, const float* out, const float* dout,
+                                          const float* lse, int BH, int T, int A, int Dv, float scale,
+                                          float drop_p, unsigned long long seed,
+                                          unsigned int rng_offset, float* dq, float* dk, float* dv,
+                                          void* stream) {
   int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(q && k && v && out && dout && lse && dq && dk && dv, "attention_bwd: null pointer");
@@ -1164,6 +1395,7 @@ extern "C" int adell_attention_bwd(const float* q, const float* k, const float* 
   a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale;
+  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
@@ -1175,6 +1407,16 @@ extern "C" int adell_attention_bwd(const float* q, const float* k, const float* 
   rc = adell_att_launch(1, a, BH, pq, (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
   return adell_att_launch(2, a, BH, pkv, (hipStream_t)stream);
+}
+
+extern "C" int adell_attention_bwd(const float* q, const float* k, const float* v,
+                                   const float* bias, int nbias, const float* out,
+                                   const float* dout, const float* lse, int BH, int T, int A,
+                                   int Dv, float scale, float drop_p, unsigned long long seed,
+                                   unsigned int rng_offset, float* dq, float* dk, float* dv,
+                                   void* stream) {
+  return adell_attention_bwd_labels(q, k, v, bias, nbias, nullptr, 0, 1, out, dout, lse, BH, T, A, Dv,
+                                    scale, drop_p, seed, rng_offset, dq, dk, dv, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1189,12 +1431,12 @@ extern "C" int adell_attention_strided_ok(int T, int A, int Dv) {
   return path == ADELL_ATT_MFMA_RESIDENT || path == ADELL_ATT_MFMA_STREAMED ? 1 : 0;
 }
 
-extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const float* v,
-                                           const float* bias, int nbias, int B, int H, int T,
-                                           int A, int Dv, const long* strides, float scale,
-                                           float drop_p, unsigned long long seed,
-                                           unsigned int rng_offset, float* out, float* lse,
-                                           void* stream) {
+extern "C" int adell_attention_fwd_strided_labels(const float* q, const float* k, const float* v,
+                                                  const float* bias, int nbias, const int* labels,
+                                                  int nlab, int B, int H, int T, int A, int Dv,
+                                                  const long* strides, float scale, float drop_p,
+                                                  unsigned long long seed, unsigned int rng_offset,
+                                                  float* out, float* lse, void* stream) {
   ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_fwd_strided: bad dims");
   int rc = adell_att_check(B * H, T, A, Dv, nbias, bias);
   if (rc != ADELL_OK) return rc;
@@ -1204,6 +1446,7 @@ extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const
   AttArgs a = {};
   a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out; a.lse_out = lse;
   a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale; a.H = H;
+  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
@@ -1214,13 +1457,24 @@ extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const
   return adell_att_launch(0, a, B * H, adell_att_plan(0, T, A, Dv, true), (hipStream_t)stream);
 }
 
-extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const float* v,
-                                           const float* bias, int nbias, const float* out,
-                                           const float* dout, const float* lse, int B, int H,
-                                           int T, int A, int Dv, const long* strides, float scale,
+extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const float* v,
+                                           const float* bias, int nbias, int B, int H, int T,
+                                           int A, int Dv, const long* strides, float scale,
                                            float drop_p, unsigned long long seed,
-                                           unsigned int rng_offset, float* dq, float* dk,
-                                           float* dv, void* stream) {
+                                           unsigned int rng_offset, float* out, float* lse,
+                                           void* stream) {
+  return adell_attention_fwd_strided_labels(q, k, v, bias, nbias, nullptr, 0, B, H, T, A, Dv, strides,
+                                            scale, drop_p, seed, rng_offset, out, lse, stream);
+}
+
+extern "C" int adell_attention_bwd_strided_labels(const float* q, const float* k, const float* v,
+                                                  const float* bias, int nbias, const int* labels,
+                                                  int nlab, const float* out, const float* dout,
+                                                  const float* lse, int B, int H, int T, int A,
+                                                  int Dv, const long* strides, float scale,
+                                                  float drop_p, unsigned long long seed,
+                                                  unsigned int rng_offset, float* dq, float* dk,
+                                                  float* dv, void* stream) {
   ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_bwd_strided: bad dims");
   int rc = adell_att_check(B * H, T, A, Dv, nbias, bias);
   if (rc != ADELL_OK) return rc;
@@ -1231,6 +1485,7 @@ extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const
   a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale; a.H = H;
+  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
   ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
   a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
   a.rng_offset = rng_offset;
@@ -1245,6 +1500,121 @@ extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const
   rc = adell_att_launch(1, a, B * H, adell_att_plan(1, T, A, Dv, true), (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
   return adell_att_launch(2, a, B * H, adell_att_plan(2, T, A, Dv, true), (hipStream_t)stream);
+}
+
+extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const float* v,
+                                           const float* bias, int nbias, const float* out,
+                                           const float* dout, const float* lse, int B, int H,
+                                           int T, int A, int Dv, const long* strides, float scale,
+                                           float drop_p, unsigned long long seed,
+                                           unsigned int rng_offset, float* dq, float* dk,
+                                           float* dv, void* stream) {
+  return adell_attention_bwd_strided_labels(q, k, v, bias, nbias, nullptr, 0, out, dout, lse, B, H, T,
+                                            A, Dv, strides, scale, drop_p, seed, rng_offset, dq, dk,
+                                            dv, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bias gradient (kernels above). The result has nbias * query tiles * key tiles block tiles; the
+// sequences of a slice are split into at most ADELL_ATT_DBIAS_BLOCKS / that many chunks (and at most
+// ADELL_ATT_DBIAS_CHUNKS), so the workspace is a fixed number of partial tiles whatever the number
+// of sequences.
+// ---------------------------------------------------------------------------------------------
+#define ADELL_ATT_DBIAS_BLOCKS 512
+#define ADELL_ATT_DBIAS_NK 4
+#define ADELL_ATT_DBIAS_CHUNKS 16   // partial results per slice at most: the workspace is <= 16 x dbias
+
+static int adell_att_dbias_max_chunks(int nbias, int T) {
+  // the MFMA tiling (128 x 128) gives the fewest tiles: its chunk count bounds the vector-ALU form's
+  const long t = adell_cdiv(T, 128), tiles = (long)nbias * t * t;
+  const long c = ADELL_ATT_DBIAS_BLOCKS / tiles;
+  return (int)(c < 1 ? 1 : (c > ADELL_ATT_DBIAS_CHUNKS ? ADELL_ATT_DBIAS_CHUNKS : c));
+}
+
+extern "C" long adell_attention_bias_grad_workspace_floats(int nbias, int T) {
+  if (nbias <= 0 || T <= 0) return 0;
+  const int c = adell_att_dbias_max_chunks(nbias, T);
+  return c > 1 ? (long)c * nbias * T * T : 0;
+}
+
+template <int AT, int DT>
+static int adell_att_dbias_mfma2(const AttArgs& a, const AttBiasGrad& g, dim3 grid, hipStream_t st) {
+  const size_t lds = sizeof(float) * 32 * ((size_t)(AT * 32 + 1) + (size_t)(DT * 32 + 1));
+  return adell_launch<adell_attn_mfma_dbias_kernel<AT, DT, ADELL_ATT_DBIAS_NK>>(grid, dim3(256), lds, st, a, g);
+}
+template <int AT>
+static int adell_att_dbias_mfma1(const AttArgs& a, const AttBiasGrad& g, dim3 grid, hipStream_t st) {
+  switch (a.Dv) {
+    case 32: return adell_att_dbias_mfma2<AT, 1>(a, g, grid, st);
+    case 64: return adell_att_dbias_mfma2<AT, 2>(a, g, grid, st);
+    default: return adell_att_dbias_mfma2<AT, 4>(a, g, grid, st);
+  }
+}
+
+extern "C" int adell_attention_bias_grad(const float* q, const float* k, const float* v,
+                                         const float* bias, int nbias, const int* labels, int nlab,
+                                         const float* out, const float* dout, const float* lse,
+                                         int B, int H, int T, int A, int Dv, const long* strides,
+                                         float scale, float drop_p, unsigned long long seed,
+                                         unsigned int rng_offset, float* dbias, float* workspace,
+                                         long workspace_floats, void* stream) {
+  ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_bias_grad: bad dims");
+  const int BH = B * H;
+  int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(nbias > 0 && nbias <= BH, "attention_bias_grad: nbias must be in [1, B * H]");
+  ADELL_REQUIRE(nbias <= 65535, "attention_bias_grad: at most 65535 bias slices (grid y), got %d", nbias);
+  ADELL_REQUIRE(q && k && v && out && dout && lse && dbias, "attention_bias_grad: null pointer");
+  AttArgs a = {};
+  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
+  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias; a.scale = scale; a.H = H;
+  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
+  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
+  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+  a.rng_offset = rng_offset;
+  AttStride* dst[5] = {&a.sq, &a.sk, &a.sv, &a.so, &a.sg};
+  const int width[5] = {A, A, Dv, Dv, Dv};
+  bool aligned = adell_att_aligned16({q, k, v, out, dout});
+  for (int i = 0; i < 5; ++i) {
+    const long* s = strides + 3 * i;
+    ADELL_REQUIRE(s[0] >= 0 && s[1] >= 0 && s[2] >= width[i], "attention_bias_grad: bad strides");
+    dst[i]->b = s[0]; dst[i]->h = s[1]; dst[i]->r = s[2];
+    aligned = aligned && s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0;
+  }
+  const AdellAttPlan p = adell_att_plan(1, T, A, Dv, aligned);   // the dQ kernel's choice of form
+  ADELL_REQUIRE(p.path != ADELL_ATT_REFUSED, "attention_bias_grad: no kernel for head dims (%d, %d)", A, Dv);
+  const bool mfma = p.path != ADELL_ATT_VALU;
+  const int nj = adell_cdiv(BH, nbias);   // sequences of slice 0, the longest list
+  int chunks = adell_att_dbias_max_chunks(nbias, T);
+  if (chunks > nj) chunks = nj;
+  AttBiasGrad g = {dbias, BH, adell_cdiv(nj, chunks), 0};
+  chunks = adell_cdiv(nj, g.chunk);
+  const long n = (long)nbias * T * T;
+  if (chunks > 1) {
+    ADELL_REQUIRE(workspace && workspace_floats >= chunks * n, "attention_bias_grad: workspace too small");
+    g.dst = workspace;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (mfma) {
+    g.tiles_k = adell_cdiv(T, 32 * ADELL_ATT_DBIAS_NK);
+    const dim3 grid((unsigned)(adell_cdiv(T, 128) * g.tiles_k), (unsigned)nbias, (unsigned)chunks);
+    switch (A) {
+      case 32: rc = adell_att_dbias_mfma1<1>(a, g, grid, st); break;
+      case 64: rc = adell_att_dbias_mfma1<2>(a, g, grid, st); break;
+      default: rc = adell_att_dbias_mfma1<4>(a, g, grid, st); break;
+    }
+  } else {
+    g.tiles_k = adell_cdiv(T, ATT_TK);
+    const dim3 grid((unsigned)(adell_cdiv(T, p.rows) * g.tiles_k), (unsigned)nbias, (unsigned)chunks);
+    rc = p.rows == ATT_ROWS
+             ? adell_launch<adell_attention_dbias_kernel<ATT_ROWS>>(grid, dim3(256), p.lds, st, a, g)
+             : adell_launch<adell_attention_dbias_kernel<ATT_ROWS / 2>>(grid, dim3(256), p.lds, st, a, g);
+  }
+  if (rc != ADELL_OK || chunks == 1) return rc;
+  long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  return adell_launch<adell_attn_dbias_fold_kernel>(dim3((unsigned)blocks), dim3(256), 0, st,
+                                                    (const float*)workspace, dbias, n, chunks);
 }
 
 // Host-only launch plan of one pass of adell_attention_fwd / _bwd (and, with aligned = 1, of the

@@ -1582,7 +1582,7 @@ class _SeqAttnFn(torch.autograd.Function):
         return tok, pak, out
 
     @staticmethod
-    def forward(ctx, qkv, qg, qb, kg, kb, bias, conf):
+    def forward(ctx, qkv, qg, qb, kg, kb, bias, labels, conf):
         B, H, T, a, hd, scale, drop_p, seed, offset, eps = conf
         per = 2 * a + hd
         flat = qkv.view(-1)
@@ -1592,17 +1592,15 @@ class _SeqAttnFn(torch.autograd.Function):
         tok, pak, out = _SeqAttnFn._strides(T, H, a, hd)
         o = torch.empty((B * T, H * hd), device=qkv.device, dtype=torch.float32)
         lse = ops.attention_fwd_strided(qn, kn, flat[2 * a:], o, tok + tok + pak + out, bias, B, H, T,
-                                        a, hd, scale, drop_p, seed, offset)
-        ctx.save_for_backward(qkv, qg, kg, qn, kn, qm, qr, km, kr, o, lse, bias)
+                                        a, hd, scale, drop_p, seed, offset, labels)
+        ctx.save_for_backward(qkv, qg, kg, qn, kn, qm, qr, km, kr, o, lse, bias, labels)
         ctx.conf = conf
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qg, kg, qn, kn, qm, qr, km, kr, o, lse, bias = ctx.saved_tensors
+        qkv, qg, kg, qn, kn, qm, qr, km, kr, o, lse, bias, labels = ctx.saved_tensors
         B, H, T, a, hd, scale, drop_p, seed, offset, eps = ctx.conf
-        if bias is not None and ctx.needs_input_grad[5]:
-            raise NotImplementedError("attention bias gradient of the full-sequence form")
         per = 2 * a + hd
         rows = B * T * H
         need = ctx.needs_input_grad
@@ -1611,14 +1609,22 @@ class _SeqAttnFn(torch.autograd.Function):
         dflat = dqkv.view(-1)
         dqn, dkn = torch.empty_like(qn), torch.empty_like(kn)
         tok, pak, out = _SeqAttnFn._strides(T, H, a, hd)
-        ops.attention_bwd_strided(qn, kn, flat[2 * a:], o, do.contiguous(), lse, dqn, dkn,
+        do = do.contiguous()
+        ops.attention_bwd_strided(qn, kn, flat[2 * a:], o, do, lse, dqn, dkn,
                                   dflat[2 * a:], tok + tok + pak + out + out + tok + tok + pak, bias,
-                                  B, H, T, a, hd, scale, drop_p, seed, offset)
+                                  B, H, T, a, hd, scale, drop_p, seed, offset, labels)
+        dbias = None
+        if bias is not None and need[5]:
+            # summed over the sequences that share a slice, never materialised per sequence
+            dbias = ops.attention_bias_grad(
+                qn, kn, flat[2 * a:], bias, o, do, lse, scale, bias.numel() // (T * T), drop_p, seed,
+                offset, labels, strides=tok + tok + pak + out + out,
+                dims=(B, H, T, a, hd)).view(bias.shape)
         dqg, dqb = ops.layernorm_rows_bwd(flat, dqn, qg, qm, qr, rows, a, 1, per, 0, dflat, per, 0,
                                           need[1] or need[2])
         dkg, dkb = ops.layernorm_rows_bwd(flat[a:], dkn, kg, km, kr, rows, a, 1, per, 0, dflat[a:],
                                           per, 0, need[3] or need[4])
-        return dqkv, dqg, dqb, dkg, dkb, None, None
+        return dqkv, dqg, dqb, dkg, dkb, dbias, None, None
 
 
 def seq_attention_ok(tokens, a, hd):
@@ -1628,10 +1634,12 @@ def seq_attention_ok(tokens, a, hd):
 
 
 def seq_attention(qkv, q_gamma, q_beta, k_gamma, k_beta, batch, n_heads, tokens, a, hd, bias=None,
-                  drop_p=0.0, training=False, eps=1e-5):
+                  drop_p=0.0, training=False, eps=1e-5, labels=None):
     """qkv: [batch * tokens, n_heads * (2a + hd)] -> [batch * tokens, n_heads * hd]; bias
     [nbias, tokens, tokens] or None is added to the scores of sequence (b, h) as
-    bias[(b * n_heads + h) % nbias]."""
+    bias[(b * n_heads + h) % nbias] (a bias that requires grad gets its gradient, summed over the
+    sequences that share a slice); labels int32 [nlab, tokens] or None: item b reads row
+    b % nlab, and scores between tokens whose labels differ gain -100 (shifted windows)."""
     p = float(drop_p) if training else 0.0
     seed, offset = 0, 0
     if p > 0.0:
@@ -1640,7 +1648,7 @@ def seq_attention(qkv, q_gamma, q_beta, k_gamma, k_beta, batch, n_heads, tokens,
     conf = (int(batch), int(n_heads), int(tokens), int(a), int(hd), 1.0 / (a ** 0.5), p, seed,
             offset, float(eps))
     bias = None if bias is None else bias.contiguous()
-    return _SeqAttnFn.apply(qkv.contiguous(), q_gamma, q_beta, k_gamma, k_beta, bias, conf)
+    return _SeqAttnFn.apply(qkv.contiguous(), q_gamma, q_beta, k_gamma, k_beta, bias, labels, conf)
 
 
 class _AddBcastFn(torch.autograd.Function):
@@ -1665,34 +1673,44 @@ def add_bcast(a, b):
 
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, bias, scale, drop):
+    def forward(ctx, q, k, v, bias, scale, drop, labels, heads):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ctx.bias_shape = None if bias is None else bias.shape
         if bias is not None:
             # an expanded mask ([1, 1, T, T] -> heads) reshapes to a stride-0 VIEW: the backward
             # must see the same materialised rows the forward used
             bias = bias.contiguous()
-        out, lse = ops.attention_fwd(q, k, v, bias, scale, *drop)
-        ctx.save_for_backward(q, k, v, bias, out, lse)
-        ctx.scale, ctx.drop = scale, drop
+        out, lse = ops.attention_fwd(q, k, v, bias, scale, *drop, labels=labels, heads=heads)
+        ctx.save_for_backward(q, k, v, bias, out, lse, labels)
+        ctx.scale, ctx.drop, ctx.heads = scale, drop, heads
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, bias, out, lse = ctx.saved_tensors
+        q, k, v, bias, out, lse, labels = ctx.saved_tensors
+        dout = dout.contiguous()
+        dq, dk, dv = ops.attention_bwd(q, k, v, bias, out, dout, lse, ctx.scale, *ctx.drop,
+                                       labels=labels, heads=ctx.heads)
+        dbias = None
         if bias is not None and ctx.needs_input_grad[3]:
-            raise NotImplementedError("attention bias gradient (SWIN relative positions): next row")
-        dq, dk, dv = ops.attention_bwd(q, k, v, bias, out, dout, lse, ctx.scale, *ctx.drop)
-        return dq, dk, dv, None, None, None
+            T = q.shape[1]
+            dbias = ops.attention_bias_grad(q, k, v, bias, out, dout, lse, ctx.scale,
+                                            bias.numel() // (T * T), *ctx.drop, labels=labels,
+                                            heads=ctx.heads).view(ctx.bias_shape)
+        return dq, dk, dv, dbias, None, None, None, None
 
 
-def attention(q, k, v, bias=None, scale=None, drop_p=0.0, training=False):
-    """dropout(softmax(q k^T * scale + bias)) v for q,k [BH,T,A], v [BH,T,Dv]."""
+def attention(q, k, v, bias=None, scale=None, drop_p=0.0, training=False, labels=None, heads=1):
+    """dropout(softmax(q k^T * scale + bias + label term)) v for q,k [BH,T,A], v [BH,T,Dv]. bias
+    [nbias,T,T] (sequence bh reads bias[bh % nbias]; its gradient is the sum over the sequences
+    that share a slice); labels int32 [nlab,T] or None: item bh // heads reads row
+    (bh // heads) % nlab, scores between tokens whose labels differ gain -100."""
     if scale is None:
         scale = 1.0 / (q.shape[-1] ** 0.5)
     drop = (0.0, 0, 0)
     if training and drop_p > 0:
         drop = (float(drop_p), torch.initial_seed(), next(_dropout_counter))
-    return _AttentionFn.apply(q, k, v, bias, float(scale), drop)
+    return _AttentionFn.apply(q, k, v, bias, float(scale), drop, labels, int(heads))
 
 
 # ---- data movement with autograd (U-Net++ dense links) ---------------------------------------

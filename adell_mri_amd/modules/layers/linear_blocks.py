@@ -84,6 +84,26 @@ class MLP(torch.nn.Module):
         return mods[-1](X, residual=residual) if residual is not None else mods[-1](X)
 
 
+def attention_route(tokens: int, a: int, h: int, qk_affine: bool = True) -> str:
+    """Which attention kernels ``MultiHeadSelfAttention`` runs for ``tokens`` tokens per sequence
+    and head widths ``a`` (q, k) and ``h`` (v); ``qk_affine``: the q / k LayerNorms carry a weight
+    (always, as this layer builds them; the in-place sequence form needs it). Host only. A 4-D
+    mask takes a "window" shape to the route the shape would have without the window kernel.
+      "window":  the one-thread-per-row kernel on the QKV buffer in place (csrc/window.hip):
+                 up to 64 tokens and head widths up to 32; takes a dense mask;
+      "seq":     the MFMA sequence kernels on the projection output in place
+                 (functional.seq_attention): head widths 32 / 64 / 128 from 16 tokens;
+      "general": sliced q / k / v through functional.attention: any head width up to 256.
+    "seq" and "general" take shifted-window masks as region labels."""
+    if tokens <= 64 and a <= 32 and h <= 32:
+        return "window"
+    return _sequence_route(tokens, a, h, qk_affine)
+
+
+def _sequence_route(tokens, a, h, qk_affine=True):
+    return "seq" if qk_affine and HF.seq_attention_ok(tokens, a, h) else "general"
+
+
 class MultiHeadSelfAttention(torch.nn.Module):
     def __init__(self, input_dim: int, attention_dim: int, hidden_dim: int, output_dim: int,
                  n_heads: int = 4, dropout_rate: float = 0.0, window_size: bool = False):
@@ -130,14 +150,29 @@ class MultiHeadSelfAttention(torch.nn.Module):
             self.relative_position_bias_table.device)
         return self.relative_position_bias_table[idx].reshape(self.n_heads, t, t)
 
-    def forward(self, X: torch.Tensor, mask=None, residual: torch.Tensor = None) -> torch.Tensor:
+    def forward(self, X: torch.Tensor, mask=None, residual: torch.Tensor = None,
+                mask_labels=None) -> torch.Tensor:
+        """mask: additive [n_windows, t, t] (or broadcastable 4-D) mask; mask_labels: int32
+        [n_windows, t] region labels, the same mask as -100 between tokens whose labels differ
+        without its t^2 floats per window (vit.shift_region_labels); the small-window kernel
+        reads a dense mask and refuses labels (vit.mask_from_labels builds the mask once). Beyond
+        that kernel a dense ``mask`` on a windowed layer ([n_windows, t, t], [n_windows, 1, t, t]
+        or [n_windows, n_heads, t, t]) is added to the relative-position bias as a
+        [n_windows * n_heads, t, t] tensor: correct, but memory-hungry -- pass labels instead."""
         sh = X.shape
         b, t = sh[:-2], sh[-2]
         nb = 1
         for i in b:
             nb *= i
         a, h = self.real_attention_dim, self.real_hidden_dim
-        if t <= 64 and a <= 32 and h <= 32 and (mask is None or mask.ndim == 3):
+        affine = self.q_norm.weight is not None
+        route = attention_route(t, a, h, affine)
+        if route == "window" and mask is not None and mask.ndim != 3:
+            route = _sequence_route(t, a, h, affine)
+        if route == "window":
+            if mask_labels is not None:
+                raise ValueError("the small-window attention kernel takes a dense mask, not region "
+                                 "labels: pass mask=vit.mask_from_labels(labels)")
             # short sequences / windows: q-norm, k-norm, bias, mask, dropout and attention on
             # the QKV buffer in place (csrc/window.hip)
             rel = self.relative_position_bias(t) if self.window_size else None
@@ -150,21 +185,35 @@ class MultiHeadSelfAttention(torch.nn.Module):
                                     drop_p=self.dropout_rate, training=self.training,
                                     eps=self.q_norm.eps)
             return self.output_layer(O.view(*b, t, self.hidden_dim), residual=residual)
-        if self.window_size:
-            raise NotImplementedError("windowed attention beyond 64 tokens per window")
         bias = None
-        if mask is not None:
+        labels = None if mask_labels is None else mask_labels.to(device=X.device, dtype=torch.int32)
+        if self.window_size:
+            # larger windows / wider heads: the sequence kernels with the relative-position bias
+            # of head h as slice h and the shift mask as region labels
+            bias = self.relative_position_bias(t)
+            if mask is not None:
+                # a dense mask: rel[None] + mask[:, None], [n_windows * n_heads, t, t]
+                m = mask.to(device=X.device, dtype=torch.float32)
+                if m.ndim == 3:
+                    m = m.unsqueeze(1)
+                if m.ndim != 4 or m.shape[1] not in (1, self.n_heads) or m.shape[2:] != (t, t):
+                    raise ValueError(f"windowed attention mask must be [n_windows, {t}, {t}] or "
+                                     f"[n_windows, 1 or {self.n_heads}, {t}, {t}], got "
+                                     f"{tuple(mask.shape)}")
+                m = m.expand(m.shape[0], self.n_heads, t, t).contiguous()
+                bias = HF.add_bcast(m, bias).reshape(-1, t, t)
+        elif mask is not None:
             m = mask.to(device=X.device, dtype=torch.float32)
             if m.ndim == 3:
                 m = m.unsqueeze(1)
             bias = m.expand(nb, self.n_heads, t, t).reshape(nb * self.n_heads, t, t)
-        if self.q_norm.weight is not None and HF.seq_attention_ok(t, a, h):
+        if route == "seq":
             # q-norm, k-norm and attention on the projection output in place: no slices, no
             # permutes (functional._SeqAttnFn)
             O = HF.seq_attention(self.qkv(X).reshape(nb * t, self.qkv_dim), self.q_norm.weight,
                                  self.q_norm.bias, self.k_norm.weight, self.k_norm.bias, nb,
                                  self.n_heads, t, a, h, bias=bias, drop_p=self.dropout_rate,
-                                 training=self.training, eps=self.q_norm.eps)
+                                 training=self.training, eps=self.q_norm.eps, labels=labels)
             return self.output_layer(O.view(*b, t, self.hidden_dim), residual=residual)
         QKV = self.qkv(X).reshape(nb, t, self.n_heads, 2 * a + h).permute(0, 2, 1, 3)
         Q = self.q_norm(QKV[..., :a].contiguous())      # per-head interleaved q | k | v
@@ -172,6 +221,6 @@ class MultiHeadSelfAttention(torch.nn.Module):
         V = QKV[..., 2 * a:].contiguous()
         O = HF.attention(Q.reshape(nb * self.n_heads, t, a), K.reshape(nb * self.n_heads, t, a),
                          V.reshape(nb * self.n_heads, t, h), bias, drop_p=self.dropout_rate,
-                         training=self.training)
+                         training=self.training, labels=labels, heads=self.n_heads)
         O = O.reshape(nb, self.n_heads, t, h).transpose(1, 2).reshape(*b, t, self.hidden_dim)
         return self.output_layer(O, residual=residual)

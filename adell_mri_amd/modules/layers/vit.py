@@ -15,7 +15,7 @@ import torch
 
 from ... import functional as HF
 from .adn_fn import get_adn_fn
-from .linear_blocks import MLP, LayerNorm, Linear, MultiHeadSelfAttention
+from .linear_blocks import MLP, LayerNorm, Linear, MultiHeadSelfAttention, attention_route
 from .regularization import ChannelDropout
 
 
@@ -420,11 +420,13 @@ def einops_rescale(X: torch.Tensor, scale) -> torch.Tensor:
     return HF.space_to_depth(X, [int(s) for s in scale])
 
 
-def generate_mask(image_size, window_size, shift_size):
-    """Additive attention mask of shifted windows (vit.py:132-207), in patch units:
-    [n_windows, tokens, tokens] with -100 between tokens of different shift regions. Host
-    logic, evaluated once per block. Like the reference, region labels are read with the
-    window index as the FAST factor of each axis ("(w1 h)": position = w1 * n_windows + h)."""
+def shift_region_labels(image_size, window_size, shift_size):
+    """Shift-region label of every token of every window (vit.py:132-207 before the expansion to
+    a mask), in patch units: int32 [n_windows, tokens], or None without a shift. Two tokens of a
+    window attend to each other iff their labels agree; the attention kernels take this array
+    as their ``labels`` operand. Host logic, evaluated once per block. Like the reference, the
+    labels are read with the window index as the FAST factor of each axis ("(w1 h)": position =
+    w1 * n_windows + h)."""
     nd = len(image_size)
     if not isinstance(window_size, list):
         window_size = [window_size for _ in image_size]
@@ -446,8 +448,23 @@ def generate_mask(image_size, window_size, shift_size):
     lab = label.reshape(shape)                                   # (w1 h w2 w w3 d)
     perm = [2 * i + 1 for i in range(nd)] + [2 * i for i in range(nd)]
     lab = lab.transpose(perm).reshape(int(np.prod(n_win)), int(np.prod(window_size)))
-    diff = lab[:, None, :] - lab[:, :, None]
-    return torch.from_numpy(np.where(diff != 0, -100.0, 0.0).astype(np.float32))
+    return torch.from_numpy(np.ascontiguousarray(lab).astype(np.int32))
+
+
+def mask_from_labels(labels):
+    """[n_windows, tokens] labels -> additive mask [n_windows, tokens, tokens]: -100 between
+    tokens of different regions."""
+    diff = labels[:, None, :] != labels[:, :, None]
+    return torch.where(diff, -100.0, 0.0).to(torch.float32)
+
+
+def generate_mask(image_size, window_size, shift_size):
+    """Additive attention mask of shifted windows (vit.py:132-207), in patch units:
+    [n_windows, tokens, tokens] with -100 between tokens of different shift regions, or None
+    without a shift. tokens^2 floats per window: the small-window kernel reads it, larger windows
+    take ``shift_region_labels`` instead."""
+    labels = shift_region_labels(image_size, window_size, shift_size)
+    return None if labels is None else mask_from_labels(labels)
 
 
 class SWINTransformerBlock(torch.nn.Module):
@@ -498,11 +515,19 @@ class SWINTransformerBlock(torch.nn.Module):
         self.input_dim_primary = self.embedding.true_n_features
 
     def init_mask_if_necessary(self):
-        self.attention_mask = generate_mask(
+        """Region labels of the shifted windows; the dense [n_windows, tokens, tokens] mask only
+        where the small-window kernel reads it (the other attention kernels take the labels)."""
+        window = [x // y for x, y in zip(self.window_size, self.patch_size)]
+        self.attention_labels = shift_region_labels(
             image_size=[x // y for x, y in zip(self.image_size, self.patch_size)],
-            window_size=[x // y for x, y in zip(self.window_size, self.patch_size)],
-            shift_size=self.shift_size)
+            window_size=window, shift_size=self.shift_size)
+        dense = attention_route(int(np.prod(window)), self.mha.real_attention_dim,
+                                self.mha.real_hidden_dim) == "window"
+        self.attention_mask = None
+        if dense and self.attention_labels is not None:
+            self.attention_mask = mask_from_labels(self.attention_labels)
         self._mask_dev = None
+        self._labels_dev = None
 
     def init_layers(self):
         if isinstance(self.mlp_structure, float):
@@ -528,6 +553,13 @@ class SWINTransformerBlock(torch.nn.Module):
             self._mask_dev = self.attention_mask.to(device)
         return self._mask_dev
 
+    def _labels(self, device):
+        if self.attention_labels is None or self.attention_mask is not None:
+            return None
+        if self._labels_dev is None or self._labels_dev.device != device:
+            self._labels_dev = self.attention_labels.to(device)
+        return self._labels_dev
+
     def _drop(self, X):
         if self.training and self.dropout_rate > 0:
             return HF.elementwise(X, drop_p=self.dropout_rate, training=True)
@@ -551,7 +583,8 @@ class SWINTransformerBlock(torch.nn.Module):
         # [b, H, W, c] -- in the lifted frame [b, 1, H, W, c] that is (0, 0, s0, s1)
         shift = (0, 0, ss[0], ss[1]) if two_d else (0, ss[0], ss[1], ss[2])
         embedded = self.embedding.window_tokens(X, shift)
-        attention = self.mha(self.norm_op_1(embedded), mask=self._mask(X.device))
+        attention = self.mha(self.norm_op_1(embedded), mask=self._mask(X.device),
+                             mask_labels=self._labels(X.device))
         shifted = self.embedding.window_image(attention)
         drop = self.training and self.dropout_rate > 0
         X = HF.add(shortcut, self._drop(shifted))

@@ -1456,8 +1456,22 @@ def sum_bcast(g, period_shape):
     return db
 
 
-def attention_fwd(q, k, v, bias, scale, drop_p=0.0, seed=0, offset=0):
-    """q,k: [BH,T,A]; v: [BH,T,Dv]; bias: [nbias,T,T] or None. Returns (out, lse)."""
+def _att_labels(labels, T):
+    """(labels, nlab) of an int32 [nlab, T] region-label operand, or (None, 0)."""
+    if labels is None:
+        return None, 0
+    if not labels.is_cuda:
+        raise AdellHipError("adell_mri_amd kernels run on MI355X only: got CPU labels")
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[1] != T:
+        raise AdellHipError(f"attention: labels must be int32 [nlab, {T}], got "
+                            f"{labels.dtype} {tuple(labels.shape)}")
+    return labels.contiguous(), int(labels.shape[0])
+
+
+def attention_fwd(q, k, v, bias, scale, drop_p=0.0, seed=0, offset=0, labels=None, heads=1):
+    """q,k: [BH,T,A]; v: [BH,T,Dv]; bias: [nbias,T,T] or None; labels: int32 [nlab,T] or None --
+    item b = bh // heads reads row b % nlab, and scores between tokens whose labels differ gain
+    -100. Returns (out, lse)."""
     _require_cuda(q, k, v, bias)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     BH, T, A = q.shape
@@ -1468,14 +1482,16 @@ def attention_fwd(q, k, v, bias, scale, drop_p=0.0, seed=0, offset=0):
     if bias is not None:
         bias = bias.contiguous()
         nb = bias.numel() // (T * T)
-    check(_lib.lib().adell_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, BH, T, A, Dv,
-                                         float(scale), float(drop_p),
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF,
-                                         _ptr(out), _ptr(lse), _stream()))
+    labels, nlab = _att_labels(labels, T)
+    check(_lib.lib().adell_attention_fwd_labels(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, int(heads), BH, T, A, Dv,
+        float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF,
+        _ptr(out), _ptr(lse), _stream()))
     return out, lse
 
 
-def attention_bwd(q, k, v, bias, out, dout, lse, scale, drop_p=0.0, seed=0, offset=0):
+def attention_bwd(q, k, v, bias, out, dout, lse, scale, drop_p=0.0, seed=0, offset=0, labels=None,
+                  heads=1):
     BH, T, A = q.shape
     Dv = v.shape[-1]
     dout = dout.contiguous()
@@ -1483,12 +1499,50 @@ def attention_bwd(q, k, v, bias, out, dout, lse, scale, drop_p=0.0, seed=0, offs
     if bias is not None:
         bias = bias.contiguous()
     nb = 0 if bias is None else bias.numel() // (T * T)
-    check(_lib.lib().adell_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(out),
-                                         _ptr(dout), _ptr(lse), BH, T, A, Dv, float(scale),
-                                         float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                         int(offset) & 0xFFFFFFFF,
-                                         _ptr(dq), _ptr(dk), _ptr(dv), _stream()))
+    labels, nlab = _att_labels(labels, T)
+    check(_lib.lib().adell_attention_bwd_labels(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, int(heads), _ptr(out),
+        _ptr(dout), _ptr(lse), BH, T, A, Dv, float(scale), float(drop_p),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF, _ptr(dq), _ptr(dk), _ptr(dv),
+        _stream()))
     return dq, dk, dv
+
+
+def attention_bias_grad(q, k, v, bias, out, dout, lse, scale, nbias, drop_p=0.0, seed=0, offset=0,
+                        labels=None, heads=1, strides=None, dims=None):
+    """Gradient of the additive bias of attention_fwd / attention_fwd_strided, summed over the
+    sequences that share a slice: [nbias, T, T] with dbias[j] = sum of dS[bh] over bh % nbias == j
+    (``nbias`` = heads: a per-head bias; = BH: dS itself). ``bias`` may be None. Contiguous
+    [BH,T,*] operands by default; with ``strides`` (15 element strides: (item, head, row) of q, k, v,
+    out, dout) and ``dims`` = (B, H, T, A, Dv) the operands are addressed as in
+    attention_bwd_strided. Device memory: the result and a workspace whose size depends on
+    (nbias, T) alone."""
+    _require_cuda(q, k, v, bias, out, dout, lse)
+    if strides is None:
+        q, k, v, out, dout = (t.contiguous() for t in (q, k, v, out, dout))
+        BH, T, A = q.shape
+        Dv = v.shape[-1]
+        H = int(heads)
+        if BH % H:
+            raise AdellHipError(f"attention_bias_grad: {BH} sequences are not items of {H} heads")
+        B = BH // H
+        strides = (H * T * A, T * A, A) * 2 + (H * T * Dv, T * Dv, Dv) * 3
+    else:
+        B, H, T, A, Dv = (int(x) for x in dims)
+    nbias = int(nbias)
+    bias = None if bias is None else bias.contiguous()
+    if bias is not None and bias.numel() != nbias * T * T:
+        raise AdellHipError("attention_bias_grad: bias is not [nbias, T, T]")
+    labels, nlab = _att_labels(labels, T)
+    dbias = torch.empty((nbias, T, T), device=q.device, dtype=torch.float32)
+    nws = _lib.lib().adell_attention_bias_grad_workspace_floats(nbias, T)
+    ws = _workspace(nws * 4, q.device) if nws else None
+    st = (ctypes.c_long * 15)(*[int(x) for x in strides])
+    check(_lib.lib().adell_attention_bias_grad(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nbias, _ptr(labels), nlab, _ptr(out), _ptr(dout),
+        _ptr(lse), B, H, T, A, Dv, st, float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        int(offset) & 0xFFFFFFFF, _ptr(dbias), _ptr(ws), nws, _stream()))
+    return dbias
 
 
 # launch plan of one attention pass (adell_attention_plan). path: one of ATT_PATHS; lds: dynamic LDS
@@ -2062,7 +2116,7 @@ def attention_strided_ok(T, A, Dv):
 
 
 def attention_fwd_strided(q, k, v, out, strides, bias, B, H, T, A, Dv, scale, drop_p=0.0, seed=0,
-                          offset=0):
+                          offset=0, labels=None):
     """q, k, v, out: tensors whose data pointers are the first rows of sequence 0 (flat views
     into packed buffers are fine); strides: 12 element strides, (item, head, row) for each of
     q, k, v, out. Writes ``out``; returns lse [B*H, T]."""
@@ -2071,21 +2125,24 @@ def attention_fwd_strided(q, k, v, out, strides, bias, B, H, T, A, Dv, scale, dr
     lse = torch.empty((B * H, T), device=q.device, dtype=torch.float32)
     nb = 0 if bias is None else bias.numel() // (T * T)
     st = (ctypes.c_long * 12)(*[int(x) for x in strides])
-    check(_lib.lib().adell_attention_fwd_strided(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, B, H, T, A, Dv, st, float(scale), float(drop_p),
+    labels, nlab = _att_labels(labels, T)
+    check(_lib.lib().adell_attention_fwd_strided_labels(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, B, H, T, A, Dv, st, float(scale), float(drop_p),
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF, _ptr(out), _ptr(lse), _stream()))
     return lse
 
 
 def attention_bwd_strided(q, k, v, out, dout, lse, dq, dk, dv, strides, bias, B, H, T, A, Dv, scale,
-                          drop_p=0.0, seed=0, offset=0):
+                          drop_p=0.0, seed=0, offset=0, labels=None):
     """strides: 24 element strides, (item, head, row) for q, k, v, out, dout, dq, dk, dv."""
     _require_cuda(q, k, v, out, dout, lse, dq, dk, dv, bias)
     bias = None if bias is None else bias.contiguous()
     nb = 0 if bias is None else bias.numel() // (T * T)
     st = (ctypes.c_long * 24)(*[int(x) for x in strides])
-    check(_lib.lib().adell_attention_bwd_strided(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(out), _ptr(dout), _ptr(lse), B, H, T, A, Dv,
+    labels, nlab = _att_labels(labels, T)
+    check(_lib.lib().adell_attention_bwd_strided_labels(
+        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, _ptr(out), _ptr(dout),
+        _ptr(lse), B, H, T, A, Dv,
         st, float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF,
         _ptr(dq), _ptr(dk), _ptr(dv), _stream()))
 

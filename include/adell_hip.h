@@ -595,6 +595,54 @@ int adell_attention_bwd_strided(const float* q, const float* k, const float* v, 
                                 float scale, float drop_p, unsigned long long seed,
                                 unsigned int rng_offset, float* dq, float* dk, float* dv,
                                 void* stream);
+/* The four entries above with region labels: labels int32 [nlab][T] or NULL. Item b (sequences
+ * b * H .. b * H + H - 1; the contiguous entries take H for this alone) reads row b % nlab, and the
+ * score of query i and key j gains -100 where labels[i] != labels[j], after scale and bias: the
+ * shifted-window mask of SWIN (vit.py:132-207) without its [n_windows][T][T] expansion. NULL labels
+ * are the entries above, bit for bit (they call these). */
+int adell_attention_fwd_labels(const float* q, const float* k, const float* v, const float* bias,
+                               int nbias, const int* labels, int nlab, int H, int BH, int T, int A,
+                               int Dv, float scale, float drop_p, unsigned long long seed,
+                               unsigned int rng_offset, float* out, float* lse, void* stream);
+int adell_attention_bwd_labels(const float* q, const float* k, const float* v, const float* bias,
+                               int nbias, const int* labels, int nlab, int H, const float* out,
+                               const float* dout, const float* lse, int BH, int T, int A, int Dv,
+                               float scale, float drop_p, unsigned long long seed,
+                               unsigned int rng_offset, float* dq, float* dk, float* dv,
+                               void* stream);
+int adell_attention_fwd_strided_labels(const float* q, const float* k, const float* v,
+                                       const float* bias, int nbias, const int* labels, int nlab,
+                                       int B, int H, int T, int A, int Dv, const long* strides,
+                                       float scale, float drop_p, unsigned long long seed,
+                                       unsigned int rng_offset, float* out, float* lse,
+                                       void* stream);
+int adell_attention_bwd_strided_labels(const float* q, const float* k, const float* v,
+                                       const float* bias, int nbias, const int* labels, int nlab,
+                                       const float* out, const float* dout, const float* lse, int B,
+                                       int H, int T, int A, int Dv, const long* strides, float scale,
+                                       float drop_p, unsigned long long seed,
+                                       unsigned int rng_offset, float* dq, float* dk, float* dv,
+                                       void* stream);
+/* Gradient of the additive bias: dbias[j] = sum over sequences bh % nbias == j of
+ * dS[bh] = P o (keep dP / (1 - drop_p) - rowsum(dO o O)), [nbias][T][T], no `scale` factor (the bias
+ * is added after it). nbias in [1, B * H] is the number of result slices whether or not `bias` is
+ * NULL: H gives the gradient of a per-head bias, B * H the plain dS. Scores, labels and the dropout
+ * mask are rebuilt as the backward kernels build them. `strides`: 15 element strides, (item, head,
+ * row) for q, k, v, out, dout; head dims 32 / 64 / 128 at T >= 16 with 16-byte aligned pointers and
+ * strides that are multiples of 4 run on the MFMA, everything else up to head dims of 256 on the
+ * vector ALU. No atomics: the sequences of a slice are summed in ascending order within a chunk, the
+ * chunks in order by a second pass through `workspace`, whose size
+ * (adell_attention_bias_grad_workspace_floats: at most 16 partial results, and at most 512 tiles of
+ * 128 x 128 floats) does not depend on the number of sequences. Nothing of B * H * T * T elements
+ * is ever written. The slices are the y dimension of the grid: nbias above 65535 is refused with
+ * ADELL_E_BADARG (the attention entries above put B * H there and fail at the launch beyond it). */
+long adell_attention_bias_grad_workspace_floats(int nbias, int T);
+int adell_attention_bias_grad(const float* q, const float* k, const float* v, const float* bias,
+                              int nbias, const int* labels, int nlab, const float* out,
+                              const float* dout, const float* lse, int B, int H, int T, int A, int Dv,
+                              const long* strides, float scale, float drop_p,
+                              unsigned long long seed, unsigned int rng_offset, float* dbias,
+                              float* workspace, long workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------
  * Data movement for the U-Net++ dense links (standard_blocks.py:365-371):
