@@ -11,6 +11,8 @@ Statistics produced by the conv epilogue ride on the output tensor as
 ``y._adell_partials`` so that the following ``norm_drop_act`` does not re-read
 ``y``; they are dropped by any other consumer.
 """
+import collections
+import ctypes
 import itertools
 import os
 import weakref
@@ -72,7 +74,6 @@ def set_conv_precision(mode):
 def _sync_dw_precision():
     """The depthwise 7^3 kernels choose their arithmetic inside the library (csrc/dw_mfma.hip: the
     f16x3 Toeplitz form on the MFMA): "fp32" keeps them on the exact fp32-FMA kernels too."""
-    from . import _lib
     if os.path.exists(_lib.LIB_PATH) and not os.environ.get("ADELL_DW_NOMFMA"):
         _lib.lib().adell_set_tuning(b"dw_nomfma", 1 if CONV_PRECISION == "fp32" else 0)
 
@@ -157,12 +158,28 @@ def _repack_registered():
     return True
 
 
+def _tensor_pack_cache(w, key, build):
+    """``build()`` cached under ``key`` ON the tensor object (so the cache dies with it), valid only for the
+    same storage address, version counter and weight epoch; a hit waits for its pack launch (_PackFence)."""
+    cache = getattr(w, "_adell_packs", None)
+    if cache is None:
+        cache = w._adell_packs = {}
+    tag = _pack_tag(w)
+    hit = cache.get(key)
+    if hit is not None and hit[0] == tag:
+        if w.is_cuda:
+            hit[2].order()
+        return hit[1]
+    p = build()
+    cache[key] = (tag, p, _PackFence() if w.is_cuda else None)
+    return p
+
+
 def _packed(w, mode):
-    """Repacked copy of a weight. The cache lives ON the tensor object (so it dies
-    with it) and is valid only for the same storage address and version counter."""
+    """Repacked copy of a weight (see _tensor_pack_cache; the f16x3 conv operands of modes 0 / 1
+    live in _PACK_REG instead, for the one-launch repack)."""
     split = CONV_PRECISION == "f16x3" and mode in (0, 1, 2, 3)
     if split and mode in (0, 1) and w.dim() == 5 and w.is_contiguous():
-        import weakref
         key = (id(w), mode)
         ent = _PACK_REG.get(key)
         if ent is not None and ent[0]() is not w:
@@ -178,77 +195,48 @@ def _packed(w, mode):
         p = ops.pack_weight_f16x3(w.detach(), mode)
         _PACK_REG[key] = [weakref.ref(w), mode, p, _pack_tag(w), _PackFence()]
         return p
-    cache = getattr(w, "_adell_packs", None)
-    if cache is None:
-        cache = {}
-        w._adell_packs = cache
-    key = (mode, split)
-    hit = cache.get(key)
-    tag = (w._version, w.data_ptr(), ops.WEIGHT_EPOCH)
-    if hit is not None and hit[0] == tag:
-        if w.is_cuda:
-            hit[2].order()
-        return hit[1]
-    wd = w.detach()
-    if wd.dim() == 2:  # torch.nn.Linear weight == 1x1x1 convolution weight
-        wd = wd.view(wd.shape[0], wd.shape[1], 1, 1, 1)
-    if split and mode == 2:
-        # transposed conv forward = 1x1x1 conv with F*Cout outputs: V[(f, co)][ci] = w[ci][co][f]
-        v = wd.permute(2, 3, 4, 1, 0).reshape(-1, wd.shape[0], 1, 1, 1)
-        p = ops.pack_weight_f16x3(v, 0)
-    elif split and mode == 3:
-        # its backward-data = kernel == stride conv with Cin outputs / Cout inputs: w as is
-        p = ops.pack_weight_f16x3(wd, 0)
-    else:
-        p = ops.pack_weight_f16x3(wd, mode) if split else ops.pack_weight(wd, mode)
-    cache[key] = (tag, p, _PackFence() if w.is_cuda else None)
-    return p
+
+    def build():
+        wd = w.detach()
+        if wd.dim() == 2:  # torch.nn.Linear weight == 1x1x1 convolution weight
+            wd = wd.view(wd.shape[0], wd.shape[1], 1, 1, 1)
+        if split and mode == 2:
+            # transposed conv forward = 1x1x1 conv with F*Cout outputs: V[(f, co)][ci] = w[ci][co][f]
+            v = wd.permute(2, 3, 4, 1, 0).reshape(-1, wd.shape[0], 1, 1, 1)
+            return ops.pack_weight_f16x3(v, 0)
+        if split and mode == 3:
+            # its backward-data = kernel == stride conv with Cin outputs / Cout inputs: w as is
+            return ops.pack_weight_f16x3(wd, 0)
+        return ops.pack_weight_f16x3(wd, mode) if split else ops.pack_weight(wd, mode)
+    return _tensor_pack_cache(w, (mode, split), build)
 
 
 def _packed_s2_classes(w, padding):
     """The 8 parity-class sub-kernels of a stride-2 k = 3 conv weight, packed for the
     backward-data kernel (mode 1); cached on the tensor."""
-    cache = getattr(w, "_adell_packs", None)
-    if cache is None:
-        cache = {}
-        w._adell_packs = cache
-    tag = _pack_tag(w)
-    key = ("s2", tuple(padding))
-    hit = cache.get(key)
-    if hit is not None and hit[0] == tag:
-        hit[2].order()
-        return hit[1]
-    wd = w.detach()
-    packs = []
-    for c in range(8):
-        par = (c >> 2, (c >> 1) & 1, c & 1)
-        t0 = [(par[a] + padding[a]) & 1 for a in range(3)]
-        sub = wd[:, :, t0[0]::2, t0[1]::2, t0[2]::2].contiguous()
-        packs.append(ops.pack_weight_f16x3(sub, 1))
-    cache[key] = (tag, packs, _PackFence())
-    return packs
+    def build():
+        wd = w.detach()
+        packs = []
+        for c in range(8):
+            par = (c >> 2, (c >> 1) & 1, c & 1)
+            t0 = [(par[a] + padding[a]) & 1 for a in range(3)]
+            sub = wd[:, :, t0[0]::2, t0[1]::2, t0[2]::2].contiguous()
+            packs.append(ops.pack_weight_f16x3(sub, 1))
+        return packs
+    return _tensor_pack_cache(w, ("s2", tuple(padding)), build)
 
 
 def _packed_folded(w):
     """f16x3 pack of W'[co][kx * Cin + ci][kz][ky][0] = w[co][ci][kz][ky][kx], zero-padded to 16
     input channels (the weight of the folded conv, see ops.fold_x_taps); cached on the tensor."""
-    cache = getattr(w, "_adell_packs", None)
-    if cache is None:
-        cache = {}
-        w._adell_packs = cache
-    tag = _pack_tag(w)
-    hit = cache.get("fold")
-    if hit is not None and hit[0] == tag:
-        hit[2].order()
-        return hit[1]
-    wd = w.detach()
-    co, ci, kd, kh, kw = wd.shape
-    wf = wd.permute(0, 4, 1, 2, 3).reshape(co, kw * ci, kd, kh, 1)
-    if kw * ci < 16:
-        wf = torch.cat([wf, wf.new_zeros(co, 16 - kw * ci, kd, kh, 1)], 1)
-    p = ops.pack_weight_f16x3(wf.contiguous(), 0)
-    cache["fold"] = (tag, p, _PackFence())
-    return p
+    def build():
+        wd = w.detach()
+        co, ci, kd, kh, kw = wd.shape
+        wf = wd.permute(0, 4, 1, 2, 3).reshape(co, kw * ci, kd, kh, 1)
+        if kw * ci < 16:
+            wf = torch.cat([wf, wf.new_zeros(co, 16 - kw * ci, kd, kh, 1)], 1)
+        return ops.pack_weight_f16x3(wf.contiguous(), 0)
+    return _tensor_pack_cache(w, "fold", build)
 
 
 # absmax by-product slots ([0]: input(s) of a conv, [1]: its dy), zeroed in bulk: every slot is
@@ -538,12 +526,126 @@ def materialize(t):
     return t if rows is None else ops.rows_to_f32(t.detach(), rows)
 
 
+class _Shape:
+    """Stands in for a tensor in the ops.*_ok predicates, which read only ``.shape`` / ``.dim()``."""
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+    def dim(self):
+        return len(self.shape)
+
+
+def conv3d_route(x0_shape, weight_shape, stride, padding, C1=None, has_residual=False,
+                 has_carry=False, has_rows=False):
+    """The forward kernel of ``conv3d`` -- the one routing decision of the forward pass. Host only: shapes
+    (or the tensors: only ``.shape`` is read), triples and flags (``C1``: channels of the second source,
+    None without one; ``has_carry``: any GradCarry; ``has_rows``: x0 holds split rows); first match wins."""
+    x0, w = x0_shape, weight_shape
+    if isinstance(x0, tuple):       # (conv3d() passes its tensors: no stand-ins built per call)
+        x0, w = _Shape(x0), _Shape(w)
+    residual = has_residual or None       # (the predicates test ``is None`` only, as for x1 / C1)
+    # A 1x1x1 stride-1 conv over channels-last memory IS a Linear layer over the voxels: the GEMM
+    # kernels take it (fused bias). On the implicit-GEMM conv kernels a brick's voxels x one 16-channel
+    # chunk per step is the wrong tiling for it: ConvNeXt's stage transitions (384 -> 768 at 64 x 2^3
+    # voxels) ran 0.79 ms forward and 0.78 ms backward-data at 0.4 TF, UNETR's 512 -> 512 at 12^3
+    # 0.19 / 0.21 / 0.32 ms. (No statistics partials then: a following instance norm computes its own.)
+    if (w.dim() == 5 and w.shape[2:] == (1, 1, 1) and stride == (1, 1, 1)
+            and padding == (0, 0, 0) and C1 is None and not has_residual and not has_carry
+            and x0.dim() == 5 and not has_rows and max(w.shape[:2]) >= 64
+            and min(w.shape[:2]) >= 8 and not FLAGS["no_pointwise_gemm"]):
+        return "pointwise_gemm"
+    # logits head: 1x1x1, Cout <= 4 -- one HBM-bound pass on canonical weights
+    if ops.conv1_small_ok(w, x0.shape[1] + (C1 or 0), stride, padding, residual):
+        return "conv1_small"
+    # 2-channel input block: exact fp32 on the vector ALU, canonical weights
+    if ops.conv_cin_small_ok(w, x0, C1, stride, padding, residual):
+        return "cin_small"
+    # K = 27 Cin im2col GEMM on the fp32 MFMA (forward, dW); dX: f16x3 igemm
+    if ops.conv_cinfold_ok(w, x0, C1, stride, padding, residual):
+        return "cinfold"
+    # Cin <= 4, Kw * Cin <= 16: the x taps ride in the 16-channel MFMA chunk (forward only: the
+    # gradients see the original tensors and weights)
+    if (CONV_PRECISION == "f16x3" and C1 is None and w.dim() == 5 and x0.shape[1] <= 4
+            and 3 <= w.shape[4] and w.shape[4] * x0.shape[1] <= 16
+            and stride == (1, 1, 1) and not FLAGS["no_fold"]):
+        return "fold"
+    return "igemm"      # fp32 or f16x3 MFMA, by CONV_PRECISION
+
+
+def conv3d_dgrad_route(fwd_route, x0_shape, weight_shape, stride, padding, C1=0, need0=True,
+                       need1=False, has_x1=False, has_add0=False, sites=False, lowrank=False):
+    """The backward-data kernel of a conv whose forward took ``fwd_route``; None when nothing needs a data
+    gradient. Host only, first match wins, the library is asked only when the cheaper conditions before a
+    query hold. ``need0`` / ``need1``: needs_input_grad of x0 / x1; ``has_add0``: a parked gradient joins
+    dx0; ``sites``: single-use ADN sites with a fused-epilogue plan; ``lowrank``: the factored logits head."""
+    f16x3 = CONV_PRECISION == "f16x3"      # (evaluated at backward time)
+    N, C0, in_size = x0_shape[0], x0_shape[1], tuple(x0_shape[2:])
+    Cout, k = weight_shape[0], tuple(weight_shape[2:]) or (1, 1, 1)
+    need1 = has_x1 and need1
+    if fwd_route == "conv1_small":
+        if lowrank and need0:
+            return "conv1_lowrank"      # dX = dy (x) weight stays factored
+        return "conv1_small" if need0 or need1 else None
+    if need0 and fwd_route == "cinfold" and _lib.lib().adell_conv_cinfold_dx_applicable(
+            ctypes.byref(ops.make_conv_desc(N, in_size, C0, 0, Cout, 3, 1, padding))):
+        return "cinfold"                # (refused: Cout > 64 or not a multiple of 4 -- falls through)
+    if need0 and fwd_route == "cin_small":
+        if Cout % 4 == 0:
+            return "cin_small"
+        # Cout <= 4 too (the 2 -> 2 conv of an input block whose input carries a gradient:
+        # SWIN-UNet): dX is the same small conv of dY with the taps flipped and the channel
+        # axes swapped (padding k - 1 - p) -- on the vector-ALU forward kernel instead of a
+        # 32-column MFMA tile that is 94 % empty (1.37 ms -> 0.1 ms at 256 x 256 x 128)
+        if (Cout <= 4 and stride == (1, 1, 1)
+                and ops.conv_out_size(in_size, k, stride, padding) == in_size):
+            return "cin_small_flipped"
+    if need0 and not has_x1 and f16x3:
+        # the U-Net downsampling layer at 32 channels: one persistent launch
+        if ops.conv3d_bwd_data_s2_fused_ok(in_size, C0, C1, Cout, k, stride, padding):
+            return "s2_fused"
+        # stride-2 backward-data by parity classes (no zero-inserted MFMA work). Eight
+        # launches: pays from ~1 M voxels (measured: 128^3 0.52 -> 0.33 ms, 32^3 0.06 -> 0.16)
+        if (stride == (2, 2, 2) and k == (3, 3, 3) and all(p <= 1 for p in padding)
+                and all(s % 2 == 0 for s in in_size) and not FLAGS["no_s2class"]
+                and (FLAGS["s2class_always"] or N * in_size[0] * in_size[1] * in_size[2] >= 1 << 20)):
+            return "s2_classes"
+    # the input(s) are outputs of norm -> dropout -> activation sites read by this conv only: their
+    # activation / dropout derivative and the two sums of the norm's backward come out of this
+    # kernel's epilogue (AdnSite)
+    if sites and need0 and (not has_x1 or need1) and (not has_add0 or C1 == 0) and f16x3:
+        return "igemm_adn"
+    return "igemm" if need0 or need1 else None
+
+
+def conv3d_wgrad_route(fwd_route, need_w=True, want_db=False):
+    """The weight-gradient kernel (which also yields the bias gradient when wanted); None when
+    neither gradient is needed. Host only."""
+    if fwd_route == "conv1_small":
+        return "conv1_small" if need_w or want_db else None
+    if need_w and fwd_route == "cinfold":
+        # (0.297 vs 0.339 ms for 2 -> 32 at 2 x 128^3, 0.167 vs 0.207 ms for 1 -> 16 at
+        # 4 x 96^3: tools/cinfold_wgrad_time.py)
+        f16 = CONV_PRECISION == "f16x3" and not FLAGS["no_cinfold_wgrad_f16"]
+        return "cinfold_f16x3" if f16 else "cinfold_fp32"
+    if need_w:
+        return "igemm_f16x3" if CONV_PRECISION == "f16x3" else "igemm_fp32"
+    return "bias_only" if want_db else None
+
+
+# One conv3d call as _Conv3dFn sees it. adn: (site0, site1, ntiles, plan epoch) of _adn_sites_of or None;
+# lowrank_site: the AdnSite that takes (dy, weight) of the logits head or None; rows0 / rows1: ops.SplitRows
+_ConvCall = collections.namedtuple("_ConvCall", "route stride padding want_stats wref carry_in "
+                                   "carry_out carry_x0 carry_cat adn lowrank_site rows0 rows1")
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, residual, wp, conf):
-        (stride, padding, want_stats, wref, ctx.carry_in, ctx.carry_out, ctx.carry_x0,
-         ctx.carry_cat, ctx.adn, rows0, rows1) = conf
-        if (rows0 is not None or rows1 is not None) and not isinstance(wp, ops.SplitWeight):
+    def forward(ctx, x0, x1, weight, bias, residual, wp, call):
+        """``wp``: the packed forward operand of the "fold" / "igemm" routes, else None."""
+        route, stride, padding, want_stats = call[:4]
+        rows0, rows1 = call.rows0, call.rows1
+        f16x3 = route == "igemm" and isinstance(wp, ops.SplitWeight)
+        if (rows0 is not None or rows1 is not None) and not f16x3:
             # a reader other than the f16x3 implicit-GEMM path: it gets fp32 values (and so does
             # its backward: the converted tensors are the ones saved)
             ops.ROWS_FALLBACKS[0] += 1
@@ -551,240 +653,151 @@ class _Conv3dFn(torch.autograd.Function):
                 x0, rows0 = ops.rows_to_f32(x0, rows0), None
             if rows1 is not None:
                 x1, rows1 = ops.rows_to_f32(x1, rows1), None
-        ctx.rows = (rows0, rows1)
-        k = tuple(weight.shape[2:]) if weight.dim() == 5 else (1, 1, 1)
+        k = tuple(weight.shape[2:]) or (1, 1, 1)     # (a 2-D Linear weight: 1x1x1)
         # the statistics partials are a non-differentiable by-product: without this autograd
         # materialises a zero gradient for them in every backward (a 2 MB fill per conv site)
         ctx.set_materialize_grads(False)
-        ctx.bias_ref = _Ref(bias)
-        ctx.cin_small = wp == "cin_small"
-        ctx.cinfold = wp == "cinfold"
-        if ctx.cinfold:
+        part = amax = None
+        if route == "conv1_small":
+            y = ops.conv1_small_fwd(x0, x1, weight, bias)
+        elif route == "cin_small":
+            y, part = ops.conv_cin_small_fwd(x0, weight, bias, padding, want_stats)
+        elif route == "cinfold":
             y, part = ops.conv_cinfold_fwd(x0, weight, bias, padding, want_stats,
                                            f16x3=CONV_PRECISION == "f16x3")
-            ctx.small1 = False
-            ctx.amax = None
-            ctx.save_for_backward(x0, x1, weight)
-            ctx.conf = (k, stride, padding, bias is not None, False, wref)
-            if part is None:
-                part = y.new_empty(0)
-            ctx.mark_non_differentiable(part)
-            return y, part
-        if ctx.cin_small:  # 2-channel input block: exact fp32 on the vector ALU, canonical weights
-            y, part = ops.conv_cin_small_fwd(x0, weight, bias, padding, want_stats)
-            ctx.small1 = False
-            ctx.amax = None
-            ctx.save_for_backward(x0, x1, weight)
-            ctx.conf = (k, stride, padding, bias is not None, False, wref)
-            if part is None:
-                part = y.new_empty(0)
-            ctx.mark_non_differentiable(part)
-            return y, part
-        if isinstance(wp, tuple) and wp[0] == "fold":
-            # Cin <= 4, Kw * Cin <= 16: the x taps ride in the 16-channel MFMA chunk (forward
-            # only: the gradients below see the original tensors and weights)
+        elif route == "fold":
             xf = ops.fold_x_taps(x0, k[2], padding[2])
-            y, part = ops.conv3d_fwd(xf, wp[1], bias, weight.shape[0], (k[0], k[1], 1), stride,
+            y, part = ops.conv3d_fwd(xf, wp, bias, weight.shape[0], (k[0], k[1], 1), stride,
                                      (padding[0], padding[1], 0), residual=residual,
                                      want_stats=want_stats)
-            ctx.small1 = False
-            ctx.amax = None
-            ctx.save_for_backward(x0, x1, weight)
-            ctx.conf = (k, stride, padding, bias is not None, residual is not None, wref)
-            if part is None:
-                part = y.new_empty(0)
-            ctx.mark_non_differentiable(part)
-            return y, part
-        ctx.small1 = wp is None
-        if ctx.small1:  # logits head: 1x1x1, Cout <= 4 -- one HBM-bound pass on canonical weights
-            y = ops.conv1_small_fwd(x0, x1, weight, bias)
-            ctx.save_for_backward(x0, x1, weight)
-            ctx.conf = (k, stride, padding, bias is not None, False, wref)
-            part = y.new_empty(0)
-            ctx.mark_non_differentiable(part)
-            return y, part
-        # [0]: absmax bits of the input(s), [1]: of dy -- by-products of the f16x3 forward /
-        # backward-data kernels that the backward-weight kernel uses as operand scales
-        amax = None
-        if isinstance(wp, ops.SplitWeight) and ctx.needs_input_grad[2]:
-            amax = _amax_pair(x0.device)
-        y, part = ops.conv3d_fwd(x0, wp, bias, weight.shape[0], k, stride, padding, x1=x1,
-                                 residual=residual, want_stats=want_stats,
-                                 amax=None if amax is None else amax[0:1], rows0=rows0, rows1=rows1)
-        ctx.amax = amax
+        elif route == "igemm":
+            # [0]: absmax bits of the input(s), [1]: of dy -- by-products of the f16x3 forward /
+            # backward-data kernels that the backward-weight kernel uses as operand scales
+            if f16x3 and ctx.needs_input_grad[2]:
+                amax = _amax_pair(x0.device)
+            y, part = ops.conv3d_fwd(x0, wp, bias, weight.shape[0], k, stride, padding, x1=x1,
+                                     residual=residual, want_stats=want_stats,
+                                     amax=None if amax is None else amax[0:1], rows0=rows0,
+                                     rows1=rows1)
+        else:
+            raise ValueError(f"conv3d: unknown forward route {route!r}")
         ctx.save_for_backward(x0, x1, weight)
-        ctx.conf = (k, stride, padding, bias is not None, residual is not None, wref)
-        if part is None:
-            part = y.new_empty(0)
+        # (a residual reaches only the "fold" / "igemm" routes: the other predicates refuse one)
+        ctx.rows, ctx.amax, ctx.bias_ref = (rows0, rows1), amax, _Ref(bias)
+        ctx.conf = (call, k, bias is not None, residual is not None)
+        part = y.new_empty(0) if part is None else part
         ctx.mark_non_differentiable(part)
         return y, part
 
     @staticmethod
     def backward(ctx, dy, _dpart):
         x0, x1, weight = ctx.saved_tensors
-        k, stride, padding, has_bias, has_res, wref = ctx.conf
+        call, k, has_bias, has_res = ctx.conf
+        stride, padding, wref = call.stride, call.padding, call.wref
         need = ctx.needs_input_grad
+        add0 = call.carry_in.take() if call.carry_in is not None else None
         if dy is None:   # the output took no part in the loss: only a parked gradient passes through
             _side_ok(wref.obj)      # (bookkeeping: this node is done)
-            add0 = ctx.carry_in.take() if ctx.carry_in is not None else None
             return (add0 if need[0] else None), None, None, None, None, None, None
         dy = ops.ndhwc(dy)
         dx0 = dx1 = dw = db = dres = None
-        add0 = ctx.carry_in.take() if ctx.carry_in is not None else None
-        C0 = x0.shape[1]
+        C0, in_size = x0.shape[1], tuple(x0.shape[2:])
         C1 = 0 if x1 is None else x1.shape[1]
-        if ctx.small1:
-            if ctx.adn is not None and need[0]:
-                # dX = dy (x) weight stays factored: a stride-0 placeholder goes down the graph
-                ctx.adn[1].lowrank = (dy, weight.detach())
-                dx0 = dy.new_zeros(()).expand(x0.shape)
-            elif need[0] or (x1 is not None and need[1]):
-                dx0, dx1 = ops.conv1_small_bwd_data(dy, weight, tuple(x0.shape[2:]), C0, C1)
-                dx0 = dx0 if need[0] else None
-                dx1 = dx1 if (x1 is not None and need[1]) else None
-            if need[2] or (has_bias and need[3]):
-                if _side_ok(wref.obj, ctx.bias_ref.obj):
-                    dw, db = side_run(lambda: ops.conv1_small_bwd_weight(
-                        x0, x1, dy, has_bias and need[3]), (x0, x1, dy))
-                else:
-                    dw, db = ops.conv1_small_bwd_weight(x0, x1, dy, has_bias and need[3])
-                dw = dw.view(weight.shape) if need[2] else None
-            if add0 is not None and dx0 is not None:
-                dx0 = dx0 + add0
-            dx0, dx1 = _park_input_grads(ctx, dx0, dx1)
-            return dx0, dx1, dw, db, None, None, None
+        f16x3 = CONV_PRECISION == "f16x3"
+        route = conv3d_dgrad_route(call.route, x0.shape, weight.shape, stride, padding, C1,
+                                   need[0], need[1], x1 is not None, add0 is not None,
+                                   call.adn is not None, call.lowrank_site is not None)
+        # (only behind an f16x3 "igemm" forward; every backward-data launch from there writes the slot)
         amax = ctx.amax
-        dy_amax = None
-        if getattr(ctx, "cinfold", False) and need[0]:
-            dx0 = ops.conv_cinfold_bwd_data(dy, weight, tuple(x0.shape[2:]), padding,
-                                            f16x3=CONV_PRECISION == "f16x3")
-        if dx0 is not None:
-            pass
-        elif ctx.cin_small and need[0] and dy.shape[1] % 4 == 0:
-            dx0 = ops.conv_cin_small_bwd_data(dy, weight, tuple(x0.shape[2:]), padding)
-        elif (ctx.cin_small and need[0] and dy.shape[1] <= 4 and stride == (1, 1, 1)
-              and tuple(dy.shape[2:]) == tuple(x0.shape[2:])):
-            # Cout <= 4 too (the 2 -> 2 conv of an input block whose input carries a gradient:
-            # SWIN-UNet): dX is the same small conv of dY with the taps flipped and the channel
-            # axes swapped (padding k - 1 - p) -- on the vector-ALU forward kernel instead of a
-            # 32-column MFMA tile that is 94 % empty (1.37 ms -> 0.1 ms at 256 x 256 x 128)
+        dy_amax = amax[1:2] if amax is not None and f16x3 and route is not None else None
+        if route == "conv1_lowrank":
+            call.lowrank_site.lowrank = (dy, weight.detach())
+            dx0 = dy.new_zeros(()).expand(x0.shape)    # a stride-0 placeholder goes down the graph
+        elif route == "conv1_small":
+            dx0, dx1 = ops.conv1_small_bwd_data(dy, weight, in_size, C0, C1)
+        elif route == "cinfold":
+            dx0 = ops.conv_cinfold_bwd_data(dy, weight, in_size, padding, f16x3=f16x3)
+        elif route == "cin_small":
+            dx0 = ops.conv_cin_small_bwd_data(dy, weight, in_size, padding)
+        elif route == "cin_small_flipped":
             wt = weight.detach().transpose(0, 1).flip(2, 3, 4).contiguous()
             pt = tuple(kk - 1 - pp for kk, pp in zip(k, padding))
             dx0, _ = ops.conv_cin_small_fwd(dy, wt, None, pt, False)
-        elif (need[0] and x1 is None and CONV_PRECISION == "f16x3"
-              and ops.conv3d_bwd_data_s2_fused_ok(x0.shape[2:], C0, C1, dy.shape[1], k, stride,
-                                                  padding)
-              and isinstance(_packed(wref.obj, 1), ops.SplitWeight)):
-            # the U-Net downsampling layer at 32 channels: one persistent launch
-            if amax is not None:
-                dy_amax = amax[1:2]
-            dx0 = ops.conv3d_bwd_data_s2_fused(dy, _packed(wref.obj, 1), tuple(x0.shape[2:]),
-                                               amax=dy_amax, add0=add0)
+        elif route == "s2_fused":
+            dx0 = ops.conv3d_bwd_data_s2_fused(dy, _packed(wref.obj, 1), in_size, amax=dy_amax,
+                                               add0=add0)
             add0 = None
-        elif (need[0] and x1 is None and CONV_PRECISION == "f16x3" and stride == (2, 2, 2)
-              and k == (3, 3, 3) and all(p <= 1 for p in padding)
-              and all(s % 2 == 0 for s in x0.shape[2:])
-              and (x0.numel() // C0 >= (1 << 20) or FLAGS["s2class_always"])
-              and not FLAGS["no_s2class"]):
-            # stride-2 backward-data by parity classes (no zero-inserted MFMA work). Eight
-            # launches: pays from ~1 M voxels (measured: 128^3 0.52 -> 0.33 ms, 32^3 0.06 -> 0.16)
-            if amax is not None:
-                dy_amax = amax[1:2]
-            dx0 = ops.conv3d_bwd_data_s2(dy, _packed_s2_classes(wref.obj, padding),
-                                         tuple(x0.shape[2:]), C0, padding, amax=dy_amax,
-                                         add0=add0)
+        elif route == "s2_classes":
+            dx0 = ops.conv3d_bwd_data_s2(dy, _packed_s2_classes(wref.obj, padding), in_size, C0,
+                                         padding, amax=dy_amax, add0=add0)
             add0 = None
-        elif (ctx.adn is not None and need[0] and (x1 is None or need[1])
-              and (add0 is None or C1 == 0) and isinstance(_packed(wref.obj, 1), ops.SplitWeight)):
-            # the input(s) are outputs of norm -> dropout -> activation sites read by this conv
-            # only: their activation / dropout derivative and the two sums of the norm's backward
-            # come out of this kernel's epilogue (AdnSite)
-            site0, site1, ntiles, epoch = ctx.adn
+        elif route in ("igemm_adn", "igemm"):
             wpb = _packed(wref.obj, 1)
-            if amax is not None:
-                dy_amax = amax[1:2]
-            if epoch != ops.plan_epoch():
-                # the launch plan changed between forward and backward (adell_set_tuning): the row
-                # count of the partial-sum buffer is the CURRENT plan's, or the plain path if that
-                # plan has no fused epilogue (the sites then run their own two passes)
-                ntiles = ops.conv3d_bwd_data_adn_ntiles(tuple(x0.shape[2:]), x0.shape[0], C0, C1,
-                                                        dy.shape[1], k, stride, padding)
+            ntiles = 0
+            if route == "igemm_adn":
+                site0, site1, ntiles, epoch = call.adn
+                if epoch != ops.plan_epoch():
+                    # the launch plan changed since the forward (adell_set_tuning): the partial-sum rows are
+                    # the CURRENT plan's, or the plain path if it has no fused epilogue (two-pass sites)
+                    ntiles = ops.conv3d_bwd_data_adn_ntiles(in_size, x0.shape[0], C0, C1,
+                                                            dy.shape[1], k, stride, padding)
             if ntiles > 0:
-                dx0, dx1, part = ops.conv3d_bwd_data_adn(dy, wpb, tuple(x0.shape[2:]), C0, C1, k,
-                                                         stride, padding, ntiles, site0=site0,
+                dx0, dx1, part = ops.conv3d_bwd_data_adn(dy, wpb, in_size, C0, C1, k, stride,
+                                                         padding, ntiles, site0=site0,
                                                          site1=site1, amax=dy_amax, add0=add0)
                 add0 = None
-                if site0 is not None:
-                    site0.fused, site0.part, site0.poff = True, part, 0
-                if site1 is not None:
-                    site1.fused, site1.part, site1.poff = True, part, C0
+                for site, poff in ((site0, 0), (site1, C0)):
+                    if site is not None:
+                        site.fused, site.part, site.poff = True, part, poff
             else:
-                fused = add0 is not None and C1 == 0
-                dx0, dx1 = ops.conv3d_bwd_data(dy, wpb, tuple(x0.shape[2:]), C0, C1, k, stride,
-                                               padding, amax=dy_amax, add0=add0 if fused else None)
+                fused = add0 is not None and C1 == 0 and f16x3    # the add in the kernel epilogue
+                dx0, dx1 = ops.conv3d_bwd_data(dy, wpb, in_size, C0, C1, k, stride, padding,
+                                               amax=dy_amax, add0=add0 if fused else None)
                 if fused:
                     add0 = None
-                if x1 is None or not need[1]:
-                    dx1 = None
-        elif need[0] or (x1 is not None and need[1]):
-            wpb = _packed(wref.obj, 1)
-            if amax is not None and isinstance(wpb, ops.SplitWeight):
-                dy_amax = amax[1:2]
-            fused = add0 is not None and C1 == 0 and isinstance(wpb, ops.SplitWeight)
-            dx0, dx1 = ops.conv3d_bwd_data(dy, wpb, tuple(x0.shape[2:]), C0, C1, k, stride,
-                                           padding, amax=dy_amax, add0=add0 if fused else None)
-            if fused:
-                add0 = None
-            if not need[0]:
-                dx0 = None
-            if x1 is None or not need[1]:
-                dx1 = None
+        elif route is not None:
+            raise ValueError(f"conv3d: unknown backward-data route {route!r}")
+        dx0 = dx0 if need[0] else None
+        dx1 = dx1 if x1 is not None and need[1] else None
         want_db = has_bias and need[3]
+        wroute = conv3d_wgrad_route(call.route, need[2], want_db)
 
         def weight_grads():
-            dw = db = None
-            if need[2] and getattr(ctx, "cinfold", False):
-                dw, db = ops.conv_cinfold_bwd_weight(
-                    x0, dy, padding, want_db,
-                    # (0.297 vs 0.339 ms for 2 -> 32 at 2 x 128^3, 0.167 vs 0.207 ms for 1 -> 16 at
-                    # 4 x 96^3: tools/cinfold_wgrad_time.py)
-                    f16x3=(CONV_PRECISION == "f16x3" and not FLAGS["no_cinfold_wgrad_f16"]))
-                dw = dw.view(weight.shape)
-            elif need[2]:
-                rows0, rows1 = getattr(ctx, "rows", (None, None))
+            db = None
+            if wroute == "conv1_small":
+                dw, db = ops.conv1_small_bwd_weight(x0, x1, dy, want_db)
+            elif wroute.startswith("cinfold"):
+                dw, db = ops.conv_cinfold_bwd_weight(x0, dy, padding, want_db,
+                                                     f16x3=wroute == "cinfold_f16x3")
+            elif wroute.startswith("igemm"):
                 dw = ops.conv3d_bwd_weight(x0, dy, k, stride, padding, x1=x1, want_db=want_db,
-                                           f16x3=(CONV_PRECISION == "f16x3"),
+                                           f16x3=wroute == "igemm_f16x3",
                                            x_amax=None if amax is None else amax[0:1],
-                                           dy_amax=dy_amax, rows0=rows0, rows1=rows1)
+                                           dy_amax=dy_amax, rows0=ctx.rows[0], rows1=ctx.rows[1])
                 if want_db:
                     dw, db = dw
-                dw = dw.view(weight.shape)
-            elif want_db:
-                db = ops.bias_grad(dy)
-            return dw, db
+            elif wroute == "bias_only":
+                return None, ops.bias_grad(dy)
+            else:
+                raise ValueError(f"conv3d: unknown weight-gradient route {wroute!r}")
+            return (dw.view(weight.shape) if need[2] else None), db
 
-        if (need[2] or want_db) and _side_ok(wref.obj, ctx.bias_ref.obj):
-            dw, db = side_run(weight_grads, (x0, x1, dy))
-        else:
-            dw, db = weight_grads()
-        if add0 is not None and dx0 is not None:   # a path without the fused add
+        if wroute is not None:
+            dw, db = (side_run(weight_grads, (x0, x1, dy))
+                      if _side_ok(wref.obj, ctx.bias_ref.obj) else weight_grads())
+        if add0 is not None and dx0 is not None:   # a route without the fused add
             dx0 = dx0 + add0
-        dx0, dx1 = _park_input_grads(ctx, dx0, dx1)
+        # skip fork: leave dX of x0 / x1 with the consumer of the same tensor that runs later
+        if dx0 is not None and call.carry_x0 is not None:
+            call.carry_x0.grad, dx0 = dx0, None
+        if dx1 is not None and call.carry_cat is not None:
+            call.carry_cat.grad, dx1 = dx1, None
         if has_res and need[4]:
-            if ctx.carry_out is not None:
-                ctx.carry_out.grad = dy      # the head conv of the block adds it to its dX
+            if call.carry_out is not None:
+                call.carry_out.grad = dy      # the head conv of the block adds it to its dX
             else:
                 dres = dy
         return dx0, dx1, dw, db, dres, None, None
-
-
-def _park_input_grads(ctx, dx0, dx1):
-    """Skip fork: leave dX of x0 / x1 with the consumer of the same tensor that runs later."""
-    if dx0 is not None and ctx.carry_x0 is not None:
-        ctx.carry_x0.grad, dx0 = dx0, None
-    if dx1 is not None and ctx.carry_cat is not None:
-        ctx.carry_cat.grad, dx1 = dx1, None
-    return dx0, dx1
 
 
 def grad_observed(t):
@@ -883,87 +896,73 @@ def conv3d(x0, weight, bias=None, stride=1, padding=0, x1=None, residual=None, w
     """Conv3d over the virtual concatenation [x0, x1] (+ bias + residual). ``carry_in`` /
     ``carry_out`` / ``carry_x0`` / ``carry_cat``: see GradCarry."""
     stride, padding = ops._triple(stride), ops._triple(padding)
-    # A 1x1x1 stride-1 conv over channels-last memory IS a Linear layer over the voxels: the GEMM
-    # kernels take it (fused bias). On the implicit-GEMM conv kernels a brick's voxels x one 16-channel
-    # chunk per step is the wrong tiling for it: ConvNeXt's stage transitions (384 -> 768 at 64 x 2^3
-    # voxels) ran 0.79 ms forward and 0.78 ms backward-data at 0.4 TF, UNETR's 512 -> 512 at 12^3
-    # 0.19 / 0.21 / 0.32 ms. (No statistics partials then: a following instance norm computes its own.)
-    if (weight.dim() == 5 and tuple(weight.shape[2:]) == (1, 1, 1) and stride == (1, 1, 1)
-            and padding == (0, 0, 0) and x1 is None and residual is None and carry_in is None
-            and carry_out is None and carry_x0 is None and carry_cat is None and x0.dim() == 5
-            and getattr(x0, "_adell_rows", None) is None and max(weight.shape[:2]) >= 64
-            and min(weight.shape[:2]) >= 8 and not FLAGS["no_pointwise_gemm"]):
+    rows0 = getattr(x0, "_adell_rows", None)
+    rows1 = getattr(x1, "_adell_rows", None) if x1 is not None else None
+    route = conv3d_route(x0, weight, stride, padding,
+                         None if x1 is None else x1.shape[1], residual is not None,
+                         not (carry_in is None and carry_out is None and carry_x0 is None
+                              and carry_cat is None), rows0 is not None)
+    if route == "pointwise_gemm":
         xr = ops.ndhwc(x0)
         N, C, D, H, W = xr.shape
         y2 = linear(xr.permute(0, 2, 3, 4, 1).reshape(-1, C), weight.view(weight.shape[0], C), bias)
         return y2.view(N, D, H, W, -1).permute(0, 4, 1, 2, 3)
     _note_use(weight)
     adn = _adn_sites_of(x0, x1, weight, stride, padding)
-    rows0 = getattr(x0, "_adell_rows", None)
-    rows1 = getattr(x1, "_adell_rows", None) if x1 is not None else None
-    conf = (stride, padding, want_stats, _Ref(weight), carry_in, carry_out, carry_x0, carry_cat,
-            adn, rows0, rows1)
-    Cin = x0.shape[1] + (0 if x1 is None else x1.shape[1])
-    small1 = ops.conv1_small_ok(weight, Cin, stride, padding, residual)
-    if small1:
-        wp = None
-        # the logits head behind a single-use site: the site's backward takes (dy, weight)
-        site = getattr(x0, "_adell_site", None) if getattr(x0, "_adell_single", False) else None
-        if (site is not None and x1 is None and carry_in is None and carry_x0 is None
-                and not grad_observed(x0)
-                and not FLAGS["no_adn_fuse"] and not FLAGS["no_lowrank"]
-                and torch.is_grad_enabled() and ops.norm_act_lowrank_ok(x0, weight.shape[0])):
-            conf = conf[:8] + (("lowrank", site),) + conf[9:]
-    elif ops.conv_cin_small_ok(weight, x0, x1, stride, padding, residual):
-        wp = "cin_small"
-    elif ops.conv_cinfold_ok(weight, x0, x1, stride, padding, residual):
-        wp = "cinfold"   # K = 27 Cin im2col GEMM on the fp32 MFMA (forward, dW); dX: f16x3 igemm
-    elif (CONV_PRECISION == "f16x3" and x1 is None and weight.dim() == 5 and x0.shape[1] <= 4
-          and 3 <= weight.shape[4] and weight.shape[4] * x0.shape[1] <= 16
-          and stride == (1, 1, 1) and not FLAGS["no_fold"]):
-        wp = ("fold", _packed_folded(weight))
-    else:
-        wp = _packed(weight, 0)
-    y, part = _Conv3dFn.apply(x0, x1, weight, bias, residual, wp, conf)
+    # the logits head behind a single-use site: the site's backward takes (dy, weight)
+    site = getattr(x0, "_adell_site", None) if getattr(x0, "_adell_single", False) else None
+    lowrank_site = site if (route == "conv1_small" and site is not None and x1 is None
+                            and carry_in is None and carry_x0 is None and not grad_observed(x0)
+                            and not FLAGS["no_adn_fuse"] and not FLAGS["no_lowrank"]
+                            and torch.is_grad_enabled()
+                            and ops.norm_act_lowrank_ok(x0, weight.shape[0])) else None
+    # (outside the Function: _packed orders this stream behind the launch that packed the weight)
+    wp = (_packed_folded(weight) if route == "fold" else
+          _packed(weight, 0) if route == "igemm" else None)
+    call = _ConvCall(route, stride, padding, want_stats, _Ref(weight), carry_in, carry_out,
+                     carry_x0, carry_cat, adn, lowrank_site, rows0, rows1)
+    y, part = _Conv3dFn.apply(x0, x1, weight, bias, residual, wp, call)
     if want_stats and part.numel() > 0:
         y._adell_partials = part
     return y
 
 
+def conv_transpose3d_route(x_shape, weight_shape):
+    """"k2": the streaming factor-2 kernels on the canonical weight (csrc/convt_k2.hip);
+    "igemm": the 1x1x1-conv form on the packed weight. Host only."""
+    return "k2" if len(x_shape) == 5 and ops.convt_k2_ok(x_shape, _Shape(weight_shape)) else "igemm"
+
+
 class _ConvT3dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, wp, wref):
+    def forward(ctx, x, weight, bias, wp, wref, route):
         factors = tuple(weight.shape[2:])
-        ctx.k2 = wp is None    # streaming factor-2 kernels on the canonical weight
-        if ctx.k2:
-            y = ops.convt_k2_fwd(x, weight, bias)
-        else:
-            y = ops.convtranspose3d_fwd(x, wp, bias, weight.shape[1], factors)
+        y = (ops.convt_k2_fwd(x, weight, bias) if route == "k2" else
+             ops.convtranspose3d_fwd(x, wp, bias, weight.shape[1], factors))
         ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        ctx.bias_ref = _Ref(bias)
-        ctx.wref = wref
-        ctx.factors = factors
+        ctx.route, ctx.wref, ctx.factors = route, wref, factors
+        ctx.has_bias, ctx.bias_ref = bias is not None, _Ref(bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         need = ctx.needs_input_grad
+        k2 = ctx.route == "k2"
         dy = ops.ndhwc(dy)
         dx = dw = db = None
         if need[0]:
-            dx = (ops.convt_k2_bwd_data(dy, weight) if ctx.k2 else
+            dx = (ops.convt_k2_bwd_data(dy, weight) if k2 else
                   ops.convtranspose3d_bwd_data(dy, _packed(ctx.wref.obj, 3), weight.shape[0],
                                                ctx.factors))
         want_db = ctx.has_bias and need[2]
 
         def weight_grads():
             dw = db = None
-            if need[1] and ctx.k2 and want_db:
+            if need[1] and k2 and want_db:
                 dw, db = ops.convt_k2_bwd_weight(x, dy, want_db=True, factors=ctx.factors)   # db from the same pass over dy
             elif need[1]:
-                dw = (ops.convt_k2_bwd_weight(x, dy, factors=ctx.factors) if ctx.k2 else
+                dw = (ops.convt_k2_bwd_weight(x, dy, factors=ctx.factors) if k2 else
                       ops.convtranspose3d_bwd_weight(x, dy, ctx.factors))
             if want_db and db is None:
                 db = ops.bias_grad(dy)
@@ -973,14 +972,15 @@ class _ConvT3dFn(torch.autograd.Function):
             dw, db = side_run(weight_grads, (x, dy))
         else:
             dw, db = weight_grads()
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 def conv_transpose3d(x, weight, bias=None):
     """ConvTranspose3d whose kernel equals its stride (each 1 or 2 per dim), padding 0."""
-    wp = None if (x.dim() == 5 and ops.convt_k2_ok(x.shape, weight)) else _packed(weight, 2)
+    route = conv_transpose3d_route(x.shape, weight.shape)
+    wp = _packed(weight, 2) if route == "igemm" else None
     _note_use(weight)
-    return _ConvT3dFn.apply(x, weight, bias, wp, _Ref(weight))
+    return _ConvT3dFn.apply(x, weight, bias, wp, _Ref(weight), route)
 
 
 conv_transpose3d_k2s2 = conv_transpose3d

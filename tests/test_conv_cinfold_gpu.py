@@ -93,6 +93,7 @@ def test_layer_takes_the_cinfold_path_and_matches_the_fold_path(cuda):
         ops.FLAGS["no_cinfold"] = mode == "fold"
         try:
             w, b = w0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
+            assert HF.conv3d_route(x.shape, w.shape, (1, 1, 1), (1, 1, 1)) == mode
             ops.KERNEL_TIMER = ops.KernelTimer()
             y = HF.conv3d(x, w, b, 1, 1)
             (y * r).sum().backward()
