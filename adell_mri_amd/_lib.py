@@ -189,6 +189,12 @@ SIGNATURES = {
     "adell_vicreg_scratch_floats": (_l, [_i, _i]),
     "adell_vicreg_fwd": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),
     "adell_vicreg_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "adell_top_pairs_workspace_words": (_l, [_i, _i, _i]),
+    "adell_top_pairs": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp]),
+    "adell_top_pairs_boxes": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _vp, _l, _vp,
+                                   _vp, _vp]),
+    "adell_gather_rows_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "adell_gather_rows_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

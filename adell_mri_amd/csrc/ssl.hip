@@ -1027,11 +1027,135 @@ __global__ __launch_bounds__(256) void adell_vicreg_bwd_kernel(
   }
 }
 
+// ---- the same forward for many rows (B >= 128: the B gamma gathered rows of the local VICReg loss,
+// csrc/vicregl.hip) -- the one-block kernel does B^2 D products on one CU with row-strided loads
+// (50 ms per call at 320 x 512). Three launches: column statistics (a thread per column: mean,
+// variance, the centred column is NOT stored; per-block partial hinge / var^2 / inv sums), the Gram
+// matrix of the centred rows in 64 x 64 tiles (4 x 4 per thread, 32 columns at a time through LDS,
+// per-tile partial sum of squares), and a one-block fold in block order (deterministic).
+// scratch (after the 4 D + 2 B^2 floats the backward reads): [nA][4] partial (hinge, var^2, inv, -),
+// then [2 views][nT][nT] partial sums of G^2.
+constexpr int VIC_WIDE_MINB = 128, VIC_WT = 64, VIC_WK = 32, VIC_WLD = 68;
+__global__ __launch_bounds__(256) void adell_vicreg_wide_stats_kernel(
+    const float* __restrict__ x1, const float* __restrict__ x2, int B, int D, float min_var,
+    float eps, float* __restrict__ scratch, float* __restrict__ partA) {
+  __shared__ float sh[16];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  float hinge = 0.f, var2 = 0.f, inv = 0.f;
+  if (j < D) {
+    for (int view = 0; view < 2; ++view) {
+      const float* x = view == 0 ? x1 : x2;
+      float m = 0.f, v = 0.f;
+      for (int b = 0; b < B; ++b) m += x[(size_t)b * D + j];
+      m /= (float)B;
+      for (int b = 0; b < B; ++b) {
+        const float d = x[(size_t)b * D + j] - m;
+        v += d * d;
+      }
+      v /= (float)(B - 1);
+      scratch[view * 2 * D + j] = m;
+      scratch[view * 2 * D + D + j] = v;
+      hinge += fmaxf(min_var - sqrtf(v + eps), 0.f);
+      var2 += v * v;
+    }
+    for (int b = 0; b < B; ++b) {
+      const float d = x1[(size_t)b * D + j] - x2[(size_t)b * D + j];
+      inv += d * d;
+    }
+  }
+  hinge = adell_block_sum(hinge, sh);
+  var2 = adell_block_sum(var2, sh);
+  inv = adell_block_sum(inv, sh);
+  if (threadIdx.x == 0) {
+    float* part = partA + (size_t)blockIdx.x * 4;
+    part[0] = hinge; part[1] = var2; part[2] = inv; part[3] = 0.f;
+  }
+}
+
+// grid (nT, nT, 2 views): G[a][b] = sum_j (x[a][j] - mean[j]) (x[b][j] - mean[j]) for a 64 x 64 tile
+__global__ __launch_bounds__(256) void adell_vicreg_wide_gram_kernel(
+    const float* __restrict__ x1, const float* __restrict__ x2, int B, int D,
+    float* __restrict__ scratch, float* __restrict__ partG) {
+  __shared__ __attribute__((aligned(16))) float As[VIC_WK * VIC_WLD];
+  __shared__ __attribute__((aligned(16))) float Bs[VIC_WK * VIC_WLD];
+  __shared__ float sh[16];
+  const int tid = threadIdx.x, view = blockIdx.z;
+  const float* x = view == 0 ? x1 : x2;
+  const float* mean = scratch + view * 2 * D;
+  float* G = scratch + 4L * D + (size_t)view * B * B;
+  const int a0 = blockIdx.y * VIC_WT, b0 = blockIdx.x * VIC_WT;
+  const int ta = tid >> 4, tb = tid & 15;
+  float acc[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
+  for (int k0 = 0; k0 < D; k0 += VIC_WK) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < (VIC_WT * VIC_WK) / 256; ++u) {
+      const int e = tid + 256 * u;
+      const int kk = e & (VIC_WK - 1), ii = e / VIC_WK;
+      const int k = k0 + kk;
+      const float mu = k < D ? mean[k] : 0.f;
+      As[kk * VIC_WLD + ii] = (a0 + ii < B && k < D) ? x[(size_t)(a0 + ii) * D + k] - mu : 0.f;
+      Bs[kk * VIC_WLD + ii] = (b0 + ii < B && k < D) ? x[(size_t)(b0 + ii) * D + k] - mu : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < VIC_WK; ++kk) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(As + kk * VIC_WLD + ta * 4);
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(Bs + kk * VIC_WLD + tb * 4);
+      const float ar[4] = {av.x, av.y, av.z, av.w};
+      const float bc[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(ar[r], bc[c], acc[r][c]);
+    }
+  }
+  float g2 = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int a = a0 + ta * 4 + r, b = b0 + tb * 4 + c;
+      if (a < B && b < B) {
+        G[(size_t)a * B + b] = acc[r][c];
+        g2 += acc[r][c] * acc[r][c];
+      }
+    }
+  g2 = adell_block_sum(g2, sh);
+  if (tid == 0) partG[((size_t)view * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = g2;
+}
+
+__global__ __launch_bounds__(64) void adell_vicreg_wide_fold_kernel(int B, int D, int nA, int nG,
+                                                                    const float* __restrict__ partA,
+                                                                    const float* __restrict__ partG,
+                                                                    float* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  float hinge = 0.f, var2 = 0.f, inv = 0.f, g2 = 0.f;
+  for (int k = 0; k < nA; ++k) {
+    hinge += partA[4 * k];
+    var2 += partA[4 * k + 1];
+    inv += partA[4 * k + 2];
+  }
+  for (int k = 0; k < nG; ++k) g2 += partG[k];
+  const float bm1 = (float)(B - 1);
+  out[0] = inv / ((float)B * (float)D);
+  out[1] = 0.5f * hinge / (float)D;
+  out[2] = 0.5f * (g2 / (bm1 * bm1) - var2) / (float)D;
+}
+
 static int adell_vicreg_chunks(int B, int D) {
   return (B <= VIC_MAXB && D >= 2 * VIC_CH) ? (D + VIC_CH - 1) / VIC_CH : 0;   // 0: the one-block kernel
 }
 
 extern "C" long adell_vicreg_scratch_floats(int B, int D) {
+  if (B >= VIC_WIDE_MINB) {
+    const long nA = (D + 255) / 256, nT = (B + VIC_WT - 1) / VIC_WT;
+    return 4L * D + 2L * B * B + 4 * nA + 2 * nT * nT;
+  }
   const long nblk = adell_vicreg_chunks(B, D);
   return 4L * D + 2L * B * B + nblk * (2L * B * B + 4);
 }
@@ -1040,6 +1164,20 @@ extern "C" int adell_vicreg_fwd(const float* x1, const float* x2, int B, int D, 
                                 float eps, float* scratch, float* out3, void* stream) {
   ADELL_REQUIRE(x1 && x2 && scratch && out3, "vicreg_fwd: null pointer");
   ADELL_REQUIRE(B > 1 && D > 0, "vicreg_fwd: need B > 1, D > 0");
+  if (B >= VIC_WIDE_MINB) {
+    const int nA = (D + 255) / 256, nT = (B + VIC_WT - 1) / VIC_WT;
+    ADELL_REQUIRE(nT <= 65535, "vicreg_fwd: too many rows");
+    float* partA = scratch + 4L * D + 2L * B * B;
+    float* partG = partA + 4L * nA;
+    hipLaunchKernelGGL(adell_vicreg_wide_stats_kernel, dim3((unsigned)nA), dim3(256), 0,
+                       (hipStream_t)stream, x1, x2, B, D, min_var, eps, scratch, partA);
+    hipLaunchKernelGGL(adell_vicreg_wide_gram_kernel, dim3((unsigned)nT, (unsigned)nT, 2), dim3(256),
+                       0, (hipStream_t)stream, x1, x2, B, D, scratch, partG);
+    hipLaunchKernelGGL(adell_vicreg_wide_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, B, D,
+                       nA, 2 * nT * nT, (const float*)partA, (const float*)partG, out3);
+    ADELL_CHECK_HIP(hipGetLastError());
+    return ADELL_OK;
+  }
   const int nblk = adell_vicreg_chunks(B, D);
   if (nblk > 0) {
     const size_t lds = (size_t)B * (VIC_CH + 1) * sizeof(float);

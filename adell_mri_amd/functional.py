@@ -2007,6 +2007,66 @@ def vicreg_terms(x1, x2, min_var=1.0, eps=1e-4):
     return _VICRegFn.apply(x1, x2, float(min_var), float(eps))
 
 
+class _TopPairsFn(torch.autograd.Function):
+    """Ranking only: the pairs are a non-differentiable output, the tokens get no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, gamma):
+        pairs = ops.top_pairs(a, b, gamma)
+        ctx.mark_non_differentiable(pairs)
+        return pairs
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None, None
+
+
+class _TopPairsBoxesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, box1, box2, spatial, gamma):
+        pairs = ops.top_pairs_boxes(box1, box2, spatial, gamma)
+        ctx.mark_non_differentiable(pairs)
+        return pairs
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None, None, None
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pairs, col):
+        ctx.save_for_backward(pairs)
+        ctx.conf = (col, tuple(x.shape))
+        return ops.gather_rows_fwd(x, pairs, col)
+
+    @staticmethod
+    def backward(ctx, g):
+        (pairs,) = ctx.saved_tensors
+        col, shape = ctx.conf
+        dx = ops.gather_rows_bwd(g, pairs, col, shape) if ctx.needs_input_grad[0] else None
+        return dx, None, None
+
+
+def top_pairs(a, b, gamma):
+    """int32 [B, gamma, 2]: per item the token pairs (i of a, j of b) with the gamma LARGEST
+    Euclidean distances between the rows of a and b ([B, T, C]); order (distance descending,
+    i * T + j ascending). The T x T matrix is never formed. No gradient."""
+    return _TopPairsFn.apply(a, b, int(gamma))
+
+
+def top_pairs_boxes(box1, box2, spatial, gamma):
+    """``top_pairs`` of the token-grid coordinates ``grid * (hi - lo) + lo`` of two boxes
+    [B, 2 * ndim]; the boxes get no gradient."""
+    return _TopPairsBoxesFn.apply(box1, box2, tuple(int(s) for s in spatial), int(gamma))
+
+
+def gather_rows(x, pairs, col):
+    """[B * gamma, C]: rows ``pairs[b, k, col]`` of x [B, T, C]; the backward adds the rows back in
+    a fixed order (duplicates allowed, bit-reproducible)."""
+    return _GatherRowsFn.apply(x, pairs, int(col))
+
+
 class _PairLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, kind, temperature, apply_relu):

@@ -5,8 +5,13 @@ adell_mri/modules/self_supervised/pl.py:170-267 ``SelfSLBasePL`` and :759-985
 Kept: constructor arguments, ``step`` arithmetic (which head feeds which loss argument,
 stop-gradient, EMA forward and update, loss symmetrisation), ``configure_optimizers``
 (AdamW over decay + no-decay parameters in one group, cosine schedule with warm-up).
-Lightning is optional as in ``segmentation/pl.py``. SimCLR (NT-Xent) and VICRegL have no
-HIP loss kernel yet and raise at construction.
+Lightning is optional as in ``segmentation/pl.py``.
+
+``ssl_method="vicregl"`` (``VICRegLocalLoss`` on the two "representation" feature maps and the
+boxes of the batch, csrc/vicregl.hip) is built by ``SelfSLResNetPL`` -- the class the factory
+``get_ssl_network`` builds for it -- and by ``SelfSLUNetPL``, whose ``forward(x)`` already is the
+feature map. ``SelfSLConvNeXtPL`` still raises ``NotImplementedError`` for it: the reference's
+factory never builds the ConvNeXt wrapper with this method, and no fixture pins its feature maps.
 """
 import warnings
 from typing import Callable
@@ -18,7 +23,7 @@ from ..layers.conv_next import ConvNeXt
 from ..layers.res_net import ResNet
 from ..segmentation.unet import UNet
 from ..learning_rate import CosineAnnealingWithWarmupLR
-from .losses import NTXentLoss, VICRegLoss, byol_loss, simsiam_loss
+from .losses import NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss, simsiam_loss
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as pl
@@ -31,6 +36,8 @@ OPTIMIZER_EPS_DEFAULT = 1e-8
 
 
 class SelfSLBasePL(_Base):
+    _supports_vicregl = True   # a wrapper without a pinned feature map for VICRegL turns it off
+
     def __init__(self):
         super().__init__()
         self.optimizer_eps = OPTIMIZER_EPS_DEFAULT
@@ -54,7 +61,11 @@ class SelfSLBasePL(_Base):
         if self.ssl_method == "vicreg":
             self.loss = VICRegLoss(**self.vic_reg_loss_params)
         if self.ssl_method == "vicregl":
-            raise NotImplementedError("ssl_method='vicregl' (VICRegLocalLoss) has no HIP kernel")
+            if not self._supports_vicregl:
+                raise NotImplementedError(
+                    f"ssl_method='vicregl' (VICRegLocalLoss) is not wired for {type(self).__name__}: "
+                    "use SelfSLResNetPL (what get_ssl_network builds) or SelfSLUNetPL")
+            self.loss = VICRegLocalLoss(**self.vic_reg_loss_params)
         if self.ssl_method == "simclr":
             self.loss = NTXentLoss(temperature=self.temperature)
 
@@ -211,7 +222,9 @@ class _TwoViewSSL:
 
 
 class SelfSLConvNeXtPL(_TwoViewSSL, ConvNeXt, SelfSLBasePL):
-    """ConvNeXt backbone (pl.py:759-985)."""
+    """ConvNeXt backbone (pl.py:759-985). ``ssl_method="vicregl"`` raises (module docstring)."""
+
+    _supports_vicregl = False
 
     def __init__(self, aug_image_key_1: str = "aug_image_1", aug_image_key_2: str = "aug_image_2",
                  box_key_1: str = "box_1", box_key_2: str = "box_2", learning_rate: float = 0.001,

@@ -2322,6 +2322,92 @@ def vicreg_bwd(x1, x2, scratch, min_var, eps, g, need1, need2):
     return dx1, dx2
 
 
+def _top_pairs_check(rc):
+    """ADELL_E_UNSUPPORTED of the top-pairs entries (gamma beyond 64 or beyond T^2) is the caller's
+    value error, not a library failure."""
+    if rc == _lib.E_UNSUPPORTED:
+        raise ValueError(_lib.lib().adell_last_error().decode("utf-8", "replace"))
+    check(rc)
+
+
+def top_pairs(a, b, gamma, return_dist2=False):
+    """int32 [B, gamma, 2]: per item the (i, j) of the gamma LARGEST Euclidean distances between the
+    rows of ``a`` and ``b`` ([B, T, C], dense), ordered by (distance descending, i * T + j
+    ascending); with ``return_dist2`` also the squared distances [B, gamma] (csrc/vicregl.hip)."""
+    _require_cuda(a, b)
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"top_pairs: two [B, T, C] tensors of one shape, got {tuple(a.shape)} "
+                         f"and {tuple(b.shape)}")
+    a, b = a.contiguous(), b.contiguous()
+    B, T, C = a.shape
+    gamma = int(gamma)
+    words = _lib.lib().adell_top_pairs_workspace_words(B, T, gamma)
+    ws = torch.empty(max(words, 1), device=a.device, dtype=torch.int64)
+    pairs = torch.empty((B, gamma, 2), device=a.device, dtype=torch.int32)
+    d2 = torch.empty((B, gamma), device=a.device, dtype=torch.float32) if return_dist2 else None
+    _top_pairs_check(_lib.lib().adell_top_pairs(
+        _ptr(a), _ptr(b), B, T, C, gamma, ctypes.c_void_p(ws.data_ptr()), words,
+        ctypes.c_void_p(pairs.data_ptr()), _ptr(d2), _stream()))
+    return (pairs, d2) if return_dist2 else pairs
+
+
+def top_pairs_boxes(box1, box2, spatial, gamma, return_dist2=False):
+    """``top_pairs`` of the distances between the token grid of shape ``spatial`` (2 or 3 sizes)
+    mapped into the boxes of the two views, ``grid * (hi - lo) + lo`` with ``box = (lo..., hi...)``
+    as [B, 2 * ndim]; the coordinates exist in registers only."""
+    box1 = box1.float().contiguous()
+    box2 = box2.float().contiguous()
+    _require_cuda(box1, box2)
+    spatial = [int(s) for s in spatial]
+    ndim = len(spatial)
+    if ndim not in (2, 3):
+        raise ValueError(f"top_pairs_boxes: 2 or 3 spatial dimensions, got {ndim}")
+    if box1.shape != box2.shape or box1.dim() != 2 or box1.shape[1] != 2 * ndim:
+        raise ValueError(f"top_pairs_boxes: boxes of shape [B, {2 * ndim}] expected, got "
+                         f"{tuple(box1.shape)} and {tuple(box2.shape)}")
+    B, T, gamma = box1.shape[0], int(math.prod(spatial)), int(gamma)
+    words = _lib.lib().adell_top_pairs_workspace_words(B, min(T, 65536), gamma)
+    ws = torch.empty(max(words, 1), device=box1.device, dtype=torch.int64)
+    pairs = torch.empty((B, gamma, 2), device=box1.device, dtype=torch.int32)
+    d2 = torch.empty((B, gamma), device=box1.device, dtype=torch.float32) if return_dist2 else None
+    dims = (ctypes.c_int * 3)(*(spatial + [1] * (3 - ndim)))
+    _top_pairs_check(_lib.lib().adell_top_pairs_boxes(
+        _ptr(box1), _ptr(box2), B, ndim, dims, gamma, ctypes.c_void_p(ws.data_ptr()), words,
+        ctypes.c_void_p(pairs.data_ptr()), _ptr(d2), _stream()))
+    return (pairs, d2) if return_dist2 else pairs
+
+
+def _pairs_arg(pairs, B):
+    if (not pairs.is_cuda or pairs.dtype != torch.int32 or pairs.dim() != 3
+            or pairs.shape[0] != B or pairs.shape[2] != 2 or not pairs.is_contiguous()):
+        raise _lib.AdellHipError("gather_rows: pairs must be a dense int32 [B, gamma, 2] device tensor")
+    return ctypes.c_void_p(pairs.data_ptr())
+
+
+def gather_rows_fwd(x, pairs, col):
+    """out[b * gamma + k] = x[b, pairs[b, k, col]] for x [B, T, C]: [B * gamma, C]."""
+    _require_cuda(x)
+    x = x.contiguous()
+    B, T, C = x.shape
+    gamma = pairs.shape[1]
+    out = torch.empty((B * gamma, C), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_gather_rows_fwd(_ptr(x), _pairs_arg(pairs, B), int(col), B, T, C, gamma,
+                                           _ptr(out), _stream()))
+    return out
+
+
+def gather_rows_bwd(dout, pairs, col, shape):
+    """dx [B, T, C] of ``gather_rows_fwd``: the rows of dout added back in the order of k."""
+    _require_cuda(dout)
+    dout = dout.contiguous()
+    B, T, C = shape
+    gamma = pairs.shape[1]
+    dx = torch.empty((B, T, C), device=dout.device, dtype=torch.float32)
+    check(_lib.lib().adell_gather_rows_bwd(_ptr(dout), _pairs_arg(pairs, B), int(col), B, T, C,
+                                           gamma, _ptr(dx), _stream()))
+    return dx
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

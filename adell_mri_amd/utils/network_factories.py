@@ -112,7 +112,8 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
                     optimizer_eps: float = OPTIMIZER_EPS_DEFAULT):
     """``network_config`` is ``parse_config_ssl``'s second return value. As in the reference,
     simclr / byol / vicreg / vicregl always build the ResNet wrapper from the three ``*_args``
-    dictionaries (defaults :754-790); every other method name with ``net_type="convnext"``
+    dictionaries (defaults :754-790) -- for vicregl with ``VICRegLocalLoss(**vic_reg_loss_params)``
+    on the "representation" feature maps and the boxes of the batch; every other method name with ``net_type="convnext"``
     builds ``SelfSLConvNeXtPL`` from the whole configuration (:998-1026)."""
     common = {"training_dataloader_call": train_loader_call, "n_epochs": max_epochs,
               "n_steps": max_steps_optim, "warmup_steps": warmup_steps, "ema": ema,

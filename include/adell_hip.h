@@ -736,6 +736,30 @@ int adell_vicreg_bwd(const float* x1, const float* x2, int B, int D, float min_v
                      const float* scratch, const float* g3, float* dx1, float* dx2,
                      void* stream);
 
+/* Local VICReg loss (VICRegLocalLoss, self_supervised/losses/vicreg.py:168-404; csrc/vicregl.hip).
+ * adell_top_pairs: per item the gamma pairs (i, j) of token rows a[b][i][:], b[b][j][:] (both
+ * [B][T][C], channels innermost) with the LARGEST Euclidean distance, ordered by (distance
+ * descending, flat index i T + j ascending): pairs is int32 [B][gamma][2], dist2 (may be NULL) the
+ * squared distances [B][gamma], fp32 sums of (a - b)^2 over the channels in order. The T x T matrix
+ * is never written. workspace: adell_top_pairs_workspace_words(B, T, gamma) 8-byte words, 8-byte
+ * aligned. 1 <= gamma <= 64, gamma <= T^2, T <= 65535, else ADELL_E_UNSUPPORTED.
+ * adell_top_pairs_boxes: the same ranking of the distances between the token grid (dims[0 .. ndim),
+ * row-major, ndim 2 or 3; dims on the host) mapped into each view's box, grid * (hi - lo) + lo with
+ * box = (lo..., hi...) as [B][2 ndim]; T = prod(dims).
+ * adell_gather_rows_fwd: out[b gamma + k][:] = x[b][pairs[b][k][col]][:] (x [B][T][C], col 0 or 1);
+ * adell_gather_rows_bwd: dx = 0, then dx[b][pairs[b][k][col]][:] += dout[b gamma + k][:] for k in
+ * order, one thread per (item, channel): no float atomics, duplicates welcome, bit-reproducible. */
+long adell_top_pairs_workspace_words(int B, int T, int gamma);
+int adell_top_pairs(const float* a, const float* b, int B, int T, int C, int gamma, void* workspace,
+                    long workspace_words, int* pairs, float* dist2, void* stream);
+int adell_top_pairs_boxes(const float* box1, const float* box2, int B, int ndim, const int* dims,
+                          int gamma, void* workspace, long workspace_words, int* pairs,
+                          float* dist2, void* stream);
+int adell_gather_rows_fwd(const float* x, const int* pairs, int col, int B, int T, int C, int gamma,
+                          float* out, void* stream);
+int adell_gather_rows_bwd(const float* dout, const int* pairs, int col, int B, int T, int C,
+                          int gamma, float* dx, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
