@@ -65,7 +65,7 @@ static ConvTile adell_pick_tile(int N, int Do, int Ho, int Wo, int Cout,
     case 0: t.BM = 256; t.BN = 64; break;
     case 1: t.BM = 256; t.BN = 32; break;
     case 2: t.BM = 64; t.BN = 64; break;
-    case 6: t.BM = 64; t.BN = 32; break;   // two-wave blocks (adell_plan_f16: strided layers)
+    case 6: t.BM = 64; t.BN = 32; break;   // two-wave blocks (adell_plan_tile_f16: strided layers)
     default: t.BM = 128; t.BN = 32; break;
   }
   adell_shape_brick(t.BM, Wo, Ho, Do, &t.lTX, &t.lTY, &t.lTZ);
@@ -84,20 +84,35 @@ static int adell_launch_conv(const ConvArgs& a, dim3 grid, size_t lds,
   return adell_launch<adell_conv_igemm_kernel<MT, NT, WM, WN>>(grid, dim3(256), lds, st, a);
 }
 
+// Brick counts and input halo of a tile's output brick (the one place they are computed).
+struct ConvBrick {
+  int ntx, nty, ntz;   // bricks per axis
+  int HX, HY, HZ, VP;  // halo dims and voxels
+};
+
+static ConvBrick adell_brick(const ConvArgs& a, const ConvTile& t) {
+  const int TX = 1 << t.lTX, TY = 1 << t.lTY, TZ = 1 << t.lTZ;
+  ConvBrick b;
+  b.ntx = adell_cdiv(a.Wo, TX);
+  b.nty = adell_cdiv(a.Ho, TY);
+  b.ntz = adell_cdiv(a.Do, TZ);
+  b.HX = (TX - 1) * a.SW + a.KW;
+  b.HY = (TY - 1) * a.SH + a.KH;
+  b.HZ = (TZ - 1) * a.SD + a.KD;
+  b.VP = b.HX * b.HY * b.HZ;
+  return b;
+}
+
+static void adell_put_brick(ConvArgs& a, const ConvTile& t, const ConvBrick& b) {
+  a.lTX = t.lTX; a.lTY = t.lTY; a.lTZ = t.lTZ;
+  a.ntx = b.ntx; a.nty = b.nty; a.ntz = b.ntz;
+  a.HX = b.HX; a.HY = b.HY; a.HZ = b.HZ; a.VP = b.VP;
+}
+
 // Generic launcher. `a` must have everything but the tile fields filled in.
 static int adell_conv_dispatch(ConvArgs a, int N, hipStream_t st) {
   const ConvTile t = adell_pick_tile(N, a.Do, a.Ho, a.Wo, a.Cout, g_conv_force_cfg);
-  a.lTX = t.lTX;
-  a.lTY = t.lTY;
-  a.lTZ = t.lTZ;
-  const int TX = 1 << t.lTX, TY = 1 << t.lTY, TZ = 1 << t.lTZ;
-  a.ntx = adell_cdiv(a.Wo, TX);
-  a.nty = adell_cdiv(a.Ho, TY);
-  a.ntz = adell_cdiv(a.Do, TZ);
-  a.HX = (TX - 1) * a.SW + a.KW;
-  a.HY = (TY - 1) * a.SH + a.KH;
-  a.HZ = (TZ - 1) * a.SD + a.KD;
-  a.VP = a.HX * a.HY * a.HZ;
+  adell_put_brick(a, t, adell_brick(a, t));
   if ((a.VP & 1) == 0) a.VP += 1;
   const int ntap = a.KD * a.KH * a.KW;
   size_t lds = ((size_t)8 * a.VP + (size_t)ntap * 8 * t.BN) * sizeof(float);
@@ -145,23 +160,12 @@ static int adell_check_desc(const adell_conv3d_desc* d) {
   return ADELL_OK;
 }
 
-extern "C" int adell_conv3d_fwd_ntiles(const adell_conv3d_desc* d) {
-  if (adell_check_desc(d) != ADELL_OK) return ADELL_E_BADARG;
-  const ConvTile t = adell_pick_tile(d->N, d->Do, d->Ho, d->Wo, d->Cout, g_conv_force_cfg);
-  return adell_cdiv(d->Wo, 1 << t.lTX) * adell_cdiv(d->Ho, 1 << t.lTY) *
-         adell_cdiv(d->Do, 1 << t.lTZ);
-}
-
-static int adell_fill_fwd(ConvArgs& a, const adell_conv3d_desc* d, const float* x0,
-                          const float* x1, const float* bias, const float* residual, float* y,
-                          float* stat_partials, int partial_rows = 0) {
+// ---- geometry of each conv form as a stride-1-output implicit GEMM: everything of ConvArgs but the
+// pointers and the tile fields, from the descriptor alone (what a plan is made from) ----
+static int adell_geom_fwd(ConvArgs& a, const adell_conv3d_desc* d) {
   int rc = adell_check_desc(d);
   if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(x0 && y, "conv_fwd: null pointer");
-  ADELL_REQUIRE(d->C1 == 0 || x1, "conv_fwd: C1 > 0 needs x1");
   a = ConvArgs{};
-  a.x0 = x0; a.x1 = x1; a.w = nullptr; a.bias = bias; a.res = residual;
-  a.y0 = y; a.y1 = nullptr; a.part = stat_partials; a.part_rows = partial_rows;
   a.D = d->D; a.H = d->H; a.W = d->W;
   a.C0 = d->C0; a.C1 = d->C1; a.Cin = d->C0 + d->C1; a.Cout = d->Cout;
   a.KD = d->KD; a.KH = d->KH; a.KW = d->KW;
@@ -171,6 +175,99 @@ static int adell_fill_fwd(ConvArgs& a, const adell_conv3d_desc* d, const float* 
   a.Do = d->Do; a.Ho = d->Ho; a.Wo = d->Wo;
   a.ysplit = d->Cout; a.shuffle = 0; a.Cs = d->Cout;
   return ADELL_OK;
+}
+
+// dX = conv_stride1(zero_insert(dY, S), flip(W)^T, pad = K-1-P), written to the
+// two sources of the forward's virtual concat (per-axis insertion factors, so anisotropic
+// strides such as the (1,2,2) of a 2-D network work); w_packed_bwd is
+// [flipped tap][Cout][Cin] (adell_pack_weight mode 1).
+static int adell_geom_bwd_data(ConvArgs& a, const adell_conv3d_desc* d) {
+  int rc = adell_check_desc(d);
+  if (rc != ADELL_OK) return rc;
+  // (pad > k - 1 -- the padded 1x1 convs of the depthwise U-Net blocks, unet.py:292-307 -- makes
+  // the padding of this stride-1 conv over dY negative: the halo origin moves INSIDE dY, which the
+  // generic halo arithmetic handles as it stands)
+  a = ConvArgs{};
+  a.D = d->Do; a.H = d->Ho; a.W = d->Wo;
+  a.C0 = d->Cout; a.C1 = 0; a.Cin = d->Cout; a.Cout = d->C0 + d->C1;
+  a.KD = d->KD; a.KH = d->KH; a.KW = d->KW;
+  a.SD = a.SH = a.SW = 1;
+  a.PD = d->KD - 1 - d->PD; a.PH = d->KH - 1 - d->PH; a.PW = d->KW - 1 - d->PW;
+  a.UPS = d->SW; a.UPSY = d->SH; a.UPSZ = d->SD;   // per-axis zero insertion
+  a.Do = d->D; a.Ho = d->H; a.Wo = d->W;
+  a.ysplit = d->C0; a.shuffle = 0; a.Cs = a.Cout;
+  return ADELL_OK;
+}
+
+// ConvTranspose3d with kernel = stride = (FD,FH,FW), each 1 or 2, padding 0: a
+// per-voxel GEMM [Cin] -> [F*Cout] whose columns scatter to the FD x FH x FW children
+// of the voxel. w_packed is [Cin][F][Cout] (adell_pack_weight mode 2).
+static int adell_convt_factors_ok(int FD, int FH, int FW) {
+  return (FD == 1 || FD == 2) && (FH == 1 || FH == 2) && (FW == 1 || FW == 2);
+}
+
+static int adell_geom_convt_fwd(ConvArgs& a, int N, int D, int H, int W, int Cin, int Cout, int FD,
+                                int FH, int FW) {
+  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "convT_fwd: bad dims");
+  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_fwd: kernel=stride must be 1 or 2 per dim");
+  a = ConvArgs{};
+  a.D = D; a.H = H; a.W = W;
+  a.C0 = Cin; a.C1 = 0; a.Cin = Cin; a.Cout = FD * FH * FW * Cout;
+  a.KD = a.KH = a.KW = 1;
+  a.SD = a.SH = a.SW = 1;
+  a.UPS = a.UPSY = a.UPSZ = 1;
+  a.Do = D; a.Ho = H; a.Wo = W;
+  a.ysplit = a.Cout; a.Cs = Cout;
+  a.shuffle = 8 | (FW - 1) | ((FH - 1) << 1) | ((FD - 1) << 2);  // bit 3 marks "scatter store"
+  return ADELL_OK;
+}
+
+// dX of the transposed conv = a kernel = stride = (FD,FH,FW), padding 0 convolution of dY
+// ([N,FD*D,FH*H,FW*W,Cout]) with w_packed_bwd [taps][Cout][Cin] (pack mode 3).
+static int adell_geom_convt_bwd_data(ConvArgs& a, int N, int D, int H, int W, int Cin, int Cout,
+                                     int FD, int FH, int FW) {
+  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
+                "convT_bwd_data: bad dims");
+  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_bwd_data: bad factors");
+  a = ConvArgs{};
+  a.D = FD * D; a.H = FH * H; a.W = FW * W;
+  a.C0 = Cout; a.C1 = 0; a.Cin = Cout; a.Cout = Cin;
+  a.KD = a.SD = FD; a.KH = a.SH = FH; a.KW = a.SW = FW;
+  a.UPS = a.UPSY = a.UPSZ = 1;
+  a.Do = D; a.Ho = H; a.Wo = W;
+  a.ysplit = a.Cout; a.shuffle = 0; a.Cs = a.Cout;
+  return ADELL_OK;
+}
+
+// ---- geometry + the call's pointers (null checks) ----
+static int adell_fill_fwd(ConvArgs& a, const adell_conv3d_desc* d, const float* x0,
+                          const float* x1, const float* bias, const float* residual, float* y,
+                          float* stat_partials, int partial_rows = 0) {
+  int rc = adell_geom_fwd(a, d);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(x0 && y, "conv_fwd: null pointer");
+  ADELL_REQUIRE(d->C1 == 0 || x1, "conv_fwd: C1 > 0 needs x1");
+  a.x0 = x0; a.x1 = x1; a.bias = bias; a.res = residual;
+  a.y0 = y; a.part = stat_partials; a.part_rows = partial_rows;
+  return ADELL_OK;
+}
+
+static int adell_fill_bwd_data(ConvArgs& a, const adell_conv3d_desc* d, const float* dy,
+                               float* dx0, float* dx1) {
+  int rc = adell_geom_bwd_data(a, d);
+  if (rc != ADELL_OK) return rc;
+  ADELL_REQUIRE(dy && dx0, "conv_bwd_data: null pointer");
+  ADELL_REQUIRE(d->C1 == 0 || dx1, "conv_bwd_data: C1 > 0 needs dx1");
+  a.x0 = dy; a.y0 = dx0; a.y1 = dx1;
+  return ADELL_OK;
+}
+
+extern "C" int adell_conv3d_fwd_ntiles(const adell_conv3d_desc* d) {
+  ConvArgs a;
+  if (adell_geom_fwd(a, d) != ADELL_OK) return ADELL_E_BADARG;
+  const ConvBrick b =
+      adell_brick(a, adell_pick_tile(d->N, d->Do, d->Ho, d->Wo, d->Cout, g_conv_force_cfg));
+  return b.ntx * b.nty * b.ntz;
 }
 
 extern "C" int adell_conv3d_fwd(const adell_conv3d_desc* d, const float* x0,
@@ -185,33 +282,6 @@ extern "C" int adell_conv3d_fwd(const adell_conv3d_desc* d, const float* x0,
   return adell_conv_dispatch(a, d->N, (hipStream_t)stream);
 }
 
-// dX = conv_stride1(zero_insert(dY, S), flip(W)^T, pad = K-1-P), written to the
-// two sources of the forward's virtual concat (per-axis insertion factors, so anisotropic
-// strides such as the (1,2,2) of a 2-D network work); w_packed_bwd is
-// [flipped tap][Cout][Cin] (adell_pack_weight mode 1).
-static int adell_fill_bwd_data(ConvArgs& a, const adell_conv3d_desc* d, const float* dy,
-                               float* dx0, float* dx1) {
-  int rc = adell_check_desc(d);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(dy && dx0, "conv_bwd_data: null pointer");
-  ADELL_REQUIRE(d->C1 == 0 || dx1, "conv_bwd_data: C1 > 0 needs dx1");
-  // (pad > k - 1 -- the padded 1x1 convs of the depthwise U-Net blocks, unet.py:292-307 -- makes
-  // the padding of this stride-1 conv over dY negative: the halo origin moves INSIDE dY, which the
-  // generic halo arithmetic handles as it stands)
-  a = ConvArgs{};
-  a.x0 = dy; a.x1 = nullptr; a.w = nullptr; a.bias = nullptr; a.res = nullptr;
-  a.y0 = dx0; a.y1 = dx1; a.part = nullptr;
-  a.D = d->Do; a.H = d->Ho; a.W = d->Wo;
-  a.C0 = d->Cout; a.C1 = 0; a.Cin = d->Cout; a.Cout = d->C0 + d->C1;
-  a.KD = d->KD; a.KH = d->KH; a.KW = d->KW;
-  a.SD = a.SH = a.SW = 1;
-  a.PD = d->KD - 1 - d->PD; a.PH = d->KH - 1 - d->PH; a.PW = d->KW - 1 - d->PW;
-  a.UPS = d->SW; a.UPSY = d->SH; a.UPSZ = d->SD;   // per-axis zero insertion
-  a.Do = d->D; a.Ho = d->H; a.Wo = d->W;
-  a.ysplit = d->C0; a.shuffle = 0; a.Cs = a.Cout;
-  return ADELL_OK;
-}
-
 extern "C" int adell_conv3d_bwd_data(const adell_conv3d_desc* d, const float* dy,
                                      const float* w_packed_bwd, float* dx0,
                                      float* dx1, void* stream) {
@@ -223,31 +293,14 @@ extern "C" int adell_conv3d_bwd_data(const adell_conv3d_desc* d, const float* dy
   return adell_conv_dispatch(a, d->N, (hipStream_t)stream);
 }
 
-// ConvTranspose3d with kernel = stride = (FD,FH,FW), each 1 or 2, padding 0: a
-// per-voxel GEMM [Cin] -> [F*Cout] whose columns scatter to the FD x FH x FW children
-// of the voxel. w_packed is [Cin][F][Cout] (adell_pack_weight mode 2).
-static int adell_convt_factors_ok(int FD, int FH, int FW) {
-  return (FD == 1 || FD == 2) && (FH == 1 || FH == 2) && (FW == 1 || FW == 2);
-}
-
 extern "C" int adell_convtranspose3d_fwd(int N, int D, int H, int W, int Cin, int Cout, int FD,
                                          int FH, int FW, const float* x, const float* w_packed,
                                          const float* bias, float* y, void* stream) {
-  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "convT_fwd: bad dims");
-  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_fwd: kernel=stride must be 1 or 2 per dim");
+  ConvArgs a;
+  int rc = adell_geom_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(x && w_packed && y, "convT_fwd: null pointer");
-  ConvArgs a = {};
-  a.x0 = x; a.x1 = nullptr; a.w = w_packed; a.bias = bias; a.res = nullptr;
-  a.y0 = y; a.y1 = nullptr; a.part = nullptr;
-  a.D = D; a.H = H; a.W = W;
-  a.C0 = Cin; a.C1 = 0; a.Cin = Cin; a.Cout = FD * FH * FW * Cout;
-  a.KD = a.KH = a.KW = 1;
-  a.SD = a.SH = a.SW = 1;
-  a.PD = a.PH = a.PW = 0;
-  a.UPS = a.UPSY = a.UPSZ = 1;
-  a.Do = D; a.Ho = H; a.Wo = W;
-  a.ysplit = a.Cout; a.Cs = Cout;
-  a.shuffle = 8 | (FW - 1) | ((FH - 1) << 1) | ((FD - 1) << 2);  // bit 3 marks "scatter store"
+  a.x0 = x; a.w = w_packed; a.bias = bias; a.y0 = y;
   return adell_conv_dispatch(a, N, (hipStream_t)stream);
 }
 
@@ -259,26 +312,15 @@ extern "C" int adell_convtranspose3d_k2s2_fwd(int N, int D, int H, int W, int Ci
   return adell_convtranspose3d_fwd(N, D, H, W, Cin, Cout, 2, 2, 2, x, w_packed, bias, y, stream);
 }
 
-// dX of the transposed conv = a kernel = stride = (FD,FH,FW), padding 0 convolution of dY
-// ([N,FD*D,FH*H,FW*W,Cout]) with w_packed_bwd [taps][Cout][Cin] (pack mode 3).
 extern "C" int adell_convtranspose3d_bwd_data(int N, int D, int H, int W, int Cin, int Cout,
                                               int FD, int FH, int FW, const float* dy,
                                               const float* w_packed_bwd, float* dx,
                                               void* stream) {
-  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
-                "convT_bwd_data: bad dims");
-  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_bwd_data: bad factors");
+  ConvArgs a;
+  int rc = adell_geom_convt_bwd_data(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(dy && w_packed_bwd && dx, "convT_bwd_data: null pointer");
-  ConvArgs a = {};
-  a.x0 = dy; a.x1 = nullptr; a.w = w_packed_bwd; a.bias = nullptr; a.res = nullptr;
-  a.y0 = dx; a.y1 = nullptr; a.part = nullptr;
-  a.D = FD * D; a.H = FH * H; a.W = FW * W;
-  a.C0 = Cout; a.C1 = 0; a.Cin = Cout; a.Cout = Cin;
-  a.KD = a.SD = FD; a.KH = a.SH = FH; a.KW = a.SW = FW;
-  a.PD = a.PH = a.PW = 0;
-  a.UPS = a.UPSY = a.UPSZ = 1;
-  a.Do = D; a.Ho = H; a.Wo = W;
-  a.ysplit = a.Cout; a.shuffle = 0; a.Cs = a.Cout;
+  a.x0 = dy; a.w = w_packed_bwd; a.y0 = dx;
   return adell_conv_dispatch(a, N, (hipStream_t)stream);
 }
 
@@ -358,28 +400,54 @@ extern "C" void adell_conv_zring16_segments(int N, int Do, int Ho, int Wo, int* 
 extern "C" int adell_conv_zring16_launch(const ConvArgs* a, const ConvF16Extra* e, int N, int seglen,
                                          int nseg, hipStream_t st);
 
-// Tile plan of the f16x3 kernel: the heuristic brick, or (when its halo does not fit
-// LDS, i.e. stride 2) the small-brick configuration of the same channel width.
-static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
+// Launch plan of the f16x3 kernels for one problem: everything decided before a pointer is looked
+// at. adell_plan_f16 fills it; the launcher (adell_conv_launch_f16) and the host-only queries read it.
+struct ConvPlanF16 {
+  ConvTile tile;     // cfg (0-3, 6: adell_pick_tile; 4: 8x8x8 bricks; 5: transposed-conv forward;
+                     // 8: 16-column z-ring), BM, BN, log2 brick dims
+  ConvBrick brick;   // (cfg 8: units = 8 x 8 columns x z segments -- ntz = segments, HZ = steps per
+                     // segment; the statistics rows per item are ntx * nty * ntz like every other plan's)
+  int GKH;           // ky rows per staged weight group
+  size_t lds;
+  long bricks;       // per batch item
+  int shares;        // K shares (1 = no split-K)
+  long slab;         // floats per share
+  int vecx, spec;    // 16-byte input loads legal; the SPEC = 1 instance of cfg 0 / 1
+  int rows_ok;       // the plan stages split-row sources
+  int adn_rows;      // rows per item of the fused-epilogue partials, 0 = the plan does not take it
+  int stat_rows;     // statistics rows per item: the fold's tiles when it splits, else the bricks
+  dim3 grid;
+};
+
+// 3x3x3 taps, stride 1, no zero insertion, plain store: the layers that carry a U-Net's FLOPs and
+// that every specialised rule below is about.
+static bool adell_is_3s1(const ConvArgs& a) {
+  return a.KD == 3 && a.KH == 3 && a.KW == 3 && a.SD == 1 && a.SH == 1 && a.SW == 1 && a.UPS == 1 &&
+         a.UPSY == 1 && a.UPSZ == 1 && a.shuffle == 0;
+}
+
+// (the f16x3 kernel's 16-byte halo loads address a batch item with 32-bit byte offsets)
+static bool adell_item_below_4g(const ConvArgs& a) {
+  return (size_t)a.D * a.H * a.W * (a.C0 > a.C1 ? a.C0 : a.C1) < ((size_t)1 << 30);
+}
+
+// Tile, brick, weight group and LDS bytes of the plan: the heuristic brick, a measured rule's, or
+// (when its halo does not fit LDS, i.e. stride 2) the small-brick configuration of the same channel
+// width.
+static int adell_plan_tile_f16(const ConvArgs& a, int N, ConvPlanF16* p) {
   ConvTile t = adell_pick_tile(N, a.Do, a.Ho, a.Wo, a.Cout, g_conv_force_cfg);
+  const bool is3s1 = adell_is_3s1(a);
   if (g_conv_force_cfg < 0 && adell_conv_zring16_ok(&a)) {
-    // cfg 8: units = 8 x 8 columns x z segments (ntz = segments, HZ = steps per segment); the
-    // statistics rows per item are ntx * nty * ntz like every other plan's
     int seglen = 0, nseg = 0;
     adell_conv_zring16_segments(N, a.Do, a.Ho, a.Wo, &seglen, &nseg);
     t.cfg = 8;
     t.BM = 64;
     t.BN = 16;
     t.lTX = 3; t.lTY = 3; t.lTZ = 0;
-    a.lTX = 3; a.lTY = 3; a.lTZ = 0;
-    a.ntx = adell_cdiv(a.Wo, 8);
-    a.nty = adell_cdiv(a.Ho, 8);
-    a.ntz = nseg;
-    a.HX = 10; a.HY = 10; a.HZ = seglen;
-    a.VP = 100;
-    a.GKH = 3;
-    *tile = t;
-    *lds_out = 0;
+    p->tile = t;
+    p->brick = {adell_cdiv(a.Wo, 8), adell_cdiv(a.Ho, 8), nseg, 10, 10, seglen, 100};
+    p->GKH = 3;
+    p->lds = 0;
     return ADELL_OK;
   }
   // kernel == stride > 1 (transposed-conv backward-data): every staged voxel feeds one tap, so
@@ -410,9 +478,7 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
   // 0.9 GB of weight reads, 214 us); 256-voxel x 32-column bricks + split-K read a quarter of
   // that (139 us). 8^3 levels: 64-voxel x 32-column two-wave bricks (256 -> 256: 89 -> 68 us).
   bool retiled = false;
-  if (g_conv_force_cfg < 0 && a.shuffle == 0 && a.KD == 3 &&
-      a.KH == 3 && a.KW == 3 && a.SD == 1 && a.SH == 1 && a.SW == 1 && a.UPS == 1 &&
-      a.UPSY == 1 && a.UPSZ == 1) {
+  if (g_conv_force_cfg < 0 && is3s1) {
     const long vox = (long)N * a.Do * a.Ho * a.Wo;
     int pick = -1;
     if (a.Cout <= 32) {
@@ -444,18 +510,10 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
   // outputs takes 64 x 64 -> 64 x 32, or 256 x 64 -> 64 x 64 -> 64 x 32 from 65 536 output voxels x
   // 64-column tiles on)
   for (int attempt = 0; attempt < 3; ++attempt) {
-    a.lTX = t.lTX; a.lTY = t.lTY; a.lTZ = t.lTZ;
-    const int TX = 1 << t.lTX, TY = 1 << t.lTY, TZ = 1 << t.lTZ;
-    a.ntx = adell_cdiv(a.Wo, TX);
-    a.nty = adell_cdiv(a.Ho, TY);
-    a.ntz = adell_cdiv(a.Do, TZ);
-    a.HX = (TX - 1) * a.SW + a.KW;
-    a.HY = (TY - 1) * a.SH + a.KH;
-    a.HZ = (TZ - 1) * a.SD + a.KD;
-    a.VP = a.HX * a.HY * a.HZ;
+    p->brick = adell_brick(a, t);
     // weights are staged one kz plane at a time, or row by row when a plane is too big
-    a.GKH = ((size_t)a.KH * a.KW * t.BN * 64 <= 40 * 1024) ? a.KH : 1;
-    lds = (size_t)a.VP * 64 + (size_t)a.GKH * a.KW * t.BN * 64 + 64;
+    p->GKH = ((size_t)a.KH * a.KW * t.BN * 64 <= 40 * 1024) ? a.KH : 1;
+    lds = (size_t)p->brick.VP * 64 + (size_t)p->GKH * a.KW * t.BN * 64 + 64;
     const size_t red = (size_t)8 * t.BN * 2 * sizeof(float);
     if (lds < red) lds = red;
     if (lds <= 160 * 1024) break;
@@ -469,19 +527,13 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
   }
   // 32-channel tiles of 3x3x3 stride-1 layers: 8x8x8 bricks (cfg 4, SPEC = 3 instance of the
   // kernel): a third less halo per output and half the weight staging of the 8x8x4 brick
-  if (t.cfg == 1 && !retiled && a.KD == 3 && a.KH == 3 && a.KW == 3 && a.SD == 1 && a.SH == 1 && a.SW == 1 &&
-      a.UPS == 1 && a.UPSY == 1 && a.UPSZ == 1 && a.shuffle == 0 && a.lTX == 3 && a.lTY == 3 &&
-      a.lTZ == 2 && a.Do >= 8 && a.C0 % 16 == 0 && a.C1 % 16 == 0 &&
-      (size_t)a.D * a.H * a.W * (a.C0 > a.C1 ? a.C0 : a.C1) < ((size_t)1 << 30) &&
-      g_conv_force_cfg < 0 && !g_adell_tune.igemm_nospec &&
-      !g_adell_tune.igemm_no8) {
+  if (t.cfg == 1 && !retiled && is3s1 && t.lTX == 3 && t.lTY == 3 && t.lTZ == 2 && a.Do >= 8 &&
+      a.C0 % 16 == 0 && a.C1 % 16 == 0 && adell_item_below_4g(a) && g_conv_force_cfg < 0 &&
+      !g_adell_tune.igemm_nospec && !g_adell_tune.igemm_no8) {
     t.cfg = 4;
     t.BM = 512;
     t.lTZ = 3;
-    a.lTZ = 3;
-    a.ntz = adell_cdiv(a.Do, 8);
-    a.HZ = 10;
-    a.VP = a.HX * a.HY * a.HZ;
+    p->brick = adell_brick(a, t);   // 10 x 10 x 10 halo
     lds = (size_t)1000 * 64 + (size_t)7 * 32 * 64 + 64;
   }
   // transposed-conv forward (1 tap, F * Cs columns with a pixel-shuffle store): one block takes a
@@ -493,18 +545,13 @@ static int adell_plan_f16(ConvArgs& a, int N, ConvTile* tile, size_t* lds_out) {
     t.BM = 64;
     t.BN = 256;
     adell_shape_brick(64, a.Wo, a.Ho, a.Do, &t.lTX, &t.lTY, &t.lTZ);
-    a.lTX = t.lTX; a.lTY = t.lTY; a.lTZ = t.lTZ;
-    a.ntx = adell_cdiv(a.Wo, 1 << t.lTX);
-    a.nty = adell_cdiv(a.Ho, 1 << t.lTY);
-    a.ntz = adell_cdiv(a.Do, 1 << t.lTZ);
-    a.HX = 1 << t.lTX; a.HY = 1 << t.lTY; a.HZ = 1 << t.lTZ;
-    a.VP = a.HX * a.HY * a.HZ;
-    a.GKH = 1;
-    lds = (size_t)a.VP * 64 + (size_t)256 * 64 + 64;
+    p->brick = adell_brick(a, t);   // one tap, stride 1: the halo is the brick
+    p->GKH = 1;
+    lds = (size_t)p->brick.VP * 64 + (size_t)256 * 64 + 64;
     if (lds < (size_t)1 * 256 * 2 * sizeof(float)) lds = (size_t)256 * 2 * sizeof(float);
   }
-  *tile = t;
-  *lds_out = lds;
+  p->tile = t;
+  p->lds = lds;
   return ADELL_OK;
 }
 
@@ -588,10 +635,10 @@ static int adell_fold_tiles(long vox, int N, int Cout, long bricks) {
 }
 
 // number of K shares for this problem (1 = no split) given the planned tile
-static int adell_splitk_shares(const ConvArgs& a, const ConvTile& t, int N) {
+static int adell_splitk_shares(const ConvArgs& a, const ConvTile& t, long bricks, int N) {
   if (g_adell_tune.no_splitk) return 1;
   const int nchunk = adell_cdiv(a.Cin, 16);
-  const long blocks = (long)a.ntx * a.nty * a.ntz * adell_cdiv(a.Cout, t.BN) * N;
+  const long blocks = bricks * adell_cdiv(a.Cout, t.BN) * N;
   const int cq = a.Cout / 4;
   if (a.shuffle || a.Cout % 4 || cq > 256 || 256 % cq || a.ysplit % 4 || nchunk < 4 || blocks > 256)
     return 1;
@@ -602,23 +649,16 @@ static int adell_splitk_shares(const ConvArgs& a, const ConvTile& t, int N) {
   return adell_cdiv(nchunk, cpk);
 }
 
-// adn: 0 plain; 1 launch the EPI = 1 instance (fused norm / dropout / activation backward in the
-// epilogue: ConvF16Extra::adn), failing when the plan does not allow it; -1 only answer whether it
-// would (returns the number of bricks per batch item = rows of the partial-sum buffer, 0 = no).
-static int adell_conv_dispatch_f16(ConvArgs a, ConvF16Extra e, int N, hipStream_t st,
-                                   void* ws = nullptr, size_t ws_bytes = 0, int adn = 0) {
-  ConvTile t;
-  size_t lds;
-  int rc = adell_plan_f16(a, N, &t, &lds);
-  if (rc != ADELL_OK) return adn < 0 ? 0 : rc;
-  // (the f16x3 kernel's 16-byte halo loads address a batch item with 32-bit byte offsets)
-  a.vecx = (a.C0 % 4 == 0) && (a.C1 % 4 == 0) && (((uintptr_t)a.x0 & 15) == 0) &&
-           (((uintptr_t)a.x1 & 15) == 0) &&
-           (size_t)a.D * a.H * a.W * (a.C0 > a.C1 ? a.C0 : a.C1) < ((size_t)1 << 30);
-  a.vecw = 1;
-  e.dbg = g_adell_tune.igemm_dbg;
-  const long nsp = (long)a.ntx * a.nty * a.ntz;
-  if (nsp > 0x0fffffffL || N > 65535) {
+// The plan of one problem, from the geometry fields of `a` (adell_geom_*; no pointer is read) and
+// what the call supplies: `aligned` -- its input tensors are 16-byte aligned; `have_ws` -- it
+// brings the split-K workspace (without one the problem never splits). Launches nothing.
+static int adell_plan_f16(const ConvArgs& a, int N, bool aligned, bool have_ws, ConvPlanF16* p) {
+  int rc = adell_plan_tile_f16(a, N, p);
+  if (rc != ADELL_OK) return rc;
+  const ConvTile& t = p->tile;
+  p->vecx = a.C0 % 4 == 0 && a.C1 % 4 == 0 && aligned && adell_item_below_4g(a);
+  p->bricks = (long)p->brick.ntx * p->brick.nty * p->brick.ntz;
+  if (p->bricks > 0x0fffffffL || N > 65535) {
     adell_set_error("conv: grid too large");
     return ADELL_E_UNSUPPORTED;
   }
@@ -626,146 +666,157 @@ static int adell_conv_dispatch_f16(ConvArgs a, ConvF16Extra e, int N, hipStream_
     // the epilogue addresses rows inside a brick with 32-bit element offsets
     const int fx = (a.shuffle & 1) + 1, fy = ((a.shuffle >> 1) & 1) + 1,
               fz = ((a.shuffle >> 2) & 1) + 1;
-    const size_t span = ((size_t)fz << a.lTZ) * ((size_t)fy * a.Ho) * ((size_t)fx * a.Wo) *
+    const size_t span = ((size_t)fz << t.lTZ) * ((size_t)fy * a.Ho) * ((size_t)fx * a.Wo) *
                         (size_t)(a.shuffle ? a.Cs : a.Cout);
     if (span >= ((size_t)1 << 32)) {
       adell_set_error("conv f16x3: a brick of %d output planes spans %zu elements (>= 2^32)",
-                      1 << a.lTZ, span);
+                      1 << t.lTZ, span);
       return ADELL_E_UNSUPPORTED;
     }
   }
-  // split-K when the caller supplied a workspace and the problem is small (see the fold kernel)
-  ConvArgs full = a;
-  int shares = ws ? adell_splitk_shares(a, t, N) : 1;
-  const long slab = (long)N * a.Do * a.Ho * a.Wo * a.Cout;
-  if (shares > 1 && (size_t)shares * slab * sizeof(float) > ws_bytes) {
+  // split-K when the caller supplies a workspace and the problem is small (see the fold kernel)
+  p->shares = have_ws ? adell_splitk_shares(a, t, p->bricks, N) : 1;
+  p->slab = (long)N * a.Do * a.Ho * a.Wo * a.Cout;
+  p->stat_rows = p->shares > 1 ? adell_fold_tiles((long)a.Do * a.Ho * a.Wo, N, a.Cout, p->bricks)
+                               : (int)p->bricks;
+  // blocks are dealt to the 8 XCDs in contiguous ranges (see the kernel): pad the grid
+  p->grid = dim3((unsigned)(8 * ((p->bricks + 7) / 8)), (unsigned)adell_cdiv(a.Cout, t.BN),
+                 (unsigned)(N * p->shares));
+  p->spec = adell_is_3s1(a) && t.lTX == 3 && t.lTY == 3 && t.lTZ == 2 && p->vecx && p->GKH == 3 &&
+            t.cfg <= 1 && a.C0 % 16 == 0 && a.C1 % 16 == 0 && !g_adell_tune.igemm_nospec;
+  // split-row sources are staged by the specialised instances only (no split-K: a share would have
+  // to know the rows' exponent of chunks it does not own... it could; it is simply not built)
+  const bool special = (t.cfg <= 1 && p->spec) || t.cfg == 4;
+  p->rows_ok = p->shares == 1 && (special || t.cfg == 8);
+  // the fused epilogue lives in the interior-brick path of the specialised instances: every brick
+  // whole, every 32-column sub-tile whole and on one side of ysplit, no split-K, no
+  // wave-specialised form (and no bias: the launcher checks that)
+  const bool adn = special && p->shares == 1 && a.Wo % 8 == 0 && a.Ho % 8 == 0 &&
+                   a.Do % (1 << t.lTZ) == 0 && a.Cout % t.BN == 0 && a.ysplit % 32 == 0 &&
+                   p->bricks * (long)a.Cout < (1L << 30);
+  p->adn_rows = adn ? (int)p->bricks : 0;
+  return ADELL_OK;
+}
+
+// The 18 instances of adell_conv_igemm_f16_kernel, each named once. Key: the plan's cfg and spec,
+// the fused norm / dropout / activation backward in the epilogue (ConvF16Extra::adn), and how many
+// sources are split rows (0 none, 1 some: the instance decides per source, 2 all: the instance
+// without the fp32 staging path). cfg 8 is not here: adell_conv_zring16_launch.
+typedef int (*ConvLaunchF16)(const ConvArgs&, const ConvF16Extra&, dim3, size_t, hipStream_t);
+static const struct ConvInstanceF16 {
+  int cfg, spec, epi, rows;
+  ConvLaunchF16 launch;
+} kConvInstancesF16[] = {
+    {0, 0, 0, 0, adell_launch_conv_f16<2, 2, 4, 1, 0>},
+    {0, 1, 0, 0, adell_launch_conv_f16<2, 2, 4, 1, 1>},
+    {0, 1, 1, 0, adell_launch_conv_f16<2, 2, 4, 1, 1, 1>},
+    {0, 1, 0, 1, adell_launch_conv_f16<2, 2, 4, 1, 1, 0, 1>},
+    {0, 1, 0, 2, adell_launch_conv_f16<2, 2, 4, 1, 1, 0, 2>},
+    {1, 0, 0, 0, adell_launch_conv_f16<2, 1, 4, 1, 0>},
+    {1, 1, 0, 0, adell_launch_conv_f16<2, 1, 4, 1, 1>},
+    {1, 1, 1, 0, adell_launch_conv_f16<2, 1, 4, 1, 1, 1>},
+    {1, 1, 0, 1, adell_launch_conv_f16<2, 1, 4, 1, 1, 0, 1>},
+    {1, 1, 0, 2, adell_launch_conv_f16<2, 1, 4, 1, 1, 0, 2>},
+    {2, 0, 0, 0, adell_launch_conv_f16<1, 1, 2, 2, 0>},
+    {3, 0, 0, 0, adell_launch_conv_f16<1, 1, 4, 1, 0>},
+    {4, 0, 0, 0, adell_launch_conv_f16<4, 1, 4, 1, 3>},   // 8x8x8 bricks, four m-tiles per wave
+    {4, 0, 1, 0, adell_launch_conv_f16<4, 1, 4, 1, 3, 1>},
+    {4, 0, 0, 1, adell_launch_conv_f16<4, 1, 4, 1, 3, 0, 1>},
+    {4, 0, 0, 2, adell_launch_conv_f16<4, 1, 4, 1, 3, 0, 2>},
+    {5, 0, 0, 0, adell_launch_conv_f16<2, 2, 1, 4, 0>},   // transposed-conv forward: 64 voxels x 256 columns
+    {6, 0, 0, 0, adell_launch_conv_f16<1, 1, 2, 1, 0>},   // two-wave blocks
+};
+
+// Launches a planned problem: checks what depends on the call's buffers, copies the plan's geometry
+// into the kernel arguments, launches the instance and, for a split-K plan, the fold. `fused`: the
+// EPI = 1 instance (ConvF16Extra::adn filled in by the caller).
+static int adell_conv_launch_f16(const ConvPlanF16& p, ConvArgs a, ConvF16Extra e, int N, bool fused,
+                                 void* ws, size_t ws_bytes, hipStream_t st) {
+  const ConvTile& t = p.tile;
+  if (p.shares > 1 && (size_t)p.shares * p.slab * sizeof(float) > ws_bytes) {
     // (the statistics rows of the split form are the fold's, adell_conv3d_fwd_ntiles_f16x3_ws:
     // falling back to one share here would write a different number of rows)
     adell_set_error("conv f16x3: split-K workspace too small (%zu bytes, adell_conv3d_splitk_workspace)",
                     ws_bytes);
     return ADELL_E_BADARG;
   }
-  a.ksplit = shares;
-  a.slab = slab;
-  if (shares > 1) a.y0 = (float*)ws;
-  // blocks are dealt to the 8 XCDs in contiguous ranges (see the kernel): pad the grid
-  dim3 grid((unsigned)(8 * ((nsp + 7) / 8)), (unsigned)adell_cdiv(a.Cout, t.BN),
-            (unsigned)(N * shares));
-  const bool spec = a.KD == 3 && a.KH == 3 && a.KW == 3 && a.SD == 1 && a.SH == 1 && a.SW == 1 &&
-                    a.UPS == 1 && a.UPSY == 1 && a.UPSZ == 1 && a.lTX == 3 && a.lTY == 3 &&
-                    a.lTZ == 2 && a.shuffle == 0 && a.vecx && a.GKH == 3 && t.cfg <= 1 &&
-                    a.C0 % 16 == 0 && a.C1 % 16 == 0 &&
-                    (size_t)a.D * a.H * a.W * (a.C0 > a.C1 ? a.C0 : a.C1) < ((size_t)1 << 30) &&
-                    !g_adell_tune.igemm_nospec;
-  // split-row sources are staged by the specialised instances only (no split-K: a share would have
-  // to know the rows' exponent of chunks it does not own... it could; it is simply not built)
-  const bool rows_ok = shares == 1 && ((t.cfg <= 1 && spec) || t.cfg == 4 || t.cfg == 8);
-  if (adn == -2) return rows_ok ? 1 : 0;
-  if ((e.xs0 != nullptr || e.xs1 != nullptr) && !rows_ok) {
+  const bool rows = e.xs0 != nullptr || e.xs1 != nullptr;
+  if (rows && !p.rows_ok) {
     adell_set_error("conv f16x3: this problem's launch plan does not take split-row sources "
                     "(adell_conv3d_f16x3_rows_ok)");
     return ADELL_E_UNSUPPORTED;
   }
-  if (adn >= 0)
-    ADELL_REQUIRE_ROWS(a.part, a.part_rows,
-                       shares > 1 ? adell_fold_tiles((long)a.Do * a.Ho * a.Wo, N, a.Cout, nsp) : nsp,
-                       "conv f16x3");
-  if (adn != 0) {
-    // the fused epilogue lives in the interior-brick path of the specialised instances: every brick
-    // whole, every 32-column sub-tile whole and on one side of ysplit, no split-K, no
-    // wave-specialised form
-    const int bz = t.cfg == 4 ? 8 : 4;
-    const bool ok = ((t.cfg <= 1 && spec) || t.cfg == 4) && shares == 1 && (a.shuffle & 16) == 0 &&
-                    a.Wo % 8 == 0 && a.Ho % 8 == 0 && a.Do % bz == 0 && a.Cout % t.BN == 0 &&
-                    a.ysplit % 32 == 0 && a.bias == nullptr && nsp * (long)a.Cout < (1L << 30);
-    if (adn < 0) return ok ? (int)nsp : 0;
-    if (!ok) {
-      adell_set_error("conv_bwd_data_f16x3_adn: this problem does not take the fused epilogue");
-      return ADELL_E_UNSUPPORTED;
-    }
-    switch (t.cfg) {
-      case 0: return adell_launch_conv_f16<2, 2, 4, 1, 1, 1>(a, e, grid, lds, st);
-      case 4: return adell_launch_conv_f16<4, 1, 4, 1, 3, 1>(a, e, grid, lds, st);
-      default: return adell_launch_conv_f16<2, 1, 4, 1, 1, 1>(a, e, grid, lds, st);
-    }
+  ADELL_REQUIRE_ROWS(a.part, a.part_rows, p.stat_rows, "conv f16x3");
+  if (fused && (p.adn_rows == 0 || a.bias != nullptr)) {
+    adell_set_error("conv_bwd_data_f16x3_adn: this problem does not take the fused epilogue");
+    return ADELL_E_UNSUPPORTED;
   }
+  if (t.cfg == 4 && !p.vecx) {
+    adell_set_error("conv f16x3: input pointers must be 16-byte aligned");
+    return ADELL_E_BADARG;
+  }
+  const ConvArgs full = a;   // the fold's destinations: the kernel's y0 becomes the workspace
+  adell_put_brick(a, t, p.brick);
+  a.GKH = p.GKH;
+  a.vecx = p.vecx;
+  a.vecw = 1;
+  a.ksplit = p.shares;
+  a.slab = p.slab;
+  if (p.shares > 1) a.y0 = (float*)ws;
+  e.dbg = g_adell_tune.igemm_dbg;
   if (t.cfg == 8) return adell_conv_zring16_launch(&a, &e, N, a.HZ, a.ntz, st);
-  int rc2 = ADELL_OK;
-  if (e.xs0 != nullptr || e.xs1 != nullptr) {
-    // split-row sources (rows_ok above): the instance without the fp32 staging path when every
-    // source is rows, else the one that decides per source
-    const bool all_rows = e.xs0 != nullptr && (a.C1 == 0 || e.xs1 != nullptr);
-    switch (t.cfg) {
-      case 0:
-        return all_rows ? adell_launch_conv_f16<2, 2, 4, 1, 1, 0, 2>(a, e, grid, lds, st)
-                        : adell_launch_conv_f16<2, 2, 4, 1, 1, 0, 1>(a, e, grid, lds, st);
-      case 4:
-        return all_rows ? adell_launch_conv_f16<4, 1, 4, 1, 3, 0, 2>(a, e, grid, lds, st)
-                        : adell_launch_conv_f16<4, 1, 4, 1, 3, 0, 1>(a, e, grid, lds, st);
-      default:
-        return all_rows ? adell_launch_conv_f16<2, 1, 4, 1, 1, 0, 2>(a, e, grid, lds, st)
-                        : adell_launch_conv_f16<2, 1, 4, 1, 1, 0, 1>(a, e, grid, lds, st);
-    }
+  const int nrows = !rows ? 0 : (e.xs0 != nullptr && (a.C1 == 0 || e.xs1 != nullptr)) ? 2 : 1;
+  ConvLaunchF16 launch = nullptr;
+  for (const ConvInstanceF16& i : kConvInstancesF16)
+    if (i.cfg == t.cfg && i.spec == p.spec && i.epi == (int)fused && i.rows == nrows) launch = i.launch;
+  if (launch == nullptr) {
+    adell_set_error("conv f16x3: no kernel instance for cfg %d (spec %d, epilogue %d, rows %d)", t.cfg,
+                    p.spec, (int)fused, nrows);
+    return ADELL_E_UNSUPPORTED;
   }
-  switch (t.cfg) {
-    case 0:
-      rc2 = spec ? adell_launch_conv_f16<2, 2, 4, 1, 1>(a, e, grid, lds, st)
-                  : adell_launch_conv_f16<2, 2, 4, 1, 0>(a, e, grid, lds, st);
-      break;
-    case 5:   // transposed-conv forward: 64 voxels x 256 columns per block
-      rc2 = adell_launch_conv_f16<2, 2, 1, 4, 0>(a, e, grid, lds, st);
-      break;
-    case 4:   // 8x8x8 bricks, four m-tiles per wave (adell_plan_f16)
-      if (!a.vecx) {
-        adell_set_error("conv f16x3: input pointers must be 16-byte aligned");
-        return ADELL_E_BADARG;
-      }
-      rc2 = adell_launch_conv_f16<4, 1, 4, 1, 3>(a, e, grid, lds, st);
-      break;
-    case 1:
-      rc2 = spec ? adell_launch_conv_f16<2, 1, 4, 1, 1>(a, e, grid, lds, st)
-                  : adell_launch_conv_f16<2, 1, 4, 1, 0>(a, e, grid, lds, st);
-      break;
-    case 2: rc2 = adell_launch_conv_f16<1, 1, 2, 2, 0>(a, e, grid, lds, st); break;
-    case 6: rc2 = adell_launch_conv_f16<1, 1, 2, 1, 0>(a, e, grid, lds, st); break;
-    default: rc2 = adell_launch_conv_f16<1, 1, 4, 1, 0>(a, e, grid, lds, st); break;
-  }
-  if (rc2 != ADELL_OK || shares == 1) return rc2;
+  int rc = launch(a, e, p.grid, p.lds, st);
+  if (rc != ADELL_OK || p.shares == 1) return rc;
   ConvFoldArgs f = {};
   f.slabs = (const float*)ws; f.bias = full.bias; f.res = full.res; f.y0 = full.y0; f.y1 = full.y1;
-  f.part = full.part; f.vox = (long)a.Do * a.Ho * a.Wo; f.slab = slab; f.ksplit = shares;
-  f.Cout = a.Cout; f.ysplit = full.ysplit; f.ntiles = adell_fold_tiles(f.vox, N, a.Cout, nsp);
+  f.part = full.part; f.vox = (long)a.Do * a.Ho * a.Wo; f.slab = p.slab; f.ksplit = p.shares;
+  f.Cout = a.Cout; f.ysplit = full.ysplit; f.ntiles = p.stat_rows;
   hipLaunchKernelGGL(adell_conv_splitk_fold_kernel, dim3((unsigned)f.ntiles, (unsigned)N), dim3(256),
                      0, st, f);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
 
-extern "C" int adell_conv3d_fwd_ntiles_f16x3(const adell_conv3d_desc* d) {
-  ConvArgs a;
-  float dummy;
-  if (adell_fill_fwd(a, d, &dummy, &dummy, nullptr, nullptr, &dummy, nullptr) != ADELL_OK)
-    return ADELL_E_BADARG;
-  ConvTile t;
-  size_t lds;
-  if (adell_plan_f16(a, d->N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
-  return a.ntx * a.nty * a.ntz;
+// Plan + launch of a filled call: the plan's two assumptions are read off the call itself.
+static int adell_conv_run_f16(const ConvArgs& a, const ConvF16Extra& e, int N, hipStream_t st,
+                              void* ws = nullptr, size_t ws_bytes = 0, bool fused = false) {
+  ConvPlanF16 p;
+  int rc = adell_plan_f16(a, N, adell_aligned16(a.x0) && adell_aligned16(a.x1), ws != nullptr, &p);
+  if (rc != ADELL_OK) return rc;
+  return adell_conv_launch_f16(p, a, e, N, fused, ws, ws_bytes, st);
 }
 
-// Statistics partial rows per batch item that adell_conv3d_fwd_f16x3_ws writes (called with the
-// workspace adell_conv3d_splitk_workspace asks for): the fold's voxel ranges when the layer runs
-// split-K, else the bricks.
-extern "C" int adell_conv3d_fwd_ntiles_f16x3_ws(const adell_conv3d_desc* d) {
+// ---- host-only queries: geometry, then the plan under the assumptions of the launch entry each
+// answers for, written at the call (aligned tensors; with or without the split-K workspace) ----
+static int adell_plan_desc_f16(const adell_conv3d_desc* d, int backward_data, bool aligned,
+                               bool have_ws, ConvPlanF16* p) {
   ConvArgs a;
-  float dummy;
-  if (adell_fill_fwd(a, d, &dummy, &dummy, nullptr, nullptr, &dummy, nullptr) != ADELL_OK)
-    return ADELL_E_BADARG;
-  ConvTile t;
-  size_t lds;
-  if (adell_plan_f16(a, d->N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
-  if (adell_splitk_shares(a, t, d->N) > 1)
-    return adell_fold_tiles((long)a.Do * a.Ho * a.Wo, d->N, a.Cout, (long)a.ntx * a.nty * a.ntz);
-  return a.ntx * a.nty * a.ntz;
+  int rc = backward_data ? adell_geom_bwd_data(a, d) : adell_geom_fwd(a, d);
+  return rc != ADELL_OK ? rc : adell_plan_f16(a, d->N, aligned, have_ws, p);
+}
+
+// Statistics partial rows per batch item that adell_conv3d_fwd_f16x3 writes: the bricks.
+extern "C" int adell_conv3d_fwd_ntiles_f16x3(const adell_conv3d_desc* d) {
+  ConvPlanF16 p;
+  int rc = adell_plan_desc_f16(d, 0, /*aligned=*/true, /*have_ws=*/false, &p);
+  return rc != ADELL_OK ? rc : p.stat_rows;
+}
+
+// ... that adell_conv3d_fwd_f16x3_ws writes (called with the workspace adell_conv3d_splitk_workspace
+// asks for): the fold's voxel ranges when the layer runs split-K, else the bricks.
+extern "C" int adell_conv3d_fwd_ntiles_f16x3_ws(const adell_conv3d_desc* d) {
+  ConvPlanF16 p;
+  int rc = adell_plan_desc_f16(d, 0, /*aligned=*/true, /*have_ws=*/true, &p);
+  return rc != ADELL_OK ? rc : p.stat_rows;
 }
 
 extern "C" long adell_pack_weight_f16x3_bytes(int mode, int dim0, int dim1, int taps) {
@@ -802,42 +853,21 @@ extern "C" int adell_pack_weight_f16x3_multi(const long* table, int entries, lon
   return ADELL_OK;
 }
 
-extern "C" int adell_conv3d_fwd_f16x3(const adell_conv3d_desc* d, const float* x0,
-                                      const float* x1, const void* w_split,
-                                      const float* wscale, const float* bias,
-                                      const float* residual, float* y, float* stat_partials,
-                                      int partial_rows, uint32_t* in_absmax, void* stream) {
-  ConvArgs a;
-  int rc = adell_fill_fwd(a, d, x0, x1, bias, residual, y, stat_partials, partial_rows);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(w_split && wscale, "conv_fwd_f16x3: null weights");
-  ConvF16Extra e = {(const _Float16*)w_split, wscale, in_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream);
-}
-
-// Workspace that lets the forward / backward-data calls below split K on small problems
-// (0: this problem never splits).
+// Workspace that lets the forward / backward-data calls below (the _ws, _add entries) split K on
+// small problems (0: this problem never splits).
 extern "C" long adell_conv3d_splitk_workspace(const adell_conv3d_desc* d, int backward_data) {
   if (!d) return ADELL_E_BADARG;
-  ConvArgs a;
-  float dummy;
-  int rc = backward_data ? adell_fill_bwd_data(a, d, &dummy, &dummy, d->C1 > 0 ? &dummy : nullptr)
-                         : adell_fill_fwd(a, d, &dummy, d->C1 > 0 ? &dummy : nullptr, nullptr,
-                                          nullptr, &dummy, nullptr);
-  if (rc != ADELL_OK) return 0;
-  ConvTile t;
-  size_t lds;
-  if (adell_plan_f16(a, d->N, &t, &lds) != ADELL_OK) return 0;
-  const int shares = adell_splitk_shares(a, t, d->N);
-  if (shares <= 1) return 0;
-  return (long)sizeof(float) * shares * d->N * a.Do * a.Ho * a.Wo * a.Cout;
+  ConvPlanF16 p;
+  if (adell_plan_desc_f16(d, backward_data, /*aligned=*/true, /*have_ws=*/true, &p) != ADELL_OK)
+    return 0;
+  return p.shares <= 1 ? 0 : (long)sizeof(float) * p.shares * p.slab;
 }
 
 // out[8] of the plan queries below: {cfg, BM, BN, lTX, lTY, lTZ, K shares, LDS bytes}
-static void adell_plan_report(const ConvTile& t, int shares, size_t lds, int* out) {
-  out[0] = t.cfg; out[1] = t.BM; out[2] = t.BN;
-  out[3] = t.lTX; out[4] = t.lTY; out[5] = t.lTZ;
-  out[6] = shares; out[7] = (int)lds;
+static void adell_plan_report(const ConvPlanF16& p, int* out) {
+  out[0] = p.tile.cfg; out[1] = p.tile.BM; out[2] = p.tile.BN;
+  out[3] = p.tile.lTX; out[4] = p.tile.lTY; out[5] = p.tile.lTZ;
+  out[6] = p.shares; out[7] = (int)p.lds;
 }
 
 // Launch plan of adell_conv3d_fwd_f16x3_ws (backward_data = 0) / adell_conv3d_bwd_data_f16x3_ws (1)
@@ -845,17 +875,10 @@ static void adell_plan_report(const ConvTile& t, int shares, size_t lds, int* ou
 // reads no pointer.
 extern "C" int adell_conv3d_f16x3_plan(const adell_conv3d_desc* d, int backward_data, int* out) {
   ADELL_REQUIRE(d && out, "conv3d_f16x3_plan: null pointer");
-  ConvArgs a;
-  float dummy;
-  int rc = backward_data ? adell_fill_bwd_data(a, d, &dummy, &dummy, d->C1 > 0 ? &dummy : nullptr)
-                         : adell_fill_fwd(a, d, &dummy, d->C1 > 0 ? &dummy : nullptr, nullptr,
-                                          nullptr, &dummy, nullptr);
-  if (rc != ADELL_OK) return rc;
-  ConvTile t;
-  size_t lds;
-  if (adell_plan_f16(a, d->N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
-  adell_plan_report(t, adell_splitk_shares(a, t, d->N), lds, out);
-  return ADELL_OK;
+  ConvPlanF16 p;
+  int rc = adell_plan_desc_f16(d, backward_data, /*aligned=*/true, /*have_ws=*/true, &p);
+  if (rc == ADELL_OK) adell_plan_report(p, out);
+  return rc;
 }
 
 extern "C" int adell_conv3d_fwd_f16x3_ws(const adell_conv3d_desc* d, const float* x0,
@@ -869,7 +892,16 @@ extern "C" int adell_conv3d_fwd_f16x3_ws(const adell_conv3d_desc* d, const float
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(w_split && wscale, "conv_fwd_f16x3: null weights");
   ConvF16Extra e = {(const _Float16*)w_split, wscale, in_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
+  return adell_conv_run_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
+}
+
+extern "C" int adell_conv3d_fwd_f16x3(const adell_conv3d_desc* d, const float* x0,
+                                      const float* x1, const void* w_split,
+                                      const float* wscale, const float* bias,
+                                      const float* residual, float* y, float* stat_partials,
+                                      int partial_rows, uint32_t* in_absmax, void* stream) {
+  return adell_conv3d_fwd_f16x3_ws(d, x0, x1, w_split, wscale, bias, residual, y, stat_partials,
+                                   partial_rows, in_absmax, nullptr, 0, stream);
 }
 
 extern "C" int adell_conv3d_bwd_data_f16x3_ws(const adell_conv3d_desc* d, const float* dy,
@@ -882,7 +914,7 @@ extern "C" int adell_conv3d_bwd_data_f16x3_ws(const adell_conv3d_desc* d, const 
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(w_split_bwd && wscale, "conv_bwd_data_f16x3: null weights");
   ConvF16Extra e = {(const _Float16*)w_split_bwd, wscale, dy_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
+  return adell_conv_run_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
 }
 
 // The same with `add0` ([N][D][H][W][C0], one destination only) added to dx0 in the epilogue: the
@@ -900,7 +932,7 @@ extern "C" int adell_conv3d_bwd_data_f16x3_add(const adell_conv3d_desc* d, const
   ADELL_REQUIRE(d->C1 == 0, "conv_bwd_data_f16x3_add: one destination only");
   a.res = add0;
   ConvF16Extra e = {(const _Float16*)w_split_bwd, wscale, dy_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
+  return adell_conv_run_f16(a, e, d->N, (hipStream_t)stream, workspace, workspace_bytes);
 }
 
 // Backward-data whose destination(s) are gradients with respect to the OUTPUT of a fused
@@ -910,17 +942,12 @@ extern "C" int adell_conv3d_bwd_data_f16x3_add(const adell_conv3d_desc* d, const
 // site0 / site1 (either may be null: plain destination) describe the sites behind dx0 / dx1;
 // partials: [N][ntiles][C0 + C1][2] floats, ntiles = adell_conv3d_bwd_data_f16x3_adn_ntiles(d)
 // (0: this problem does not take the fused epilogue -- small / ragged / split-K launches).
+// The query answers for adell_conv3d_bwd_data_f16x3_adn on aligned tensors, planned WITH the
+// workspace: a problem that would split K in adell_conv3d_bwd_data_f16x3_ws (the call the caller
+// otherwise makes) is too small to gain from the fused epilogue and answers 0.
 extern "C" int adell_conv3d_bwd_data_f16x3_adn_ntiles(const adell_conv3d_desc* d) {
-  if (!d) return 0;
-  ConvArgs a;
-  alignas(16) static float dummy[4];   // (the plan looks at pointer alignment)
-  if (adell_fill_bwd_data(a, d, dummy, dummy, d->C1 > 0 ? dummy : nullptr) != ADELL_OK) return 0;
-  ConvF16Extra e = {};
-  // the plan of the real call (which passes the split-K workspace when there is one)
-  static float ws_probe;
-  const long wsb = adell_conv3d_splitk_workspace(d, 1);
-  return adell_conv_dispatch_f16(a, e, d->N, nullptr, wsb > 0 ? &ws_probe : nullptr,
-                                 wsb > 0 ? (size_t)wsb : 0, -1);
+  ConvPlanF16 p;
+  return adell_plan_desc_f16(d, 1, /*aligned=*/true, /*have_ws=*/true, &p) == ADELL_OK ? p.adn_rows : 0;
 }
 
 extern "C" int adell_conv3d_bwd_data_f16x3_adn(const adell_conv3d_desc* d, const float* dy,
@@ -958,7 +985,7 @@ extern "C" int adell_conv3d_bwd_data_f16x3_adn(const adell_conv3d_desc* d, const
     e.adn[k].act = s->act;
     e.adn[k].groups = (int)((V * C + 255) / 256);
   }
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream, nullptr, 0, 1);
+  return adell_conv_run_f16(a, e, d->N, (hipStream_t)stream, nullptr, 0, /*fused=*/true);
 }
 
 // Backward-data of a stride-2 conv by parity classes. dX[2i + p] (p in {0,1}^3) only receives the
@@ -1007,7 +1034,7 @@ static int adell_bwd_data_s2_classes(const adell_conv3d_desc* d, const float* dy
     a.shuffle = 8 | 7 | (add0 ? 16 : 0);         // rows on the stride-2 lattice, sub-position 0
     ConvF16Extra e = {(const _Float16*)w_split[c], wscale[c], c == 0 ? dy_absmax : nullptr,
                       nullptr, nullptr, nullptr};
-    rc = adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream);
+    rc = adell_conv_run_f16(a, e, d->N, (hipStream_t)stream);
     if (rc != ADELL_OK) return rc;
   }
   return ADELL_OK;
@@ -1034,81 +1061,54 @@ extern "C" int adell_conv3d_bwd_data_s2_f16x3_add(const adell_conv3d_desc* d, co
 // VIRTUAL 1x1x1 conv weight V[(f, co)][ci] = w[ci][co][f] packed with mode 0 (wscale has
 // F*Cout entries); backward-data: the torch weight [Cin][Cout][taps] read as a conv weight with
 // Cin outputs and Cout inputs, packed with mode 0 as well.
-static int adell_fill_convt_fwd(ConvArgs& a, int N, int D, int H, int W, int Cin, int Cout, int FD,
-                                int FH, int FW) {
-  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "convT_fwd: bad dims");
-  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_fwd: kernel=stride must be 1 or 2 per dim");
-  a = ConvArgs{};
-  a.D = D; a.H = H; a.W = W;
-  a.C0 = Cin; a.C1 = 0; a.Cin = Cin; a.Cout = FD * FH * FW * Cout;
-  a.KD = a.KH = a.KW = 1;
-  a.SD = a.SH = a.SW = 1;
-  a.UPS = a.UPSY = a.UPSZ = 1;
-  a.Do = D; a.Ho = H; a.Wo = W;
-  a.ysplit = a.Cout; a.Cs = Cout;
-  a.shuffle = 8 | (FW - 1) | ((FH - 1) << 1) | ((FD - 1) << 2);
-  return ADELL_OK;
-}
-
 extern "C" int adell_convtranspose3d_fwd_f16x3(int N, int D, int H, int W, int Cin, int Cout,
                                                int FD, int FH, int FW, const float* x,
                                                const void* w_split, const float* wscale,
                                                const float* bias, float* y, uint32_t* in_absmax,
                                                void* stream) {
   ConvArgs a;
-  int rc = adell_fill_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  int rc = adell_geom_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
   if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(x && w_split && wscale && y, "convT_fwd_f16x3: null pointer");
   a.x0 = x; a.bias = bias; a.y0 = y;
   ConvF16Extra e = {(const _Float16*)w_split, wscale, in_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, N, (hipStream_t)stream);
+  return adell_conv_run_f16(a, e, N, (hipStream_t)stream);
 }
 
 // Launch plan of adell_convtranspose3d_fwd_f16x3 (out[8] as adell_conv3d_f16x3_plan; host only).
-// Its backward-data is the kernel = stride conv of adell_conv3d_f16x3_plan.
+// The K shares are reported as if a workspace were given, although that launch passes none (a
+// scatter store never splits, so both are 1). Its backward-data is the kernel = stride conv of
+// adell_conv3d_f16x3_plan.
 extern "C" int adell_convtranspose3d_f16x3_plan(int N, int D, int H, int W, int Cin, int Cout,
                                                 int FD, int FH, int FW, int* out) {
   ADELL_REQUIRE(out, "convtranspose3d_f16x3_plan: null pointer");
   ConvArgs a;
-  int rc = adell_fill_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
-  if (rc != ADELL_OK) return rc;
-  ConvTile t;
-  size_t lds;
-  if (adell_plan_f16(a, N, &t, &lds) != ADELL_OK) return ADELL_E_UNSUPPORTED;
-  adell_plan_report(t, adell_splitk_shares(a, t, N), lds, out);
-  return ADELL_OK;
+  ConvPlanF16 p;
+  int rc = adell_geom_convt_fwd(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc == ADELL_OK) rc = adell_plan_f16(a, N, /*aligned=*/true, /*have_ws=*/true, &p);
+  if (rc == ADELL_OK) adell_plan_report(p, out);
+  return rc;
 }
 
 extern "C" int adell_convtranspose3d_bwd_data_f16x3(int N, int D, int H, int W, int Cin, int Cout,
                                                     int FD, int FH, int FW, const float* dy,
                                                     const void* w_split_bwd, const float* wscale,
                                                     float* dx, uint32_t* dy_absmax, void* stream) {
-  ADELL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
-                "convT_bwd_data: bad dims");
-  ADELL_REQUIRE(adell_convt_factors_ok(FD, FH, FW), "convT_bwd_data: bad factors");
+  ConvArgs a;
+  int rc = adell_geom_convt_bwd_data(a, N, D, H, W, Cin, Cout, FD, FH, FW);
+  if (rc != ADELL_OK) return rc;
   ADELL_REQUIRE(dy && w_split_bwd && wscale && dx, "convT_bwd_data_f16x3: null pointer");
-  ConvArgs a = {};
   a.x0 = dy; a.y0 = dx;
-  a.D = FD * D; a.H = FH * H; a.W = FW * W;
-  a.C0 = Cout; a.C1 = 0; a.Cin = Cout; a.Cout = Cin;
-  a.KD = a.SD = FD; a.KH = a.SH = FH; a.KW = a.SW = FW;
-  a.UPS = a.UPSY = a.UPSZ = 1;
-  a.Do = D; a.Ho = H; a.Wo = W;
-  a.ysplit = a.Cout; a.shuffle = 0; a.Cs = a.Cout;
   ConvF16Extra e = {(const _Float16*)w_split_bwd, wscale, dy_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, N, (hipStream_t)stream);
+  return adell_conv_run_f16(a, e, N, (hipStream_t)stream);
 }
 
 extern "C" int adell_conv3d_bwd_data_f16x3(const adell_conv3d_desc* d, const float* dy,
                                            const void* w_split_bwd, const float* wscale,
                                            float* dx0, float* dx1, uint32_t* dy_absmax,
                                            void* stream) {
-  ConvArgs a;
-  int rc = adell_fill_bwd_data(a, d, dy, dx0, dx1);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(w_split_bwd && wscale, "conv_bwd_data_f16x3: null weights");
-  ConvF16Extra e = {(const _Float16*)w_split_bwd, wscale, dy_absmax, nullptr, nullptr, nullptr};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream);
+  return adell_conv3d_bwd_data_f16x3_ws(d, dy, w_split_bwd, wscale, dx0, dx1, dy_absmax, nullptr, 0,
+                                        stream);
 }
 
 
@@ -1119,19 +1119,12 @@ extern "C" int adell_conv3d_bwd_data_f16x3(const adell_conv3d_desc* d, const flo
 // xk[N][C / 16]; null: fp32 as in adell_conv3d_fwd_f16x3. _rows_ok: 1 when the forward plan of
 // `d` stages rows (the specialised instances; never split-K).
 // ---------------------------------------------------------------------------
+// (answers for adell_conv3d_fwd_f16x3_rows on aligned tensors; planned WITH the workspace: a layer
+// that would split K in adell_conv3d_fwd_f16x3_ws, which the caller would otherwise use, is too
+// small to gain from rows and answers 0)
 extern "C" int adell_conv3d_f16x3_rows_ok(const adell_conv3d_desc* d) {
-  ConvArgs a;
-  alignas(16) static float dummy[4];
-  if (adell_fill_fwd(a, d, dummy, d && d->C1 > 0 ? dummy : nullptr, nullptr, nullptr, dummy,
-                     nullptr) != ADELL_OK)
-    return 0;
-  ConvF16Extra e = {};
-  // (the plan of adell_conv3d_fwd_f16x3_ws, which the caller would otherwise use: a layer that
-  // runs split-K there is too small to gain from rows)
-  static float ws_probe;
-  const long wsb = adell_conv3d_splitk_workspace(d, 0);
-  return adell_conv_dispatch_f16(a, e, d->N, nullptr, wsb > 0 ? &ws_probe : nullptr,
-                                 wsb > 0 ? (size_t)wsb : 0, -2);
+  ConvPlanF16 p;
+  return adell_plan_desc_f16(d, 0, /*aligned=*/true, /*have_ws=*/true, &p) == ADELL_OK ? p.rows_ok : 0;
 }
 
 extern "C" int adell_conv3d_fwd_f16x3_rows(const adell_conv3d_desc* d, const void* x0,
@@ -1149,5 +1142,5 @@ extern "C" int adell_conv3d_fwd_f16x3_rows(const adell_conv3d_desc* d, const voi
   ADELL_REQUIRE(!xk1 || x1, "conv_fwd_f16x3_rows: xk1 without x1");
   ConvF16Extra e = {(const _Float16*)w_split, wscale, in_absmax,
                     xk0 ? (const char*)x0 : nullptr, xk1 ? (const char*)x1 : nullptr, xk0, xk1};
-  return adell_conv_dispatch_f16(a, e, d->N, (hipStream_t)stream);
+  return adell_conv_run_f16(a, e, d->N, (hipStream_t)stream);
 }

@@ -32,10 +32,21 @@ def _site(cuda, g, n, c, size, act, p, seed):
     return _Site(y, mean, rstd, mask, p, act, 0.2 if act == "leaky_relu" else 0.0), out
 
 
-@pytest.mark.parametrize("n,c0,c1,cout,size", [(2, 32, 0, 32, (16, 16, 16)),     # 8x8x8 bricks
-                                               (2, 32, 0, 48, (32, 32, 32)),     # 8x8x4 bricks
-                                               (1, 64, 0, 32, (64, 64, 32)),     # 64-column tile
-                                               (1, 32, 32, 64, (32, 64, 64))])   # two destinations
+# n, c0, c1, cout, size, cfg: the backward-data plan's config (ops.conv3d_plan; the GEMM's columns are
+# the c0 + c1 destination channels). One case at least per EPI = 1 instance of the kernel: cfg 0, 1, 4.
+FUSED_CASES = [
+    (2, 32, 0, 32, (16, 16, 16), 1),     # 8x8x4 bricks, 32 columns: below the 8x8x8 bricks' 262 144 voxels
+    (2, 32, 0, 48, (32, 32, 32), 1),     # 8x8x4 bricks, 48 forward outputs = 3 K chunks
+    (1, 64, 0, 32, (64, 64, 32), 1),     # 64 columns as two 32-column tiles
+    (1, 32, 32, 64, (32, 64, 64), 1),    # two destinations, one 32-column tile each
+    (1, 128, 0, 32, (32, 32, 32), 0),    # 64-column tiles
+    (1, 64, 64, 32, (32, 32, 32), 0),    # 64-column tiles, two destinations
+    (2, 32, 0, 32, (32, 64, 64), 4),     # 8x8x8 bricks
+]
+_FUSED_CFG = {c[:5]: c[5] for c in FUSED_CASES}
+
+
+@pytest.mark.parametrize("n,c0,c1,cout,size", [c[:5] for c in FUSED_CASES])
 @pytest.mark.parametrize("act,p", [("swish", 0.15), ("relu", 0.0), ("leaky_relu", 0.3),
                                    ("identity", 0.5)])
 def test_fused_epilogue_equals_the_two_pass_backward(cuda, n, c0, c1, cout, size, act, p):
@@ -44,6 +55,8 @@ def test_fused_epilogue_equals_the_two_pass_backward(cuda, n, c0, c1, cout, size
 
     g = torch.Generator().manual_seed(c0 + 3 * c1 + cout)
     k, st, pad = (3, 3, 3), (1, 1, 1), (1, 1, 1)
+    plan = ops.conv3d_plan(n, size, c0, c1, cout, k, st, pad, backward_data=True)
+    assert plan.cfg == _FUSED_CFG[(n, c0, c1, cout, size)] and plan.shares == 1, plan
     nt = ops.conv3d_bwd_data_adn_ntiles(size, n, c0, c1, cout, k, st, pad)
     assert nt > 0, "this shape must take the fused epilogue"
     w = (torch.randn(cout, c0 + c1, 3, 3, 3, generator=g) * 0.05).to(cuda)

@@ -4,7 +4,8 @@ the z-ring weight gradient, from one case table:
 - on the build host (no GPU), each case still gets the plan it is in the table for
   (ops.conv3d_plan / ops.convtranspose3d_plan / adell_wgrad_zring_plan), and every branch of the
   planner has at least one case. A retune that moves a shape onto another branch fails here, naming
-  the branch, so the table is updated on purpose instead of the branch losing its coverage;
+  the branch, so the table is updated on purpose instead of the branch losing its coverage (such a
+  retune also regenerates the dense record of tests/test_conv_plan_sweep.py: tools/conv_plan_sweep.py);
 - on the GPU, each case runs through functional.conv3d / conv_transpose3d (forward with its
   statistics partials, backward-data for both concat sources, dW, db) against torch's fp64
   convolution on the CPU; split-K launches must also be bit-identical across two calls (the fold

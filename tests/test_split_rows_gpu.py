@@ -51,15 +51,25 @@ def test_fused_producer_writes_the_rows_of_the_fp32_output(cuda, act, p, C, size
         assert torch.equal(mask, mask_ref)
 
 
-CASES = [  # N, C0, C1, Cout, size
-    (2, 32, 0, 32, (16, 16, 16)),      # 8x8x4 bricks
-    (2, 32, 0, 32, (64, 64, 64)),      # 8x8x8 bricks
-    (1, 64, 0, 32, (76, 44, 68)),      # ragged bricks, four chunks
-    (2, 64, 0, 64, (32, 32, 32)),      # 64-column tile
-    (1, 32, 32, 64, (48, 48, 44)),     # virtual concat, ragged in z
-    (2, 16, 0, 16, (32, 32, 32)),      # one chunk, half-empty column tile
-    (1, 32, 0, 16, (24, 24, 24)),      # 16 x 16 weight-gradient tiles over a two-chunk rows source
+# N, C0, C1, Cout, size, cfg: the forward plan's config (ops.conv3d_plan). The forward test runs every
+# rows instance of the kernel: all sources rows ("both", or one source) and mixed ("first" /
+# "second") on cfg 0, 1 and 4, and the 16-column z-ring (cfg 8).
+CASES = [
+    (2, 32, 0, 32, (16, 16, 16), 1),      # 8x8x4 bricks
+    (2, 32, 0, 32, (64, 64, 64), 4),      # 8x8x8 bricks
+    (1, 64, 0, 32, (76, 44, 68), 1),      # ragged bricks, four chunks
+    (2, 64, 0, 64, (32, 32, 32), 1),      # 64 outputs as two 32-column tiles
+    (1, 32, 32, 64, (48, 48, 44), 1),     # virtual concat, ragged in z
+    (2, 16, 0, 16, (32, 32, 32), 8),      # one chunk, the 16-column z-ring kernel
+    (1, 32, 0, 16, (24, 24, 24), 1),      # 16 x 16 weight-gradient tiles over a two-chunk rows source
 ]
+# forward only (the weight gradient does not go through these instances)
+FORWARD_CASES = CASES + [
+    (1, 32, 0, 128, (32, 32, 32), 0),     # 64-column tiles, all rows
+    (1, 32, 16, 128, (32, 32, 32), 0),    # 64-column tiles, virtual concat: mixed
+    (2, 16, 16, 32, (32, 64, 64), 4),     # 8x8x8 bricks, virtual concat: mixed
+]
+_CFG = {c[:5]: c[5] for c in FORWARD_CASES}
 
 
 def _operands(cuda, N, C0, C1, Cout, size, seed):
@@ -73,15 +83,16 @@ def _operands(cuda, N, C0, C1, Cout, size, seed):
     return x0, x1, w, b
 
 
-@pytest.mark.parametrize("N,C0,C1,Cout,size", CASES)
+@pytest.mark.parametrize("N,C0,C1,Cout,size", [c[:5] for c in FORWARD_CASES])
 @pytest.mark.parametrize("which", ["both", "first", "second"])
 def test_forward_on_rows_equals_forward_on_the_values_they_hold(cuda, N, C0, C1, Cout, size, which):
     from adell_mri_amd import ops
 
     if C1 == 0 and which != "both":
         pytest.skip("one source")
-    if not ops.conv3d_rows_ok(N, size, C0, C1, Cout, 3, 1, 1):
-        pytest.skip("this shape's launch plan does not stage rows")
+    plan = ops.conv3d_plan(N, size, C0, C1, Cout, 3, 1, 1)
+    assert plan.cfg == _CFG[(N, C0, C1, Cout, size)] and plan.shares == 1, plan
+    assert ops.conv3d_rows_ok(N, size, C0, C1, Cout, 3, 1, 1), "this shape's plan must stage rows"
     x0, x1, w, b = _operands(cuda, N, C0, C1, Cout, size, 3)
     wp = ops.pack_weight_f16x3(w, 0)
     r0, s0 = ops.rows_from_f32(x0, 9)
@@ -102,7 +113,7 @@ def test_forward_on_rows_equals_forward_on_the_values_they_hold(cuda, N, C0, C1,
     assert _rel(part, part_ref) <= 2e-5
 
 
-@pytest.mark.parametrize("N,C0,C1,Cout,size", CASES)
+@pytest.mark.parametrize("N,C0,C1,Cout,size", [c[:5] for c in CASES])
 def test_weight_gradient_on_rows(cuda, N, C0, C1, Cout, size):
     from adell_mri_amd import ops
 
