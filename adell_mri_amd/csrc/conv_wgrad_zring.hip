@@ -7,10 +7,12 @@
 // natural [voxel][32 channels] fp16 hi / lo planes). What is different is the work decomposition:
 // a block owns ONE 32 x 32 channel tile and ALL 27 taps, and walks a column of 8 x 8 x 1 output
 // bricks along z. LDS keeps a ring of 10 x 10 input planes (three live, a fourth being written), so each step converts and
-// stores ONE new input plane (100 rows) and ONE dY plane (64 rows) and then runs 27 taps x 4
-// k-steps x 3 MFMAs on them -- three times the MFMA work per staged byte of the per-kz-plane
-// kernel, whose staging (fp32 -> fp16 hi/lo conversion on the vector ALU) bounds it.
-// Wave w owns taps w, w+4, w+8, ... (7 accumulators of 16 registers), every k-step.
+// stores ONE new input plane (100 rows) and ONE dY plane (64 rows) and then runs 27 taps x 2
+// k-steps of 32 voxels x 2 x 2 sub-tiles of 16 x 16 channels x 3 MFMAs (v_mfma_f32_16x16x32_f16)
+// on them -- three times the MFMA work per staged byte of the per-kz-plane kernel, whose staging
+// (fp32 -> fp16 hi/lo conversion on the vector ALU) bounds it. The chip holds a higher clock on
+// this MFMA shape than on 32x32x16 at the same cycles per product (docs/LABBOOK.md, z-ring 16x16x32).
+// Wave w owns taps w, w+4, w+8, ... (7 x 4 accumulators of 4 registers), every k-step.
 // Work units are (column, z segment) pairs dealt round-robin to the blocks; every block writes
 // one partial slab, folded in fixed order by adell_wgrad_reduce_kernel (deterministic).
 #include "common.h"
@@ -22,7 +24,7 @@ typedef __fp16 zr_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 __device__ __forceinline__ zr_half8 adell_zr_frag(const char* p) {
   typedef __attribute__((address_space(3))) zr_fp16x4* lds_p;
   const zr_fp16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_p)(p));
-  const zr_fp16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_p)(p + 4 * 64));
+  const zr_fp16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_p)(p + 4 * 32));
   zr_half8 r;
   r[0] = (_Float16)lo4[0]; r[1] = (_Float16)lo4[1]; r[2] = (_Float16)lo4[2]; r[3] = (_Float16)lo4[3];
   r[4] = (_Float16)hi4[0]; r[5] = (_Float16)hi4[1]; r[6] = (_Float16)hi4[2]; r[7] = (_Float16)hi4[3];
@@ -93,7 +95,20 @@ __device__ __forceinline__ float4 adell_zr_gload4(const ADELL_GLOBAL char* p) {
 }
 
 constexpr int ZR_HX = 10, ZR_HV = 100;      // halo plane of an 8 x 8 brick
-constexpr int ZR_PLANE = ZR_HV * 64;        // bytes of one fp16 plane of 32 channels
+// LDS images hold 16 channels of one plane (32-byte rows), hi and lo halves and the two channel
+// halves of the tile as images of their own, input and dY images alike with 10 rows = 320 B per y.
+// A transposed read's 16-lane group takes 4 rows = 128 contiguous bytes of one brick row. The two
+// groups of a 32-lane half must sit 128 B (mod 256) apart: consecutive brick rows would need a y
+// pitch of 384 B (the 16 x 16 form's pitch 12: 84 KB here, one block per CU). Instead the four
+// k-blocks of a k-step are dealt to the lane groups as brick rows 0, 2, 1, 3, so a half reads rows
+// y and y + 2: 640 B = 128 (mod 256) at the natural pitch. (+ 64 B per image: the staging stores of
+// a 16-lane group go to both channel halves, which then fall into different banks.) 71.5 KB, two
+// blocks per CU.
+constexpr int ZR_YP = 10 * 32;              // bytes per y of an image
+constexpr int ZR_XIMG = ZR_HV * 32 + 64;    // bytes of one input image
+constexpr int ZR_YIMG = 8 * ZR_YP + 64;     // bytes of one dY image
+constexpr int ZR_PLANE = 4 * ZR_XIMG;       // a ring slot: [hi | lo][channel half]
+constexpr int ZR_YBUF = 4 * ZR_YIMG;        // a dY buffer: [hi | lo][channel half]
 constexpr int ZR_NX = 4, ZR_NY = 2;         // 16-byte loads per thread: 100 x 8 and 64 x 8 slots
 constexpr int ZR_MAXJ = 7;                  // taps per wave
 // Ring of FOUR plane slots and two dY buffers: step z reads slots z..z+2 (mod 4) and dY buffer
@@ -103,12 +118,11 @@ constexpr int ZR_SLOTS = 4;
 
 __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrArgs a) {
   extern __shared__ float smem[];
-  char* sXh = reinterpret_cast<char*>(smem);          // [4 ring slots][100][32 halfs]
-  char* sXl = sXh + ZR_SLOTS * ZR_PLANE;
-  char* sYh = sXl + ZR_SLOTS * ZR_PLANE;              // [2 steps][64][32 halfs]
-  char* sYl = sYh + 2 * 64 * 64;
+  char* sXh = reinterpret_cast<char*>(smem);          // [4 ring slots][hi | lo][2 halves] images
+  char* sXl = sXh + 2 * ZR_XIMG;
+  char* sYh = sXh + ZR_SLOTS * ZR_PLANE;              // [2 steps][hi | lo][2 halves] images
+  char* sYl = sYh + 2 * ZR_YIMG;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
   // consecutive blocks go round-robin to the 8 XCDs (one L2 each): an XCD takes a contiguous eighth
   // of the regions, i.e. neighbouring columns, whose 10 x 10 input halos then meet in one L2 (the
   // blocks of one region over the channel tiles share an XCD already: R is a multiple of 8)
@@ -134,12 +148,13 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
   const float* xsrc = first ? a.x0 + ci0 : a.x1 + (ci0 - a.C0);
   const unsigned xcs = first ? a.C0 : a.C1;
 
-  // transposed-read lane roles (conv_wgrad_f16.hip): lane 4q+p of a 16-lane group addresses
-  // voxel row q, channels 4p..4p+3 of channel half cg; the two lane halves take two brick rows
-  const int cg = (lane >> 4) & 1, tq = (lane >> 2) & 3, tp = lane & 3;
-  const int colb = (16 * cg + 4 * tp) * 2;
-  const int abase = (lh * ZR_HX + tq) * 64 + colb;   // + tap offset + k-step * 2 rows
-  const int bbase = (lh * 8 + tq) * 64 + colb;       // + k-step * 16 rows
+  // transposed-read lane roles: lane 4q + p of 16-lane group g addresses voxel q of brick row g,
+  // channels 4p .. 4p + 3 of a 16-channel image; after the transpose lane j of the group holds
+  // channel j, 4 voxels. A k-step of v_mfma_f32_16x16x32_f16 is 32 voxels = FOUR brick rows (g is
+  // the k-block), two k-steps per 8 x 8 plane.
+  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+  const int gy = ((g & 1) << 1) | (g >> 1);          // brick row of k-block g: 0, 2, 1, 3
+  const int bbase = gy * ZR_YP + tq * 32 + tp * 8;   // + tap offset + k-step * 4 brick rows
   int tapoff[ZR_MAXJ], tapkz[ZR_MAXJ];
   bool jok[ZR_MAXJ];
 #pragma unroll
@@ -149,13 +164,15 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
     if (!jok[q]) t = 0;
     const int kz = t / 9, ky = (t - 9 * kz) / 3, kx = t - 9 * kz - 3 * ky;
     tapkz[q] = kz;
-    tapoff[q] = abase + (ky * ZR_HX + kx) * 64;
+    tapoff[q] = bbase + ky * ZR_YP + kx * 32;
   }
-  f32x16 acc[ZR_MAXJ];
+  f32x4 acc[ZR_MAXJ][2][2];   // [tap][input-channel half][output-channel half]
 #pragma unroll
   for (int q = 0; q < ZR_MAXJ; ++q)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    for (int r = 0; r < 4; ++r) {
+      acc[q][0][0][r] = 0.f; acc[q][0][1][r] = 0.f; acc[q][1][0][r] = 0.f; acc[q][1][1][r] = 0.f;
+    }
 
   // staging slots of this thread: 16-byte piece c4 = tid & 7 of rows tid / 8 + 32 u
   const int c4 = tid & 7, row0 = tid >> 3;
@@ -166,6 +183,18 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
   const bool yvalid = co0 + 4 * c4 < a.Cout;
   const bool do_db = a.wsdb != nullptr && cit == 0;
   float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
+  // LDS offsets of this thread's pieces: image of channel half c4 >> 2, 8 bytes per 4 channels. A
+  // split-row piece (16 bytes) is chunk c4 >> 2, pieces 0, 1 = hi halves (channels 0-7, 8-15 of the
+  // chunk), 2, 3 = lo halves.
+  const unsigned xpiece = xrows ? (unsigned)((c4 >> 2) * ZR_XIMG + (c4 & 2) * ZR_XIMG + (c4 & 1) * 16)
+                                : (unsigned)((c4 >> 2) * ZR_XIMG + (c4 & 3) * 8);
+  unsigned xlds[ZR_NX];
+#pragma unroll
+  for (int u = 0; u < ZR_NX; ++u) {
+    const int hv = row0 + 32 * u;
+    xlds[u] = xpiece + (unsigned)(hv * 32);
+  }
+  const unsigned ylds = (unsigned)((row0 >> 3) * ZR_YP + (row0 & 7) * 32 + (c4 >> 2) * ZR_YIMG + (c4 & 3) * 8);
 
   const int ncols = a.N * a.ntx * a.nty;
   const long nunits = (long)ncols * a.nseg;
@@ -230,15 +259,11 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
     };
     auto store_x = [&](int slot) {
       if (xrows) {
-        // piece c4 of the tile's 128 bytes: chunk c4 >> 2, pieces 0, 1 = hi halves (channels 0-7,
-        // 8-15 of the chunk), 2, 3 = lo halves
-        char* plane = (c4 & 2) ? sXl : sXh;
-        const unsigned po = (unsigned)((c4 >> 2) * 32 + (c4 & 1) * 16);
 #pragma unroll
         for (int u = 0; u < ZR_NX; ++u) {
           const int hv = row0 + 32 * u;
           if (hv < ZR_HV)
-            *reinterpret_cast<float4*>(plane + slot * ZR_PLANE + hv * 64 + po) = xr[u];
+            *reinterpret_cast<float4*>(sXh + slot * ZR_PLANE + xlds[u]) = xr[u];
         }
         return;
       }
@@ -246,15 +271,15 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
       for (int u = 0; u < ZR_NX; ++u) {
         const int hv = row0 + 32 * u;
         if (hv < ZR_HV)
-          adell_zr_split_store(sXh, sXl, (unsigned)(slot * ZR_PLANE + hv * 64 + c4 * 8), xr[u], sX);
+          adell_zr_split_store(sXh, sXl, (unsigned)(slot * ZR_PLANE) + xlds[u], xr[u], sX);
       }
     };
     auto store_y = [&](int buf) {
 #pragma unroll
       for (int u = 0; u < ZR_NY; ++u) {
-        const int v = row0 + 32 * u;
         dbacc.x += yr[u].x; dbacc.y += yr[u].y; dbacc.z += yr[u].z; dbacc.w += yr[u].w;
-        adell_zr_split_store(sYh, sYl, (unsigned)(buf * 64 * 64 + v * 64 + c4 * 8), yr[u], sY);
+        // (rows row0 + 32 u: four brick rows on)
+        adell_zr_split_store(sYh, sYl, (unsigned)(buf * ZR_YBUF + u * 4 * ZR_YP) + ylds, yr[u], sY);
       }
     };
     // prime the ring: planes of taps kz = 0, 1 of the first step. Plane p = z - PD + kz sits in
@@ -280,45 +305,57 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
       int slotoff[3];   // byte offset of the ring slot holding tap plane kz
 #pragma unroll
       for (int kz = 0; kz < 3; ++kz) slotoff[kz] = ((z + kz) & 3) * ZR_PLANE;
-      const int ybuf = (z & 1) * 64 * 64;
-      // 4 k-steps of 16 voxels (two brick rows) x 7 taps, flattened and software-pipelined: the
-      // fragments of job i+1 are read while the 3 MFMAs of job i run (two register sets)
+      const int ybuf = (z & 1) * ZR_YBUF;
       int tslot[ZR_MAXJ];
 #pragma unroll
       for (int q = 0; q < ZR_MAXJ; ++q)
         tslot[q] = tapoff[q] + (tapkz[q] == 0 ? slotoff[0] : (tapkz[q] == 1 ? slotoff[1] : slotoff[2]));
-      zr_half8 ah[2], al[2], bh[2], bl[2];
       if (ADELL_DBG(a.dbg) & 4) continue;
-      bh[0] = adell_zr_frag(sYh + ybuf + bbase);
-      bl[0] = adell_zr_frag(sYl + ybuf + bbase);
+      // 2 k-steps of 32 voxels x 7 taps; a job (k-step, tap) is 2 x 2 sub-tiles of 16 x 16, three
+      // products each. Flattened into half jobs (one input-channel half against both output halves,
+      // 6 MFMAs) and software-pipelined: the input fragments of half job h + 1 are read while the
+      // MFMAs of half job h run, into the registers half job h - 1 used; the dY fragments of the
+      // second k-step are read under the last job of the first.
+      zr_half8 ah[2], al[2], bh[2][2], bl[2][2];   // [input half] / [k-step][output half]
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        bh[0][ni] = adell_zr_frag(sYh + ybuf + bbase + ni * ZR_YIMG);
+        bl[0][ni] = adell_zr_frag(sYl + ybuf + bbase + ni * ZR_YIMG);
+      }
       ah[0] = adell_zr_frag(sXh + tslot[0]);
       al[0] = adell_zr_frag(sXl + tslot[0]);
 #pragma unroll
-      for (int i = 0; i < 4 * ZR_MAXJ; ++i) {
+      for (int h = 0; h < 4 * ZR_MAXJ; ++h) {
+        const int i = h >> 1, mi = h & 1;
         const int s = i / ZR_MAXJ, q = i - s * ZR_MAXJ;
-        const int cur = i & 1, nxt = cur ^ 1;
-        const bool more = i + 1 < 4 * ZR_MAXJ;
-        const bool newb = more && q + 1 == ZR_MAXJ;
+        const bool more = h + 1 < 4 * ZR_MAXJ;
+        const bool newb = s == 0 && q + 1 == ZR_MAXJ;   // the last job of the first k-step
         if (more) {
-          const int s2 = (i + 1) / ZR_MAXJ, q2 = (i + 1) - s2 * ZR_MAXJ;
-          if (newb) {
-            bh[s2 & 1] = adell_zr_frag(sYh + ybuf + bbase + s2 * 16 * 64);
-            bl[s2 & 1] = adell_zr_frag(sYl + ybuf + bbase + s2 * 16 * 64);
-          }
-          ah[nxt] = adell_zr_frag(sXh + tslot[q2] + s2 * 2 * ZR_HX * 64);
-          al[nxt] = adell_zr_frag(sXl + tslot[q2] + s2 * 2 * ZR_HX * 64);
+          const int i2 = (h + 1) >> 1, m2 = (h + 1) & 1;
+          const int s2 = i2 / ZR_MAXJ, q2 = i2 - s2 * ZR_MAXJ;
+          ah[m2] = adell_zr_frag(sXh + tslot[q2] + s2 * 4 * ZR_YP + m2 * ZR_XIMG);
+          al[m2] = adell_zr_frag(sXl + tslot[q2] + s2 * 4 * ZR_YP + m2 * ZR_XIMG);
         }
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cur], bh[s & 1], acc[q], 0, 0, 0);
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bl[s & 1], acc[q], 0, 0, 0);
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bh[s & 1], acc[q], 0, 0, 0);
-        if (more) {  // pin: the next job's LDS reads go between this job's MFMAs
+        if (newb) {
+          bh[1][mi] = adell_zr_frag(sYh + ybuf + bbase + 4 * ZR_YP + mi * ZR_YIMG);
+          bl[1][mi] = adell_zr_frag(sYl + ybuf + bbase + 4 * ZR_YP + mi * ZR_YIMG);
+        }
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+          acc[q][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[mi], bh[s][ni], acc[q][mi][ni], 0, 0, 0);
+          acc[q][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mi], bl[s][ni], acc[q][mi][ni], 0, 0, 0);
+          acc[q][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mi], bh[s][ni], acc[q][mi][ni], 0, 0, 0);
+        }
+        if (more) {  // pin: the next half job's LDS reads go between this one's MFMAs
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (newb) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (newb) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (newb) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (newb) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         }
       }
     }
@@ -341,32 +378,33 @@ __global__ __launch_bounds__(256, 2) void adell_conv_wgrad_zring_kernel(WgradZrA
       }
     }
   }
-  // ---- partial slab (undo the operand scales) --------------------------------
+  // ---- partial slab (undo the operand scales): C[row = ci 4 g + r][col = co lane & 15] per sub-tile
   const float unscale = __int_as_float((127 - kX - kY) << 23);
-  const int co = co0 + li;
 #pragma unroll
   for (int q = 0; q < ZR_MAXJ; ++q) {
     const int tap = wave + 4 * q;
-    const int cib = ci0 + 4 * lh;
-    float* base = a.ws + (((size_t)region * 27 + tap) * a.Cin + cib) * a.Cout + co;
-    if (jok[q] && co < a.Cout) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2);
-        if (cib + row < a.Cin) base[(size_t)row * a.Cout] = acc[q][r] * unscale;
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        const int cib = ci0 + 16 * mi + 4 * g, co = co0 + 16 * ni + (lane & 15);
+        float* base = a.ws + (((size_t)region * 27 + tap) * a.Cin + cib) * a.Cout + co;
+        if (jok[q] && cib < a.Cin && co < a.Cout) {   // (channel counts are whole 16s)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) base[(size_t)r * a.Cout] = acc[q][mi][ni][r] * unscale;
+        }
       }
-    }
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// 16 x 16 channel tiles on v_mfma_f32_16x16x32_f16 (layers with 16 input or 16 output channels: the
-// full-resolution levels of UNETR). On the 32 x 32 tile above such a layer fills a quarter (16 -> 16)
-// or half (32 -> 16) of every MFMA: 54 / 75 TF algorithmic at 4 x 96^3. Same march, same ring, same
-// slabs; what changes:
-//  * a k-step is 32 voxels = FOUR brick rows (lane group g = lane >> 4 is the k-block = brick row
-//    4 s + g; lane & 15 the channel), two k-steps per 8 x 8 plane, 27 taps over the four waves;
+// 16 x 16 channel tiles (layers with 16 input or 16 output channels: the full-resolution levels of
+// UNETR). On the 32 x 32 tile above such a layer computes a quarter (16 -> 16) or half (32 -> 16) of
+// its sub-tiles for nothing: 54 / 75 TF algorithmic at 4 x 96^3. Same march, same ring, same slabs,
+// same MFMA and k-step (lane group g = lane >> 4 is the k-block, here brick row 4 s + g; lane & 15
+// the channel); what changes:
+//  * one sub-tile per tap, 27 taps over the four waves;
 //  * plane images hold 16 channels (32-byte rows) with a row pitch of 12 voxels for X and dY alike:
 //    the two 16-lane groups of a transposed read's 32-lane half are then 384 B = 128 B (mod 256)
 //    apart -- disjoint bank halves for every tap offset;
@@ -376,16 +414,6 @@ constexpr int Z16_HXP = 12;
 constexpr int Z16_XPLANE = 10 * Z16_HXP * 32;   // bytes of one fp16 plane (hi or lo), 16 channels
 constexpr int Z16_YPLANE = 8 * Z16_HXP * 32;
 constexpr int Z16_PF = 4;                       // steps of register prefetch
-
-__device__ __forceinline__ zr_half8 adell_z16_frag(const char* p) {
-  typedef __attribute__((address_space(3))) zr_fp16x4* lds_p;
-  const zr_fp16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_p)(p));
-  const zr_fp16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_p)(p + 4 * 32));
-  zr_half8 r;
-  r[0] = (_Float16)lo4[0]; r[1] = (_Float16)lo4[1]; r[2] = (_Float16)lo4[2]; r[3] = (_Float16)lo4[3];
-  r[4] = (_Float16)hi4[0]; r[5] = (_Float16)hi4[1]; r[6] = (_Float16)hi4[2]; r[7] = (_Float16)hi4[3];
-  return r;
-}
 
 __device__ __forceinline__ void adell_z16_split_store(char* hi_plane, char* lo_plane, unsigned off,
                                                       float4 f, float scale) {
@@ -551,10 +579,10 @@ __global__ __launch_bounds__(256, 3) void adell_conv_wgrad_zring16_kernel(WgradZ
         tslot[q] = tapoff[q] + (tapkz[q] == 0 ? slotoff[0] : (tapkz[q] == 1 ? slotoff[1] : slotoff[2]));
       // 2 k-steps of 32 voxels (four brick rows) x 7 taps, flattened and software-pipelined
       zr_half8 ah[2], al[2], bh[2], bl[2];
-      bh[0] = adell_z16_frag(sYh + ybuf + fbase);
-      bl[0] = adell_z16_frag(sYl + ybuf + fbase);
-      ah[0] = adell_z16_frag(sXh + tslot[0]);
-      al[0] = adell_z16_frag(sXl + tslot[0]);
+      bh[0] = adell_zr_frag(sYh + ybuf + fbase);
+      bl[0] = adell_zr_frag(sYl + ybuf + fbase);
+      ah[0] = adell_zr_frag(sXh + tslot[0]);
+      al[0] = adell_zr_frag(sXl + tslot[0]);
 #pragma unroll
       for (int i = 0; i < 2 * ZR_MAXJ; ++i) {
         const int s = i / ZR_MAXJ, q = i - s * ZR_MAXJ;
@@ -564,11 +592,11 @@ __global__ __launch_bounds__(256, 3) void adell_conv_wgrad_zring16_kernel(WgradZ
         if (more) {
           const int s2 = (i + 1) / ZR_MAXJ, q2 = (i + 1) - s2 * ZR_MAXJ;
           if (newb) {
-            bh[s2 & 1] = adell_z16_frag(sYh + ybuf + fbase + s2 * 4 * Z16_HXP * 32);
-            bl[s2 & 1] = adell_z16_frag(sYl + ybuf + fbase + s2 * 4 * Z16_HXP * 32);
+            bh[s2 & 1] = adell_zr_frag(sYh + ybuf + fbase + s2 * 4 * Z16_HXP * 32);
+            bl[s2 & 1] = adell_zr_frag(sYl + ybuf + fbase + s2 * 4 * Z16_HXP * 32);
           }
-          ah[nxt] = adell_z16_frag(sXh + tslot[q2] + s2 * 4 * Z16_HXP * 32);
-          al[nxt] = adell_z16_frag(sXl + tslot[q2] + s2 * 4 * Z16_HXP * 32);
+          ah[nxt] = adell_zr_frag(sXh + tslot[q2] + s2 * 4 * Z16_HXP * 32);
+          al[nxt] = adell_zr_frag(sXl + tslot[q2] + s2 * 4 * Z16_HXP * 32);
         }
         acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[cur], bh[s & 1], acc[q], 0, 0, 0);
         acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cur], bl[s & 1], acc[q], 0, 0, 0);
@@ -692,7 +720,7 @@ extern "C" int adell_wgrad_zring_launch(const WgradZrPlan* p, int N, int D, int 
     ADELL_CHECK_HIP(hipGetLastError());
     return ADELL_OK;
   }
-  const size_t lds = 2 * (ZR_SLOTS * (size_t)ZR_PLANE + 2 * 64 * 64);
+  const size_t lds = ZR_SLOTS * (size_t)ZR_PLANE + 2 * (size_t)ZR_YBUF;
   return adell_launch<adell_conv_wgrad_zring_kernel>(dim3((unsigned)p->R, (unsigned)(p->nci * p->nco)),
                                                      dim3(256), lds, st, a);
 }
