@@ -195,6 +195,25 @@ SIGNATURES = {
                                    _vp, _vp]),
     "adell_gather_rows_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "adell_gather_rows_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "adell_dino_loss_plan": (_i, [_i, _i, _vp]),
+    "adell_dino_loss_workspace_floats": (_l, [_i, _i]),
+    "adell_dino_loss_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _l, _vp, _vp, _vp, _vp]),
+    "adell_dino_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _f, _i, _vp, _vp,
+                                 _vp]),
+    "adell_dino_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "adell_dino_center_sum": (_i, [_vp, _i, _i, _vp, _vp]),
+    "adell_dino_center_apply": (_i, [_vp, _vp, _i, _f, _f, _f, _vp]),
+    "adell_dino_sk_proto_sums": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
+    "adell_dino_sk_sample_weights": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),
+    "adell_dino_sk_final": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
+    "adell_l2_normalize_rows_fwd": (_i, [_vp, _i, _i, _f, _vp, _vp, _vp]),
+    "adell_l2_normalize_rows_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "adell_row_inv_norm_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "adell_row_inv_norm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "adell_row_mean_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "adell_row_mean_bwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "adell_col_scale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "adell_col_scale_dscale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

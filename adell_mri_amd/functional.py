@@ -2067,6 +2067,118 @@ def gather_rows(x, pairs, col):
     return _GatherRowsFn.apply(x, pairs, int(col))
 
 
+# ---- DINO (csrc/dino.hip) -------------------------------------------------------------------------
+class _DinoLossFn(torch.autograd.Function):
+    """Mean over the rows of the fused DINO cross-entropy. Saved: the inputs and [R, 4] statistics;
+    the backward recomputes both probabilities from them."""
+
+    @staticmethod
+    def forward(ctx, a, b, centers, t1, t2, teacher_is_scores):
+        a, b = a.contiguous(), b.contiguous()
+        _, stats, mean = ops.dino_loss_fwd(a, b, centers, t1, t2, teacher_is_scores, want_mean=True)
+        ctx.save_for_backward(a, b, centers, stats)
+        ctx.conf = (t1, t2, teacher_is_scores)
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, centers, stats = ctx.saved_tensors
+        t1, t2, scores = ctx.conf
+        need_a = ctx.needs_input_grad[0]
+        need_b = ctx.needs_input_grad[1] and not scores
+        if not (need_a or need_b):
+            return None, None, None, None, None, None
+        da, db = ops.dino_loss_bwd(a, b, centers, stats, t1, t2, None, need_a, need_b, scores,
+                                   g_mean=g)
+        return da, db, None, None, None, None
+
+
+def dino_loss(a, b, centers, t1, t2, teacher_is_scores=False):
+    """-mean_r sum_k p_t[r, k] log_softmax(a / t1)[r, k] with p_t = softmax((b - centers) / t2), or
+    ``b`` as given (``teacher_is_scores``: Sinkhorn-Knopp scores, no gradient to them). The centres
+    take no gradient. Inputs of more than two dimensions are rows of their last one."""
+    if teacher_is_scores:
+        b = b.detach()
+    return _DinoLossFn.apply(a, b, None if centers is None else centers.detach(), float(t1),
+                             float(t2), bool(teacher_is_scores))
+
+
+class _L2NormalizeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        y, inv = ops.l2_normalize_rows_fwd(x)
+        ctx.save_for_backward(y, inv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, inv = ctx.saved_tensors
+        return ops.l2_normalize_rows_bwd(y, dy, inv)
+
+
+def l2_normalize(x):
+    """torch.nn.functional.normalize(x, dim=-1, p=2): x / max(||x||, 1e-12)."""
+    return _L2NormalizeFn.apply(x)
+
+
+class _RowInvNormFn(torch.autograd.Function):
+    """s = g / ||v_row||; g is frozen (DINO.initialize_last_layer), so only v gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, g, v):
+        ctx.save_for_backward(g, v)
+        return ops.row_inv_norm_fwd(v, g)
+
+    @staticmethod
+    def backward(ctx, ds):
+        g, v = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("weight_norm_linear: the magnitude g is frozen as the reference "
+                                      "freezes it; no kernel computes its gradient")
+        return None, (ops.row_inv_norm_bwd(v, g, ds) if ctx.needs_input_grad[1] else None)
+
+
+class _ColScaleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y0, s):
+        ctx.save_for_backward(y0, s)
+        return ops.col_scale(y0, s)
+
+    @staticmethod
+    def backward(ctx, dy):
+        y0, s = ctx.saved_tensors
+        dy = dy.contiguous()
+        d0 = ops.col_scale(dy, s) if ctx.needs_input_grad[0] else None
+        ds = ops.col_scale_dscale(dy, y0) if ctx.needs_input_grad[1] else None
+        return d0, ds
+
+
+def weight_norm_linear(x, g, v):
+    """Bias-free Linear under torch's weight_norm (dim 0): x (g v / ||v_row||)^T computed as
+    (x v^T) * (g / ||v_row||) -- the GEMM on the raw direction ``v``, then one scale per output
+    column. The normalised [out, in] weight is never formed, forward or backward."""
+    s = _RowInvNormFn.apply(g, v)
+    y0 = linear(x, v)
+    lead = y0.shape[:-1]
+    return _ColScaleFn.apply(y0.reshape(-1, y0.shape[-1]), s).view(*lead, y0.shape[-1])
+
+
+class _RowMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.shape = tuple(x.shape)
+        return ops.row_mean_fwd(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.row_mean_bwd(g, ctx.shape)
+
+
+def row_mean(x):
+    """x.mean(-1)."""
+    return _RowMeanFn.apply(x)
+
+
 class _PairLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, kind, temperature, apply_relu):

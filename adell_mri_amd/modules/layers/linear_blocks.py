@@ -29,6 +29,39 @@ class LayerNorm(torch.nn.LayerNorm):
         return HF.layer_norm(X, self.weight, self.bias, self.eps)
 
 
+class _WeightNormPair(torch.nn.Module):
+    """``original0`` (magnitude g, [out, 1]) and ``original1`` (direction v, [out, in]): the two
+    tensors torch.nn.utils.parametrizations.weight_norm keeps for a Linear weight (dim 0)."""
+
+    def __init__(self, weight: torch.Tensor):
+        super().__init__()
+        self.original0 = torch.nn.Parameter(weight.norm(2, dim=1, keepdim=True))
+        self.original1 = torch.nn.Parameter(weight)
+
+
+class WeightNormLinear(torch.nn.Module):
+    """Bias-free ``weight_norm(torch.nn.Linear(in, out, bias=False))`` whose state keys are the
+    parametrised module's, ``parametrizations.weight.original0`` and ``.original1``. The forward is
+    the GEMM on the direction followed by one scale g / ||v_row|| per output column
+    (functional.weight_norm_linear): the normalised weight is never formed, so there is no ``weight``
+    attribute. The magnitude must be frozen (as DINO freezes it): no kernel computes its gradient."""
+
+    def __init__(self, in_features: int, out_features: int):
+        super().__init__()
+        self.in_features = in_features
+        self.out_features = out_features
+        weight = torch.empty((out_features, in_features))
+        torch.nn.init.kaiming_uniform_(weight, a=5 ** 0.5)      # torch.nn.Linear.reset_parameters
+        self.parametrizations = torch.nn.ModuleDict({"weight": _WeightNormPair(weight)})
+
+    def forward(self, X):
+        pair = self.parametrizations.weight
+        if pair.original0.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("WeightNormLinear: a trainable magnitude (original0) has no "
+                                      "gradient kernel; freeze it as DINO.initialize_last_layer does")
+        return HF.weight_norm_linear(X, pair.original0, pair.original1)
+
+
 def get_relative_position_indices(window_size) -> torch.Tensor:
     """Index into the relative-position bias table for every ordered pair of positions of a
     window (linear_blocks.py:17-51; row-major positions, offsets shifted to start at 0 and

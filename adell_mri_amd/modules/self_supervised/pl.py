@@ -12,6 +12,11 @@ boxes of the batch, csrc/vicregl.hip) is built by ``SelfSLResNetPL`` -- the clas
 ``get_ssl_network`` builds for it -- and by ``SelfSLUNetPL``, whose ``forward(x)`` already is the
 feature map. ``SelfSLConvNeXtPL`` still raises ``NotImplementedError`` for it: the reference's
 factory never builds the ConvNeXt wrapper with this method, and no fixture pins its feature maps.
+
+``DINOPL`` (pl.py:1168-1282) is the wrapper of the ViT method ``ssl_method="dino"``: both views
+stacked through the student in one pass, the EMA teacher under ``no_grad`` on the same stack, the
+fused ``DinoLoss`` (csrc/dino.hip) both ways, the EMA update in training only and the centre update
+in every step.
 """
 import warnings
 from typing import Callable
@@ -23,7 +28,9 @@ from ..layers.conv_next import ConvNeXt
 from ..layers.res_net import ResNet
 from ..segmentation.unet import UNet
 from ..learning_rate import CosineAnnealingWithWarmupLR
-from .losses import NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss, simsiam_loss
+from .dino import DINO
+from .losses import (DinoLoss, NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss,
+                     simsiam_loss)
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as pl
@@ -275,3 +282,77 @@ class SelfSLUNetPL(_TwoViewSSL, UNet, SelfSLBasePL):
                  optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
         hp = {k: v for k, v in locals().items() if k not in ("self", "args", "kwargs", "__class__")}
         self._init_two_view(hp, args, kwargs)
+
+
+class DINOPL(DINO, SelfSLBasePL):
+    """DINO on a ViT encoder (pl.py:1168-1282). ``ema`` is the teacher and is required. The centres
+    of the loss stay out of the EMA (``exclude_keys=["centers"]``); they are updated from the
+    teacher's outputs in every step, training or not, and applied lazily by the next loss call."""
+
+    def __init__(self, aug_image_key_1: str = "aug_image_1", aug_image_key_2: str = "aug_image_2",
+                 learning_rate: float = 1e-3, batch_size: int = 1, weight_decay: float = 1e-6,
+                 training_dataloader_call: Callable = None, n_epochs: int = 100,
+                 n_steps: int = None, warmup_steps: int = 0, start_decay: int = 0,
+                 temperature: float = 0.1, stop_gradient: bool = True,
+                 channels_to_batch: bool = False, optimizer_eps: float = OPTIMIZER_EPS_DEFAULT,
+                 ema: torch.nn.Module = None, centers_m: float = 0.9,
+                 teacher_score_method: str = "center", *args, **kwargs):
+        hp = dict(aug_image_key_1=aug_image_key_1, aug_image_key_2=aug_image_key_2,
+                  learning_rate=learning_rate, batch_size=batch_size, weight_decay=weight_decay,
+                  training_dataloader_call=training_dataloader_call, n_epochs=n_epochs,
+                  n_steps=n_steps, warmup_steps=warmup_steps, start_decay=start_decay,
+                  temperature=temperature, stop_gradient=stop_gradient,
+                  channels_to_batch=channels_to_batch, centers_m=centers_m,
+                  teacher_score_method=teacher_score_method, ssl_method="dino")
+        for k, v in hp.items():   # plain attributes: set before Module.__init__, as the reference does
+            object.__setattr__(self, k, v)
+        if channels_to_batch is True:
+            kwargs["backbone_args"]["in_channels"] = 1
+        super().__init__(*args, **kwargs)   # DINO.__init__: raises for a configuration that cannot run
+        self.optimizer_eps = optimizer_eps
+        self.ema = ema
+        if self.ema is None:
+            raise ValueError("DINO requires an EMA (teacher) copy of the network "
+                             "(`ema` must be an ExponentialMovingAverage module).")
+        self.save_hyperparameters()
+        self.setup_metrics()
+        self.init_loss()
+        self.ema.update(self, exclude_keys=["centers"])
+
+    def init_loss(self):
+        self.loss = DinoLoss(temperatures=(self.temperature, self.temperature),
+                             n_features=self.out_dim, center_m=self.centers_m,
+                             teacher_score_method=self.teacher_score_method)
+
+    def calculate_loss(self, y_1, y_2, *args):
+        return self.loss(y_1, y_2)
+
+    def step(self, batch, loss_str: str, metrics: dict | None = None, train=False):
+        x1, x2 = batch[self.aug_image_key_1], batch[self.aug_image_key_2]
+        if self.channels_to_batch is True:
+            x1 = x1.reshape(-1, 1, *x1.shape[2:])
+            x2 = x2.reshape(-1, 1, *x2.shape[2:])
+        stacked_x = torch.cat([x1, x2])
+        sh = [x1.shape[0], x2.shape[0]]
+        s_1, s_2 = self.forward(stacked_x).split(sh, dim=0)
+        with torch.no_grad():
+            t_all = self.ema(stacked_x).detach()
+        t_1, t_2 = t_all.split(sh, dim=0)
+        loss_value = torch.add(self.calculate_loss(s_1, t_2) / 2.0,
+                               self.calculate_loss(s_2, t_1) / 2.0)
+        if metrics is not None:
+            self.update_metrics(torch.cat([s_1, s_2]), t_all, metrics, log=True)
+        self.log(loss_str, loss_value, on_step=True, on_epoch=True, prog_bar=True)
+        if self.ema is not None and train is True:
+            self.ema.update(self, exclude_keys=["centers"])
+        self.loss.update_centers(t_all)     # cat([t_1, t_2]) is the teacher's stacked output
+        return loss_value
+
+    def training_step(self, batch, batch_idx):
+        return self.step(batch, "loss", train=True)
+
+    def validation_step(self, batch, batch_idx):
+        return self.step(batch, "val_loss")
+
+    def test_step(self, batch, batch_idx):
+        return self.step(batch, "test_loss")

@@ -2408,6 +2408,237 @@ def gather_rows_bwd(dout, pairs, col, shape):
     return dx
 
 
+# ---- DINO (csrc/dino.hip) ---------------------------------------------------------------------
+def dino_loss_plan(R, K):
+    """(chunks per row, chunk length): how dino_loss_fwd / dino_loss_bwd split each of the R rows of
+    K columns over workgroups. Host only: no GPU needed; the launches call the same function."""
+    out = (ctypes.c_int * 2)()
+    check(_lib.lib().adell_dino_loss_plan(int(R), int(K), out))
+    return int(out[0]), int(out[1])
+
+
+def _dino_rows(x):
+    """[..., K] -> dense [R, K]."""
+    return x.reshape(-1, x.shape[-1]).contiguous()
+
+
+def _dino_centers(centers, K):
+    if centers is None:
+        return None
+    centers = centers.reshape(-1).contiguous()
+    if centers.numel() != K:
+        raise ValueError(f"dino: {centers.numel()} centres for {K} columns")
+    return centers
+
+
+def dino_loss_fwd(a, b, centers, t1, t2, teacher_is_scores=False, want_mean=False):
+    """(loss_rows [R], stats [R, 4]) with loss_r = -sum_k p_t[r, k] log_softmax(a / t1)[r, k] and
+    p_t = softmax((b - centers) / t2), or ``b`` itself with ``teacher_is_scores``. stats = (lse of
+    a / t1, lse of (b - centers) / t2 | sum_k b, loss_r, sum_k p_t a | 0): all the backward needs. Inputs of more
+    than two dimensions are rows of their last one. One pass over a and b, rows split over
+    workgroups as ``dino_loss_plan`` says. ``want_mean``: also the mean of the rows (a 0-d tensor,
+    from the merge launch itself)."""
+    _require_cuda(a, b, centers)
+    if a.shape != b.shape:
+        raise ValueError(f"dino_loss: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    a, b = _dino_rows(a), _dino_rows(b)
+    R, K = a.shape
+    centers = None if teacher_is_scores else _dino_centers(centers, K)
+    floats = _lib.lib().adell_dino_loss_workspace_floats(R, K)
+    # one allocation: statistics, row losses, the mean, then the partials of the plan
+    buf = torch.empty((5 * R + 4 + floats,), device=a.device, dtype=torch.float32)
+    stats, loss_rows, mean = buf[:4 * R].view(R, 4), buf[4 * R:5 * R], buf[5 * R]
+    base = buf.data_ptr()
+    check(_lib.lib().adell_dino_loss_fwd(_ptr(a), _ptr(b), _ptr(centers), R, K, float(t1), float(t2),
+                                         int(bool(teacher_is_scores)),
+                                         ctypes.c_void_p(base + 4 * (5 * R + 4)), floats,
+                                         ctypes.c_void_p(base + 16 * R), ctypes.c_void_p(base),
+                                         ctypes.c_void_p(base + 20 * R) if want_mean else None,
+                                         _stream()))
+    return (loss_rows, stats, mean) if want_mean else (loss_rows, stats)
+
+
+def dino_loss_bwd(a, b, centers, stats, t1, t2, g_rows, need_a=True, need_b=False,
+                  teacher_is_scores=False, g_mean=None):
+    """(da, db) of ``dino_loss_fwd`` for the row gradients ``g_rows`` [R] -- or, with ``g_rows``
+    None, for the gradient ``g_mean`` (one element) of the mean of the rows; everything is
+    recomputed from ``stats``. db exists in centre mode only and is allocated only with ``need_b``."""
+    _require_cuda(a, b, centers, stats, g_rows, g_mean)
+    if g_rows is None and g_mean is None:
+        raise ValueError("dino_loss_bwd: g_rows or g_mean")
+    if need_b and teacher_is_scores:
+        raise ValueError("dino_loss_bwd: scores given as they are take no gradient")
+    shape = a.shape
+    a, b = _dino_rows(a), _dino_rows(b)
+    R, K = a.shape
+    centers = None if teacher_is_scores else _dino_centers(centers, K)
+    da = torch.empty_like(a) if need_a else None
+    db = torch.empty_like(b) if need_b else None
+    check(_lib.lib().adell_dino_loss_bwd(_ptr(a), _ptr(b), _ptr(centers), _ptr(stats.contiguous()),
+                                         None if g_rows is None else _ptr(g_rows.contiguous()),
+                                         None if g_rows is not None else _ptr(g_mean.contiguous()),
+                                         1.0 / R, R, K, float(t1), float(t2),
+                                         int(bool(teacher_is_scores)), _ptr(da), _ptr(db), _stream()))
+    return (None if da is None else da.view(shape)), (None if db is None else db.view(shape))
+
+
+def dino_log_softmax(x, t):
+    """log_softmax(x / t) over the last dimension (any width)."""
+    x2 = _dino_rows(x)
+    _, stats = dino_loss_fwd(x2, x2, None, t, t)
+    out = torch.empty_like(x2)
+    check(_lib.lib().adell_dino_scores(_ptr(x2), None, _ptr(stats), 0, 0, x2.shape[0], x2.shape[1],
+                                       float(t), _ptr(out), _stream()))
+    return out.view(x.shape)
+
+
+def dino_softmax(x, centers, t):
+    """softmax((x - centers) / t) over the last dimension (any width)."""
+    x2 = _dino_rows(x)
+    centers = _dino_centers(centers, x2.shape[1])
+    _, stats = dino_loss_fwd(x2, x2, centers, t, t)
+    out = torch.empty_like(x2)
+    check(_lib.lib().adell_dino_scores(_ptr(x2), _ptr(centers), _ptr(stats), 1, 1, x2.shape[0],
+                                       x2.shape[1], float(t), _ptr(out), _stream()))
+    return out.view(x.shape)
+
+
+def dino_center_sum(x):
+    """[1, K]: the sum of the rows of x [R, K], rows added in order."""
+    _require_cuda(x)
+    x = _dino_rows(x)
+    out = torch.empty((1, x.shape[1]), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_dino_center_sum(_ptr(x), x.shape[0], x.shape[1], _ptr(out), _stream()))
+    return out
+
+
+def dino_center_apply(centers, batch_sum, m, denom):
+    """In place: centers = centers * m + (batch_sum / denom) * (1 - m)."""
+    _require_cuda(centers, batch_sum)
+    if not centers.is_contiguous() or batch_sum.numel() != centers.numel():
+        raise ValueError("dino_center_apply: dense centres and a sum of the same length expected")
+    check(_lib.lib().adell_dino_center_apply(_ptr(centers), _ptr(batch_sum.contiguous()),
+                                             centers.numel(), float(m), 1 - float(m), float(denom),
+                                             _stream()))
+    return centers
+
+
+def dino_sk_scores(x, t2, iterations, world_size=1, reduce=None):
+    """Sinkhorn-Knopp assignment of exp(x / t2) for x [R, K] (DinoLoss.sinkhorn_knopp_teacher): [R, K]
+    scores whose rows sum to 1. Factored form Q[k, r] = u_k exp(x[r, k] / t2) v_r: each iteration
+    updates the prototype weights u [K] (a column reduction; ``reduce(tensor)`` is called on the
+    prototype sums between launches -- torch.distributed.all_reduce where the reference all-reduces
+    ``sum_of_rows``) and the sample weights v [R]; exp is recomputed per pass and only the final
+    scores are written. The reference's first division by the (all-reduced) total cancels in the
+    first prototype normalisation and is not computed."""
+    _require_cuda(x)
+    if int(iterations) < 1:
+        raise ValueError("dino_sk_scores: at least one iteration")
+    shape = x.shape
+    x = _dino_rows(x)
+    R, K = x.shape
+    samples = float(R * int(world_size))
+    v = torch.ones((R,), device=x.device, dtype=torch.float32)
+    t = torch.empty((K,), device=x.device, dtype=torch.float32)
+    lib = _lib.lib()
+    for _ in range(int(iterations)):
+        check(lib.adell_dino_sk_proto_sums(_ptr(x), _ptr(v), R, K, float(t2), _ptr(t), _stream()))
+        if reduce is not None:
+            reduce(t)
+        check(lib.adell_dino_sk_sample_weights(_ptr(x), _ptr(t), R, K, float(t2), samples, _ptr(v),
+                                               _stream()))
+    out = torch.empty_like(x)
+    check(lib.adell_dino_sk_final(_ptr(x), _ptr(t), _ptr(v), R, K, float(t2), samples, _ptr(out),
+                                  _stream()))
+    return out.view(shape)
+
+
+L2_NORMALIZE_EPS = 1e-12   # torch.nn.functional.normalize
+
+
+def l2_normalize_rows_fwd(x):
+    """(y, inv): y = x / max(||x||, 1e-12) over the last dimension, inv [rows] the factor."""
+    _require_cuda(x)
+    x = x.contiguous()
+    C = x.shape[-1]
+    rows = x.numel() // C
+    y = torch.empty_like(x)
+    inv = torch.empty((rows,), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_l2_normalize_rows_fwd(_ptr(x), rows, C, L2_NORMALIZE_EPS, _ptr(y),
+                                                 _ptr(inv), _stream()))
+    return y, inv
+
+
+def l2_normalize_rows_bwd(y, dy, inv):
+    _require_cuda(y, dy, inv)
+    dy = dy.contiguous()
+    C = y.shape[-1]
+    dx = torch.empty_like(y)
+    check(_lib.lib().adell_l2_normalize_rows_bwd(_ptr(y), _ptr(dy), _ptr(inv), y.numel() // C, C,
+                                                 L2_NORMALIZE_EPS, _ptr(dx), _stream()))
+    return dx
+
+
+def row_inv_norm_fwd(v, g):
+    """s [out] = g / ||v_row|| for v [out, in] and g [out] or [out, 1] (weight norm over dim 0)."""
+    _require_cuda(v, g)
+    v = v.contiguous()
+    rows, C = v.shape
+    s = torch.empty((rows,), device=v.device, dtype=torch.float32)
+    check(_lib.lib().adell_row_inv_norm_fwd(_ptr(v), _ptr(g.reshape(-1).contiguous()), rows, C,
+                                            _ptr(s), _stream()))
+    return s
+
+
+def row_inv_norm_bwd(v, g, ds):
+    """dv of ``row_inv_norm_fwd`` (g is frozen: no gradient to it)."""
+    _require_cuda(v, g, ds)
+    v = v.contiguous()
+    rows, C = v.shape
+    dv = torch.empty_like(v)
+    check(_lib.lib().adell_row_inv_norm_bwd(_ptr(v), _ptr(g.reshape(-1).contiguous()),
+                                            _ptr(ds.contiguous()), rows, C, _ptr(dv), _stream()))
+    return dv
+
+
+def row_mean_fwd(x):
+    """[..., C] -> [...]: the mean over the last dimension."""
+    _require_cuda(x)
+    x = x.contiguous()
+    C = x.shape[-1]
+    out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_row_mean_fwd(_ptr(x), x.numel() // C, C, _ptr(out), _stream()))
+    return out
+
+
+def row_mean_bwd(dout, shape):
+    _require_cuda(dout)
+    dout = dout.contiguous()
+    dx = torch.empty(shape, device=dout.device, dtype=torch.float32)
+    check(_lib.lib().adell_row_mean_bwd(_ptr(dout), dout.numel(), shape[-1], _ptr(dx), _stream()))
+    return dx
+
+
+def col_scale(x, s):
+    """x [R, K] * s [K]."""
+    _require_cuda(x, s)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    check(_lib.lib().adell_col_scale(_ptr(x), _ptr(s.contiguous()), x.shape[0], x.shape[1], _ptr(y),
+                                     _stream()))
+    return y
+
+
+def col_scale_dscale(dy, y0):
+    """ds [K] = sum_r dy[r, k] * y0[r, k], rows added in order."""
+    _require_cuda(dy, y0)
+    dy, y0 = dy.contiguous(), y0.contiguous()
+    ds = torch.empty((dy.shape[1],), device=dy.device, dtype=torch.float32)
+    check(_lib.lib().adell_col_scale_dscale(_ptr(dy), _ptr(y0), dy.shape[0], dy.shape[1], _ptr(ds),
+                                            _stream()))
+    return ds
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

@@ -1,9 +1,10 @@
 """Network factories of the hot path: ``get_segmentation_network``
 (adell_mri/utils/network_factories.py:493-701) and ``get_ssl_network`` (:705-1028) on this
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
-constructors, same ``ValueError`` for an unknown ``net_type``. Members outside the built
-path (the MONAI wrappers, the ViT-based SSL methods) raise ``NotImplementedError`` --
-there is no eager-torch fallback.
+constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
+``DINOPL`` on a ViT encoder (:869-905; ``TypeError`` for any other ``net_type``). Members outside the
+built path (the MONAI wrappers, the other ViT-based SSL methods: I-JEPA, MAE, iBOT; Barlow Twins)
+raise ``NotImplementedError`` -- there is no eager-torch fallback.
 """
 from typing import Any, Callable
 
@@ -11,7 +12,8 @@ import torch
 
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
-from ..modules.self_supervised.pl import SelfSLConvNeXtPL, SelfSLResNetPL, SelfSLUNetPL
+from ..modules.self_supervised.pl import (DINOPL, SelfSLConvNeXtPL, SelfSLResNetPL,
+                                          SelfSLUNetPL)
 
 OPTIMIZER_EPS_DEFAULT = 1e-8
 ALLOWED_NET_TYPES = {
@@ -106,6 +108,11 @@ _RESNET_DEFAULTS = dict(
                           "adn_fn": torch.nn.Identity})
 
 
+_DINO_BACKBONE_DEFAULTS = {"image_size": [224, 224], "patch_size": [16, 16], "in_channels": 1,
+                           "number_of_blocks": 4, "attention_dim": 96, "embedding_size": 96,
+                           "n_heads": 3}
+
+
 def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_optim: int,
                     warmup_steps: int, ssl_method: str, ema: torch.nn.Module, net_type: str,
                     network_config: dict[str, Any], stop_gradient: bool,
@@ -114,7 +121,8 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
     simclr / byol / vicreg / vicregl always build the ResNet wrapper from the three ``*_args``
     dictionaries (defaults :754-790) -- for vicregl with ``VICRegLocalLoss(**vic_reg_loss_params)``
     on the "representation" feature maps and the boxes of the batch; every other method name with ``net_type="convnext"``
-    builds ``SelfSLConvNeXtPL`` from the whole configuration (:998-1026)."""
+    builds ``SelfSLConvNeXtPL`` from the whole configuration (:998-1026). ``"dino"`` builds
+    ``DINOPL`` (ViT backbone + MLP projection head, defaults :875-901) and needs ``ema``."""
     common = {"training_dataloader_call": train_loader_call, "n_epochs": max_epochs,
               "n_steps": max_steps_optim, "warmup_steps": warmup_steps, "ema": ema,
               "batch_size": network_config.get("batch_size", 32),
@@ -130,7 +138,20 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
                       temperature=network_config.get("temperature", 0.1),
                       vic_reg_loss_params=network_config.get("vic_reg_loss_params", {}))
         return SelfSLResNetPL(**{**common, **config})
-    if ssl_method in ("ijepa", "mae", "dino", "ibot", "barlow"):
+    if ssl_method == "dino":
+        if net_type != "vit":
+            raise TypeError("DINO only supports net_type='vit', got %s" % net_type)
+        config = {"aug_image_key_1": "augmented_image_1", "aug_image_key_2": "augmented_image_2",
+                  "backbone_args": network_config.get("backbone_args", dict(_DINO_BACKBONE_DEFAULTS)),
+                  "projection_head_args": network_config.get("projection_head_args",
+                                                             {"structure": [512, 256, 128]}),
+                  "out_dim": network_config.get("out_dim", 65536),
+                  "temperature": network_config.get("temperature", 0.1),
+                  "centers_m": network_config.get("centers_m", 0.9),
+                  "teacher_score_method": network_config.get("teacher_score_method", "center"),
+                  "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
+        return DINOPL(**{**common, **config})
+    if ssl_method in ("ijepa", "mae", "ibot", "barlow"):
         raise NotImplementedError(f"ssl_method {ssl_method!r} (ViT / Barlow-Twins wrappers) is "
                                   "outside the HIP path (SURVEY.md section 2: out of scope)")
     boilerplate = {"training_dataloader_call": train_loader_call,

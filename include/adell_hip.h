@@ -760,6 +760,61 @@ int adell_gather_rows_fwd(const float* x, const int* pairs, int col, int B, int 
 int adell_gather_rows_bwd(const float* dout, const int* pairs, int col, int B, int T, int C,
                           int gamma, float* dx, void* stream);
 
+/* DINO (self_supervised/dino.py, losses/dino.py; csrc/dino.hip). All tensors fp32 and dense, rows of
+ * K floats at any 4-byte address; no float atomics, results repeat bit for bit.
+ * adell_dino_loss_plan: out = {chunks per row, chunk length}: how adell_dino_loss_fwd / _bwd split a
+ * row over workgroups (host only; the launches call this same function).
+ * adell_dino_loss_fwd: loss_rows[r] = -sum_k p_t[r][k] log_softmax(a / t1)[r][k], p_t =
+ * softmax((b - centers) / t2) (centers [K] or NULL = zeros) or, with teacher_is_scores, b itself
+ * (its row sum is accumulated, not assumed 1). stats [R][4] = (lse of a / t1, lse of (b - centers) / t2
+ * | sum_k b, loss_r, sum_k p_t a | 0) is all the backward needs. workspace: adell_dino_loss_workspace_floats(R, K).
+ * loss_mean (may be NULL): 1 float, the mean of loss_rows in a fixed order.
+ * adell_dino_loss_bwd: da = g_r (softmax_s sum_k p_t - p_t) / t1, db = -g_r p_t
+ * (log_softmax_s - sum_k p_t log_softmax_s) / t2 (centre mode only); either may be NULL. g_r =
+ * g_rows[r], or with g_rows NULL g_all[0] * g_scale (the gradient of the mean: g_scale = 1 / R). R <= 65535.
+ * adell_dino_scores: out = x / t - stats[r][slot] (mode 0) or exp((x - centers) / t - stats[r][slot])
+ * (mode 1): the log-softmax / softmax of a row whose lse a forward left in stats. */
+int adell_dino_loss_plan(int R, int K, int* out);
+long adell_dino_loss_workspace_floats(int R, int K);
+int adell_dino_loss_fwd(const float* a, const float* b, const float* centers, int R, int K, float t1,
+                        float t2, int teacher_is_scores, float* workspace, long workspace_floats,
+                        float* loss_rows, float* stats, float* loss_mean, void* stream);
+int adell_dino_loss_bwd(const float* a, const float* b, const float* centers, const float* stats,
+                        const float* g_rows, const float* g_all, float g_scale, int R, int K, float t1,
+                        float t2, int teacher_is_scores, float* da, float* db, void* stream);
+int adell_dino_scores(const float* x, const float* centers, const float* stats, int slot, int mode,
+                      int R, int K, float t, float* out, void* stream);
+/* Centres: out[k] = sum_r x[r][k] (rows in order); centers = centers m + (batch_sum / denom) rest with
+ * rest = 1 - m formed by the caller in double. */
+int adell_dino_center_sum(const float* x, int R, int K, float* out, void* stream);
+int adell_dino_center_apply(float* centers, const float* batch_sum, int K, float m, float rest,
+                            float denom, void* stream);
+/* Sinkhorn-Knopp teacher scores in factored form Q[k][r] = u_k exp(x[r][k] / t2) v_r:
+ * proto_sums: t[k] = sum_r exp(x[r][k] / t2) v[r] (the caller all-reduces t over the ranks);
+ * sample_weights: v[r] = 1 / (samples sum_k exp(x[r][k] / t2) / (K t[k]));
+ * final: out[r][k] = exp(x[r][k] / t2) / (K t[k]) v[r] samples. samples = R x world size. */
+int adell_dino_sk_proto_sums(const float* x, const float* v, int R, int K, float t2, float* t,
+                             void* stream);
+int adell_dino_sk_sample_weights(const float* x, const float* t, int R, int K, float t2, float samples,
+                                 float* v, void* stream);
+int adell_dino_sk_final(const float* x, const float* t, const float* v, int R, int K, float t2,
+                        float samples, float* out, void* stream);
+/* Head. l2_normalize_rows: y = x / max(||x||, eps) per row of C floats, inv[row] = 1 / max(||x||, eps)
+ * kept for the backward (which takes y). row_inv_norm: s[row] = g[row] / ||v[row]|| for v [rows][C]
+ * (weight norm over dim 0); its backward is the gradient to v alone. row_mean: the mean of each row.
+ * col_scale: y[r][k] = x[r][k] s[k]; col_scale_dscale: ds[k] = sum_r dy[r][k] y0[r][k]. */
+int adell_l2_normalize_rows_fwd(const float* x, int rows, int C, float eps, float* y, float* inv,
+                                void* stream);
+int adell_l2_normalize_rows_bwd(const float* y, const float* dy, const float* inv, int rows, int C,
+                                float eps, float* dx, void* stream);
+int adell_row_inv_norm_fwd(const float* v, const float* g, int rows, int C, float* s, void* stream);
+int adell_row_inv_norm_bwd(const float* v, const float* g, const float* ds, int rows, int C, float* dv,
+                           void* stream);
+int adell_row_mean_fwd(const float* x, int rows, int C, float* out, void* stream);
+int adell_row_mean_bwd(const float* dout, int rows, int C, float* dx, void* stream);
+int adell_col_scale(const float* x, const float* s, int R, int K, float* y, void* stream);
+int adell_col_scale_dscale(const float* dy, const float* y0, int R, int K, float* ds, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
