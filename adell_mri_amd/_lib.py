@@ -214,6 +214,16 @@ SIGNATURES = {
     "adell_row_mean_bwd": (_i, [_vp, _i, _i, _vp, _vp]),
     "adell_col_scale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "adell_col_scale_dscale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "adell_ibot_mask_tokens_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_ibot_mask_tokens_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "adell_ibot_token_sums_plan": (_i, [_i, _i, _i, _vp]),
+    "adell_ibot_token_sums_workspace_doubles": (_l, [_i, _i, _i]),
+    "adell_ibot_center_sum": (_i, [_vp, _i, _i, _vp, _vp]),
+    "adell_ibot_token_sums": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _l, _vp, _vp, _vp]),
+    "adell_ibot_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _l, _vp, _vp,
+                                 _vp, _vp]),
+    "adell_ibot_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i,
+                            _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

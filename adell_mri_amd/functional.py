@@ -2179,6 +2179,114 @@ def row_mean(x):
     return _RowMeanFn.apply(x)
 
 
+# ---- iBOT (csrc/ibot.hip) -------------------------------------------------------------------------
+class _MaskTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, token, rows):
+        ctx.rows = rows
+        return ops.ibot_mask_tokens_fwd(x.contiguous(), rows, token)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dtoken = ops.ibot_mask_tokens_bwd(dy.contiguous(), ctx.rows, ctx.needs_input_grad[0],
+                                              ctx.needs_input_grad[1])
+        return dx, dtoken, None
+
+
+def mask_tokens(x, idx, token):
+    """x [B, N, E] with the rows ``idx`` (host indices, sorted and unique, or an ``ops.TokenRows``)
+    of every item replaced by ``token`` [E], out of place. The replaced rows pass no gradient to
+    ``x``; the token's gradient is their sum. IndexError for an index outside [0, N)."""
+    if x.dim() != 3:
+        raise ValueError(f"mask_tokens: [B, N, E] expected, got {tuple(x.shape)}")
+    return _MaskTokensFn.apply(x, token, ops.token_rows(idx, x.shape[1], x.device))
+
+
+class _TokenMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, first):
+        ctx.conf = (tuple(x.shape), first)
+        return ops.ibot_token_sums(x.contiguous(), first, 1.0 / (x.shape[1] - first))
+
+    @staticmethod
+    def backward(ctx, g):
+        shape, first = ctx.conf
+        return ops.ibot_bwd(None, None, None, None, None, g, None, first, "mean", 1.0, 1.0,
+                            shape=shape), None
+
+
+def token_mean(x, class_token=False):
+    """x[:, c:].mean(1) for x [B, c + T, K], c = 1 with a class token (which gets a zero gradient)."""
+    return _TokenMeanFn.apply(x, int(bool(class_token)))
+
+
+class _IbotViewFn(torch.autograd.Function):
+    """One view of iBOT on the token logits s [B, Tt, K]: the reduced output and the mean masked-row
+    DINO loss. Saved: the inputs and [B * M, 4] statistics; the backward takes both incoming
+    gradients and writes ds in one launch."""
+
+    @staticmethod
+    def forward(ctx, s, y, third, rows, t1, t2, class_token, reduce, scores):
+        s, y = s.contiguous(), y.contiguous()
+        if reduce == "cls":
+            s_red = s[:, 0].contiguous()
+        else:
+            s_red = ops.ibot_token_sums(s, class_token, 1.0 / (s.shape[1] - class_token))
+        teacher = third if scores else y
+        _, stats, mean = ops.ibot_loss_fwd(s, teacher, rows, None if scores else third, t1, t2, scores,
+                                           want_mean=True)
+        ctx.save_for_backward(s, teacher, None if scores else third, stats)
+        ctx.conf = (rows, t1, t2, class_token, reduce, scores)
+        return s_red, mean
+
+    @staticmethod
+    def backward(ctx, d_red, g):
+        s, teacher, centers, stats = ctx.saved_tensors
+        rows, t1, t2, class_token, reduce, scores = ctx.conf
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 9
+        ds = ops.ibot_bwd(s, teacher, rows, centers, stats, d_red, g, class_token, reduce, t1, t2,
+                          scores)
+        return (ds,) + (None,) * 8
+
+
+def ibot_view(s, y, rows, centers_or_scores, t1, t2, class_token, reduce, teacher_is_scores=False):
+    """(s_red [B, K], loss_mask): the reduction of the student's token logits s [B, Tt, K] ("cls":
+    the class row, "mean": the mean of the patch rows) and DinoLoss over the PATCH rows ``rows``
+    (host indices into s[:, c:], c = 1 with a class token; or what ``patch_rows`` made of them) of s
+    against the same rows of the teacher y [B, Tt, K], read in place. ``centers_or_scores``: the centres [K] or, with
+    ``teacher_is_scores``, the dense [B * M, K] scores of the teacher's masked rows (Sinkhorn-Knopp).
+    The teacher takes no gradient. IndexError for a row outside the T patch tokens."""
+    if s.dim() != 3 or y.shape != s.shape:
+        raise ValueError(f"ibot_view: [B, tokens, K] logits of one shape expected, got "
+                         f"{tuple(s.shape)} and {tuple(y.shape)}")
+    if reduce not in ("cls", "mean"):
+        raise ValueError(f"ibot_view: reduce {reduce!r} (\"cls\" or \"mean\")")
+    c = int(bool(class_token))
+    if reduce == "cls" and not c:
+        raise ValueError("ibot_view: the \"cls\" reduction needs a class token")
+    table = patch_rows(rows, s.shape[1], c, s.device)
+    third = centers_or_scores
+    return _IbotViewFn.apply(s, y.detach(), None if third is None else third.detach(), table,
+                             float(t1), float(t2), c, reduce, bool(teacher_is_scores))
+
+
+def patch_rows(rows, tokens, class_token, device):
+    """``ops.TokenRows`` of the rows ``c + rows`` of a [B, tokens, K] tensor for indices ``rows``
+    into its ``tokens - c`` patch rows; IndexError, on the host, for an index beyond them (what
+    ``a[:, 1:][:, rows]`` raises)."""
+    c = int(bool(class_token))
+    if isinstance(rows, ops.TokenRows):
+        return ops.token_rows(rows, tokens, device)
+    if isinstance(rows, torch.Tensor):
+        rows = rows.detach().cpu().numpy()
+    rows = np.asarray(rows).reshape(-1)
+    T = int(tokens) - c
+    if rows.size and (int(rows.max()) >= T or int(rows.min()) < 0):
+        raise IndexError(f"index {int(rows.max())} is out of bounds for dimension 1 with size {T}")
+    return ops.token_rows(rows + c, tokens, device)
+
+
 class _PairLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, kind, temperature, apply_relu):

@@ -17,18 +17,31 @@ factory never builds the ConvNeXt wrapper with this method, and no fixture pins 
 stacked through the student in one pass, the EMA teacher under ``no_grad`` on the same stack, the
 fused ``DinoLoss`` (csrc/dino.hip) both ways, the EMA update in training only and the centre update
 in every step.
+
+``iBOTPL`` (pl.py:1285-1431) is the wrapper of ``ssl_method="ibot"``: the student on both views with
+two consecutive masker draws, the EMA teacher under ``no_grad`` without masking, the centre updates
+of both losses BEFORE the losses (the lazy ``DinoLoss`` applies them inside the first loss call of
+the same step), the global loss across the views on the reduced outputs and the masked-token loss
+within each view. The token logits [B, tokens, out_dim] are read in place: per view one fused
+function (functional.ibot_view, csrc/ibot.hip) gives the reduced output and the masked-row loss and
+writes the whole gradient in one launch; the teacher's logits are read once for its "mean"
+reduction and the centre sum.
 """
 import warnings
 from typing import Callable
 
 import torch
+import torch.distributed as dist
 
+from ... import functional as HF
+from ... import ops
 from ...optim import FusedAdamW
 from ..layers.conv_next import ConvNeXt
 from ..layers.res_net import ResNet
 from ..segmentation.unet import UNet
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from .dino import DINO
+from .ibot import iBOT
 from .losses import (DinoLoss, NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss,
                      simsiam_loss)
 
@@ -347,6 +360,138 @@ class DINOPL(DINO, SelfSLBasePL):
             self.ema.update(self, exclude_keys=["centers"])
         self.loss.update_centers(t_all)     # cat([t_1, t_2]) is the teacher's stacked output
         return loss_value
+
+    def training_step(self, batch, batch_idx):
+        return self.step(batch, "loss", train=True)
+
+    def validation_step(self, batch, batch_idx):
+        return self.step(batch, "val_loss")
+
+    def test_step(self, batch, batch_idx):
+        return self.step(batch, "test_loss")
+
+
+class iBOTPL(iBOT, SelfSLBasePL):
+    """iBOT on a ViT encoder (pl.py:1285-1431). ``ema`` is the teacher and is required. Two
+    ``DinoLoss`` modules: ``loss_global`` on the reduced outputs, across the views, and ``loss_mask``
+    on the masked patch tokens, within a view. Their centres stay out of the EMA and are updated
+    from the teacher's outputs -- all of its patch tokens for ``loss_mask``, not only the masked ones
+    -- before the losses of the same step, training or not.
+
+    Kept as written: ``calculate_loss_mask(a, b, m)`` indexes the PATCH tokens with the masker's
+    coordinates, which still carry the ``+ skip_n`` offset (ibot.py docstring); an index that
+    reaches the number of patch tokens raises ``IndexError``, here on the host before any kernel."""
+
+    def __init__(self, aug_image_key_1: str = "aug_image_1", aug_image_key_2: str = "aug_image_2",
+                 learning_rate: float = 1e-3, batch_size: int = 1, weight_decay: float = 1e-6,
+                 training_dataloader_call: Callable = None, n_epochs: int = 100,
+                 n_steps: int = None, warmup_steps: int = 0, start_decay: int = 0,
+                 temperature: float = 0.1, stop_gradient: bool = True,
+                 channels_to_batch: bool = False, optimizer_eps: float = OPTIMIZER_EPS_DEFAULT,
+                 ema: torch.nn.Module = None, centers_m: float = 0.9,
+                 teacher_score_method: str = "center", *args, **kwargs):
+        hp = dict(aug_image_key_1=aug_image_key_1, aug_image_key_2=aug_image_key_2,
+                  learning_rate=learning_rate, batch_size=batch_size, weight_decay=weight_decay,
+                  training_dataloader_call=training_dataloader_call, n_epochs=n_epochs,
+                  n_steps=n_steps, warmup_steps=warmup_steps, start_decay=start_decay,
+                  temperature=temperature, stop_gradient=stop_gradient,
+                  channels_to_batch=channels_to_batch, centers_m=centers_m,
+                  teacher_score_method=teacher_score_method, ssl_method="ibot")
+        for k, v in hp.items():   # plain attributes: set before Module.__init__, as the reference does
+            object.__setattr__(self, k, v)
+        if channels_to_batch is True:
+            kwargs["backbone_args"]["in_channels"] = 1
+        super().__init__(*args, **kwargs)   # iBOT.__init__: raises for a configuration that cannot run
+        self.optimizer_eps = optimizer_eps
+        self.ema = ema
+        if self.ema is None:
+            raise ValueError("iBOT requires an EMA (teacher) copy of the network "
+                             "(`ema` must be an ExponentialMovingAverage module).")
+        self.save_hyperparameters()
+        self.setup_metrics()
+        self.init_loss()
+        self.ema.update(self, exclude_keys=["centers"])
+
+    def init_loss(self):
+        conf = dict(temperatures=(self.temperature, self.temperature), n_features=self.out_dim,
+                    center_m=self.centers_m, teacher_score_method=self.teacher_score_method)
+        self.loss_mask = DinoLoss(**conf)
+        self.loss_global = DinoLoss(**conf)
+
+    def calculate_loss_global(self, y_red_1: torch.Tensor, y_red_2: torch.Tensor):
+        return self.loss_global(a=y_red_1, b=y_red_2.detach())
+
+    def calculate_loss_mask(self, a: torch.Tensor, b: torch.Tensor, m):
+        """``loss_mask(a[:, m], b[:, m])`` on the patch tokens a, b [B, T, K] -- the composed path:
+        the rows are gathered, then the dense loss. ``step`` computes the same value without the
+        gather (functional.ibot_view)."""
+        table = HF.patch_rows(m, a.shape[1], 0, a.device)     # IndexError on the host
+        return self.loss_mask(a.index_select(1, table.dev), b.detach().index_select(1, table.dev))
+
+    @torch.no_grad()
+    def _teacher_view(self, x, sums):
+        """(reduced [B, K], token logits [B, c + T, K]) of the teacher; the fp64 sums of its patch
+        rows go to ``sums`` [B, K]: one read of the logits for the "mean" reduction and the centre
+        sum."""
+        shadow = self.ema.shadow
+        y = shadow.token_logits(x).detach()
+        c = shadow.class_token
+        mean, _ = ops.ibot_token_sums(y, c, 1.0 / (y.shape[1] - c), raw_out=sums)
+        return (y[:, 0] if shadow.reduce_fn == "cls" else mean), y
+
+    @torch.no_grad()
+    def _pending_mask_centers(self, sums, rows):
+        """``loss_mask.update_centers(cat[t_1, t_2])`` from the per-item sums of the patch rows,
+        [2B, K] in fp64: the column sum over the ``rows`` teacher rows, pending as update_centers
+        leaves it."""
+        crit = self.loss_mask
+        crit.updated = False
+        crit.len_teacher_output = rows
+        crit.async_batch_center = ops.ibot_center_sum(sums)
+        if dist.is_initialized():
+            crit.reduce_handle = dist.all_reduce(crit.async_batch_center, async_op=True)
+
+    def _mask_view(self, s, y, m):
+        """(s_red, loss_mask) of one view from the token logits of student and teacher."""
+        crit, c = self.loss_mask, self.class_token
+        if crit.teacher_score_method == "center":
+            crit.apply_center_update()
+            return HF.ibot_view(s, y, m, crit.centers, crit.t1, crit.t2, c, self.reduce_fn)
+        table = HF.patch_rows(m, s.shape[1], c, s.device)
+        scores = crit.sinkhorn_knopp_teacher(y.index_select(1, table.dev))
+        return HF.ibot_view(s, y, table, scores, crit.t1, crit.t2, c, self.reduce_fn,
+                            teacher_is_scores=True)
+
+    def step(self, batch, loss_str: str, metrics: dict | None = None, train=False):
+        x1, x2 = batch[self.aug_image_key_1], batch[self.aug_image_key_2]
+        if self.channels_to_batch is True:
+            x1 = x1.reshape(-1, 1, *x1.shape[2:])
+            x2 = x2.reshape(-1, 1, *x2.shape[2:])
+        s_1, mc_1 = self.token_logits(x1, mask=True)
+        s_2, mc_2 = self.token_logits(x2, mask=True)
+        sums = torch.empty((x1.shape[0] + x2.shape[0], self.out_dim), device=x1.device,
+                           dtype=torch.float64)
+        t_red_1, t_1 = self._teacher_view(x1, sums[:x1.shape[0]])
+        t_red_2, t_2 = self._teacher_view(x2, sums[x1.shape[0]:])
+        c = self.class_token
+        # centre updates first: applied by the first loss call below
+        self.loss_global.update_centers(torch.cat([t_red_1, t_red_2]))
+        self._pending_mask_centers(
+            sums, t_1.shape[0] * (t_1.shape[1] - c) + t_2.shape[0] * (t_2.shape[1] - c))
+        s_red_1, mask_1 = self._mask_view(s_1, t_1, mc_1)
+        s_red_2, mask_2 = self._mask_view(s_2, t_2, mc_2)
+        loss_global = torch.add(self.calculate_loss_global(s_red_1, t_red_2) / 2.0,
+                                self.calculate_loss_global(s_red_2, t_red_1) / 2.0)
+        loss_mask = torch.add(mask_1 / 2.0, mask_2 / 2.0)
+        if metrics is not None:
+            self.update_metrics(torch.cat([s_red_1, s_red_2]), torch.cat([t_red_1, t_red_2]),
+                                metrics, log=True)
+        self.log(loss_str + "_global", loss_global, on_step=True, on_epoch=True, prog_bar=True)
+        self.log(loss_str + "_mask", loss_mask, on_step=True, on_epoch=True, prog_bar=True)
+        if self.ema is not None and train is True:
+            self.ema.update(self, exclude_keys=["centers"])
+        self.last_losses = (loss_mask, loss_global)
+        return loss_mask + loss_global
 
     def training_step(self, batch, batch_idx):
         return self.step(batch, "loss", train=True)

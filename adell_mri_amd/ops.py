@@ -10,6 +10,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2636,6 +2637,224 @@ def col_scale_dscale(dy, y0):
     ds = torch.empty((dy.shape[1],), device=dy.device, dtype=torch.float32)
     check(_lib.lib().adell_col_scale_dscale(_ptr(dy), _ptr(y0), dy.shape[0], dy.shape[1], _ptr(ds),
                                             _stream()))
+    return ds
+
+
+# ---- iBOT (csrc/ibot.hip) ---------------------------------------------------------------------
+class TokenRows:
+    """A set of token rows of a sequence of ``n`` tokens, checked on the host -- the kernels read the
+    tables unchecked: ``host`` (int64 numpy, sorted, unique, every entry in [0, n)), ``dev`` the same
+    as int32 [M] on ``device`` and ``inv`` int32 [n], token -> its position in ``host`` or -1. Both
+    tables travel to the device in one copy."""
+
+    def __init__(self, idx, n, device):
+        if isinstance(idx, torch.Tensor):
+            idx = idx.detach().cpu().numpy()
+        host = np.asarray(idx).reshape(-1)
+        if host.size < 1:
+            raise ValueError("token rows: at least one row (M >= 1)")
+        if not np.issubdtype(host.dtype, np.integer):
+            raise TypeError(f"token rows: integer indices expected, got {host.dtype}")
+        host = host.astype(np.int64)
+        if int(host.min()) < 0 or int(host.max()) >= int(n):
+            bad = int(host.max()) if int(host.max()) >= int(n) else int(host.min())
+            raise IndexError(f"index {bad} is out of bounds for a sequence of {int(n)} tokens")
+        if host.size > 1 and bool((np.diff(host) <= 0).any()):
+            raise ValueError("token rows: indices must be sorted and unique")
+        self.host, self.n, self.device = host, int(n), torch.device(device)
+        both = np.full((host.size + self.n,), -1, dtype=np.int32)
+        both[:host.size] = host
+        both[host.size + host] = np.arange(host.size, dtype=np.int32)
+        self._both = torch.from_numpy(both).to(self.device)
+        self.dev, self.inv = self._both[:host.size], self._both[host.size:]
+
+    def __len__(self):
+        return int(self.host.size)
+
+
+_TOKEN_ROWS = collections.OrderedDict()    # (indices, n, device) -> TokenRows, the last few
+_TOKEN_ROWS_KEPT = 16
+
+
+def token_rows(idx, n, device):
+    """``TokenRows`` of host indices ``idx`` (numpy / list / tensor; a ``TokenRows`` of the same
+    length and device passes through). Raises IndexError for an index outside [0, n) -- before
+    anything touches the device. The last few tables per (indices, n, device) are kept: a fixed
+    mask costs one upload."""
+    device = torch.device(device)
+    if isinstance(idx, TokenRows):
+        if idx.n != int(n) or idx.device != device:
+            return token_rows(idx.host, n, device)
+        return idx
+    if isinstance(idx, torch.Tensor):
+        idx = idx.detach().cpu().numpy()
+    arr = np.asarray(idx).reshape(-1)
+    key = (arr.astype(np.int64).tobytes() if np.issubdtype(arr.dtype, np.integer) else None,
+           int(n), str(device))
+    hit = _TOKEN_ROWS.get(key) if key[0] is not None else None
+    if hit is not None:
+        _TOKEN_ROWS.move_to_end(key)
+        return hit
+    rows = TokenRows(arr, n, device)
+    _TOKEN_ROWS[key] = rows
+    while len(_TOKEN_ROWS) > _TOKEN_ROWS_KEPT:
+        _TOKEN_ROWS.popitem(last=False)
+    return rows
+
+
+def _ibot_3d(what, *ts):
+    for t in ts:
+        if t.dim() != 3 or not t.is_contiguous():
+            raise ValueError(f"{what}: dense [B, tokens, features] tensors expected, got shape "
+                             f"{tuple(t.shape)}, strides {t.stride()}")
+
+
+def ibot_mask_tokens_fwd(x, idx, token):
+    """y = x [B, N, E] with the rows ``idx`` of every item replaced by ``token`` [E] (out of place)."""
+    if x.dim() != 3:
+        raise ValueError(f"ibot_mask_tokens: [B, N, E] expected, got {tuple(x.shape)}")
+    B, N, E = x.shape
+    rows = token_rows(idx, N, x.device)
+    _require_cuda(x, token)
+    _ibot_3d("ibot_mask_tokens", x)
+    token = token.reshape(-1).contiguous()
+    if token.numel() != E:
+        raise ValueError(f"ibot_mask_tokens: a token of {token.numel()} features for {E}")
+    y = torch.empty_like(x)
+    check(_lib.lib().adell_ibot_mask_tokens_fwd(_ptr(x), _ptr(rows.dev), _ptr(token), B, N, E,
+                                                len(rows), _ptr(y), _stream()))
+    return y
+
+
+def ibot_mask_tokens_bwd(dy, idx, need_x=True, need_token=True):
+    """(dx, dtoken): dy with the rows ``idx`` zeroed, and their sum over items and rows [E]."""
+    if dy.dim() != 3:
+        raise ValueError(f"ibot_mask_tokens: [B, N, E] expected, got {tuple(dy.shape)}")
+    B, N, E = dy.shape
+    rows = token_rows(idx, N, dy.device)
+    _require_cuda(dy)
+    _ibot_3d("ibot_mask_tokens", dy)
+    dx = torch.empty_like(dy) if need_x else None
+    dtoken = torch.empty((E,), device=dy.device, dtype=torch.float32) if need_token else None
+    check(_lib.lib().adell_ibot_mask_tokens_bwd(_ptr(dy), _ptr(rows.dev), B, N, E, len(rows),
+                                                _ptr(dx), _ptr(dtoken), _stream()))
+    return dx, dtoken
+
+
+def ibot_token_sums_plan(B, T, K):
+    """(splits of the token axis, tokens per split) of ``ibot_token_sums`` over T tokens. Host only."""
+    out = (ctypes.c_int * 2)()
+    check(_lib.lib().adell_ibot_token_sums_plan(int(B), int(T), int(K), out))
+    return int(out[0]), int(out[1])
+
+
+def ibot_token_sums(x, first=0, scale=1.0, want_raw=False, raw_out=None):
+    """out [B, K] = scale * sum_{t >= first} x[b, t, :] for x [B, Tt, K], accumulated in fp64; with
+    ``want_raw`` also the unscaled sums kept in fp64 ([B, K] float64: what ``ibot_center_sum`` adds
+    up), written into ``raw_out`` when given (B dense rows of a caller's buffer: no ``cat`` of the
+    views). One read of x; tokens added in a fixed order."""
+    _require_cuda(x)
+    _ibot_3d("ibot_token_sums", x)
+    B, Tt, K = x.shape
+    if not 0 <= int(first) < Tt:
+        raise IndexError(f"ibot_token_sums: first token {first} of {Tt}")
+    raw = None
+    if want_raw or raw_out is not None:
+        raw = torch.empty((B, K), device=x.device, dtype=torch.float64) if raw_out is None else raw_out
+        if (raw.dtype != torch.float64 or tuple(raw.shape) != (B, K) or not raw.is_contiguous()
+                or raw.device != x.device):
+            raise ValueError(f"ibot_token_sums: raw_out must be a dense float64 [{B}, {K}] on "
+                             f"{x.device}, got {raw.dtype} {tuple(raw.shape)}")
+    doubles = _lib.lib().adell_ibot_token_sums_workspace_doubles(B, Tt - int(first), K)
+    out = torch.empty((B, K), device=x.device, dtype=torch.float32)
+    work = torch.empty((doubles,), device=x.device, dtype=torch.float64) if doubles else None
+    check(_lib.lib().adell_ibot_token_sums(_ptr(x), B, Tt, K, int(first), float(scale), _ptr(work),
+                                           doubles, _ptr(out), _ptr(raw), _stream()))
+    return (out, raw) if raw is not None else out
+
+
+def ibot_center_sum(sums):
+    """[1, K] float32: the sum over the rows of fp64 token sums [R, K] (``ibot_token_sums``'s raw
+    output for the items of every view), rounded once -- ``dino_center_sum`` of all the teacher's
+    patch tokens without reading them again."""
+    if (not sums.is_cuda or sums.dtype != torch.float64 or sums.dim() != 2
+            or not sums.is_contiguous()):
+        raise _lib.AdellHipError("ibot_center_sum: dense float64 [R, K] sums on the GPU expected "
+                                 "(adell_mri_amd kernels run on MI355X only)")
+    out = torch.empty((1, sums.shape[1]), device=sums.device, dtype=torch.float32)
+    check(_lib.lib().adell_ibot_center_sum(_ptr(sums), sums.shape[0], sums.shape[1], _ptr(out),
+                                           _stream()))
+    return out
+
+
+def ibot_loss_fwd(s, y, rows, centers, t1, t2, teacher_is_scores=False, want_mean=False):
+    """``dino_loss_fwd`` over the rows ``(b, rows[j])`` of s [B, Tt, K], read in place: (loss_rows
+    [B * M], stats [B * M, 4]) and with ``want_mean`` their mean. The teacher is y [B, Tt, K], read
+    at the same rows, or with ``teacher_is_scores`` the dense scores [B * M, K] of those rows."""
+    if s.dim() != 3:
+        raise ValueError(f"ibot_loss: [B, tokens, K] expected, got {tuple(s.shape)}")
+    B, Tt, K = s.shape
+    rows = token_rows(rows, Tt, s.device)
+    M = len(rows)
+    _require_cuda(s, y, centers)
+    _ibot_3d("ibot_loss", s)
+    if teacher_is_scores:
+        if tuple(y.shape) != (B * M, K) or not y.is_contiguous():
+            raise ValueError(f"ibot_loss: dense scores [{B * M}, {K}] expected, got {tuple(y.shape)}")
+        centers = None
+    else:
+        _ibot_3d("ibot_loss", y)
+        if y.shape != s.shape:
+            raise ValueError(f"ibot_loss: shapes {tuple(s.shape)} and {tuple(y.shape)} differ")
+        centers = _dino_centers(centers, K)
+    R = B * M
+    floats = _lib.lib().adell_dino_loss_workspace_floats(R, K)
+    buf = torch.empty((5 * R + 4 + floats,), device=s.device, dtype=torch.float32)
+    stats, loss_rows, mean = buf[:4 * R].view(R, 4), buf[4 * R:5 * R], buf[5 * R]
+    base = buf.data_ptr()
+    check(_lib.lib().adell_ibot_loss_fwd(_ptr(s), _ptr(y), _ptr(centers), _ptr(rows.dev), B, Tt, K, M,
+                                         float(t1), float(t2), int(bool(teacher_is_scores)),
+                                         ctypes.c_void_p(base + 4 * (5 * R + 4)), floats,
+                                         ctypes.c_void_p(base + 16 * R), ctypes.c_void_p(base),
+                                         ctypes.c_void_p(base + 20 * R) if want_mean else None,
+                                         _stream()))
+    return (loss_rows, stats, mean) if want_mean else (loss_rows, stats)
+
+
+def ibot_bwd(s, y, rows, centers, stats, d_red, g_loss, class_token, reduce, t1, t2,
+             teacher_is_scores=False, shape=None):
+    """ds [B, Tt, K], every element written once by one launch: the gradient ``d_red`` [B, K] of the
+    reduced output (``reduce`` "cls": to the class row; "mean": to every patch row, / T) plus, on the
+    rows ``rows``, the gradient of the mean masked-row loss for its incoming gradient ``g_loss`` (one
+    element), recomputed from ``stats``. Either gradient may be None; without ``g_loss`` only
+    ``shape`` (or ``s``) and ``d_red`` are read."""
+    if reduce not in ("cls", "mean"):
+        raise ValueError(f"ibot_bwd: reduce {reduce!r}")
+    B, Tt, K = tuple(s.shape) if shape is None else tuple(shape)
+    c = int(bool(class_token))
+    M, inv = 0, None
+    if g_loss is not None:
+        rows = token_rows(rows, Tt, s.device)
+        M, inv = len(rows), rows.inv
+        _require_cuda(s, y, centers, stats, g_loss)
+        _ibot_3d("ibot_bwd", s)
+        centers = None if teacher_is_scores else _dino_centers(centers, K)
+        stats, g_loss = stats.contiguous(), g_loss.contiguous()
+    else:
+        s = y = centers = stats = None
+    if d_red is None and g_loss is None:
+        raise ValueError("ibot_bwd: d_red or g_loss")
+    _require_cuda(d_red)
+    if d_red is not None:
+        d_red = d_red.contiguous()
+        if tuple(d_red.shape) != (B, K):
+            raise ValueError(f"ibot_bwd: d_red {tuple(d_red.shape)} for [{B}, {K}]")
+    dev = d_red.device if d_red is not None else g_loss.device
+    ds = torch.empty((B, Tt, K), device=dev, dtype=torch.float32)
+    check(_lib.lib().adell_ibot_bwd(_ptr(s), _ptr(y), _ptr(centers), _ptr(stats), _ptr(inv),
+                                    _ptr(d_red), _ptr(g_loss), B, Tt, K, M, c,
+                                    int(reduce == "cls"), float(t1), float(t2),
+                                    int(bool(teacher_is_scores)), _ptr(ds), _stream()))
     return ds
 
 

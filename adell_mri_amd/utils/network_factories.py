@@ -2,8 +2,9 @@
 (adell_mri/utils/network_factories.py:493-701) and ``get_ssl_network`` (:705-1028) on this
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
 constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
-``DINOPL`` on a ViT encoder (:869-905; ``TypeError`` for any other ``net_type``). Members outside the
-built path (the MONAI wrappers, the other ViT-based SSL methods: I-JEPA, MAE, iBOT; Barlow Twins)
+``DINOPL`` and ``ssl_method="ibot"`` ``iBOTPL`` on a ViT encoder (:869-956; ``TypeError`` for any
+other ``net_type``). Members outside the built path (the MONAI wrappers, the other ViT-based SSL
+methods: I-JEPA and MAE; Barlow Twins)
 raise ``NotImplementedError`` -- there is no eager-torch fallback.
 """
 from typing import Any, Callable
@@ -13,7 +14,7 @@ import torch
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
 from ..modules.self_supervised.pl import (DINOPL, SelfSLConvNeXtPL, SelfSLResNetPL,
-                                          SelfSLUNetPL)
+                                          SelfSLUNetPL, iBOTPL)
 
 OPTIMIZER_EPS_DEFAULT = 1e-8
 ALLOWED_NET_TYPES = {
@@ -122,7 +123,14 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
     dictionaries (defaults :754-790) -- for vicregl with ``VICRegLocalLoss(**vic_reg_loss_params)``
     on the "representation" feature maps and the boxes of the batch; every other method name with ``net_type="convnext"``
     builds ``SelfSLConvNeXtPL`` from the whole configuration (:998-1026). ``"dino"`` builds
-    ``DINOPL`` (ViT backbone + MLP projection head, defaults :875-901) and needs ``ema``."""
+    ``DINOPL`` (ViT backbone + MLP projection head, defaults :875-901) and needs ``ema``.
+    ``"ibot"`` builds ``iBOTPL`` (:907-956) in the reference's order: ``TypeError`` unless
+    ``net_type == "vit"``, ``feature_map_dimensions`` (image size // patch size) and
+    ``n_encoder_features`` (``embedding_size``, else ``attention_dim``) derived from
+    ``backbone_args``, the masker's patch sizes [4, 4] ... [8, 8] by default, ``ValueError`` without
+    ``ema`` (raised by ``iBOTPL``). One difference on purpose: the reference's built-in 224 x 224
+    default backbone is not mirrored for iBOT -- a configuration without ``"backbone_args"`` raises
+    ``NotImplementedError``; every real configuration names its backbone."""
     common = {"training_dataloader_call": train_loader_call, "n_epochs": max_epochs,
               "n_steps": max_steps_optim, "warmup_steps": warmup_steps, "ema": ema,
               "batch_size": network_config.get("batch_size", 32),
@@ -151,7 +159,31 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
                   "teacher_score_method": network_config.get("teacher_score_method", "center"),
                   "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
         return DINOPL(**{**common, **config})
-    if ssl_method in ("ijepa", "mae", "ibot", "barlow"):
+    if ssl_method == "ibot":
+        if net_type != "vit":
+            raise TypeError("iBOT only supports net_type='vit', got %s" % net_type)
+        if "backbone_args" not in network_config:
+            raise NotImplementedError(
+                "ssl_method 'ibot': the reference's built-in 224 x 224 default backbone is not "
+                "mirrored for iBOT; `backbone_args` must be given in the network configuration")
+        backbone_args = network_config["backbone_args"]
+        config = {"aug_image_key_1": "augmented_image_1", "aug_image_key_2": "augmented_image_2",
+                  "backbone_args": backbone_args,
+                  "projection_head_args": network_config.get("projection_head_args",
+                                                             {"structure": [512, 256, 128]}),
+                  "out_dim": network_config.get("out_dim", 65536),
+                  "feature_map_dimensions": [s // p for s, p in zip(backbone_args["image_size"],
+                                                                    backbone_args["patch_size"])],
+                  "n_encoder_features": backbone_args.get("embedding_size",
+                                                          backbone_args["attention_dim"]),
+                  "min_patch_size": network_config.get("min_patch_size", [4, 4]),
+                  "max_patch_size": network_config.get("max_patch_size", [8, 8]),
+                  "temperature": network_config.get("temperature", 0.1),
+                  "centers_m": network_config.get("centers_m", 0.9),
+                  "teacher_score_method": network_config.get("teacher_score_method", "center"),
+                  "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
+        return iBOTPL(**{**common, **config})
+    if ssl_method in ("ijepa", "mae", "barlow"):
         raise NotImplementedError(f"ssl_method {ssl_method!r} (ViT / Barlow-Twins wrappers) is "
                                   "outside the HIP path (SURVEY.md section 2: out of scope)")
     boilerplate = {"training_dataloader_call": train_loader_call,

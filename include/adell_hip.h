@@ -815,6 +815,47 @@ int adell_row_mean_bwd(const float* dout, int rows, int C, float* dx, void* stre
 int adell_col_scale(const float* x, const float* s, int R, int K, float* y, void* stream);
 int adell_col_scale_dscale(const float* dy, const float* y0, int R, int K, float* ds, void* stream);
 
+/* iBOT (self_supervised/ibot.py, iBOTPL; csrc/ibot.hip): the masked-token objective on the prototype
+ * logits of every token. fp32, dense, no float atomics, results repeat bit for bit. Index tables are
+ * int32 on the device and are NOT range-checked here: the caller checks them on the host.
+ * adell_ibot_mask_tokens_fwd: y [B][N][E] = x with the rows idx[0..M) (sorted, unique, < N) of every
+ * item replaced by token [E]. _bwd: dx = dy with those rows zeroed, dtoken[e] = sum_b sum_j
+ * dy[b][idx[j]][e] in a fixed order; either may be NULL.
+ * adell_ibot_token_sums: out[b][k] = scale sum_{t >= first} x[b][t][k] for x [B][Tt][K], accumulated
+ * in fp64; raw [B][K] (may be NULL) the same sums unscaled and kept in fp64; one read of x.
+ * adell_ibot_token_sums_plan(B, T = Tt - first, K): out = {splits of the token axis, tokens per
+ * split} (host only); with more than one split the launch needs
+ * adell_ibot_token_sums_workspace_doubles(B, T, K) doubles. adell_ibot_center_sum: out[k] = the sum
+ * over the R rows of such fp64 sums [R][K] (the items of every view), rounded to fp32 once.
+ * adell_ibot_loss_fwd: adell_dino_loss_fwd over the R = B M rows r = b M + j: the student row is
+ * s[b][rows[j]][:] of s [B][Tt][K], the teacher row y[b][rows[j]][:] of y [B][Tt][K] or, with
+ * teacher_is_scores, row r of the dense scores y [R][K]. Plan and workspace: adell_dino_loss_plan(R, K),
+ * adell_dino_loss_workspace_floats(R, K); stats [R][4] as there. R <= 65535.
+ * adell_ibot_bwd: one launch writes every element of ds [B][Tt][K] once:
+ *   ds[b][t][:] = (reduce_cls and t == 0 ? d_red[b][:] : 0)
+ *               + (not reduce_cls and t >= class_token ? d_red[b][:] / (Tt - class_token) : 0)
+ *               + (inv[t] = j >= 0 ? g_loss[0] / (B M) (softmax(s / t1) sum p_t - p_t) / t1 : 0)
+ * with the probabilities recomputed from stats; inv [Tt] maps a token to its j or -1. d_red [B][K]
+ * and g_loss (1 float) may each be NULL (no such term; without g_loss s, y, stats, inv are unused). */
+int adell_ibot_mask_tokens_fwd(const float* x, const int* idx, const float* token, int B, int N, int E,
+                               int M, float* y, void* stream);
+int adell_ibot_mask_tokens_bwd(const float* dy, const int* idx, int B, int N, int E, int M, float* dx,
+                               float* dtoken, void* stream);
+int adell_ibot_token_sums_plan(int B, int T, int K, int* out);
+long adell_ibot_token_sums_workspace_doubles(int B, int T, int K);
+int adell_ibot_token_sums(const float* x, int B, int Tt, int K, int first, float scale,
+                          double* workspace, long workspace_doubles, float* out, double* raw,
+                          void* stream);
+int adell_ibot_center_sum(const double* sums, int R, int K, float* out, void* stream);
+int adell_ibot_loss_fwd(const float* s, const float* y, const float* centers, const int* rows, int B,
+                        int Tt, int K, int M, float t1, float t2, int teacher_is_scores,
+                        float* workspace, long workspace_floats, float* loss_rows, float* stats,
+                        float* loss_mean, void* stream);
+int adell_ibot_bwd(const float* s, const float* y, const float* centers, const float* stats,
+                   const int* inv, const float* d_red, const float* g_loss, int B, int Tt, int K, int M,
+                   int class_token, int reduce_cls, float t1, float t2, int teacher_is_scores,
+                   float* ds, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
