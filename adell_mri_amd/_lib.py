@@ -109,6 +109,7 @@ SIGNATURES = {
     "adell_split_rows_to_f32": (_i, [_vp, _i, _l, _i, _vp, _vp, _vp]),
     "adell_conv3d_f16x3_rows_ok": (_i, [ctypes.POINTER(ConvDesc)]),
     "adell_conv3d_bwd_weight_f16x3_rows_ok": (_i, [ctypes.POINTER(ConvDesc)]),
+    "adell_conv3d_bwd_weight_f16x3_plan": (_i, [ctypes.POINTER(ConvDesc), _vp]),
     "adell_conv3d_bwd_weight_f16x3_rows": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 10
                                            + [ctypes.c_size_t, _vp]),
     "adell_conv3d_fwd_f16x3_rows": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 10 + [_i, _vp, _vp]),

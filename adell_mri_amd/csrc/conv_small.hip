@@ -9,7 +9,7 @@
 //    head): one pass over the activation, HBM-bound.
 //
 // Called from the conv entry points of conv3d.hip / conv_wgrad*.hip when the shapes qualify.
-#include "common.h"
+#include "conv_wgrad_host.h"
 
 // ---------------------------------------------------------------------------
 // small-Cin weight gradient

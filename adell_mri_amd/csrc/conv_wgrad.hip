@@ -13,7 +13,7 @@
 // region writes its partial dW slab to the workspace; a second kernel reduces
 // the slabs in fixed order (deterministic) straight into torch's canonical
 // [Cout][Cin][kD][kH][kW] layout.
-#include "common.h"
+#include "conv_wgrad_host.h"
 
 struct WgradArgs {
   const float* x0;
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(1024) void adell_wgrad_reduce4_kernel(
   if (db != nullptr && blockIdx.x == 0) adell_db_fold(wsdb, db, R, Cout);
 }
 
-// shared with conv_wgrad_f16.hip
+// (declared in conv_wgrad_host.h: conv_wgrad_f16.hip folds its slabs with it too)
 extern "C" int adell_wgrad_reduce_launch(const float* ws, float* out, int R, int ntap, int Cin,
                                          int Cout, const float* wsdb, float* db, void* stream) {
   const long total = (long)ntap * Cin * Cout;
@@ -369,14 +369,24 @@ extern "C" int adell_wgrad_reduce_launch(const float* ws, float* out, int R, int
   return ADELL_OK;
 }
 
-struct WgradPlan {
-  int lTX, lTY, lTZ, HX, HY, HZ, TCI, TCO, nci, nco, KDg, ngrp, R, maxj;
-  size_t lds;
-  long ntiles;
+// fp32 instances of adell_conv_wgrad_kernel<MAXJ>, smallest first: a plan runs on the first one
+// that holds its jobs per wave
+template <int MAXJ>
+static int adell_launch_wgrad(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  return adell_launch<adell_conv_wgrad_kernel<MAXJ>>(grid, dim3(256), lds, st, a);
+}
+struct WgradInstance {
+  int maxj;
+  int (*launch)(const WgradArgs&, dim3, size_t, hipStream_t);
 };
+static const WgradInstance kWgradInstances[] = {
+    {2, adell_launch_wgrad<2>}, {5, adell_launch_wgrad<5>}, {7, adell_launch_wgrad<7>},
+    {9, adell_launch_wgrad<9>}};
 
-static int adell_wgrad_plan(int N, int Cin, int Cout, int KD, int KH, int KW, int SD,
-                            int SH, int SW, int Do, int Ho, int Wo, WgradPlan* p) {
+int adell_wgrad_plan(const adell_conv3d_desc& c, WgradPlan* p) {
+  const int Cin = c.C0 + c.C1, Cout = c.Cout;
+  const int KD = c.KD, KH = c.KH, KW = c.KW, SD = c.SD, SH = c.SH, SW = c.SW;
+  const int Do = c.Do, Ho = c.Ho, Wo = c.Wo;
   p->TCI = Cin > 32 ? 64 : 32;
   p->TCO = Cout > 32 ? 64 : 32;
   p->nci = adell_cdiv(Cin, p->TCI);
@@ -390,6 +400,11 @@ static int adell_wgrad_plan(int N, int Cin, int Cout, int KD, int KH, int KW, in
     adell_set_error("wgrad: %d jobs per wave unsupported", p->maxj);
     return ADELL_E_UNSUPPORTED;
   }
+  for (const WgradInstance& k : kWgradInstances)
+    if (p->maxj <= k.maxj) {
+      p->maxj_inst = k.maxj;
+      break;
+    }
   // brick: start from 8x8x2 and shrink until the LDS budget (<= 80 KiB, two
   // blocks per CU) is met; the brick keeps >= 4 voxels (two k-steps per loop trip).
   int l[3] = {3, 3, 1};
@@ -418,7 +433,7 @@ static int adell_wgrad_plan(int N, int Cin, int Cout, int KD, int KH, int KW, in
     --l[d];
   }
   p->lTX = l[0]; p->lTY = l[1]; p->lTZ = l[2];
-  p->ntiles = (long)N * adell_cdiv(Wo, 1 << l[0]) * adell_cdiv(Ho, 1 << l[1]) *
+  p->ntiles = (long)c.N * adell_cdiv(Wo, 1 << l[0]) * adell_cdiv(Ho, 1 << l[1]) *
               adell_cdiv(Do, 1 << l[2]);
   // One resident wave of blocks: 2 blocks per CU by registers (<= 256 per lane at
   // MAXJ <= 9), fewer if LDS does not allow it; R regions fill exactly that.
@@ -433,77 +448,56 @@ static int adell_wgrad_plan(int N, int Cin, int Cout, int KD, int KH, int KW, in
   return ADELL_OK;
 }
 
-static size_t adell_wgrad_ws_bytes(const WgradPlan& p, int ntap, int Cin, int Cout) {
-  return ((size_t)p.R * ntap * Cin * Cout + (size_t)p.R * Cout) * sizeof(float);
-}
-
-template <int MAXJ>
-static int adell_launch_wgrad(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  return adell_launch<adell_conv_wgrad_kernel<MAXJ>>(grid, dim3(256), lds, st, a);
+static size_t adell_wgrad_ws_bytes(const WgradPlan& p, const adell_conv3d_desc& d) {
+  const size_t Cin = d.C0 + d.C1, ntap = (size_t)d.KD * d.KH * d.KW;
+  return ((size_t)p.R * ntap * Cin * d.Cout + (size_t)p.R * d.Cout) * sizeof(float);
 }
 
 // Core: X is the strided/haloed operand (its channels index dW's "Cin" axis), dY
 // the dense one. out is [CoutY][CinX][ntap].
-static int adell_wgrad_core(int N, int D, int H, int W, int C0, int C1, const float* x0,
-                            const float* x1, int Cout, int Do, int Ho, int Wo,
-                            const float* dy, int KD, int KH, int KW, int SD, int SH,
-                            int SW, int PD, int PH, int PW, float* out, float* db, void* ws,
-                            size_t ws_bytes, hipStream_t st) {
-  const int Cin = C0 + C1;
+static int adell_wgrad_core(const adell_conv3d_desc& d, const float* x0, const float* x1,
+                            const float* dy, float* out, float* db, void* ws, size_t ws_bytes,
+                            hipStream_t st) {
+  const int Cin = d.C0 + d.C1;
   WgradPlan p;
-  int rc = adell_wgrad_plan(N, Cin, Cout, KD, KH, KW, SD, SH, SW, Do, Ho, Wo, &p);
+  int rc = adell_wgrad_plan(d, &p);
   if (rc != ADELL_OK) return rc;
-  const int ntap = KD * KH * KW;
-  const size_t need = adell_wgrad_ws_bytes(p, ntap, Cin, Cout);
+  const int ntap = d.KD * d.KH * d.KW;
+  const size_t need = adell_wgrad_ws_bytes(p, d);
   ADELL_REQUIRE(ws != nullptr && ws_bytes >= need, "wgrad: workspace too small (%zu < %zu)",
                 ws_bytes, need);
   WgradArgs a = {};
   a.x0 = x0; a.x1 = x1; a.dy = dy; a.ws = (float*)ws;
-  a.wsdb = db ? (float*)ws + (size_t)p.R * ntap * Cin * Cout : nullptr;
-  a.N = N; a.D = D; a.H = H; a.W = W;
-  a.C0 = C0; a.C1 = C1; a.Cin = Cin; a.Cout = Cout;
-  a.KD = KD; a.KH = KH; a.KW = KW; a.SD = SD; a.SH = SH; a.SW = SW;
-  a.PD = PD; a.PH = PH; a.PW = PW;
-  a.Do = Do; a.Ho = Ho; a.Wo = Wo;
+  a.wsdb = db ? (float*)ws + (size_t)p.R * ntap * Cin * d.Cout : nullptr;
+  a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
+  a.C0 = d.C0; a.C1 = d.C1; a.Cin = Cin; a.Cout = d.Cout;
+  a.KD = d.KD; a.KH = d.KH; a.KW = d.KW; a.SD = d.SD; a.SH = d.SH; a.SW = d.SW;
+  a.PD = d.PD; a.PH = d.PH; a.PW = d.PW;
+  a.Do = d.Do; a.Ho = d.Ho; a.Wo = d.Wo;
   a.lTX = p.lTX; a.lTY = p.lTY; a.lTZ = p.lTZ;
-  a.ntx = adell_cdiv(Wo, 1 << p.lTX);
-  a.nty = adell_cdiv(Ho, 1 << p.lTY);
-  a.ntz = adell_cdiv(Do, 1 << p.lTZ);
+  a.ntx = adell_cdiv(d.Wo, 1 << p.lTX);
+  a.nty = adell_cdiv(d.Ho, 1 << p.lTY);
+  a.ntz = adell_cdiv(d.Do, 1 << p.lTZ);
   a.HX = p.HX; a.HY = p.HY; a.HZ = p.HZ;
   a.TCI = p.TCI; a.TCO = p.TCO; a.nci = p.nci; a.nco = p.nco;
   a.KDg = p.KDg; a.R = p.R;
-  a.vecx = (C0 % 4 == 0) && (C1 % 4 == 0) && (((uintptr_t)x0 & 15) == 0) &&
+  a.vecx = (d.C0 % 4 == 0) && (d.C1 % 4 == 0) && (((uintptr_t)x0 & 15) == 0) &&
            (((uintptr_t)x1 & 15) == 0);
-  a.vecy = (Cout % 4 == 0) && (((uintptr_t)dy & 15) == 0);
-  dim3 grid((unsigned)p.R, (unsigned)(p.nci * p.nco), (unsigned)p.ngrp);
-  if (p.maxj <= 2)
-    rc = adell_launch_wgrad<2>(a, grid, p.lds, st);
-  else if (p.maxj <= 5)
-    rc = adell_launch_wgrad<5>(a, grid, p.lds, st);
-  else if (p.maxj <= 7)
-    rc = adell_launch_wgrad<7>(a, grid, p.lds, st);
-  else
-    rc = adell_launch_wgrad<9>(a, grid, p.lds, st);
+  a.vecy = (d.Cout % 4 == 0) && (((uintptr_t)dy & 15) == 0);
+  const dim3 grid((unsigned)p.R, (unsigned)(p.nci * p.nco), (unsigned)p.ngrp);
+  for (const WgradInstance& k : kWgradInstances)
+    if (k.maxj == p.maxj_inst) rc = k.launch(a, grid, p.lds, st);
   if (rc != ADELL_OK) return rc;
-  return adell_wgrad_reduce_launch((const float*)ws, out, p.R, ntap, Cin, Cout,
+  return adell_wgrad_reduce_launch((const float*)ws, out, p.R, ntap, Cin, d.Cout,
                                    (const float*)a.wsdb, db, st);
 }
-
-// small-channel paths (conv_small.hip)
-extern "C" long adell_wgrad_small_workspace(const adell_conv3d_desc* d);
-extern "C" int adell_wgrad_small(const adell_conv3d_desc* d, const float* x0, const float* x1,
-                                 const float* dy, float* dw, float* db, void* workspace,
-                                 size_t workspace_bytes, void* stream);
 
 extern "C" long adell_conv3d_bwd_weight_workspace(const adell_conv3d_desc* d) {
   if (!d) return ADELL_E_BADARG;
   if (adell_wgrad_small_workspace(d) > 0) return adell_wgrad_small_workspace(d);
   WgradPlan p;
-  const int Cin = d->C0 + d->C1;
-  if (adell_wgrad_plan(d->N, Cin, d->Cout, d->KD, d->KH, d->KW, d->SD, d->SH, d->SW, d->Do,
-                       d->Ho, d->Wo, &p) != ADELL_OK)
-    return ADELL_E_UNSUPPORTED;
-  return (long)adell_wgrad_ws_bytes(p, d->KD * d->KH * d->KW, Cin, d->Cout);
+  if (adell_wgrad_plan(*d, &p) != ADELL_OK) return ADELL_E_UNSUPPORTED;
+  return (long)adell_wgrad_ws_bytes(p, *d);
 }
 
 extern "C" int adell_conv3d_bwd_weight(const adell_conv3d_desc* d, const float* x0,
@@ -514,19 +508,23 @@ extern "C" int adell_conv3d_bwd_weight(const adell_conv3d_desc* d, const float* 
   ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight: C1 > 0 needs x1");
   if (adell_wgrad_small_workspace(d) > 0)
     return adell_wgrad_small(d, x0, x1, dy, dw, db, workspace, workspace_bytes, stream);
-  return adell_wgrad_core(d->N, d->D, d->H, d->W, d->C0, d->C1, x0, x1, d->Cout, d->Do,
-                          d->Ho, d->Wo, dy, d->KD, d->KH, d->KW, d->SD, d->SH, d->SW, d->PD,
-                          d->PH, d->PW, dw, db, workspace, workspace_bytes, (hipStream_t)stream);
+  return adell_wgrad_core(*d, x0, x1, dy, dw, db, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // dW[ci][co][tap] = sum_v x[v][ci] * dy[2v+tap][co]: the same GEMM with the roles
-// swapped (dy is the strided operand, x the dense one).
+// swapped (dy is the strided operand, x the dense one): the descriptor of that conv, whose
+// "input" is the transposed conv's output and whose "output" is its input.
+static adell_conv3d_desc adell_convt_wgrad_desc(int N, int D, int H, int W, int Cin, int Cout,
+                                                int FD, int FH, int FW) {
+  return {N, FD * D, FH * H, FW * W, Cout, 0, Cin, FD, FH, FW, FD, FH, FW, 0, 0, 0, D, H, W};
+}
+
 extern "C" long adell_convtranspose3d_bwd_weight_workspace(int N, int D, int H, int W, int Cin,
                                                            int Cout, int FD, int FH, int FW) {
+  const adell_conv3d_desc d = adell_convt_wgrad_desc(N, D, H, W, Cin, Cout, FD, FH, FW);
   WgradPlan p;
-  if (adell_wgrad_plan(N, Cout, Cin, FD, FH, FW, FD, FH, FW, D, H, W, &p) != ADELL_OK)
-    return ADELL_E_UNSUPPORTED;
-  return (long)adell_wgrad_ws_bytes(p, FD * FH * FW, Cout, Cin);
+  if (adell_wgrad_plan(d, &p) != ADELL_OK) return ADELL_E_UNSUPPORTED;
+  return (long)adell_wgrad_ws_bytes(p, d);
 }
 
 extern "C" long adell_convtranspose3d_k2s2_bwd_weight_workspace(int N, int D, int H, int W,
@@ -541,9 +539,8 @@ extern "C" int adell_convtranspose3d_bwd_weight(int N, int D, int H, int W, int 
   ADELL_REQUIRE(x && dy && dw, "convT_bwd_weight: null pointer");
   ADELL_REQUIRE((FD == 1 || FD == 2) && (FH == 1 || FH == 2) && (FW == 1 || FW == 2),
                 "convT_bwd_weight: kernel=stride must be 1 or 2 per dim");
-  return adell_wgrad_core(N, FD * D, FH * H, FW * W, Cout, 0, dy, nullptr, Cin, D, H, W, x, FD,
-                          FH, FW, FD, FH, FW, 0, 0, 0, dw, nullptr, workspace, workspace_bytes,
-                          (hipStream_t)stream);
+  return adell_wgrad_core(adell_convt_wgrad_desc(N, D, H, W, Cin, Cout, FD, FH, FW), dy, nullptr,
+                          x, dw, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int adell_convtranspose3d_k2s2_bwd_weight(int N, int D, int H, int W, int Cin,

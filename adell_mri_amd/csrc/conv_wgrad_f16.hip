@@ -15,7 +15,7 @@
 // read once per k-step and shared by its taps. Ranges: X and dY carry one power-of-two
 // scale per tensor (absmax kernels below), undone when the slab is written. Split-K
 // over brick regions + fixed-order slab reduction as in conv_wgrad.hip.
-#include "common.h"
+#include "conv_wgrad_host.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -427,43 +427,10 @@ __global__ void adell_absmax2_kernel(const float* __restrict__ x, long n, unsign
   if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(mx));
 }
 
-// implemented in conv_wgrad.hip
-extern "C" int adell_wgrad_reduce_launch(const float* ws, float* out, int R, int ntap, int Cin,
-                                         int Cout, const float* wsdb, float* db, void* stream);
-
-// z-ring kernel for 3^3 stride-1 convolutions (conv_wgrad_zring.hip)
-struct WgradZrPlan {
-  int ntx, nty, nseg, seglen, nci, nco, R, t16;
-};
-extern "C" int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
-                                      int KH, int KW, int SD, int SH, int SW, int Do, int Ho, int Wo,
-                                      int* plan);   // plan: the eight ints of a WgradZrPlan
-extern "C" size_t adell_wgrad_zring_ws_floats(const WgradZrPlan* p, int Cin, int Cout);
-// the 32 -> 32 stride-2 downsampling layer (conv_wgrad_s2.hip)
-struct WgradS2Plan {
-  int ntx, nty, ntz, nbricks, blocks, R;
-};
-extern "C" int adell_wgrad_s2_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
-                                   int KH, int KW, int SD, int SH, int SW, int PD, int PH, int PW,
-                                   int Do, int Ho, int Wo, WgradS2Plan* p);
-extern "C" int adell_wgrad_s2_launch(const WgradS2Plan* p, int N, int D, int H, int W, const float* x,
-                                     int Do, int Ho, int Wo, const float* dy, float* slabs,
-                                     float* wsdb, const unsigned* xmax, const unsigned* ymax,
-                                     hipStream_t st);
-extern "C" int adell_wgrad_zring_launch(const WgradZrPlan* p, int N, int D, int H, int W, int C0,
-                                        int C1, const float* x0, const float* x1, int Cout, int Do,
-                                        int Ho, int Wo, const float* dy, int PD, int PH, int PW,
-                                        float* slabs, float* wsdb, const unsigned* xmax,
-                                        const unsigned* ymax, hipStream_t st,
-                                        const int* xk0 = nullptr, const int* xk1 = nullptr);
-
-struct WgradF16Plan {
-  int lTY, HX, HY, TCI, TCO, nci, nco, maxj, R, ntx, nty, GKH, NGY, ksplit;
-  size_t lds;
-};
-
-static int adell_wgrad_f16_plan(int N, int Cin, int Cout, int KD, int KH, int KW, int SH, int SW,
-                                int Do, int Ho, int Wo, WgradF16Plan* p) {
+// ---- host side ----------------------------------------------------------------------------------
+static int adell_wgrad_f16_plan(const adell_conv3d_desc& d, WgradF16Plan* p) {
+  const int Cin = d.C0 + d.C1, Cout = d.Cout, KH = d.KH, KW = d.KW, SH = d.SH, SW = d.SW;
+  const int Ho = d.Ho;
   p->TCI = Cin > 32 ? 64 : 32;
   p->TCO = Cout > 32 ? 64 : 32;
   p->nci = adell_cdiv(Cin, p->TCI);
@@ -500,10 +467,10 @@ static int adell_wgrad_f16_plan(int N, int Cin, int Cout, int KD, int KH, int KW
     adell_set_error("wgrad f16x3: cannot fit LDS (%zu B)", p->lds);
     return ADELL_E_UNSUPPORTED;
   }
-  p->ntx = adell_cdiv(Wo, 8);
+  p->ntx = adell_cdiv(d.Wo, 8);
   p->nty = adell_cdiv(Ho, 1 << p->lTY);
-  const long nbricks = (long)N * p->ntx * p->nty * Do;
-  const long chan_blocks = (long)p->nci * p->nco * KD * p->NGY;
+  const long nbricks = (long)d.N * p->ntx * p->nty * d.Do;
+  const long chan_blocks = (long)p->nci * p->nco * d.KD * p->NGY;
   int per_cu = (int)((160 * 1024) / p->lds);
   if (per_cu > 2) per_cu = 2;
   if (per_cu < 1) per_cu = 1;
@@ -514,147 +481,202 @@ static int adell_wgrad_f16_plan(int N, int Cin, int Cout, int KD, int KH, int KW
   return ADELL_OK;
 }
 
-static size_t adell_wgrad_f16_ws(const WgradF16Plan& p, int ntap, int Cin, int Cout) {
-  // slabs + db slabs + two absmax words
-  return ((size_t)p.R * ntap * Cin * Cout + (size_t)p.R * Cout + 4) * sizeof(float);
-}
-
-template <int MAXJ, int PFX = 0, int PFY = 0, int MINB = 2>
+// The instances of the per-plane kernel. A plan runs on the first row that holds its jobs per wave
+// (maxj), whose k-split requirement it meets, and -- for a pipelined row, pfx > 0 -- whose pfx / pfy
+// 16-byte loads per thread cover the plan's X halo brick / dY brick.
+template <int MAXJ, int PFX = 0, int PFY = 0>
 static int adell_launch_wgrad_f16(const WgradF16Args& a, dim3 grid, size_t lds, hipStream_t st) {
-  return adell_launch<adell_conv_wgrad_f16_kernel<MAXJ, PFX, PFY, MINB>>(grid, dim3(256), lds, st, a);
+  return adell_launch<adell_conv_wgrad_f16_kernel<MAXJ, PFX, PFY>>(grid, dim3(256), lds, st, a);
+}
+struct WgradF16Instance {
+  int maxj, pfx, pfy;
+  bool ksplit;          // only plans that split the k-steps over the waves (32 x 32 channels)
+  int (*launch)(const WgradF16Args&, dim3, size_t, hipStream_t);
+};
+static const WgradF16Instance kWgradF16Instances[] = {
+    {2, 0, 0, false, adell_launch_wgrad_f16<2>},
+    {3, 0, 0, false, adell_launch_wgrad_f16<3>},
+    {5, 4, 2, true, adell_launch_wgrad_f16<5, 4, 2>},    // 32 x 32 channels: pipelined
+    {5, 7, 2, false, adell_launch_wgrad_f16<5, 7, 2>},   // 64 x 32 channels: pipelined
+    {5, 4, 4, false, adell_launch_wgrad_f16<5, 4, 4>},   // 32 x 64 channels: pipelined
+    {5, 0, 0, false, adell_launch_wgrad_f16<5>},
+    {7, 0, 0, false, adell_launch_wgrad_f16<7>},
+    // 64 x 64 channels: the prefetch does not fit 256 registers, and at one block per CU
+    // (512 registers, accumulators in AGPRs) it measured 152 TF against 194 TF in place
+    {9, 0, 0, false, adell_launch_wgrad_f16<9>},
+};
+
+static const WgradF16Instance* adell_wgrad_f16_instance(const WgradF16Plan& p) {
+  const long xloads = (long)p.HX * p.HY * (p.TCI / 4), yloads = 8L * (1 << p.lTY) * (p.TCO / 4);
+  for (const WgradF16Instance& k : kWgradF16Instances)
+    if (p.maxj <= k.maxj && (!k.ksplit || p.ksplit > 1) &&
+        (k.pfx == 0 || (xloads <= k.pfx * 256 && yloads <= k.pfy * 256)))
+      return &k;
+  return nullptr;   // (not reached: a plan has maxj <= 9)
 }
 
-static int adell_wgrad_f16_core(int N, int D, int H, int W, int C0, int C1, const float* x0,
-                                const float* x1, int Cout, int Do, int Ho, int Wo,
-                                const float* dy, int KD, int KH, int KW, int SD, int SH, int SW,
-                                int PD, int PH, int PW, float* out, float* db,
-                                const uint32_t* xmax_in, const uint32_t* ymax_in, void* ws,
-                                size_t ws_bytes, hipStream_t st, const int* xk0 = nullptr,
-                                const int* xk1 = nullptr) {
-  const int Cin = C0 + C1;
-  WgradF16Plan p = {};
-  WgradZrPlan zp;
-  const bool zring = adell_wgrad_zring_plan(N, D, H, W, C0, C1, Cout, KD, KH, KW, SD, SH, SW, Do, Ho,
-                                            Wo, reinterpret_cast<int*>(&zp)) != 0;
-  // split-row sources: the z-ring kernel only, and no 32-channel tile across the two sources
-  ADELL_REQUIRE((!xk0 && !xk1) || (zring && (C1 == 0 || C0 % 32 == 0)),
+// The route of one weight gradient, from the descriptor and the tuning switches alone (operand
+// alignment only sets vecx / vecy at the launch). Order: small-channel kernel, z-ring, stride-2
+// sub-lattice kernel, per-plane kernel. The launcher, the workspace query, rows_ok and the plan query
+// all read this one value. route: the ADELL_WGRAD_* ids of include/adell_hip.h.
+struct WgradRoute {
+  int route;
+  WgradZrPlan zr;                  // ADELL_WGRAD_ZRING32 / _ZRING16
+  WgradS2Plan s2;                  // ADELL_WGRAD_S2
+  WgradF16Plan pl;                 // ADELL_WGRAD_PLANE, with its instance and grid
+  const WgradF16Instance* inst;
+  dim3 grid;
+  int R;                           // regions = slabs the route writes (0: small)
+  bool rows_ok;                    // takes split-row sources: z-ring, and no 32-channel tile across
+                                   // the two sources
+};
+
+static int adell_wgrad_route(const adell_conv3d_desc& d, WgradRoute* r) {
+  *r = WgradRoute();
+  if (adell_wgrad_small_workspace(&d) > 0) {   // Cin <= 4: vector-ALU kernel, exact fp32
+    r->route = ADELL_WGRAD_SMALL;
+  } else if (adell_wgrad_zring_plan_desc(d, r->zr)) {
+    r->route = r->zr.t16 ? ADELL_WGRAD_ZRING16 : ADELL_WGRAD_ZRING32;
+    r->R = r->zr.R;
+    r->rows_ok = d.C1 == 0 || d.C0 % 32 == 0;
+  } else if (adell_wgrad_s2_plan(d, r->s2)) {
+    r->route = ADELL_WGRAD_S2;
+    r->R = r->s2.R;
+  } else {
+    r->route = ADELL_WGRAD_PLANE;
+    const int rc = adell_wgrad_f16_plan(d, &r->pl);
+    if (rc != ADELL_OK) return rc;
+    r->inst = adell_wgrad_f16_instance(r->pl);
+    r->grid = dim3((unsigned)r->pl.R, (unsigned)(r->pl.nci * r->pl.nco), (unsigned)(d.KD * r->pl.NGY));
+    r->R = r->pl.R;
+  }
+  return ADELL_OK;
+}
+
+// slabs + db slabs + two absmax words, for R regions
+static size_t adell_wgrad_f16_ws(int R, const adell_conv3d_desc& d) {
+  const size_t Cin = d.C0 + d.C1, ntap = (size_t)d.KD * d.KH * d.KW;
+  return ((size_t)R * ntap * Cin * d.Cout + (size_t)R * d.Cout + 4) * sizeof(float);
+}
+
+// Regions the workspace QUERY sizes the slabs for: the larger of the route's own count and the
+// per-plane plan's, so that a later call may take either kernel (adell_set_tuning may flip
+// wgrad_nozring between the query and the launch, and the per-plane kernel is what the z-ring and
+// stride-2 routes fall back to). The launch itself needs its own route's R only.
+static int adell_wgrad_ws_regions(const adell_conv3d_desc& d, const WgradRoute& r) {
+  if (r.route == ADELL_WGRAD_PLANE) return r.R;
+  WgradF16Plan q = {};
+  if (adell_wgrad_f16_plan(d, &q) != ADELL_OK) q.R = 0;
+  return r.R > q.R ? r.R : q.R;
+}
+
+static long adell_wgrad_f16_workspace(const adell_conv3d_desc& d, const WgradRoute& r) {
+  if (r.route == ADELL_WGRAD_SMALL) return adell_wgrad_small_workspace(&d);
+  return (long)adell_wgrad_f16_ws(adell_wgrad_ws_regions(d, r), d);
+}
+
+static int adell_wgrad_plane_launch(const adell_conv3d_desc& d, const WgradRoute& r, const float* x0,
+                                    const float* x1, const float* dy, float* slabs, float* wsdb,
+                                    const unsigned* xmax, const unsigned* ymax, hipStream_t st) {
+  const WgradF16Plan& p = r.pl;
+  WgradF16Args a = {};
+  a.x0 = x0; a.x1 = x1; a.dy = dy; a.ws = slabs; a.wsdb = wsdb;
+  a.xmax = xmax; a.ymax = ymax;
+  a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
+  a.C0 = d.C0; a.C1 = d.C1; a.Cin = d.C0 + d.C1; a.Cout = d.Cout;
+  a.KD = d.KD; a.KH = d.KH; a.KW = d.KW; a.SD = d.SD; a.SH = d.SH; a.SW = d.SW;
+  a.PD = d.PD; a.PH = d.PH; a.PW = d.PW;
+  a.Do = d.Do; a.Ho = d.Ho; a.Wo = d.Wo;
+  a.lTY = p.lTY; a.ntx = p.ntx; a.nty = p.nty; a.HX = p.HX; a.HY = p.HY;
+  a.GKH = p.GKH; a.NGY = p.NGY;
+  a.TCI = p.TCI; a.TCO = p.TCO; a.nci = p.nci; a.nco = p.nco; a.R = p.R;
+  a.ksplit = p.ksplit;
+  a.vecx = (d.C0 % 4 == 0) && (d.C1 % 4 == 0) && (((uintptr_t)x0 & 15) == 0) &&
+           (((uintptr_t)x1 & 15) == 0);
+  a.vecy = (d.Cout % 4 == 0) && (((uintptr_t)dy & 15) == 0);
+  return r.inst->launch(a, r.grid, p.lds, st);
+}
+
+// xk0 / xk1 non-null = that source holds split rows (adell_conv3d_bwd_weight_f16x3_rows)
+static int adell_wgrad_f16_run(const adell_conv3d_desc& d, const float* x0, const float* x1,
+                               const float* dy, float* out, float* db, const uint32_t* xmax_in,
+                               const uint32_t* ymax_in, void* ws, size_t ws_bytes, hipStream_t st,
+                               const int* xk0 = nullptr, const int* xk1 = nullptr) {
+  WgradRoute r;
+  const int prc = adell_wgrad_route(d, &r);
+  ADELL_REQUIRE((!xk0 && !xk1) || r.rows_ok,
                 "wgrad f16x3: this problem does not take split-row sources "
                 "(adell_conv3d_bwd_weight_f16x3_rows_ok)");
-  WgradS2Plan sp;
-  const bool s2 = !zring && adell_wgrad_s2_plan(N, D, H, W, C0, C1, Cout, KD, KH, KW, SD, SH, SW, PD,
-                                                PH, PW, Do, Ho, Wo, &sp) != 0;
-  int rc = ADELL_OK;
-  if (zring)
-    p.R = zp.R;
-  else if (s2)
-    p.R = sp.R;
-  else
-    rc = adell_wgrad_f16_plan(N, Cin, Cout, KD, KH, KW, SH, SW, Do, Ho, Wo, &p);
-  if (rc != ADELL_OK) return rc;
-  const int ntap = KD * KH * KW;
-  const size_t need = adell_wgrad_f16_ws(p, ntap, Cin, Cout);
+  if (prc != ADELL_OK) return prc;
+  if (r.route == ADELL_WGRAD_SMALL)
+    return adell_wgrad_small(&d, x0, x1, dy, out, db, ws, ws_bytes, st);
+  const int Cin = d.C0 + d.C1, Cout = d.Cout, ntap = d.KD * d.KH * d.KW;
+  const size_t need = adell_wgrad_f16_ws(r.R, d);
   ADELL_REQUIRE(ws != nullptr && ws_bytes >= need, "wgrad f16x3: workspace too small (%zu < %zu)",
                 ws_bytes, need);
   float* slabs = (float*)ws;
-  float* wsdb = slabs + (size_t)p.R * ntap * Cin * Cout;
-  unsigned* amax = reinterpret_cast<unsigned*>(wsdb + (size_t)p.R * Cout);
+  float* wsdb = slabs + (size_t)r.R * ntap * Cin * Cout;
+  unsigned* amax = reinterpret_cast<unsigned*>(wsdb + (size_t)r.R * Cout);
   // operand scales: taken from the caller when the forward / backward-data kernels
   // already produced them as a by-product, otherwise one reduction pass each
-  const long nx0 = (long)N * D * H * W * C0, nx1 = (long)N * D * H * W * C1;
-  const long ny = (long)N * Do * Ho * Wo * Cout;
+  const long nvox = (long)d.N * d.D * d.H * d.W;
+  const long nx0 = nvox * d.C0, nx1 = nvox * d.C1, ny = (long)d.N * d.Do * d.Ho * d.Wo * Cout;
   auto blocks_for = [](long n) { long b = (n / 4 + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); };
   if (!xmax_in || !ymax_in) ADELL_CHECK_HIP(hipMemsetAsync(amax, 0, 4 * sizeof(unsigned), st));
   if (!xmax_in) {   // (a split-row source carries its own exponent: its bytes are not fp32 values)
     if (!xk0)
       hipLaunchKernelGGL(adell_absmax2_kernel, dim3(blocks_for(nx0)), dim3(256), 0, st, x0, nx0, amax);
-    if (C1 > 0 && !xk1)
+    if (d.C1 > 0 && !xk1)
       hipLaunchKernelGGL(adell_absmax2_kernel, dim3(blocks_for(nx1)), dim3(256), 0, st, x1, nx1, amax);
   }
   if (!ymax_in)
     hipLaunchKernelGGL(adell_absmax2_kernel, dim3(blocks_for(ny)), dim3(256), 0, st, dy, ny, amax + 1);
-  if (zring) {
-    rc = adell_wgrad_zring_launch(&zp, N, D, H, W, C0, C1, x0, x1, Cout, Do, Ho, Wo, dy, PD, PH, PW,
-                                  slabs, db ? wsdb : nullptr, xmax_in ? xmax_in : amax,
-                                  ymax_in ? ymax_in : amax + 1, st, xk0, xk1);
-    if (rc != ADELL_OK) return rc;
-    return adell_wgrad_reduce_launch(slabs, out, zp.R, ntap, Cin, Cout, db ? wsdb : nullptr, db, st);
-  }
-  if (s2) {
-    rc = adell_wgrad_s2_launch(&sp, N, D, H, W, x0, Do, Ho, Wo, dy, slabs, db ? wsdb : nullptr,
-                               xmax_in ? xmax_in : amax, ymax_in ? ymax_in : amax + 1, st);
-    if (rc != ADELL_OK) return rc;
-    return adell_wgrad_reduce_launch(slabs, out, sp.R, ntap, Cin, Cout, db ? wsdb : nullptr, db, st);
-  }
-  WgradF16Args a = {};
-  a.x0 = x0; a.x1 = x1; a.dy = dy; a.ws = slabs; a.wsdb = db ? wsdb : nullptr;
-  a.xmax = xmax_in ? xmax_in : amax;
-  a.ymax = ymax_in ? ymax_in : amax + 1;
-  a.N = N; a.D = D; a.H = H; a.W = W;
-  a.C0 = C0; a.C1 = C1; a.Cin = Cin; a.Cout = Cout;
-  a.KD = KD; a.KH = KH; a.KW = KW; a.SD = SD; a.SH = SH; a.SW = SW;
-  a.PD = PD; a.PH = PH; a.PW = PW;
-  a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-  a.lTY = p.lTY; a.ntx = p.ntx; a.nty = p.nty; a.HX = p.HX; a.HY = p.HY;
-  a.GKH = p.GKH; a.NGY = p.NGY;
-  a.TCI = p.TCI; a.TCO = p.TCO; a.nci = p.nci; a.nco = p.nco; a.R = p.R;
-  a.ksplit = p.ksplit;
-  a.vecx = (C0 % 4 == 0) && (C1 % 4 == 0) && (((uintptr_t)x0 & 15) == 0) &&
-           (((uintptr_t)x1 & 15) == 0);
-  a.vecy = (Cout % 4 == 0) && (((uintptr_t)dy & 15) == 0);
-  dim3 grid((unsigned)p.R, (unsigned)(p.nci * p.nco), (unsigned)(KD * p.NGY));
-  if (p.maxj <= 2)
-    rc = adell_launch_wgrad_f16<2>(a, grid, p.lds, st);
-  else if (p.maxj <= 3)
-    rc = adell_launch_wgrad_f16<3>(a, grid, p.lds, st);
-  else if (p.maxj <= 5 && p.ksplit > 1 && (long)p.HX * p.HY * (p.TCI / 4) <= 4 * 256 &&
-           8L * (1 << p.lTY) * (p.TCO / 4) <= 2 * 256)
-    rc = adell_launch_wgrad_f16<5, 4, 2>(a, grid, p.lds, st);  // 32 x 32 channels: pipelined
-  else if (p.maxj <= 5 && (long)p.HX * p.HY * (p.TCI / 4) <= 7 * 256 &&
-           8L * (1 << p.lTY) * (p.TCO / 4) <= 2 * 256)
-    rc = adell_launch_wgrad_f16<5, 7, 2>(a, grid, p.lds, st);  // 64 x 32 channels: pipelined
-  else if (p.maxj <= 5 && (long)p.HX * p.HY * (p.TCI / 4) <= 4 * 256 &&
-           8L * (1 << p.lTY) * (p.TCO / 4) <= 4 * 256)
-    rc = adell_launch_wgrad_f16<5, 4, 4>(a, grid, p.lds, st);  // 32 x 64 channels: pipelined
-  else if (p.maxj <= 5)
-    rc = adell_launch_wgrad_f16<5>(a, grid, p.lds, st);
-  else if (p.maxj <= 7)
-    rc = adell_launch_wgrad_f16<7>(a, grid, p.lds, st);
-  else  // 64 x 64 channels: the prefetch does not fit 256 registers, and at one block per CU
-        // (512 registers, accumulators in AGPRs) it measured 152 TF against 194 TF in place
-    rc = adell_launch_wgrad_f16<9>(a, grid, p.lds, st);
+  const unsigned* xmax = xmax_in ? xmax_in : amax;
+  const unsigned* ymax = ymax_in ? ymax_in : amax + 1;
+  float* dbs = db ? wsdb : nullptr;
+  int rc;
+  if (r.route == ADELL_WGRAD_ZRING32 || r.route == ADELL_WGRAD_ZRING16)
+    rc = adell_wgrad_zring_launch(d, r.zr, x0, x1, dy, slabs, dbs, xmax, ymax, st, xk0, xk1);
+  else if (r.route == ADELL_WGRAD_S2)
+    rc = adell_wgrad_s2_launch(d, r.s2, x0, dy, slabs, dbs, xmax, ymax, st);
+  else
+    rc = adell_wgrad_plane_launch(d, r, x0, x1, dy, slabs, dbs, xmax, ymax, st);
   if (rc != ADELL_OK) return rc;
-  return adell_wgrad_reduce_launch(slabs, out, p.R, ntap, Cin, Cout, a.wsdb, db, st);
+  return adell_wgrad_reduce_launch(slabs, out, r.R, ntap, Cin, Cout, dbs, db, st);
 }
-
-// small-channel paths (conv_small.hip)
-extern "C" long adell_wgrad_small_workspace(const adell_conv3d_desc* d);
-extern "C" int adell_wgrad_small(const adell_conv3d_desc* d, const float* x0, const float* x1,
-                                 const float* dy, float* dw, float* db, void* workspace,
-                                 size_t workspace_bytes, void* stream);
 
 extern "C" long adell_conv3d_bwd_weight_f16x3_workspace(const adell_conv3d_desc* d) {
   if (!d) return ADELL_E_BADARG;
-  if (adell_wgrad_small_workspace(d) > 0) return adell_wgrad_small_workspace(d);
-  WgradF16Plan p = {};
-  WgradZrPlan zp;
-  const int Cin = d->C0 + d->C1;
-  if (adell_wgrad_zring_plan(d->N, d->D, d->H, d->W, d->C0, d->C1, d->Cout, d->KD, d->KH, d->KW,
-                             d->SD, d->SH, d->SW, d->Do, d->Ho, d->Wo, reinterpret_cast<int*>(&zp))) {
-    // the larger of the two plans, so that a later call may take either kernel
-    WgradF16Plan q = {};
-    if (adell_wgrad_f16_plan(d->N, Cin, d->Cout, d->KD, d->KH, d->KW, d->SH, d->SW, d->Do, d->Ho,
-                             d->Wo, &q) != ADELL_OK)
-      q.R = 0;
-    p.R = zp.R > q.R ? zp.R : q.R;
-  } else if (adell_wgrad_f16_plan(d->N, Cin, d->Cout, d->KD, d->KH, d->KW, d->SH, d->SW, d->Do,
-                                  d->Ho, d->Wo, &p) != ADELL_OK)
-    return ADELL_E_UNSUPPORTED;
-  WgradS2Plan sp;
-  if (adell_wgrad_s2_plan(d->N, d->D, d->H, d->W, d->C0, d->C1, d->Cout, d->KD, d->KH, d->KW, d->SD,
-                          d->SH, d->SW, d->PD, d->PH, d->PW, d->Do, d->Ho, d->Wo, &sp) &&
-      sp.R > p.R)
-    p.R = sp.R;   // the larger plan, so that a later call may take either kernel
-  return (long)adell_wgrad_f16_ws(p, d->KD * d->KH * d->KW, Cin, d->Cout);
+  WgradRoute r;
+  if (adell_wgrad_route(*d, &r) != ADELL_OK) return ADELL_E_UNSUPPORTED;
+  return adell_wgrad_f16_workspace(*d, r);
+}
+
+// Launch plan of adell_conv3d_bwd_weight_f16x3, host only (out[25]: include/adell_hip.h); the last
+// entry is the instance of the fp32 entry point adell_conv3d_bwd_weight for the same descriptor.
+extern "C" int adell_conv3d_bwd_weight_f16x3_plan(const adell_conv3d_desc* d, int* out) {
+  ADELL_REQUIRE(d && out, "conv_bwd_weight_f16x3_plan: null pointer");
+  WgradRoute r;
+  const int rc = adell_wgrad_route(*d, &r);
+  if (rc != ADELL_OK) return rc;
+  for (int i = 0; i < 25; ++i) out[i] = 0;
+  const long ws = adell_wgrad_f16_workspace(*d, r);
+  out[0] = r.route;
+  out[1] = r.R;
+  out[2] = (int)(ws & 0x7fffffff);
+  out[3] = (int)(ws >> 31);
+  out[4] = r.rows_ok ? 1 : 0;
+  if (r.route == ADELL_WGRAD_PLANE) {
+    const int v[11] = {r.inst->maxj, r.inst->pfx, r.inst->pfy, r.pl.lTY, r.pl.TCI, r.pl.TCO,
+                       r.pl.ksplit, (int)r.pl.lds, (int)r.grid.x, (int)r.grid.y, (int)r.grid.z};
+    for (int i = 0; i < 11; ++i) out[5 + i] = v[i];
+  } else if (r.route == ADELL_WGRAD_ZRING32 || r.route == ADELL_WGRAD_ZRING16) {
+    const int v[8] = {r.zr.ntx, r.zr.nty, r.zr.nseg, r.zr.seglen, r.zr.nci, r.zr.nco, r.zr.R, r.zr.t16};
+    for (int i = 0; i < 8; ++i) out[16 + i] = v[i];
+  }
+  WgradPlan p32;
+  if (r.route != ADELL_WGRAD_SMALL && adell_wgrad_plan(*d, &p32) == ADELL_OK) out[24] = p32.maxj_inst;
+  return ADELL_OK;
 }
 
 extern "C" int adell_conv3d_bwd_weight_f16x3(const adell_conv3d_desc* d, const float* x0,
@@ -664,24 +686,16 @@ extern "C" int adell_conv3d_bwd_weight_f16x3(const adell_conv3d_desc* d, const f
                                              size_t workspace_bytes, void* stream) {
   ADELL_REQUIRE(d && x0 && dy && dw, "conv_bwd_weight_f16x3: null pointer");
   ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3: C1 > 0 needs x1");
-  if (adell_wgrad_small_workspace(d) > 0)  // Cin <= 4: vector-ALU kernel, exact fp32
-    return adell_wgrad_small(d, x0, x1, dy, dw, db, workspace, workspace_bytes, stream);
-  return adell_wgrad_f16_core(d->N, d->D, d->H, d->W, d->C0, d->C1, x0, x1, d->Cout, d->Do,
-                              d->Ho, d->Wo, dy, d->KD, d->KH, d->KW, d->SD, d->SH, d->SW, d->PD,
-                              d->PH, d->PW, dw, db, x_absmax, dy_absmax, workspace, workspace_bytes,
-                              (hipStream_t)stream);
+  return adell_wgrad_f16_run(*d, x0, x1, dy, dw, db, x_absmax, dy_absmax, workspace,
+                             workspace_bytes, (hipStream_t)stream);
 }
 
 // The same with split-row sources of X (adell_norm_act_fwd_split; include/adell_hip.h): xk0 / xk1
 // non-null = that source holds rows (ONE exponent per tensor: xk[0]). _rows_ok: 1 when this problem
 // runs on the z-ring kernel with every 32-channel tile inside one source.
 extern "C" int adell_conv3d_bwd_weight_f16x3_rows_ok(const adell_conv3d_desc* d) {
-  if (!d || adell_wgrad_small_workspace(d) > 0) return 0;
-  WgradZrPlan zp;
-  if (!adell_wgrad_zring_plan(d->N, d->D, d->H, d->W, d->C0, d->C1, d->Cout, d->KD, d->KH, d->KW,
-                              d->SD, d->SH, d->SW, d->Do, d->Ho, d->Wo, reinterpret_cast<int*>(&zp)))
-    return 0;
-  return (d->C1 == 0 || d->C0 % 32 == 0) ? 1 : 0;
+  WgradRoute r;
+  return d && adell_wgrad_route(*d, &r) == ADELL_OK && r.rows_ok ? 1 : 0;
 }
 
 extern "C" int adell_conv3d_bwd_weight_f16x3_rows(const adell_conv3d_desc* d, const void* x0,
@@ -693,10 +707,6 @@ extern "C" int adell_conv3d_bwd_weight_f16x3_rows(const adell_conv3d_desc* d, co
   ADELL_REQUIRE(d && x0 && dy && dw, "conv_bwd_weight_f16x3_rows: null pointer");
   ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3_rows: C1 > 0 needs x1");
   ADELL_REQUIRE(xk0 || xk1, "conv_bwd_weight_f16x3_rows: no split-row source");
-  ADELL_REQUIRE(adell_conv3d_bwd_weight_f16x3_rows_ok(d),
-                "conv_bwd_weight_f16x3_rows: this problem does not take split-row sources");
-  return adell_wgrad_f16_core(d->N, d->D, d->H, d->W, d->C0, d->C1, (const float*)x0,
-                              (const float*)x1, d->Cout, d->Do, d->Ho, d->Wo, dy, d->KD, d->KH,
-                              d->KW, d->SD, d->SH, d->SW, d->PD, d->PH, d->PW, dw, db, x_absmax,
-                              dy_absmax, workspace, workspace_bytes, (hipStream_t)stream, xk0, xk1);
+  return adell_wgrad_f16_run(*d, (const float*)x0, (const float*)x1, dy, dw, db, x_absmax,
+                             dy_absmax, workspace, workspace_bytes, (hipStream_t)stream, xk0, xk1);
 }

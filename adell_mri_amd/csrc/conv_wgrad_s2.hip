@@ -19,7 +19,7 @@
 // Roofline: HBM (x 537 MB + dY 67 MB read once at 2 x 128^3).
 #include <type_traits>
 #include <utility>
-#include "common.h"
+#include "conv_wgrad_host.h"
 
 typedef _Float16 ws2_half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 ws2_half4 __attribute__((ext_vector_type(4)));
@@ -337,46 +337,40 @@ __global__ __launch_bounds__(kThreads, 2) void adell_conv_wgrad_s2_kernel(WgradS
 }
 
 // ---- host side (called from conv_wgrad_f16.hip) ------------------------------------------------
-struct WgradS2Plan {
-  int ntx, nty, ntz, nbricks, blocks, R;
-};
-
-// 1 + plan when the kernel takes the problem: 32 -> 32 channels, k = 3, stride 2, padding 1, even
+// true + plan when the kernel takes the problem: 32 -> 32 channels, k = 3, stride 2, padding 1, even
 // input dims, one source
-extern "C" int adell_wgrad_s2_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
-                                   int KH, int KW, int SD, int SH, int SW, int PD, int PH, int PW,
-                                   int Do, int Ho, int Wo, WgradS2Plan* p) {
-  if (C1 != 0 || C0 != 32 || Cout != 32 || KD != 3 || KH != 3 || KW != 3 || SD != 2 || SH != 2 ||
-      SW != 2 || PD != 1 || PH != 1 || PW != 1)
-    return 0;
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || (D | H | W) & 1 || Do != D / 2 || Ho != H / 2 || Wo != W / 2)
-    return 0;
-  if ((size_t)D * H * W * 32 >= ((size_t)1 << 29)) return 0;   // 32-bit offsets inside an item
-  if (g_adell_tune.wgrad_nozring) return 0;                     // the A/B switch of the z-ring kernel
-  p->ntx = adell_cdiv(Wo, 8);
-  p->nty = adell_cdiv(Ho, 8);
-  p->ntz = adell_cdiv(Do, kBZ);
-  const long nb = (long)N * p->ntx * p->nty * p->ntz;
-  if (nb >= 0x0fffffffL) return 0;
+bool adell_wgrad_s2_plan(const adell_conv3d_desc& d, WgradS2Plan& p) {
+  if (d.C1 != 0 || d.C0 != 32 || d.Cout != 32 || d.KD != 3 || d.KH != 3 || d.KW != 3 || d.SD != 2 ||
+      d.SH != 2 || d.SW != 2 || d.PD != 1 || d.PH != 1 || d.PW != 1)
+    return false;
+  if (d.N <= 0 || d.D <= 0 || d.H <= 0 || d.W <= 0 || (d.D | d.H | d.W) & 1 || d.Do != d.D / 2 ||
+      d.Ho != d.H / 2 || d.Wo != d.W / 2)
+    return false;
+  if ((size_t)d.D * d.H * d.W * 32 >= ((size_t)1 << 29)) return false;   // 32-bit offsets inside an item
+  if (g_adell_tune.wgrad_nozring) return false;                 // the A/B switch of the z-ring kernel
+  p.ntx = adell_cdiv(d.Wo, 8);
+  p.nty = adell_cdiv(d.Ho, 8);
+  p.ntz = adell_cdiv(d.Do, kBZ);
+  const long nb = (long)d.N * p.ntx * p.nty * p.ntz;
+  if (nb >= 0x0fffffffL) return false;
   // every (block, group) writes a 108 KB slab: below a few bricks per block the slab fold costs more
   // than the kernel saves (2 x 64^3: 0.087 ms here against 0.077 on the generic kernel)
-  if (nb < 8L * adell_cu_count()) return 0;
-  p->nbricks = (int)nb;
+  if (nb < 8L * adell_cu_count()) return false;
+  p.nbricks = (int)nb;
   const long want = 2L * adell_cu_count();     // two resident blocks per CU
-  p->blocks = (int)(nb < want ? nb : want);
-  p->R = p->blocks;
-  return 1;
+  p.blocks = (int)(nb < want ? nb : want);
+  p.R = p.blocks;
+  return true;
 }
 
-extern "C" int adell_wgrad_s2_launch(const WgradS2Plan* p, int N, int D, int H, int W, const float* x,
-                                     int Do, int Ho, int Wo, const float* dy, float* slabs,
-                                     float* wsdb, const unsigned* xmax, const unsigned* ymax,
-                                     hipStream_t st) {
+int adell_wgrad_s2_launch(const adell_conv3d_desc& d, const WgradS2Plan& p, const float* x,
+                          const float* dy, float* slabs, float* wsdb, const unsigned* xmax,
+                          const unsigned* ymax, hipStream_t st) {
   WgradS2Args a = {};
   a.x = x; a.dy = dy; a.ws = slabs; a.wsdb = wsdb; a.xmax = xmax; a.ymax = ymax;
-  a.N = N; a.D = D; a.H = H; a.W = W; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-  a.ntx = p->ntx; a.nty = p->nty; a.ntz = p->ntz; a.nbricks = p->nbricks;
-  const dim3 grid((unsigned)p->blocks);
+  a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W; a.Do = d.Do; a.Ho = d.Ho; a.Wo = d.Wo;
+  a.ntx = p.ntx; a.nty = p.nty; a.ntz = p.ntz; a.nbricks = p.nbricks;
+  const dim3 grid((unsigned)p.blocks);
 #ifdef ADELL_DEBUG
   switch (g_adell_tune.zr_dbg) {
     case 1: return adell_launch<adell_conv_wgrad_s2_kernel<1>>(grid, dim3(kThreads), kLds, st, a);

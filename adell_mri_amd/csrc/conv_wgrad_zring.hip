@@ -15,7 +15,7 @@
 // Wave w owns taps w, w+4, w+8, ... (7 x 4 accumulators of 4 registers), every k-step.
 // Work units are (column, z segment) pairs dealt round-robin to the blocks; every block writes
 // one partial slab, folded in fixed order by adell_wgrad_reduce_kernel (deterministic).
-#include "common.h"
+#include "conv_wgrad_host.h"
 
 typedef _Float16 zr_half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 zr_half4 __attribute__((ext_vector_type(4)));
@@ -634,38 +634,32 @@ __global__ __launch_bounds__(256, 3) void adell_conv_wgrad_zring16_kernel(WgradZ
   }
 }
 
-struct WgradZrPlan {
-  int ntx, nty, nseg, seglen, nci, nco, R, t16;
-};
-
-// 1 when the z-ring kernel serves this problem (3^3 taps, stride 1, channel counts in whole 16s)
-extern "C" int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
-                                      int KH, int KW, int SD, int SH, int SW, int Do, int Ho, int Wo,
-                                      int* plan) {
-  static_assert(sizeof(WgradZrPlan) == 8 * sizeof(int), "plan[8] of include/adell_hip.h");
-  WgradZrPlan* p = reinterpret_cast<WgradZrPlan*>(plan);
+// true when the z-ring kernel serves this problem (3^3 taps, stride 1, channel counts in whole 16s)
+bool adell_wgrad_zring_plan_desc(const adell_conv3d_desc& d, WgradZrPlan& p) {
+  const int N = d.N, H = d.H, W = d.W, C0 = d.C0, C1 = d.C1, Cout = d.Cout;
+  const int Do = d.Do, Ho = d.Ho, Wo = d.Wo;
   const int Cin = C0 + C1;
-  if (KD != 3 || KH != 3 || KW != 3 || SD != 1 || SH != 1 || SW != 1) return 0;
+  if (d.KD != 3 || d.KH != 3 || d.KW != 3 || d.SD != 1 || d.SH != 1 || d.SW != 1) return false;
   // whole 16-channel pieces: tiles are 32 x 32 channels, a ragged last tile or one that straddles
   // the two sources of a virtual concat is masked per 4-channel piece (half the MFMA columns idle,
   // still far ahead of the generic kernel on the 16-channel decoder levels of UNETR)
-  if (Cin % 16 || Cout % 16 || C0 % 16) return 0;
-  if (Wo < 8 || Ho < 8 || Do < 4) return 0;   // small planes: the per-plane kernel wastes less
+  if (Cin % 16 || Cout % 16 || C0 % 16) return false;
+  if (Wo < 8 || Ho < 8 || Do < 4) return false;   // small planes: the per-plane kernel wastes less
   const size_t cmax = (size_t)(C0 > C1 ? C0 : C1);
   if ((size_t)H * W * cmax >= ((size_t)1 << 30) || (size_t)Ho * Wo * Cout >= ((size_t)1 << 30))
-    return 0;                                  // 32-bit byte offsets inside a plane
-  if (g_adell_tune.wgrad_nozring) return 0;
-  p->ntx = adell_cdiv(Wo, 8);
-  p->nty = adell_cdiv(Ho, 8);
+    return false;                              // 32-bit byte offsets inside a plane
+  if (g_adell_tune.wgrad_nozring) return false;
+  p.ntx = adell_cdiv(Wo, 8);
+  p.nty = adell_cdiv(Ho, 8);
   // 16 x 16 tiles (adell_conv_wgrad_zring16_kernel) when a 32-wide tile would be half empty on
   // either side
-  p->t16 = (Cin == 16 || Cout == 16) && !g_adell_tune.wgrad_no16 ? 1 : 0;
-  p->nci = adell_cdiv(Cin, p->t16 ? 16 : 32);
-  p->nco = adell_cdiv(Cout, p->t16 ? 16 : 32);
-  const long ncols = (long)N * p->ntx * p->nty;
-  const long chan_blocks = (long)p->nci * p->nco;
+  p.t16 = (Cin == 16 || Cout == 16) && !g_adell_tune.wgrad_no16 ? 1 : 0;
+  p.nci = adell_cdiv(Cin, p.t16 ? 16 : 32);
+  p.nco = adell_cdiv(Cout, p.t16 ? 16 : 32);
+  const long ncols = (long)N * p.ntx * p.nty;
+  const long chan_blocks = (long)p.nci * p.nco;
   // two (three: the 16-channel form) blocks per CU over all channel tiles
-  long target = (p->t16 ? 768 : 512) / chan_blocks;
+  long target = (p.t16 ? 768 : 512) / chan_blocks;
   if (target < 8) target = 8;
   // z segments: at least 4 steps each (2 priming planes), enough units to fill the target,
   // and -- round 4 -- a unit count the blocks share out evenly: units are dealt round-robin, so the
@@ -688,39 +682,46 @@ extern "C" int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1
       if (best < 0 || cost < best) { best = cost; nseg = cand; }
     }
   }
-  p->seglen = (int)adell_cdiv(Do, (int)nseg);
-  p->nseg = adell_cdiv(Do, p->seglen);
-  const long nunits = ncols * p->nseg;
-  p->R = (int)(nunits < target ? nunits : target);
+  p.seglen = (int)adell_cdiv(Do, (int)nseg);
+  p.nseg = adell_cdiv(Do, p.seglen);
+  const long nunits = ncols * p.nseg;
+  p.R = (int)(nunits < target ? nunits : target);
+  return true;
+}
+
+// The exported query (include/adell_hip.h): the same plan as eight ints.
+extern "C" int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD,
+                                      int KH, int KW, int SD, int SH, int SW, int Do, int Ho, int Wo,
+                                      int* plan) {
+  // (the planner reads no padding)
+  const adell_conv3d_desc d = {N, D, H, W, C0, C1, Cout, KD, KH, KW, SD, SH, SW, 0, 0, 0, Do, Ho, Wo};
+  WgradZrPlan p;
+  if (!adell_wgrad_zring_plan_desc(d, p)) return 0;
+  const int v[8] = {p.ntx, p.nty, p.nseg, p.seglen, p.nci, p.nco, p.R, p.t16};
+  for (int i = 0; i < 8; ++i) plan[i] = v[i];
   return 1;
 }
 
-extern "C" size_t adell_wgrad_zring_ws_floats(const WgradZrPlan* p, int Cin, int Cout) {
-  return (size_t)p->R * 27 * Cin * Cout + (size_t)p->R * Cout + 4;
-}
-
-extern "C" int adell_wgrad_zring_launch(const WgradZrPlan* p, int N, int D, int H, int W, int C0,
-                                        int C1, const float* x0, const float* x1, int Cout, int Do,
-                                        int Ho, int Wo, const float* dy, int PD, int PH, int PW,
-                                        float* slabs, float* wsdb, const unsigned* xmax,
-                                        const unsigned* ymax, hipStream_t st,
-                                        const int* xk0 = nullptr, const int* xk1 = nullptr) {
+int adell_wgrad_zring_launch(const adell_conv3d_desc& d, const WgradZrPlan& p, const float* x0,
+                             const float* x1, const float* dy, float* slabs, float* wsdb,
+                             const unsigned* xmax, const unsigned* ymax, hipStream_t st,
+                             const int* xk0, const int* xk1) {
   WgradZrArgs a = {};
   a.x0 = x0; a.x1 = x1; a.dy = dy; a.ws = slabs; a.wsdb = wsdb; a.xmax = xmax; a.ymax = ymax;
   a.xk0 = xk0; a.xk1 = xk1;
-  a.N = N; a.D = D; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.Cout = Cout;
-  a.PD = PD; a.PH = PH; a.PW = PW; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-  a.ntx = p->ntx; a.nty = p->nty; a.nseg = p->nseg; a.seglen = p->seglen;
-  a.nci = p->nci; a.nco = p->nco; a.R = p->R;
+  a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W; a.C0 = d.C0; a.C1 = d.C1; a.Cin = d.C0 + d.C1;
+  a.Cout = d.Cout;
+  a.PD = d.PD; a.PH = d.PH; a.PW = d.PW; a.Do = d.Do; a.Ho = d.Ho; a.Wo = d.Wo;
+  a.ntx = p.ntx; a.nty = p.nty; a.nseg = p.nseg; a.seglen = p.seglen;
+  a.nci = p.nci; a.nco = p.nco; a.R = p.R;
   a.dbg = g_adell_tune.zr_dbg;
-  if (p->t16) {
+  const dim3 grid((unsigned)p.R, (unsigned)(p.nci * p.nco));
+  if (p.t16) {
     const size_t lds16 = 2 * (ZR_SLOTS * (size_t)Z16_XPLANE + 2 * (size_t)Z16_YPLANE);
-    hipLaunchKernelGGL(adell_conv_wgrad_zring16_kernel, dim3((unsigned)p->R, (unsigned)(p->nci * p->nco)),
-                       dim3(256), lds16, st, a);
+    hipLaunchKernelGGL(adell_conv_wgrad_zring16_kernel, grid, dim3(256), lds16, st, a);
     ADELL_CHECK_HIP(hipGetLastError());
     return ADELL_OK;
   }
   const size_t lds = ZR_SLOTS * (size_t)ZR_PLANE + 2 * (size_t)ZR_YBUF;
-  return adell_launch<adell_conv_wgrad_zring_kernel>(dim3((unsigned)p->R, (unsigned)(p->nci * p->nco)),
-                                                     dim3(256), lds, st, a);
+  return adell_launch<adell_conv_wgrad_zring_kernel>(grid, dim3(256), lds, st, a);
 }

@@ -760,6 +760,31 @@ def conv3d_bwd_weight_rows_ok(N, in_size, C0, C1, Cout, kernel, stride, padding)
     return bool(_lib.lib().adell_conv3d_bwd_weight_f16x3_rows_ok(ctypes.byref(d)))
 
 
+# launch plan of an f16x3 weight gradient (adell_conv3d_bwd_weight_f16x3_plan). route: one of
+# WGRAD_ROUTES; R: partial slabs; instance: (MAXJ, PFX, PFY) of the per-plane kernel, else None;
+# lTY .. grid: that kernel's geometry (else zeros); zring: the eight ints of adell_wgrad_zring_plan on
+# the z-ring routes, else None; fp32_maxj: the instance conv3d_bwd_weight(f16x3=False) runs (0: none)
+WGRAD_ROUTES = ("small", "zring32", "zring16", "s2", "plane")
+WgradPlan = collections.namedtuple(
+    "WgradPlan", "route R workspace rows_ok instance lTY TCI TCO ksplit lds grid zring fp32_maxj")
+
+
+def conv3d_bwd_weight_plan(N, in_size, C0, C1, Cout, kernel, stride, padding):
+    """What conv3d_bwd_weight(f16x3=True) would run under the current tuning switches; None when no
+    kernel takes the problem. Host only: no GPU needed."""
+    d = make_conv_desc(N, tuple(in_size), C0, C1, Cout, kernel, stride, padding)
+    out = (ctypes.c_int * 25)()
+    rc = _lib.lib().adell_conv3d_bwd_weight_f16x3_plan(ctypes.byref(d), out)
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    check(rc)
+    o = list(out)
+    route = WGRAD_ROUTES[o[0]]
+    return WgradPlan(route, o[1], o[2] + (o[3] << 31), bool(o[4]),
+                     tuple(o[5:8]) if route == "plane" else None, o[8], o[9], o[10], o[11], o[12],
+                     tuple(o[13:16]), tuple(o[16:24]) if route.startswith("zring") else None, o[24])
+
+
 def conv3d_bwd_weight(x0, dy, kernel, stride, padding, x1=None, want_db=False, f16x3=False,
                       x_amax=None, dy_amax=None, rows0=None, rows1=None):
     """dW in torch's canonical [Cout, Cin, kD, kH, kW] layout (and db when want_db).

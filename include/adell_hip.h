@@ -265,6 +265,25 @@ int adell_conv3d_bwd_weight_f16x3_rows(const adell_conv3d_desc* d, const void* x
                                        float* db, const uint32_t* x_absmax,
                                        const uint32_t* dy_absmax, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* Launch plan of adell_conv3d_bwd_weight_f16x3 (and _rows), host only (no launch, no tensor read, no
+ * device needed): what the call would run under the current tuning switches, from the same plan the
+ * launch, the workspace query and _rows_ok read. Returns ADELL_OK, or ADELL_E_UNSUPPORTED when no
+ * kernel takes the problem. out[25]:
+ *   [0] route (ADELL_WGRAD_*); [1] regions = partial slabs the route writes (small: 0);
+ *   [2], [3] adell_conv3d_bwd_weight_f16x3_workspace(d) as bytes & 0x7fffffff and bytes >> 31;
+ *   [4] adell_conv3d_bwd_weight_f16x3_rows_ok(d);
+ *   per-plane route (else 0): [5] MAXJ, [6] PFX, [7] PFY of the kernel instance (jobs per wave,
+ *   16-byte prefetch loads per thread of X / dY; 0, 0 = staged in place), [8] log2 of the brick rows,
+ *   [9] / [10] input / output channel tile, [11] k-groups of a 32 x 32 tile, [12] LDS bytes,
+ *   [13] .. [15] grid extents x, y, z;
+ *   z-ring routes (else 0): [16] .. [23] the plan[8] of adell_wgrad_zring_plan;
+ *   [24] MAXJ of the instance adell_conv3d_bwd_weight (fp32) runs for d (0: small route or refused). */
+#define ADELL_WGRAD_SMALL 0    /* Cin <= 4: vector-ALU kernel, exact fp32 */
+#define ADELL_WGRAD_ZRING32 1  /* z-ring kernel, 32 x 32 channel tiles */
+#define ADELL_WGRAD_ZRING16 2  /* z-ring kernel, 16 x 16 channel tiles */
+#define ADELL_WGRAD_S2 3       /* stride-2 sub-lattice kernel (32 -> 32 downsampling layer) */
+#define ADELL_WGRAD_PLANE 4    /* per-plane kernel */
+int adell_conv3d_bwd_weight_f16x3_plan(const adell_conv3d_desc* d, int* out);
 
 /* db[c] = sum over rows of dy[rows][C] (torch's bias gradient of Conv3d /
  * ConvTranspose3d). workspace >= adell_bias_grad_workspace(rows, C) bytes. */

@@ -45,3 +45,25 @@ def test_every_query_answers_as_recorded():
         tool, conv, a, gold["conv_answers"], tool.ANSWER_COLUMNS, tool.SWITCHES)
     assert np.array_equal(t, gold["convt_answers"]), _report(
         tool, convt, t, gold["convt_answers"], tool.CONVT_COLUMNS, tool.SWITCHES)
+
+
+def test_every_weight_gradient_query_answers_as_recorded():
+    """The weight-gradient host path (csrc/conv_wgrad_f16.hip adell_wgrad_route, csrc/conv_wgrad.hip)
+    the same way, from tests/golden/conv_wgrad_plan_sweep.npz: both workspace queries, rows_ok, the
+    z-ring plan, every entry of adell_conv3d_bwd_weight_f16x3_plan (route, regions, per-plane and fp32
+    instance) under no switch, wgrad_nozring and wgrad_no16, and the transposed-conv workspace. The
+    stride-2 route reads the CU count, which is 256 without a device and on the MI355X."""
+    tool = _tool()
+    gold = np.load(tool.WGRAD_GOLDEN)
+    _, convt = tool.grid()
+    wg = tool.wgrad_grid()
+    want = gold["wgrad_answers"].T       # (stored column by column)
+    assert np.array_equal(wg, gold["wgrad"].T) and np.array_equal(convt, gold["convt"]), (
+        "the descriptor grid changed: regenerate the file (tools/conv_plan_sweep.py wgrad)")
+    a, t = tool.wgrad_answers(wg, convt)
+    tool.check_wgrad_coverage(wg, a, t)
+    assert np.array_equal(a, want), _report(tool, wg, a, want, tool.WGRAD_COLUMNS,
+                                            tool.WGRAD_SWITCHES)
+    bad = np.nonzero(t != gold["convt_workspace"])[0]
+    assert len(bad) == 0, [(convt[i, 1:].tolist(), int(t[i]), int(gold["convt_workspace"][i]))
+                          for i in bad[:10]]

@@ -2,7 +2,7 @@
 the z-ring weight gradient, from one case table:
 
 - on the build host (no GPU), each case still gets the plan it is in the table for
-  (ops.conv3d_plan / ops.convtranspose3d_plan / adell_wgrad_zring_plan), and every branch of the
+  (ops.conv3d_plan / ops.convtranspose3d_plan / ops.conv3d_bwd_weight_plan), and every branch of the
   planner has at least one case. A retune that moves a shape onto another branch fails here, naming
   the branch, so the table is updated on purpose instead of the branch losing its coverage (such a
   retune also regenerates the dense record of tests/test_conv_plan_sweep.py: tools/conv_plan_sweep.py);
@@ -30,10 +30,12 @@ from adell_mri_amd._lib import AdellHipError
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # direction: "fwd" / "bwd" (adell_conv3d_f16x3_plan, backward_data = 0 / 1), "convt" (transposed-conv
-# forward: c0 = Cin, cout = Cs, k = the factors), "wgrad" (adell_wgrad_zring_plan). cfg: the plan's
-# config, None = refused; for "wgrad": "zring" (32 x 32 tiles), "zring:1seg" / "zring:segs" (one /
-# several z segments), "zring:t16" (16 x 16 tiles), "plane" (the per-plane kernel). split: the K
-# shares > 1 (True / False), or the exact share count.
+# forward: c0 = Cin, cout = Cs, k = the factors), "wgrad" (ops.conv3d_bwd_weight_plan). cfg: the plan's
+# config, None = refused; for "wgrad" the route: "small" (<= 4 input channels), "zring" (32 x 32
+# tiles), "zring:1seg" / "zring:segs" (one / several z segments), "zring:t16" (16 x 16 tiles), "s2"
+# (the stride-2 sub-lattice kernel), "plane" (the per-plane kernel, any instance) or
+# "plane:MAXJ,PFX,PFY" (that instance of it). split: the K shares > 1 (True / False), or the exact
+# share count.
 Case = collections.namedtuple("Case", "branch direction N size c0 c1 cout k s p cfg split")
 
 CASES = [
@@ -142,7 +144,45 @@ CASES = [
     Case("wgrad z-ring, C1 > 0", "wgrad", 1, (16, 16, 16), 48, 16, 32, 3, 1, 1, "zring", False),
     Case("wgrad per-plane: 5^3", "wgrad", 1, (32, 32, 64), 64, 0, 64, 5, 1, 2, "plane", False),
     Case("wgrad per-plane: Do < 4", "wgrad", 1, (3, 8, 8), 16, 0, 16, 3, 1, 1, "plane", False),
+    # the eight instances <MAXJ, PFX, PFY> of the per-plane kernel (csrc/conv_wgrad_f16.hip
+    # kWgradF16Instances), each with a neighbour just across the threshold that selects it
+    Case("wgrad plane <2>", "wgrad", 1, (4, 8, 8), 32, 0, 32, 1, 1, 0, "plane:2,0,0", False),
+    Case("wgrad plane <2> neighbour: 9 taps per plane", "wgrad", 1, (3, 4, 8), 32, 0, 32, 3, 1, 1,
+         "plane:3,0,0", False),
+    Case("wgrad plane <3>", "wgrad", 1, (4, 4, 8), 32, 0, 32, 3, 1, 1, "plane:3,0,0", False),
+    Case("wgrad plane <3> neighbour: plane height 5, k-split", "wgrad", 1, (4, 5, 8), 32, 0, 32, 3, 1,
+         1, "plane:5,4,2", False),
+    Case("wgrad plane <5,4,2>", "wgrad", 1, (3, 8, 8), 32, 0, 32, 3, 1, 1, "plane:5,4,2", False),
+    Case("wgrad plane <5,4,2> neighbour: Cin > 32", "wgrad", 1, (3, 8, 8), 48, 0, 32, 3, 1, 1,
+         "plane:5,7,2", False),
+    Case("wgrad plane <5,7,2>", "wgrad", 1, (3, 8, 8), 64, 0, 32, 3, 1, 1, "plane:5,7,2", False),
+    Case("wgrad plane <5,7,2> neighbour: Cout > 32", "wgrad", 1, (3, 8, 8), 64, 0, 48, 3, 1, 1,
+         "plane:9,0,0", False),
+    Case("wgrad plane <5,4,4>", "wgrad", 1, (3, 8, 8), 32, 0, 64, 3, 1, 1, "plane:5,4,4", False),
+    Case("wgrad plane <5,4,4> neighbour: plane height 4, dY brick in two loads", "wgrad", 1,
+         (3, 4, 8), 32, 0, 64, 3, 1, 1, "plane:5,7,2", False),
+    Case("wgrad plane <9>", "wgrad", 1, (3, 8, 8), 64, 0, 64, 3, 1, 1, "plane:9,0,0", False),
+    Case("wgrad plane <9> neighbour: 5^3, one ky row per block", "wgrad", 1, (8, 8, 8), 64, 0, 64, 5,
+         1, 2, "plane:5,0,0", False),
+    Case("wgrad plane <7>", "wgrad", 1, (8, 8, 8), 32, 0, 32, 5, 1, 2, "plane:7,0,0", False),
+    Case("wgrad plane <7> neighbour: Cin > 32", "wgrad", 1, (8, 8, 8), 64, 0, 32, 5, 1, 2,
+         "plane:9,0,0", False),
+    Case("wgrad plane <5>", "wgrad", 1, (10, 10, 10), 48, 0, 32, 3, 2, 1, "plane:5,0,0", False),
+    Case("wgrad plane <5> neighbour: Cout > 32", "wgrad", 1, (10, 10, 10), 48, 0, 64, 3, 2, 1,
+         "plane:9,0,0", False),
+    # plan only (PLAN_ONLY): these routes have their own GPU tests (tests/test_ops_gpu.py,
+    # tests/test_wgrad_s2_gpu.py)
+    Case("wgrad small-channel route", "wgrad", 1, (8, 8, 8), 4, 0, 16, 3, 1, 1, "small", False),
+    Case("wgrad small-channel neighbour: 5 channels", "wgrad", 1, (8, 8, 8), 5, 0, 16, 3, 1, 1,
+         "plane:5,4,2", False),
+    Case("wgrad stride-2 route", "wgrad", 2, (64, 128, 128), 32, 0, 32, 3, 2, 1, "s2", False),
+    Case("wgrad stride-2 neighbour: < 8 bricks per CU", "wgrad", 2, (64, 64, 64), 32, 0, 32, 3, 2, 1,
+         "plane:3,0,0", False),
 ]
+
+# cases checked on the build host only
+PLAN_ONLY = {"wgrad small-channel route", "wgrad small-channel neighbour: 5 channels",
+             "wgrad stride-2 route", "wgrad stride-2 neighbour: < 8 bricks per CU"}
 
 # branches the table must cover (each needs at least one case)
 BRANCHES = {
@@ -158,7 +198,9 @@ BRANCHES = {
     "LDS fallback, 128 x 32 -> 64 x 32", "LDS fallback, 256 x 32 -> 128 x 32 -> 64 x 32", "refused",
     "pack staged / not", "wgrad z-ring, one segment", "wgrad z-ring, several segments",
     "wgrad z-ring, 16 x 16 tiles", "wgrad z-ring, ragged column tiles", "wgrad z-ring, C1 > 0",
-    "wgrad per-plane: 5^3",
+    "wgrad per-plane: 5^3", "wgrad plane <2>", "wgrad plane <3>", "wgrad plane <5,4,2>",
+    "wgrad plane <5,7,2>", "wgrad plane <5,4,4>", "wgrad plane <5>", "wgrad plane <7>",
+    "wgrad plane <9>", "wgrad small-channel route", "wgrad stride-2 route",
 }
 
 
@@ -187,22 +229,17 @@ def _out_size(c):
     return ops.conv_out_size(c.size, _triple(c.k), _triple(c.s), _triple(c.p))
 
 
-def _wgrad_plan(c):
-    plan = (ctypes.c_int * 8)()
-    D, H, W = c.size
-    Do, Ho, Wo = _out_size(c)
-    rc = _lib.lib().adell_wgrad_zring_plan(c.N, D, H, W, c.c0, c.c1, c.cout, *_triple(c.k),
-                                           *_triple(c.s), Do, Ho, Wo, plan)
-    return list(plan) if rc else None
-
-
 def _plan_of(c):
     """(what the planner does now, as the table's cfg / split values)"""
     if c.direction == "wgrad":
-        p = _wgrad_plan(c)
-        if p is None:
-            return "plane", False
-        return ("zring:t16" if p[7] else "zring:1seg" if p[2] == 1 else "zring:segs"), False
+        p = ops.conv3d_bwd_weight_plan(c.N, c.size, c.c0, c.c1, c.cout, c.k, c.s, c.p)
+        if p.route == "plane":
+            return "plane:{},{},{}".format(*p.instance), False
+        if p.route == "zring16":
+            return "zring:t16", False
+        if p.route == "zring32":
+            return ("zring:1seg" if p.zring[2] == 1 else "zring:segs"), False
+        return p.route, False
     if c.direction == "convt":
         p = ops.convtranspose3d_plan(c.N, c.size, c.c0, c.cout, c.k)
     else:
@@ -216,7 +253,8 @@ def _plan_of(c):
 def _matches(c, cfg, shares):
     if c.direction == "wgrad":
         want = c.cfg
-        return cfg == want or (want == "zring" and cfg in ("zring:1seg", "zring:segs"))
+        return (cfg == want or (want == "zring" and cfg in ("zring:1seg", "zring:segs"))
+                or (want == "plane" and cfg.startswith("plane:")))
     if cfg != c.cfg:
         return False
     if cfg is None:
@@ -331,7 +369,7 @@ def _conv_shapes():
     """The distinct conv problems of the table (a shape listed for several branches runs once)."""
     seen, out = set(), []
     for c in CASES:
-        if c.direction == "convt" or c.cfg is None:
+        if c.direction == "convt" or c.cfg is None or c.branch in PLAN_ONLY:
             continue
         key = (c.N, c.size, c.c0, c.c1, c.cout, _triple(c.k), _triple(c.s), _triple(c.p))
         if key not in seen:

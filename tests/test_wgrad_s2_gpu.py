@@ -66,7 +66,7 @@ def test_other_shapes_keep_their_kernels(cuda):
 
 def test_large_problem_takes_the_sublattice_kernel(cuda):
     """2 x 64 x 128 x 128 input: 2048 bricks of 8 x 8 x 2 -> csrc/conv_wgrad_s2.hip (checked through the
-    workspace size, which follows the larger of the plans), against fp64."""
+    plan query's route and the workspace size, which follows the larger of the plans), against fp64."""
     import ctypes
 
     from adell_mri_amd import _lib, ops
@@ -81,6 +81,8 @@ def test_large_problem_takes_the_sublattice_kernel(cuda):
     finally:
         L.adell_set_tuning(b"wgrad_nozring", 0)
     assert ws_big > ws_big_generic          # one slab per block of the sub-lattice kernel
+    assert ops.conv3d_bwd_weight_plan(2, (64, 128, 128), 32, 0, 32, 3, 2, 1).route == "s2"
+    assert ops.conv3d_bwd_weight_plan(2, (64, 64, 64), 32, 0, 32, 3, 2, 1).route == "plane"
     assert L.adell_conv3d_bwd_weight_f16x3_workspace(ctypes.byref(d_small)) > 0
     g = torch.Generator().manual_seed(2)
     x = torch.randn(2, 32, 64, 128, 128, generator=g)
