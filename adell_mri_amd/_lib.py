@@ -225,6 +225,12 @@ SIGNATURES = {
                                  _vp, _vp]),
     "adell_ibot_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i,
                             _vp, _vp]),
+    "adell_ijepa_gather_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_ijepa_gather_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_ijepa_predictor_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "adell_ijepa_predictor_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_ijepa_loss_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_ijepa_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -2287,6 +2287,83 @@ def patch_rows(rows, tokens, class_token, device):
     return ops.token_rows(rows + c, tokens, device)
 
 
+# ---- I-JEPA (csrc/ijepa.hip) ----------------------------------------------------------------------
+class _GatherTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rows):
+        ctx.conf = (rows, x.shape[1])
+        return ops.ijepa_gather_fwd(x.contiguous(), rows)
+
+    @staticmethod
+    def backward(ctx, dy):
+        rows, N = ctx.conf
+        return ops.ijepa_gather_bwd(dy.contiguous(), rows, N), None
+
+
+def gather_tokens(x, rows):
+    """``x[:, rows]`` for x [B, N, E] and sorted unique host indices ``rows`` (or an
+    ``ops.TokenRows``), the same rows of every item. The backward writes the whole gradient of x in
+    one launch (zeros on the rows that were not taken). IndexError, on the host and before any
+    launch, for a row outside [0, N)."""
+    if x.dim() != 3:
+        raise ValueError(f"gather_tokens: [B, N, E] expected, got {tuple(x.shape)}")
+    return _GatherTokensFn.apply(x, ops.token_rows(rows, x.shape[1], x.device))
+
+
+class _PredictorTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e, pos, mask, ctx_rows, tgt_rows):
+        ctx.conf = (ctx_rows, tgt_rows, pos.shape[1])
+        return ops.ijepa_predictor_fwd(e.contiguous(), pos.contiguous(), mask, ctx_rows, tgt_rows)
+
+    @staticmethod
+    def backward(ctx, dout):
+        ctx_rows, tgt_rows, T = ctx.conf
+        de, dpos, dmask = ops.ijepa_predictor_bwd(dout.contiguous(), ctx_rows, tgt_rows, T,
+                                                  *ctx.needs_input_grad[:3])
+        return de, dpos, dmask, None, None
+
+
+def predictor_tokens(e, pos, mask, ctx_rows, tgt_rows):
+    """The I-JEPA predictor's input [B, nc + nt, P] in one launch: ``cat([e + pos[:, ctx_rows],
+    (mask + pos[:, tgt_rows]).expand(B, -1, -1)], 1)`` for the embedded context e [B, nc, P], the
+    positional embedding pos [1, T, P] and the mask token [1, 1, P]; the two (sorted, unique) row
+    sets are disjoint. The backward writes the whole gradient of pos."""
+    T = pos.shape[1]
+    return _PredictorTokensFn.apply(e, pos, mask, ops.token_rows(ctx_rows, T, e.device),
+                                    ops.token_rows(tgt_rows, T, e.device))
+
+
+class _IjepaBlockLossFn(torch.autograd.Function):
+    """Saved: pred, h and two floats per target row (mean, rstd)."""
+
+    @staticmethod
+    def forward(ctx, pred, h, rows):
+        pred, h = pred.contiguous(), h.contiguous()
+        loss, stats = ops.ijepa_loss_fwd(pred, h, rows)
+        ctx.save_for_backward(pred, h, stats)
+        ctx.rows = rows
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, h, stats = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.ijepa_loss_bwd(pred, h, ctx.rows, stats, g), None, None
+
+
+def ijepa_block_loss(pred, h, rows):
+    """``SmoothL1Loss()(pred, layer_norm(h, (E,))[:, rows])`` for the predictions pred [B, nt, E] of
+    one target block and the teacher's raw output h [B, N, E]: neither the normalised h nor the
+    gathered target is written. h takes no gradient. IndexError on the host for a row outside
+    [0, N)."""
+    if pred.dim() != 3 or h.dim() != 3:
+        raise ValueError(f"ijepa_block_loss: [B, nt, E] and [B, N, E] expected, got "
+                         f"{tuple(pred.shape)} and {tuple(h.shape)}")
+    return _IjepaBlockLossFn.apply(pred, h.detach(), ops.token_rows(rows, h.shape[1], h.device))
+
+
 class _PairLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, kind, temperature, apply_relu):

@@ -26,6 +26,13 @@ within each view. The token logits [B, tokens, out_dim] are read in place: per v
 function (functional.ibot_view, csrc/ibot.hip) gives the reduced output and the masked-row loss and
 writes the whole gradient in one launch; the teacher's logits are read once for its "mean"
 reduction and the centre sum.
+
+``IJEPAPL`` (pl.py:987-1165) is the wrapper of ``ssl_method="ijepa"``: one image, no view pair. The
+student predicts the features of a few target blocks from the tokens of the context blocks; the EMA
+teacher sees the whole image under ``no_grad``. ``step`` takes the smooth-L1 loss of every block
+from the teacher's raw output (functional.ijepa_block_loss, csrc/ijepa.hip: layer norm, row gather
+and loss in one pass, nothing of the teacher's size written) and never builds the targets;
+``calculate_loss(predictions, targets)`` stays, composed, for callers that hold the two lists.
 """
 import warnings
 from typing import Callable
@@ -42,6 +49,7 @@ from ..segmentation.unet import UNet
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from .dino import DINO
 from .ibot import iBOT
+from .jepa import IJEPA
 from .losses import (DinoLoss, NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss,
                      simsiam_loss)
 
@@ -501,3 +509,78 @@ class iBOTPL(iBOT, SelfSLBasePL):
 
     def test_step(self, batch, batch_idx):
         return self.step(batch, "test_loss")
+
+
+class IJEPAPL(IJEPA, SelfSLBasePL):
+    """I-JEPA on a ViT encoder (pl.py:987-1165). ``ema`` is the teacher and is required. The
+    reference's order in ``__init__``: ``init_loss``, ``ema.update(self)`` (which makes the teacher
+    from the initial weights), ``save_hyperparameters``, ``setup_metrics``. Every ``step`` draws new
+    context and target blocks, validation included; the EMA moves in training only."""
+
+    def __init__(self, image_key: str = "image", learning_rate: float = 0.001, batch_size: int = 4,
+                 weight_decay: float = 0.005, training_dataloader_call: Callable = None,
+                 n_epochs: int = 1000, n_steps: int = None, warmup_steps: int = 0,
+                 start_decay: int = None, ema: torch.nn.Module = None, ssl_method: str = "simclr",
+                 temperature: float = 1.0, vic_reg_loss_params: dict = {},
+                 stop_gradient: bool = True, channels_to_batch: bool = False,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        hp = dict(image_key=image_key, learning_rate=learning_rate, batch_size=batch_size,
+                  weight_decay=weight_decay, training_dataloader_call=training_dataloader_call,
+                  n_epochs=n_epochs, n_steps=n_steps, warmup_steps=warmup_steps,
+                  start_decay=start_decay, temperature=temperature,
+                  vic_reg_loss_params=vic_reg_loss_params, stop_gradient=stop_gradient,
+                  channels_to_batch=channels_to_batch, ssl_method="ijepa")
+        for k, v in hp.items():   # plain attributes: set before Module.__init__, as the reference does
+            object.__setattr__(self, k, v)
+        if channels_to_batch is True:
+            kwargs["backbone_args"]["in_channels"] = 1
+        super().__init__(*args, **kwargs)
+        self.optimizer_eps = optimizer_eps
+        self.ema = ema
+        if self.ema is None:
+            raise ValueError("I-JEPA requires an EMA (teacher) copy of the network "
+                             "(`ema` must be an ExponentialMovingAverage module).")
+        self.init_loss()
+        self.ema.update(self)
+        self.save_hyperparameters()
+        self.setup_metrics()
+
+    def init_loss(self):
+        self.loss = torch.nn.SmoothL1Loss()
+
+    def calculate_loss(self, predictions, targets, *args):
+        """The mean over the blocks of ``SmoothL1Loss()(p, t)`` on lists of predictions and
+        (normalised, gathered) targets: the composed path. ``step`` computes the same value from
+        the teacher's raw output without building the targets."""
+        return torch.stack([self.loss(p, t) for p, t in zip(predictions, targets)]).mean()
+
+    def step(self, batch, loss_str: str, train=False):
+        x = batch[self.image_key]
+        if self.channels_to_batch is True:
+            x = x.reshape(-1, 1, *x.shape[2:])
+        predictions, h, rows = self.forward_blocks(x, self.ema)
+        loss = torch.stack([HF.ijepa_block_loss(p, h, r)
+                            for p, r in zip(predictions, rows)]).mean()
+        if train is True:
+            self.ema.update(self)
+        self.log(loss_str, loss, batch_size=x.shape[0], on_epoch=True, on_step=False,
+                 prog_bar=True, sync_dist=True)
+        return loss
+
+    def training_step(self, batch, batch_idx):
+        return self.step(batch, "loss", train=True)
+
+    def validation_step(self, batch, batch_idx):
+        return self.step(batch, "val_loss")
+
+    def test_step(self, batch, batch_idx):
+        return self.step(batch, "test_loss")
+
+    def configure_optimizers(self) -> dict:
+        """pl.py:1129-1165: AdamW over decay + "normalization" parameters in one group (the
+        latter last), cosine schedule with warm-up down to 1e-6."""
+        conf = super().configure_optimizers()
+        conf["lr_scheduler"]["scheduler"] = CosineAnnealingWithWarmupLR(
+            conf["optimizer"], T_max=self.n_steps if self.n_steps is not None else self.n_epochs,
+            start_decay=self.start_decay, n_warmup_steps=self.warmup_steps, eta_min=1e-6)
+        return conf

@@ -2883,6 +2883,133 @@ def ibot_bwd(s, y, rows, centers, stats, d_red, g_loss, class_token, reduce, t1,
     return ds
 
 
+# ---- I-JEPA (csrc/ijepa.hip) ------------------------------------------------------------------
+def ijepa_gather_fwd(x, rows):
+    """y [B, M, E] = x[:, rows] for x [B, N, E] and sorted unique ``rows`` (host indices or a
+    ``TokenRows``). IndexError, on the host, for a row outside [0, N)."""
+    if x.dim() != 3:
+        raise ValueError(f"ijepa_gather: [B, N, E] expected, got {tuple(x.shape)}")
+    B, N, E = x.shape
+    rows = token_rows(rows, N, x.device)
+    _require_cuda(x)
+    _ibot_3d("ijepa_gather", x)
+    y = torch.empty((B, len(rows), E), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_ijepa_gather_fwd(_ptr(x), _ptr(rows.dev), B, N, E, len(rows), _ptr(y),
+                                            _stream()))
+    return y
+
+
+def ijepa_gather_bwd(dy, rows, N):
+    """dx [B, N, E], written whole by one launch: row n is dy[:, inv[n]] or zeros."""
+    if dy.dim() != 3:
+        raise ValueError(f"ijepa_gather: [B, M, E] expected, got {tuple(dy.shape)}")
+    rows = token_rows(rows, N, dy.device)
+    B, M, E = dy.shape
+    if M != len(rows):
+        raise ValueError(f"ijepa_gather: a gradient of {M} rows for a table of {len(rows)}")
+    _require_cuda(dy)
+    _ibot_3d("ijepa_gather", dy)
+    dx = torch.empty((B, int(N), E), device=dy.device, dtype=torch.float32)
+    check(_lib.lib().adell_ijepa_gather_bwd(_ptr(dy), _ptr(rows.inv), B, int(N), E, M, _ptr(dx),
+                                            _stream()))
+    return dx
+
+
+def _ijepa_predictor_tables(ctx_rows, tgt_rows, T, device):
+    ctx, tgt = token_rows(ctx_rows, T, device), token_rows(tgt_rows, T, device)
+    if np.intersect1d(ctx.host, tgt.host).size:
+        raise ValueError("ijepa_predictor: context and target rows must be disjoint")
+    return ctx, tgt
+
+
+def ijepa_predictor_fwd(e, pos, mask, ctx_rows, tgt_rows):
+    """out [B, nc + nt, P]: ``e + pos[:, ctx]`` followed by ``mask + pos[:, tgt]`` for e [B, nc, P],
+    pos [1, T, P] and mask [1, 1, P]; the two row sets are disjoint."""
+    if e.dim() != 3 or pos.dim() != 3 or pos.shape[0] != 1 or pos.shape[2] != e.shape[2]:
+        raise ValueError(f"ijepa_predictor: e [B, nc, P] and pos [1, T, P] expected, got "
+                         f"{tuple(e.shape)} and {tuple(pos.shape)}")
+    B, nc, P = e.shape
+    T = pos.shape[1]
+    ctx, tgt = _ijepa_predictor_tables(ctx_rows, tgt_rows, T, e.device)
+    if len(ctx) != nc:
+        raise ValueError(f"ijepa_predictor: {nc} context tokens for a table of {len(ctx)}")
+    if mask.numel() != P:
+        raise ValueError(f"ijepa_predictor: a mask token of {mask.numel()} features for {P}")
+    _require_cuda(e, pos, mask)
+    _ibot_3d("ijepa_predictor", e, pos)
+    mask = mask.reshape(-1).contiguous()
+    out = torch.empty((B, nc + len(tgt), P), device=e.device, dtype=torch.float32)
+    check(_lib.lib().adell_ijepa_predictor_fwd(_ptr(e), _ptr(pos), _ptr(mask), _ptr(ctx.dev),
+                                               _ptr(tgt.dev), B, nc, len(tgt), T, P, _ptr(out),
+                                               _stream()))
+    return out
+
+
+def ijepa_predictor_bwd(dout, ctx_rows, tgt_rows, T, need_e=True, need_pos=True, need_mask=True):
+    """(de [B, nc, P], dpos [1, T, P], dmask [1, 1, P]) of ``ijepa_predictor_fwd``; dpos is written
+    whole (zeros outside both tables), every sum in a fixed order. A gradient that is not needed
+    is None (dmask is summed from dpos, which is then computed too)."""
+    if dout.dim() != 3:
+        raise ValueError(f"ijepa_predictor: [B, nc + nt, P] expected, got {tuple(dout.shape)}")
+    ctx, tgt = _ijepa_predictor_tables(ctx_rows, tgt_rows, T, dout.device)
+    B, n, P = dout.shape
+    nc, nt = len(ctx), len(tgt)
+    if n != nc + nt:
+        raise ValueError(f"ijepa_predictor: a gradient of {n} rows for {nc} + {nt}")
+    _require_cuda(dout)
+    _ibot_3d("ijepa_predictor", dout)
+    dev = dout.device
+    de = torch.empty((B, nc, P), device=dev, dtype=torch.float32) if need_e else None
+    dpos = torch.empty((1, int(T), P), device=dev, dtype=torch.float32) \
+        if (need_pos or need_mask) else None
+    dmask = torch.empty((1, 1, P), device=dev, dtype=torch.float32) if need_mask else None
+    check(_lib.lib().adell_ijepa_predictor_bwd(_ptr(dout), _ptr(tgt.dev), _ptr(ctx.inv), _ptr(tgt.inv),
+                                               B, nc, nt, int(T), P, _ptr(de), _ptr(dpos),
+                                               _ptr(dmask), _stream()))
+    return de, (dpos if need_pos else None), dmask
+
+
+def ijepa_loss_fwd(pred, h, rows):
+    """(loss, stats [B * nt, 2]): ``SmoothL1Loss()(pred, layer_norm(h, (E,))[:, rows])`` for pred
+    [B, nt, E] and the teacher's raw output h [B, N, E]; the normalised h is never written. stats
+    holds (mean, rstd) of every target row for the backward."""
+    if pred.dim() != 3 or h.dim() != 3 or h.shape[0] != pred.shape[0] or h.shape[2] != pred.shape[2]:
+        raise ValueError(f"ijepa_loss: pred [B, nt, E] and h [B, N, E] expected, got "
+                         f"{tuple(pred.shape)} and {tuple(h.shape)}")
+    B, nt, E = pred.shape
+    N = h.shape[1]
+    rows = token_rows(rows, N, pred.device)
+    if len(rows) != nt:
+        raise ValueError(f"ijepa_loss: {nt} predicted rows for a table of {len(rows)}")
+    _require_cuda(pred, h)
+    _ibot_3d("ijepa_loss", pred, h)
+    R = B * nt
+    buf = torch.empty((3 * R + 1,), device=pred.device, dtype=torch.float32)
+    stats, part, loss = buf[:2 * R].view(R, 2), buf[2 * R:3 * R], buf[3 * R]
+    base = buf.data_ptr()
+    check(_lib.lib().adell_ijepa_loss_fwd(_ptr(pred), _ptr(h), _ptr(rows.dev), B, nt, N, E,
+                                          ctypes.c_void_p(base), ctypes.c_void_p(base + 8 * R),
+                                          ctypes.c_void_p(base + 12 * R), _stream()))
+    return loss, stats
+
+
+def ijepa_loss_bwd(pred, h, rows, stats, g):
+    """dpred = g * clamp(pred - target, -1, 1) / (B * nt * E) from the saved statistics; g is the
+    incoming gradient (one element, on the device)."""
+    B, nt, E = pred.shape
+    N = h.shape[1]
+    rows = token_rows(rows, N, pred.device)
+    _require_cuda(pred, h, stats, g)
+    _ibot_3d("ijepa_loss", pred, h)
+    if len(rows) != nt or tuple(stats.shape) != (B * nt, 2) or not stats.is_contiguous():
+        raise ValueError(f"ijepa_loss: rows / statistics do not match pred {tuple(pred.shape)}")
+    g = g.reshape(-1).contiguous()
+    dpred = torch.empty_like(pred)
+    check(_lib.lib().adell_ijepa_loss_bwd(_ptr(pred), _ptr(h), _ptr(rows.dev), _ptr(stats), _ptr(g),
+                                          B, nt, N, E, _ptr(dpred), _stream()))
+    return dpred
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

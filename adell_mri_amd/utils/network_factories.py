@@ -2,9 +2,9 @@
 (adell_mri/utils/network_factories.py:493-701) and ``get_ssl_network`` (:705-1028) on this
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
 constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
-``DINOPL`` and ``ssl_method="ibot"`` ``iBOTPL`` on a ViT encoder (:869-956; ``TypeError`` for any
-other ``net_type``). Members outside the built path (the MONAI wrappers, the other ViT-based SSL
-methods: I-JEPA and MAE; Barlow Twins)
+``DINOPL``, ``ssl_method="ibot"`` ``iBOTPL`` and ``ssl_method="ijepa"`` ``IJEPAPL`` on a ViT encoder
+(:799-956; ``TypeError`` for any other ``net_type``). Members outside the built path (the MONAI
+wrappers, the ViT masked autoencoder, Barlow Twins)
 raise ``NotImplementedError`` -- there is no eager-torch fallback.
 """
 from typing import Any, Callable
@@ -13,7 +13,7 @@ import torch
 
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
-from ..modules.self_supervised.pl import (DINOPL, SelfSLConvNeXtPL, SelfSLResNetPL,
+from ..modules.self_supervised.pl import (DINOPL, IJEPAPL, SelfSLConvNeXtPL, SelfSLResNetPL,
                                           SelfSLUNetPL, iBOTPL)
 
 OPTIMIZER_EPS_DEFAULT = 1e-8
@@ -130,7 +130,12 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
     ``backbone_args``, the masker's patch sizes [4, 4] ... [8, 8] by default, ``ValueError`` without
     ``ema`` (raised by ``iBOTPL``). One difference on purpose: the reference's built-in 224 x 224
     default backbone is not mirrored for iBOT -- a configuration without ``"backbone_args"`` raises
-    ``NotImplementedError``; every real configuration names its backbone."""
+    ``NotImplementedError``; every real configuration names its backbone.
+    ``"ijepa"`` builds ``IJEPAPL`` (:799-849) the same way: ``TypeError`` unless ``net_type ==
+    "vit"``, the predictor's ``projection_head_args`` two blocks of ``n_encoder_features`` with 3
+    heads by default, patch sizes [4, 4] ... [8, 8], one context and four target blocks,
+    ``predictor_dim`` None, ``image_key="image"``, ``ValueError`` without ``ema`` (raised by
+    ``IJEPAPL``) -- and, as for iBOT, ``NotImplementedError`` without ``"backbone_args"``."""
     common = {"training_dataloader_call": train_loader_call, "n_epochs": max_epochs,
               "n_steps": max_steps_optim, "warmup_steps": warmup_steps, "ema": ema,
               "batch_size": network_config.get("batch_size", 32),
@@ -183,7 +188,31 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
                   "teacher_score_method": network_config.get("teacher_score_method", "center"),
                   "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
         return iBOTPL(**{**common, **config})
-    if ssl_method in ("ijepa", "mae", "barlow"):
+    if ssl_method == "ijepa":
+        if net_type != "vit":
+            raise TypeError("IJEPA only supports net_type='vit', got %s" % net_type)
+        if "backbone_args" not in network_config:
+            raise NotImplementedError(
+                "ssl_method 'ijepa': the reference's built-in 224 x 224 default backbone is not "
+                "mirrored for I-JEPA; `backbone_args` must be given in the network configuration")
+        backbone_args = network_config["backbone_args"]
+        n_encoder_features = backbone_args.get("embedding_size", backbone_args["attention_dim"])
+        config = {"image_key": "image", "backbone_args": backbone_args,
+                  "projection_head_args": network_config.get(
+                      "projection_head_args",
+                      {"number_of_blocks": 2, "attention_dim": n_encoder_features,
+                       "hidden_dim": n_encoder_features, "n_heads": 3}),
+                  "feature_map_dimensions": [s // p for s, p in zip(backbone_args["image_size"],
+                                                                    backbone_args["patch_size"])],
+                  "n_encoder_features": n_encoder_features,
+                  "min_patch_size": network_config.get("min_patch_size", [4, 4]),
+                  "max_patch_size": network_config.get("max_patch_size", [8, 8]),
+                  "n_patches": network_config.get("n_patches", 1),
+                  "n_masked_patches": network_config.get("n_masked_patches", 4),
+                  "predictor_dim": network_config.get("predictor_dim", None),
+                  "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
+        return IJEPAPL(**{**common, **config})
+    if ssl_method in ("mae", "barlow"):
         raise NotImplementedError(f"ssl_method {ssl_method!r} (ViT / Barlow-Twins wrappers) is "
                                   "outside the HIP path (SURVEY.md section 2: out of scope)")
     boilerplate = {"training_dataloader_call": train_loader_call,

@@ -875,6 +875,36 @@ int adell_ibot_bwd(const float* s, const float* y, const float* centers, const f
                    int class_token, int reduce_cls, float t1, float t2, int teacher_is_scores,
                    float* ds, void* stream);
 
+/* I-JEPA (self_supervised/jepa.py, IJEPAPL; csrc/ijepa.hip): token plumbing and loss. fp32, dense, one
+ * wave per row, no float atomics, results repeat bit for bit. Index tables are int32 on the device,
+ * sorted and unique, and are NOT range-checked here: the caller checks them on the host.
+ * adell_ijepa_gather_fwd: y [B][M][E], y[b][j] = x[b][rows[j]] of x [B][N][E]. _bwd: every row of
+ * dx [B][N][E] written once: dx[b][n] = dy[b][inv[n]], zeros where inv[n] < 0 (inv [N]: token -> j).
+ * adell_ijepa_predictor_fwd: out [B][nc + nt][P]; out[b][j] = e[b][j] + pos[ctx[j]] for j < nc (e
+ * [B][nc][P], pos [T][P]), out[b][nc + j] = mask[:] + pos[tgt[j]] (mask [P]); ctx and tgt disjoint.
+ * _bwd: de [B][nc][P] = dout[:, :nc]; dpos [T][P] whole: row t = sum_b dout[b][inv_ctx[t]] or sum_b
+ * dout[b][nc + inv_tgt[t]] (b in order) or zeros; dmask [P] = sum_j dpos[tgt[j]] (j in order, fp64),
+ * a second launch. de, dpos, dmask may each be NULL (dmask needs dpos).
+ * adell_ijepa_loss_fwd: loss[0] = mean over B nt E of smooth_l1(pred - t), beta 1, with t[b][j] the
+ * layer norm (no affine, eps 1e-5, biased variance) of h[b][rows[j]][:]; pred [B][nt][E], h
+ * [B][N][E]. stats [B nt][2] takes (mean, rstd) per row, part [B nt] the row sums, which a one-wave
+ * second launch adds in a fixed order in fp64. _bwd: dpred = g[0] clamp(pred - t, -1, 1) / (B nt E)
+ * from the saved stats; h takes no gradient. */
+int adell_ijepa_gather_fwd(const float* x, const int* rows, int B, int N, int E, int M, float* y,
+                           void* stream);
+int adell_ijepa_gather_bwd(const float* dy, const int* inv, int B, int N, int E, int M, float* dx,
+                           void* stream);
+int adell_ijepa_predictor_fwd(const float* e, const float* pos, const float* mask, const int* ctx,
+                              const int* tgt, int B, int nc, int nt, int T, int P, float* out,
+                              void* stream);
+int adell_ijepa_predictor_bwd(const float* dout, const int* tgt, const int* inv_ctx, const int* inv_tgt,
+                              int B, int nc, int nt, int T, int P, float* de, float* dpos, float* dmask,
+                              void* stream);
+int adell_ijepa_loss_fwd(const float* pred, const float* h, const int* rows, int B, int nt, int N, int E,
+                         float* stats, float* part, float* loss, void* stream);
+int adell_ijepa_loss_bwd(const float* pred, const float* h, const int* rows, const float* stats,
+                         const float* g, int B, int nt, int N, int E, float* dpred, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
