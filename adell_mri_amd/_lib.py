@@ -121,6 +121,8 @@ SIGNATURES = {
                                         + [ctypes.POINTER(AdnSite), ctypes.POINTER(AdnSite), _vp, _i, _vp]),
     "adell_norm_act_bwd_workspace": (_l, [ctypes.POINTER(NormActDesc)]),
     "adell_norm_act_bwd": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 11 + [ctypes.c_size_t, _vp]),
+    "adell_norm_act_plan": (_i, [ctypes.POINTER(NormActDesc)] + [_i] * 6 + [_vp]),
+    "adell_norm_act_stats_plan": (_i, [_i, _i, _i, _vp]),
     "adell_norm_act_bwd_sums": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 11 + [ctypes.c_size_t, _vp]),
     "adell_norm_act_bwd_apply_sums": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 10
                                       + [ctypes.c_size_t, _vp]),

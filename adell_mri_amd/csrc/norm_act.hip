@@ -7,6 +7,21 @@
 ADELL_RNG_STEP_DEFINE(norm_act)
 
 // ---------------------------------------------------------------------------
+// Thresholds of this file's routes. adell_na_plan / adell_na_stats_plan below are the only readers
+// on the host, and adell_norm_act_plan / adell_norm_act_stats_plan report what they decide
+// (tests/test_norm_act_plans.py keeps a case on each side of each of them).
+// ---------------------------------------------------------------------------
+#define ADELL_NA_GENERIC_MAXBLOCKS (256 * 16)  // grid cap of the generic kernels: above it they grid-stride
+#define ADELL_NA_FAST_MAXROWS 1024             // blocks (= partial rows) per item of the fast partials kernel
+#define ADELL_NA_FAST_MAXC 1024                // widest power-of-two C of the bandwidth-tuned kernels
+#define ADELL_STATS_FOLD_ABOVE 512             // more partial rows than this: two-level fold
+#define ADELL_STATS_FOLD_ROWS 256              // rows one block of the first level folds
+// row loops of the finalize kernels: 8 lanes x eight rows in flight while row t + 56 exists (from 57
+// rows), 32 lanes x two rows in flight while row t + 32 exists (from 33 rows)
+#define ADELL_FIN8_SPAN 56
+#define ADELL_FIN2_SPAN 32
+
+// ---------------------------------------------------------------------------
 // Per-(n,c) statistics from per-block partials [N][ntiles][C][2] (sum, sumsq)
 // written by the conv epilogue or by adell_channel_partials_kernel.
 // ---------------------------------------------------------------------------
@@ -23,7 +38,7 @@ __global__ __launch_bounds__(256) void adell_stats_finalize_kernel(
       // eight rows in flight, added in row order (the launch is latency-bound: 2-16 blocks)
       const float* p = part + ((size_t)n * ntiles * C + c) * 2;
       int t = sl;
-      for (; t + 56 < ntiles; t += 64) {
+      for (; t + ADELL_FIN8_SPAN < ntiles; t += 64) {
         float2 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
@@ -72,14 +87,14 @@ __global__ __launch_bounds__(256) void adell_stats_fold_kernel(const float* __re
   __shared__ double sh[8][32][2];
   const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cl, n = blockIdx.y, z = blockIdx.z;
-  const int t0 = z * 256;
-  const int t1 = t0 + 256 < ntiles ? t0 + 256 : ntiles;
+  const int t0 = z * ADELL_STATS_FOLD_ROWS;
+  const int t1 = t0 + ADELL_STATS_FOLD_ROWS < ntiles ? t0 + ADELL_STATS_FOLD_ROWS : ntiles;
   double s1 = 0.0, s2 = 0.0;
   if (c < C) {
     // eight rows in flight, added in row order
     const float* p = part + ((size_t)n * ntiles * pstride + poff + c) * 2;
     int t = t0 + sl;
-    for (; t + 56 < t1; t += 64) {
+    for (; t + ADELL_FIN8_SPAN < t1; t += 64) {
       float2 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u)
@@ -112,24 +127,53 @@ __global__ __launch_bounds__(256) void adell_stats_fold_kernel(const float* __re
   }
 }
 
+// How a chain of `ntiles` partial rows per item is reduced: in one level by the finalize kernel, or
+// -- above ADELL_STATS_FOLD_ABOVE rows -- first folded ADELL_STATS_FOLD_ROWS rows at a time into Z
+// rows per item (adell_stats_fold_kernel, `ws_bytes` of workspace). The decision of
+// adell_stats_finalize, adell_bn_stats_sums and adell_norm_act_bwd_from_dt, and what
+// adell_norm_act_stats_plan reports. Host only.
+struct AdellNaStatsPlan {
+  int levels;     // 1 or 2
+  int Z;          // rows per item after the first level (0 with one level)
+  long ws_bytes;  // folded rows [N][Z][C][2]
+};
+
+static AdellNaStatsPlan adell_na_stats_plan(long N, long ntiles, long C) {
+  AdellNaStatsPlan p = {1, 0, 0};
+  if (ntiles <= ADELL_STATS_FOLD_ABOVE) return p;
+  p.levels = 2;
+  p.Z = (int)((ntiles + ADELL_STATS_FOLD_ROWS - 1) / ADELL_STATS_FOLD_ROWS);
+  p.ws_bytes = (long)sizeof(float) * N * p.Z * C * 2;
+  return p;
+}
+
 extern "C" long adell_stats_finalize_workspace(int N, int ntiles, int C) {
-  if (ntiles <= 512) return 0;
-  const long Z = (ntiles + 255) / 256;
-  return (long)sizeof(float) * N * Z * C * 2;
+  return adell_na_stats_plan(N, ntiles, C).ws_bytes;
+}
+
+extern "C" int adell_norm_act_stats_plan(int N, int ntiles, int C, long* out) {
+  ADELL_REQUIRE(out && N > 0 && ntiles > 0 && C > 0, "norm_act_stats_plan: bad arguments");
+  const AdellNaStatsPlan p = adell_na_stats_plan(N, ntiles, C);
+  out[0] = p.levels;
+  out[1] = p.Z;
+  out[2] = p.ws_bytes;
+  out[3] = ADELL_FIN8_SPAN + 1;  // rows from which the all-items / record kernels keep eight in flight
+  out[4] = ADELL_FIN2_SPAN + 1;  // rows from which the per-item backward finalize keeps two in flight
+  return ADELL_OK;
 }
 
 extern "C" int adell_stats_finalize(const float* partials, int N, int ntiles, int C,
                                     long count, float eps, int per_item, float* mean,
                                     float* rstd, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  ADELL_REQUIRE(partials && mean && rstd, "stats_finalize: null pointer");
   ADELL_REQUIRE(N > 0 && ntiles > 0 && C > 0 && count > 0, "stats_finalize: bad dims");
+  const AdellNaStatsPlan sp = adell_na_stats_plan(N, ntiles, C);
+  ADELL_REQUIRE(sp.levels == 1 || (workspace && (long)workspace_bytes >= sp.ws_bytes),
+                "stats_finalize: workspace too small");
+  ADELL_REQUIRE(partials && mean && rstd, "stats_finalize: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const long need = adell_stats_finalize_workspace(N, ntiles, C);
-  if (need > 0) {
-    ADELL_REQUIRE(workspace && (long)workspace_bytes >= need,
-                  "stats_finalize: workspace too small");
-    const int Z = (ntiles + 255) / 256;
+  if (sp.levels == 2) {
+    const int Z = sp.Z;
     hipLaunchKernelGGL(adell_stats_fold_kernel, dim3(adell_cdiv(C, 32), N, Z), dim3(256), 0, st,
                        partials, ntiles, C, Z, (float*)workspace, C, 0);
     partials = (const float*)workspace;
@@ -467,16 +511,141 @@ static int adell_na_fill(NormActArgs* a, const adell_norm_act_desc* d) {
   return ADELL_OK;
 }
 
-static int adell_ew_blocks(long n4) {
-  long b = (n4 + 255) / 256;
-  if (b > 256 * 16) b = 256 * 16;
+// ---------------------------------------------------------------------------
+// Routes of a site: every decision the launchers of this file take, and what adell_norm_act_plan
+// reports. Host only (no device property is read).
+//   scalar : any C, any alignment; one element per thread, grid-strided above the grid cap
+//   float4 : C % 4 == 0 and 16-byte aligned tensors; one float4 per thread, grid-strided likewise
+//   fast   : float4's conditions and a power-of-two C <= ADELL_NA_FAST_MAXC: one grid row per item,
+//            contiguous chunks of a multiple of 1024 float4 per block (the "bandwidth-tuned" kernels)
+//   narrow : the fast kernels at C = 1 or 2 with V * C % 4 == 0 (a float4 spans 4 / C voxels)
+// The forward looks at x and out, the backward at x, dout and dx (both of its passes take the same
+// route). Keep bits and split rows exist on the fast route only (never narrow); the low-rank
+// backward and adell_norm_act_bwd_from_dt need the fast route too.
+// ---------------------------------------------------------------------------
+struct AdellNaPlan {
+  int fwd;                 // ADELL_NA_* (ADELL_NA_REFUSED: mask or split rows off the fast route)
+  long fwd_gx, fwd_gy;     // forward grid
+  int bwd;                 // ADELL_NA_* (ADELL_NA_REFUSED: low-rank gradient off the fast route)
+  long rows;               // partial rows per item the reduction pass writes (0: no such pass)
+  long apply_gx, apply_gy; // grid of the dx pass
+  int finalize;            // ADELL_NA_FIN_*
+  long ws_bytes;           // workspace adell_norm_act_bwd requires (0 without a reduction pass)
+  long mask_bytes;         // keep bits the forward stores (0: none)
+};
+
+// grid x of the generic kernels for `units` float4 (float4 route) or elements (scalar route)
+static long adell_ew_blocks(long units) {
+  long b = (units + 255) / 256;
+  if (b > ADELL_NA_GENERIC_MAXBLOCKS) b = ADELL_NA_GENERIC_MAXBLOCKS;
   if (b < 1) b = 1;
-  return (int)b;
+  return b;
+}
+// grid x (blocks per item) of the fast forward / dx kernels
+static long adell_na_fast_grid(long VC) {
+  long bx = ((VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
+  if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
+  if (bx < 1) bx = 1;
+  return bx;
+}
+// blocks per item of the fast partials kernel (each covers >= 1024 float4; above the cap the chunk
+// of a block grows to the next multiple of 1024 float4 and the last blocks write zero rows)
+static long adell_na_fast_blocks(long V, int C) {
+  long bx = ((V * C >> 2) + 256 * 4 - 1) / (256 * 4);
+  if (bx > ADELL_NA_FAST_MAXROWS) bx = ADELL_NA_FAST_MAXROWS;
+  if (bx < 1) bx = 1;
+  return bx;
+}
+
+static long adell_na_mask_bytes(const adell_norm_act_desc* d) {
+  return d->N * ((d->V * d->C + 255) / 256) * 32;
+}
+// partials [N][rows][C][2] for the larger of the two row counts + c1 [N][C] + c2 [N][C]: sized
+// before the tensors' alignment (and with it the route) is known
+static long adell_na_bwd_ws_bytes(const adell_norm_act_desc* d) {
+  long nt = adell_channel_partials_ntiles(d->V);
+  const long ntf = adell_na_fast_blocks(d->V, d->C);
+  if (ntf > nt) nt = ntf;
+  return (long)sizeof(float) * (d->N * nt * d->C * 2 + 2 * d->N * d->C);
+}
+
+// al_*: the tensor is 16-byte aligned (a tensor the call does not have counts as aligned);
+// want_mask: keep bits are stored (they are only with dropout); lr_co: factors of a low-rank dout
+// (0: a full dout); norm: the site has statistics; affine_grads: dgamma or dbeta is wanted.
+static AdellNaPlan adell_na_plan(const adell_norm_act_desc* d, bool al_x, bool al_out, bool al_dout,
+                                 bool al_dx, bool want_mask, bool split, int lr_co, bool norm,
+                                 bool affine_grads) {
+  AdellNaPlan p = {};
+  const long VC = d->V * d->C, total = d->N * VC;
+  const bool mask = want_mask && d->drop_p > 0.f;
+  const bool fast_c = adell_is_pow2(d->C) && d->C <= ADELL_NA_FAST_MAXC;
+  // ---- forward ----
+  {
+    const bool aligned = al_x && al_out;
+    const bool vec = d->C % 4 == 0 && aligned;
+    const bool narrow = d->C < 4 && VC % 4 == 0 && !mask && aligned;
+    if ((vec || narrow) && fast_c && (VC >> 2) < (1L << 40)) {
+      p.fwd = vec ? ADELL_NA_FAST : ADELL_NA_NARROW;
+      p.fwd_gx = adell_na_fast_grid(VC);
+      p.fwd_gy = d->N;
+    } else if (mask || split) {
+      p.fwd = ADELL_NA_REFUSED;
+    } else {
+      p.fwd = vec ? ADELL_NA_FLOAT4 : ADELL_NA_SCALAR;
+      p.fwd_gx = adell_ew_blocks(vec ? total >> 2 : total);
+      p.fwd_gy = 1;
+    }
+    if (split && d->C < 16) p.fwd = ADELL_NA_REFUSED, p.fwd_gx = p.fwd_gy = 0;
+    p.mask_bytes = mask && p.fwd == ADELL_NA_FAST ? adell_na_mask_bytes(d) : 0;
+  }
+  // ---- backward ----
+  {
+    const bool aligned = al_x && al_dout && al_dx;
+    const bool vec = d->C % 4 == 0 && aligned;
+    const bool narrow = d->C < 4 && VC % 4 == 0 && lr_co == 0 && aligned;
+    const bool fast = (vec || narrow) && fast_c;
+    const bool reduce = norm || affine_grads;
+    if (fast) {
+      p.bwd = vec ? ADELL_NA_FAST : ADELL_NA_NARROW;
+      p.rows = reduce ? adell_na_fast_blocks(d->V, d->C) : 0;
+      p.apply_gx = adell_na_fast_grid(VC);
+      p.apply_gy = d->N;
+    } else if (lr_co != 0) {
+      p.bwd = ADELL_NA_REFUSED;
+    } else {
+      p.bwd = vec ? ADELL_NA_FLOAT4 : ADELL_NA_SCALAR;
+      p.rows = reduce ? adell_channel_partials_ntiles(d->V) : 0;
+      p.apply_gx = adell_ew_blocks(vec ? total / 4 : total);
+      p.apply_gy = 1;
+    }
+    if (p.bwd != ADELL_NA_REFUSED && reduce) {
+      p.finalize = d->stats_per_item && !affine_grads && d->N <= 65535 ? ADELL_NA_FIN_PER_ITEM
+                                                                       : ADELL_NA_FIN_ALL_ITEMS;
+      p.ws_bytes = adell_na_bwd_ws_bytes(d);
+    }
+  }
+  return p;
+}
+
+static bool adell_na_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int adell_norm_act_plan(const adell_norm_act_desc* d, int aligned, int want_mask,
+                                   int split, int lowrank, int norm, int affine_grads, long* out) {
+  ADELL_REQUIRE(d && out && d->N > 0 && d->V > 0 && d->C > 0, "norm_act_plan: bad arguments");
+  ADELL_REQUIRE(lowrank >= 0 && lowrank <= 4, "norm_act_plan: 0..4 low-rank factors");
+  const AdellNaPlan p =
+      adell_na_plan(d, (aligned & ADELL_NA_ALIGNED_X) != 0, (aligned & ADELL_NA_ALIGNED_OUT) != 0,
+                    (aligned & ADELL_NA_ALIGNED_DOUT) != 0, (aligned & ADELL_NA_ALIGNED_DX) != 0,
+                    want_mask != 0, split != 0, lowrank, norm != 0, affine_grads != 0);
+  out[0] = p.fwd; out[1] = p.fwd_gx; out[2] = p.fwd_gy;
+  out[3] = p.bwd; out[4] = p.rows; out[5] = p.apply_gx; out[6] = p.apply_gy;
+  out[7] = p.finalize; out[8] = p.ws_bytes; out[9] = p.mask_bytes;
+  return ADELL_OK;
 }
 
 extern "C" long adell_norm_act_mask_bytes(const adell_norm_act_desc* d) {
   if (!d || d->N <= 0 || d->V <= 0 || d->C <= 0) return ADELL_E_BADARG;
-  return d->N * ((d->V * d->C + 255) / 256) * 32;
+  return adell_na_mask_bytes(d);
 }
 
 static int adell_norm_act_fwd_impl(const adell_norm_act_desc* d, const float* x,
@@ -497,27 +666,21 @@ static int adell_norm_act_fwd_impl(const adell_norm_act_desc* d, const float* x,
                 "norm_act_fwd: C %% 4 != 0 needs < 2^31 elements");
   a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta;
   a.act_w = act_w; a.out = out;
-  a.vec = (d->C % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)out & 15) == 0);
   // (1 / 2 channels -- the 2-channel input block, the sigmoid head -- take the bandwidth-tuned
   // kernels too: a float4 is then 4 / C voxels)
-  const bool narrow = d->C < 4 && a.VC % 4 == 0 && keep_mask == nullptr &&
-                      (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  if ((a.vec || narrow) && adell_is_pow2(d->C) && d->C <= 1024 && (a.VC >> 2) < (1L << 40)) {
-    long bx = ((a.VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
-    if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
-    if (bx < 1) bx = 1;
-    ADELL_ACT_DISPATCH(adell_norm_act_fwd_fast_kernel, d->act, dim3((unsigned)bx, (unsigned)d->N),
-                       (hipStream_t)stream, a);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  }
-  if (keep_mask != nullptr || split) {
+  const AdellNaPlan p = adell_na_plan(d, adell_na_al16(x), adell_na_al16(out), true, true,
+                                      keep_mask != nullptr, split != 0, 0, false, false);
+  if (p.fwd == ADELL_NA_REFUSED) {
     adell_set_error("norm_act_fwd_mask / _split: needs a power-of-two C <= 1024 and 16-byte aligned tensors");
     return ADELL_E_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(adell_norm_act_fwd_kernel,
-                     dim3(adell_ew_blocks(a.vec ? (a.total >> 2) : a.total)), dim3(256), 0,
-                     (hipStream_t)stream, a);
+  a.vec = p.fwd == ADELL_NA_FLOAT4;
+  const dim3 grid((unsigned)p.fwd_gx, (unsigned)p.fwd_gy);
+  if (p.fwd == ADELL_NA_FAST || p.fwd == ADELL_NA_NARROW) {
+    ADELL_ACT_DISPATCH(adell_norm_act_fwd_fast_kernel, d->act, grid, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(adell_norm_act_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  }
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -547,11 +710,11 @@ extern "C" int adell_norm_act_fwd_split(const adell_norm_act_desc* d, const floa
                                         const float* gamma, const float* beta,
                                         const float* act_w, void* out_rows, int split_exp,
                                         void* keep_mask, void* stream) {
-  ADELL_REQUIRE(d && d->C >= 16 && d->C % 16 == 0 && adell_is_pow2(d->C) && d->C <= 1024,
-                "norm_act_fwd_split: C must be a power of two in 16..1024");
+  ADELL_REQUIRE(d && d->N > 0 && d->V > 0 && d->C > 0, "norm_act_fwd_split: bad dims");
   ADELL_REQUIRE(split_exp >= -100 && split_exp <= 100, "norm_act_fwd_split: bad exponent");
-  ADELL_REQUIRE((((uintptr_t)x | (uintptr_t)out_rows) & 15) == 0,
-                "norm_act_fwd_split: 16-byte aligned tensors");
+  ADELL_REQUIRE(adell_na_plan(d, adell_na_al16(x), adell_na_al16(out_rows), true, true,
+                              keep_mask != nullptr, true, 0, false, false).fwd == ADELL_NA_FAST,
+                "norm_act_fwd_split: C must be a power of two in 16..1024, the tensors 16-byte aligned");
   return adell_norm_act_fwd_impl(d, x, mean, rstd, gamma, beta, act_w, (float*)out_rows,
                                  d->drop_p > 0.f ? keep_mask : nullptr, stream, 1, split_exp);
 }
@@ -833,7 +996,7 @@ __global__ __launch_bounds__(256) void adell_na_bwd_finalize_item_kernel(
   double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
   if (c < C) {
     int t = sl;
-    for (; t + 32 < ntiles; t += 64) {
+    for (; t + ADELL_FIN2_SPAN < ntiles; t += 64) {
       const float2 u =
           *reinterpret_cast<const float2*>(part + (((size_t)n * ntiles + t) * pstride + poff + c) * 2);
       const float2 v = *reinterpret_cast<const float2*>(
@@ -908,13 +1071,6 @@ __global__ __launch_bounds__(256) void adell_na_bwd_apply_kernel(NormActBwdArgs 
 
 template <int ACT, bool LR = false> __global__ void adell_na_bwd_apply_fast_kernel(NormActBwdArgs a);
 template <int ACT, bool LR = false> __global__ void adell_na_bwd_partials_fast_kernel(NormActBwdArgs a);
-// blocks per item of the grid-strided partials kernel (each covers >= 1024 float4)
-static long adell_na_fast_blocks(long V, int C) {
-  long bx = ((V * C >> 2) + 256 * 4 - 1) / (256 * 4);
-  if (bx > 1024) bx = 1024;
-  if (bx < 1) bx = 1;
-  return bx;
-}
 
 static int adell_nab_fill(NormActBwdArgs* a, const adell_norm_act_desc* d) {
   ADELL_REQUIRE(d != nullptr, "norm_act_bwd: null descriptor");
@@ -940,10 +1096,7 @@ static int adell_nab_fill(NormActBwdArgs* a, const adell_norm_act_desc* d) {
 // workspace floats: partials [N][ntiles][C][2] + c1 [N][C] + c2 [N][C]
 extern "C" long adell_norm_act_bwd_workspace(const adell_norm_act_desc* d) {
   if (!d || d->N <= 0 || d->V <= 0 || d->C <= 0) return ADELL_E_BADARG;
-  long nt = adell_channel_partials_ntiles(d->V);
-  const long ntf = adell_na_fast_blocks(d->V, d->C);
-  if (ntf > nt) nt = ntf;
-  return (long)sizeof(float) * (d->N * nt * d->C * 2 + 2 * d->N * d->C);
+  return adell_na_bwd_ws_bytes(d);
 }
 
 static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
@@ -973,38 +1126,31 @@ extern "C" int adell_norm_act_bwd_lowrank(const adell_norm_act_desc* d, const fl
                                           const float* mean, const float* rstd, float* dx,
                                           void* workspace, size_t workspace_bytes, void* stream) {
   ADELL_REQUIRE(d && g && w && co >= 1 && co <= 4, "norm_act_bwd_lowrank: 1..4 factors expected");
-  ADELL_REQUIRE(adell_is_pow2(d->C) && d->C >= 4 && d->C <= 1024 &&
-                    (((uintptr_t)x | (uintptr_t)dx) & 15) == 0,
-                "norm_act_bwd_lowrank: needs a power-of-two C in 4..1024 and aligned tensors");
   return adell_norm_act_bwd_impl(d, x, x, mean, rstd, nullptr, nullptr, nullptr, dx, nullptr,
                                  nullptr, workspace, workspace_bytes, stream, g, w, co);
 }
 
-// Which kernels run: float4 (C % 4 == 0, aligned x / dout / dx), and the bandwidth-tuned ones
-// (power-of-two C <= 1024; C < 4 when a float4 spans voxels).
-static void adell_na_bwd_route(const NormActBwdArgs& a, const adell_norm_act_desc* d, bool* vec,
-                               bool* fast) {
-  const bool aligned = ((((uintptr_t)a.x | (uintptr_t)a.dout | (uintptr_t)a.dx) & 15) == 0);
-  *vec = (d->C % 4 == 0) && aligned;
-  const bool narrow = d->C < 4 && a.VC % 4 == 0 && !a.lr_g && aligned;
-  *fast = (*vec || narrow) && adell_is_pow2(d->C) && d->C <= 1024;
+// The backward half of adell_na_plan for the tensors of `a` (a.dx may be null: the record half of
+// a synchronised batch-norm site has none).
+static AdellNaPlan adell_na_bwd_plan(const NormActBwdArgs& a, const adell_norm_act_desc* d, bool norm,
+                                     bool affine_grads) {
+  return adell_na_plan(d, adell_na_al16(a.x), true, adell_na_al16(a.dout), adell_na_al16(a.dx), false,
+                       false, a.lr_g ? a.lr_co : 0, norm, affine_grads);
 }
 
-// Pass 1 of the backward: per-slab partials (sum dt, sum dt*hn) into a.part; the bandwidth-tuned
-// kernels have their own tile count, left in a.ntiles.
-static void adell_na_bwd_partials_launch(NormActBwdArgs& a, const adell_norm_act_desc* d, bool fast,
-                                         bool vec, hipStream_t st) {
-  dim3 grid(a.ntiles, (unsigned)d->N);
-  if (fast) {
-    a.ntiles = (int)adell_na_fast_blocks(d->V, d->C);
+// Pass 1 of the backward: per-slab partials (sum dt, sum dt*hn) into a.part; the row count of the
+// plan's route is left in a.ntiles.
+static void adell_na_bwd_partials_launch(NormActBwdArgs& a, const adell_norm_act_desc* d,
+                                         const AdellNaPlan& p, hipStream_t st) {
+  a.ntiles = (int)p.rows;
+  const dim3 grid(a.ntiles, (unsigned)d->N);
+  if (p.bwd == ADELL_NA_FAST || p.bwd == ADELL_NA_NARROW) {
     if (a.lr_g) {
-      ADELL_ACT_DISPATCH_LR(adell_na_bwd_partials_fast_kernel, d->act,
-                            dim3(a.ntiles, (unsigned)d->N), st, a);
+      ADELL_ACT_DISPATCH_LR(adell_na_bwd_partials_fast_kernel, d->act, grid, st, a);
     } else {
-      ADELL_ACT_DISPATCH(adell_na_bwd_partials_fast_kernel, d->act,
-                         dim3(a.ntiles, (unsigned)d->N), st, a);
+      ADELL_ACT_DISPATCH(adell_na_bwd_partials_fast_kernel, d->act, grid, st, a);
     }
-  } else if (vec)
+  } else if (p.bwd == ADELL_NA_FLOAT4)
     hipLaunchKernelGGL(adell_na_bwd_partials_kernel<true>, grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(adell_na_bwd_partials_kernel<false>, grid, dim3(256), 0, st, a);
@@ -1012,25 +1158,18 @@ static void adell_na_bwd_partials_launch(NormActBwdArgs& a, const adell_norm_act
 
 // Pass 2: dx from a.c1 / a.c2.
 static void adell_na_bwd_apply_launch(const NormActBwdArgs& a, const adell_norm_act_desc* d,
-                                      bool fast, bool vec, hipStream_t st) {
-  const long nw = vec ? a.total / 4 : a.total;
-  if (fast) {
-    long bx = ((a.VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
-    if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
-    if (bx < 1) bx = 1;
+                                      const AdellNaPlan& p, hipStream_t st) {
+  const dim3 grid((unsigned)p.apply_gx, (unsigned)p.apply_gy);
+  if (p.bwd == ADELL_NA_FAST || p.bwd == ADELL_NA_NARROW) {
     if (a.lr_g) {
-      ADELL_ACT_DISPATCH_LR(adell_na_bwd_apply_fast_kernel, d->act,
-                            dim3((unsigned)bx, (unsigned)d->N), st, a);
+      ADELL_ACT_DISPATCH_LR(adell_na_bwd_apply_fast_kernel, d->act, grid, st, a);
     } else {
-      ADELL_ACT_DISPATCH(adell_na_bwd_apply_fast_kernel, d->act,
-                         dim3((unsigned)bx, (unsigned)d->N), st, a);
+      ADELL_ACT_DISPATCH(adell_na_bwd_apply_fast_kernel, d->act, grid, st, a);
     }
-  } else if (vec)
-    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<true>, dim3(adell_ew_blocks(nw)), dim3(256), 0,
-                       st, a);
+  } else if (p.bwd == ADELL_NA_FLOAT4)
+    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<true>, grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<false>, dim3(adell_ew_blocks(nw)), dim3(256),
-                       0, st, a);
+    hipLaunchKernelGGL(adell_na_bwd_apply_kernel<false>, grid, dim3(256), 0, st, a);
 }
 
 static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
@@ -1044,24 +1183,24 @@ static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
   if (rc != ADELL_OK) return rc;
   a.lr_g = lr_g; a.lr_w = lr_w; a.lr_co = lr_co;
   a.lr_shift = adell_ilog2(d->C) - 2;
-  ADELL_REQUIRE(x && dout && dx, "norm_act_bwd: null pointer");
-  ADELL_REQUIRE((mean == nullptr) == (rstd == nullptr), "norm_act_bwd: mean/rstd mismatch");
   hipStream_t st = (hipStream_t)stream;
   a.x = x; a.dout = dout; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta;
   a.act_w = act_w; a.dx = dx;
-  bool vec, fast;
-  adell_na_bwd_route(a, d, &vec, &fast);
-  if (mean || dgamma || dbeta) {
-    ADELL_REQUIRE(workspace && (long)workspace_bytes >= adell_norm_act_bwd_workspace(d),
-                  "norm_act_bwd: workspace too small");
+  const AdellNaPlan p = adell_na_bwd_plan(a, d, mean != nullptr, dgamma || dbeta);
+  ADELL_REQUIRE(p.bwd != ADELL_NA_REFUSED,
+                "norm_act_bwd_lowrank: needs a power-of-two C in 4..1024 and aligned tensors");
+  // (the workspace is checked first: a short one is refused whatever else the call carries)
+  ADELL_REQUIRE(p.finalize == ADELL_NA_FIN_NONE || (workspace && (long)workspace_bytes >= p.ws_bytes),
+                "norm_act_bwd: workspace too small");
+  ADELL_REQUIRE(x && dout && dx, "norm_act_bwd: null pointer");
+  ADELL_REQUIRE((mean == nullptr) == (rstd == nullptr), "norm_act_bwd: mean/rstd mismatch");
+  if (p.finalize != ADELL_NA_FIN_NONE) {
     float* part = (float*)workspace;
-    long ntmax = a.ntiles;
-    if (adell_na_fast_blocks(d->V, d->C) > ntmax) ntmax = adell_na_fast_blocks(d->V, d->C);
-    float* c1 = part + (size_t)d->N * ntmax * d->C * 2;
+    float* c1 = part + (size_t)p.ws_bytes / sizeof(float) - 2 * (size_t)d->N * d->C;
     float* c2 = c1 + (size_t)d->N * d->C;
     a.part = part; a.c1 = c1; a.c2 = c2;
-    adell_na_bwd_partials_launch(a, d, fast, vec, st);
-    if (d->stats_per_item && !dgamma && !dbeta && d->N <= 65535)
+    adell_na_bwd_partials_launch(a, d, p, st);
+    if (p.finalize == ADELL_NA_FIN_PER_ITEM)
       hipLaunchKernelGGL(adell_na_bwd_finalize_item_kernel,
                          dim3(adell_cdiv(d->C, 8), (unsigned)d->N), dim3(256), 0, st,
                          (const float*)part, a.ntiles, d->C, (double)d->V, gamma, c1, c2, d->C, 0);
@@ -1070,7 +1209,7 @@ static int adell_norm_act_bwd_impl(const adell_norm_act_desc* d, const float* x,
                          st, (const float*)part, (int)d->N, a.ntiles, d->C, (double)d->V,
                          d->stats_per_item, gamma, c1, c2, dgamma, dbeta);
   }
-  adell_na_bwd_apply_launch(a, d, fast, vec, st);
+  adell_na_bwd_apply_launch(a, d, p, st);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -1193,14 +1332,24 @@ __global__ __launch_bounds__(256) void adell_norm_act_fwd_fast_kernel(NormActArg
       }
       if (a.mask != nullptr) {
         // the 64 lanes of a wave hold 64 consecutive float4 = one 256-element group: word q of
-        // the group = the keep bits of sub-element q, bit = lane (lanes past the end: 0)
+        // the group = the keep bits of sub-element q, bit = lane. Lanes past the end of the item have
+        // left the loop and do not vote: their bits are 0. Lanes 0..3 store one word each; in an
+        // item's last group with fewer than four float4, lane 0 stores the words of the lanes that
+        // have left, so all four words of every group are written.
         unsigned long long b[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) b[q] = __ballot(kept[q]);
         const int ln = threadIdx.x & 63;
-        if (ln < 4)
-          a.mask[((long)n * a.groups + (jj >> 6)) * 4 + ln] =
-              ln == 0 ? b[0] : (ln == 1 ? b[1] : (ln == 2 ? b[2] : b[3]));
+        unsigned long long* w = a.mask + ((long)n * a.groups + (jj >> 6)) * 4;
+        if (ln < 4) w[ln] = ln == 0 ? b[0] : (ln == 1 ? b[1] : (ln == 2 ? b[2] : b[3]));
+        // (wave-uniform test on the lanes still in the loop, a prefix of the wave: testing jend - jj
+        // per lane cost the kernel a VGPR and with it a wave of occupancy)
+        const unsigned long long live = __ballot(true);
+        if (live < 15 && ln == 0) {
+          if (!(live & 2)) w[1] = b[1];
+          if (!(live & 4)) w[2] = b[2];
+          w[3] = b[3];
+        }
       }
     }
   }
@@ -1384,20 +1533,22 @@ extern "C" int adell_norm_act_bwd_from_dt(const adell_norm_act_desc* d, const fl
   NormActBwdArgs a = {};
   int rc = adell_nab_fill(&a, d);
   if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(x && dt && dx && mean && rstd && partials && workspace,
-                "norm_act_bwd_from_dt: null pointer");
   ADELL_REQUIRE(d->stats_per_item == 1 && d->N <= 65535,
                 "norm_act_bwd_from_dt: instance statistics only");
   ADELL_REQUIRE(ntiles > 0 && pstride >= d->C && poff >= 0 && poff + d->C <= pstride,
                 "norm_act_bwd_from_dt: bad partials layout");
-  ADELL_REQUIRE(adell_is_pow2(d->C) && d->C % 4 == 0 && d->C <= 1024 &&
-                    (((uintptr_t)x | (uintptr_t)dt | (uintptr_t)dx) & 15) == 0,
+  a.x = x; a.dout = dt; a.dx = dx;
+  const AdellNaPlan p = adell_na_bwd_plan(a, d, true, false);
+  ADELL_REQUIRE(p.bwd == ADELL_NA_FAST,
                 "norm_act_bwd_from_dt: needs a power-of-two C in 4..1024 and aligned tensors");
   // the fused epilogue leaves one row per BRICK (thousands per item): fold them 256 at a time
   // first, on a grid that fills the chip (a single-level fold runs on C / 8 x N blocks: 80 us)
-  const int Z = ntiles > 512 ? (ntiles + 255) / 256 : 0;
-  ADELL_REQUIRE(workspace_bytes >= sizeof(float) * (2 + 2 * (size_t)Z) * d->N * d->C,
+  const AdellNaStatsPlan sp = adell_na_stats_plan(d->N, ntiles, d->C);
+  const int Z = sp.Z;
+  // (c1 and c2 [N][C], then the folded rows)
+  ADELL_REQUIRE(workspace && workspace_bytes >= sizeof(float) * 2 * (size_t)d->N * d->C + (size_t)sp.ws_bytes,
                 "norm_act_bwd_from_dt: workspace too small");
+  ADELL_REQUIRE(x && dt && dx && mean && rstd && partials, "norm_act_bwd_from_dt: null pointer");
   hipStream_t st = (hipStream_t)stream;
   float* c1 = (float*)workspace;
   float* c2 = c1 + (size_t)d->N * d->C;
@@ -1414,11 +1565,8 @@ extern "C" int adell_norm_act_bwd_from_dt(const adell_norm_act_desc* d, const fl
                      dim3(256), 0, st, partials, ntiles, d->C, (double)d->V, (const float*)nullptr,
                      c1, c2, pstride, poff);
   a.x = x; a.dout = dt; a.mean = mean; a.rstd = rstd; a.c1 = c1; a.c2 = c2; a.dx = dx;
-  long bx = ((a.VC >> 2) + 256 * ADELL_EW_UNROLL - 1) / (256 * ADELL_EW_UNROLL);
-  if (bx > ADELL_EW_MAXBLOCKS) bx = ADELL_EW_MAXBLOCKS;
-  if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(adell_na_bwd_apply_dt_kernel, dim3((unsigned)bx, (unsigned)d->N), dim3(256), 0,
-                     st, a);
+  hipLaunchKernelGGL(adell_na_bwd_apply_dt_kernel, dim3((unsigned)p.apply_gx, (unsigned)p.apply_gy),
+                     dim3(256), 0, st, a);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -1553,7 +1701,7 @@ __global__ __launch_bounds__(256) void adell_bn_sums_kernel(const float* __restr
       // (the loop of adell_stats_finalize_kernel: eight rows in flight, added in row order)
       const float* p = part + ((size_t)n * ntiles * C + c) * 2;
       int t = sl;
-      for (; t + 56 < ntiles; t += 64) {
+      for (; t + ADELL_FIN8_SPAN < ntiles; t += 64) {
         float2 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
@@ -1590,13 +1738,14 @@ __global__ __launch_bounds__(256) void adell_bn_sums_kernel(const float* __restr
 extern "C" int adell_bn_stats_sums(const float* partials, int N, int ntiles, int C, long count,
                                    double* sums, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-  ADELL_REQUIRE(partials && sums, "bn_stats_sums: null pointer");
   ADELL_REQUIRE(N > 0 && ntiles > 0 && C > 0 && count > 0, "bn_stats_sums: bad dims");
+  const AdellNaStatsPlan sp = adell_na_stats_plan(N, ntiles, C);
+  ADELL_REQUIRE(sp.levels == 1 || (workspace && (long)workspace_bytes >= sp.ws_bytes),
+                "bn_stats_sums: workspace too small");
+  ADELL_REQUIRE(partials && sums, "bn_stats_sums: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const long need = adell_stats_finalize_workspace(N, ntiles, C);
-  if (need > 0) {
-    ADELL_REQUIRE(workspace && (long)workspace_bytes >= need, "bn_stats_sums: workspace too small");
-    const int Z = (ntiles + 255) / 256;
+  if (sp.levels == 2) {
+    const int Z = sp.Z;
     hipLaunchKernelGGL(adell_stats_fold_kernel, dim3(adell_cdiv(C, 32), N, Z), dim3(256), 0, st,
                        partials, ntiles, C, Z, (float*)workspace, C, 0);
     partials = (const float*)workspace;
@@ -1729,14 +1878,14 @@ extern "C" int adell_norm_act_bwd_sums(const adell_norm_act_desc* d, const float
   NormActBwdArgs a = {};
   int rc = adell_na_sync_fill(&a, d, x, dout, mean, rstd, gamma, beta, act_w, "norm_act_bwd_sums");
   if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(sums, "norm_act_bwd_sums: null record");
-  ADELL_REQUIRE(workspace && (long)workspace_bytes >= adell_norm_act_bwd_workspace(d),
+  // (a.dx is null: dx is the apply's business)
+  const AdellNaPlan p = adell_na_bwd_plan(a, d, true, dgamma || dbeta);
+  ADELL_REQUIRE(workspace && (long)workspace_bytes >= p.ws_bytes,
                 "norm_act_bwd_sums: workspace too small");
+  ADELL_REQUIRE(sums, "norm_act_bwd_sums: null record");
   hipStream_t st = (hipStream_t)stream;
-  bool vec, fast;
-  adell_na_bwd_route(a, d, &vec, &fast);   // (a.dx is null: dx is the apply's business)
   a.part = (float*)workspace;
-  adell_na_bwd_partials_launch(a, d, fast, vec, st);
+  adell_na_bwd_partials_launch(a, d, p, st);
   hipLaunchKernelGGL(adell_na_bwd_sums_kernel, dim3(adell_cdiv(d->C, 32)), dim3(1024), 0, st,
                      (const float*)a.part, (int)d->N, a.ntiles, d->C, (double)d->V, sums, dgamma,
                      dbeta);
@@ -1763,9 +1912,7 @@ extern "C" int adell_norm_act_bwd_apply_sums(const adell_norm_act_desc* d, const
   a.c2 = a.c1 + d->C;
   hipLaunchKernelGGL(adell_na_bwd_c12_kernel, dim3(adell_cdiv(d->C, 256)), dim3(256), 0, st, sums,
                      d->C, gamma, (float*)a.c1, (float*)a.c2);
-  bool vec, fast;
-  adell_na_bwd_route(a, d, &vec, &fast);
-  adell_na_bwd_apply_launch(a, d, fast, vec, st);
+  adell_na_bwd_apply_launch(a, d, adell_na_bwd_plan(a, d, true, false), st);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }

@@ -1147,9 +1147,53 @@ def make_na_desc(x, act, stats_per_item=1, act_p=0.0, act_w_n=0, drop_p=0.0, see
 
 def norm_act_mask_ok(x):
     """The forward can store its dropout keep bits (the bandwidth-tuned kernel runs: power-of-two
-    channel count, 16-byte aligned NDHWC tensor)."""
+    channel count from 4 to 1024, 16-byte aligned NDHWC tensor; norm_act_plan's "fast" route). All
+    four words of every 256-element group are then written -- also of an item's last group when it
+    holds fewer than four float4 (C = 4 or 8 with few voxels left) -- and the bits past the end of
+    an item are 0."""
     C = x.shape[1]
     return x.dim() == 5 and C % 4 == 0 and C <= 1024 and (C & (C - 1)) == 0
+
+
+# launch plan of a norm / dropout / activation site (adell_norm_act_plan). fwd, bwd: one of NA_ROUTES;
+# fwd_grid, apply_grid: (x, y) of the forward / dx launch; rows: partial rows per item the backward's
+# reduction pass writes (0: none); finalize: one of NA_FINALIZE; workspace: bytes norm_act_bwd
+# requires; mask_bytes: keep bits the forward stores
+NormActPlan = collections.namedtuple(
+    "NormActPlan", "fwd fwd_grid bwd rows apply_grid finalize workspace mask_bytes")
+NA_ROUTES = ("scalar", "float4", "fast", "narrow", "refused")
+NA_FINALIZE = ("none", "per_item", "all_items")
+_NA_ALIGNED = {"x": 1, "out": 2, "dout": 4, "dx": 8}
+# reduction of a chain of partial rows (adell_norm_act_stats_plan). levels: 1 or 2; Z: rows per item
+# after the first level; workspace: bytes of the folded rows; unroll8_from / unroll2_from: rows from
+# which the all-items (and record) / per-item backward finalize kernels enter their unrolled loops
+NormActStatsPlan = collections.namedtuple("NormActStatsPlan",
+                                          "levels Z workspace unroll8_from unroll2_from")
+
+
+def norm_act_plan(N, V, C, stats_per_item=1, drop_p=0.0, unaligned=(), want_mask=False, split=False,
+                  lowrank=0, norm=True, affine_grads=False):
+    """What norm_act_fwd / norm_act_bwd (and their _mask, _split, _lowrank, _sums, _from_dt forms)
+    launch for a site of N items of V voxels and C channels. ``unaligned``: names among "x", "out",
+    "dout", "dx" of the tensors that are NOT 16-byte aligned (none, from torch, unless a view starts
+    inside a storage). Host only: no GPU needed."""
+    d = NormActDesc(int(N), int(V), int(C), int(stats_per_item), 0, 0, 0.0, float(drop_p), 0, 0)
+    al = sum(bit for name, bit in _NA_ALIGNED.items() if name not in unaligned)
+    assert set(unaligned) <= set(_NA_ALIGNED), unaligned
+    out = (ctypes.c_long * 10)()
+    check(_lib.lib().adell_norm_act_plan(ctypes.byref(d), al, int(bool(want_mask)), int(bool(split)),
+                                         int(lowrank), int(bool(norm)), int(bool(affine_grads)), out))
+    o = list(out)
+    return NormActPlan(NA_ROUTES[o[0]], (o[1], o[2]), NA_ROUTES[o[3]], o[4], (o[5], o[6]),
+                       NA_FINALIZE[o[7]], o[8], o[9])
+
+
+def norm_act_stats_plan(N, ntiles, C):
+    """How stats_finalize, bn_stats_sums and norm_act_bwd_from_dt reduce ``ntiles`` partial rows per
+    item (host only)."""
+    out = (ctypes.c_long * 5)()
+    check(_lib.lib().adell_norm_act_stats_plan(int(N), int(ntiles), int(C), out))
+    return NormActStatsPlan(*list(out))
 
 
 # ---- split rows: activations stored as the f16x3 kernels' LDS row image ------------------------------

@@ -399,7 +399,8 @@ int adell_norm_act_fwd(const adell_norm_act_desc* d, const float* x,
 
 /* The same, also writing the dropout keep bits (drop_p > 0): element el of batch item n is bit
  * (el >> 2) & 63 of 64-bit word (n * groups + (el >> 8)) * 4 + (el & 3), groups = ceil(V C / 256);
- * adell_norm_act_mask_bytes(d) bytes. Needs C % 4 == 0 and a power-of-two C <= 1024 (returns
+ * adell_norm_act_mask_bytes(d) bytes. All four words of every group are written, the bits past the
+ * end of an item as 0. Needs C % 4 == 0 and a power-of-two C <= 1024 (returns
  * ADELL_E_UNSUPPORTED otherwise: the caller then keeps the regenerating backward). */
 long adell_norm_act_mask_bytes(const adell_norm_act_desc* d);
 int adell_norm_act_fwd_mask(const adell_norm_act_desc* d, const float* x, const float* mean,
@@ -470,6 +471,48 @@ int adell_norm_act_bwd_apply_sums(const adell_norm_act_desc* d, const float* x, 
 int adell_norm_act_bwd_lowrank(const adell_norm_act_desc* d, const float* x, const float* g,
                                const float* w, int co, const float* mean, const float* rstd,
                                float* dx, void* workspace, size_t workspace_bytes, void* stream);
+/* Launch plan of a norm / dropout / activation site, host only (no launch, no tensor read, no
+ * device needed): what adell_norm_act_fwd(_mask / _split), adell_norm_act_bwd(_lowrank / _sums /
+ * _apply_sums) and adell_norm_act_bwd_from_dt would run, decided by the same function the launches
+ * call. Routes:
+ *   scalar: any C, any alignment; float4: C % 4 == 0 and 16-byte aligned tensors (both grid-stride
+ *   above a grid cap); fast: float4's conditions and a power-of-two C <= 1024 (one grid row per
+ *   item, contiguous chunks per block); narrow: the fast kernels at C = 1 or 2 with V C % 4 == 0.
+ * The forward looks at x and out, the backward (both passes) at x, dout and dx.
+ * aligned: ADELL_NA_ALIGNED_* bits of the tensors that are 16-byte aligned (set the bit of a tensor
+ *   the call does not have); want_mask: keep bits are wanted (stored only when drop_p > 0);
+ *   split: split-row output; lowrank: factors of a low-rank dout (0: a full dout); norm: the site
+ *   has mean / rstd; affine_grads: dgamma or dbeta is wanted. out[10]:
+ *   [0] forward route (ADELL_NA_*; REFUSED: keep bits or split rows off the fast route -- what the
+ *       entry points answer with ADELL_E_UNSUPPORTED / ADELL_E_BADARG); [1], [2] forward grid x, y;
+ *   [3] backward route (REFUSED: a low-rank dout off the fast route; adell_norm_act_bwd_from_dt
+ *       needs ADELL_NA_FAST); [4] partial rows per item its reduction pass writes (0: no such
+ *       pass); [5], [6] grid x, y of its dx pass;
+ *   [7] finalize kernel (ADELL_NA_FIN_*; the record of adell_norm_act_bwd_sums is its own);
+ *   [8] workspace bytes adell_norm_act_bwd requires (adell_norm_act_bwd_workspace, or 0 without a
+ *       reduction pass); [9] bytes of keep bits the forward stores (0: none).
+ * adell_norm_act_stats_plan: how adell_stats_finalize, adell_bn_stats_sums and
+ *   adell_norm_act_bwd_from_dt reduce `ntiles` partial rows per item. out[5]: [0] levels (1, or 2
+ *   above 512 rows: 256 rows at a time are folded first); [1] rows per item after the first level
+ *   (0 with one level); [2] workspace bytes of the folded rows (adell_stats_finalize_workspace;
+ *   adell_norm_act_bwd_from_dt adds 2 N C floats); [3] rows from which the all-items finalize and
+ *   the record kernel keep eight rows in flight; [4] rows from which the per-item backward
+ *   finalize keeps two. */
+#define ADELL_NA_SCALAR 0
+#define ADELL_NA_FLOAT4 1
+#define ADELL_NA_FAST 2
+#define ADELL_NA_NARROW 3
+#define ADELL_NA_REFUSED 4
+#define ADELL_NA_FIN_NONE 0
+#define ADELL_NA_FIN_PER_ITEM 1
+#define ADELL_NA_FIN_ALL_ITEMS 2
+#define ADELL_NA_ALIGNED_X 1
+#define ADELL_NA_ALIGNED_OUT 2
+#define ADELL_NA_ALIGNED_DOUT 4
+#define ADELL_NA_ALIGNED_DX 8
+int adell_norm_act_plan(const adell_norm_act_desc* d, int aligned, int want_mask, int split,
+                        int lowrank, int norm, int affine_grads, long* out);
+int adell_norm_act_stats_plan(int N, int ntiles, int C, long* out);
 /* Gradient of the PReLU weight(s) of the same fused op (torch.nn.PReLU is the reference's
  * default activation_fn): dact_w[act_w_n] with act_w_n = 1 or C; operands as above. */
 long adell_prelu_wgrad_workspace(const adell_norm_act_desc* d);
