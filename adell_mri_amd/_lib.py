@@ -233,6 +233,15 @@ SIGNATURES = {
     "adell_ijepa_predictor_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "adell_ijepa_loss_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "adell_ijepa_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mae_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mae_restore_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mae_restore_bwd_chunks": (_i, [_i, _i]),
+    "adell_mae_restore_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                   _i, _vp]),
+    "adell_mae_loss_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "adell_mae_loss_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mae_to_image": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mae_from_image": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

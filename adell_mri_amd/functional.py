@@ -2364,6 +2364,121 @@ def ijepa_block_loss(pred, h, rows):
     return _IjepaBlockLossFn.apply(pred, h.detach(), ops.token_rows(rows, h.shape[1], h.device))
 
 
+# ---- masked autoencoder (csrc/mae.hip) ------------------------------------------------------------
+class _MaeKeepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, shuffle):
+        ctx.shuffle = shuffle
+        return ops.mae_keep_fwd(x.contiguous(), shuffle)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.mae_keep_bwd(dy.contiguous(), ctx.shuffle), None
+
+
+def mae_keep_tokens(x, shuffle):
+    """``torch.gather(x, 1, ids_keep)`` for x [B, L, E] and an ``ops.MaeShuffle``: the kept tokens
+    of every item, in its own shuffled order. The backward writes the whole gradient of x in one
+    launch (zeros on the masked tokens)."""
+    if x.dim() != 3:
+        raise ValueError(f"mae_keep_tokens: [B, L, E] expected, got {tuple(x.shape)}")
+    return _MaeKeepFn.apply(x, shuffle)
+
+
+class _MaeRestoreFn(torch.autograd.Function):
+    """Saved: the mask token and its scale (E + 1 floats)."""
+
+    @staticmethod
+    def forward(ctx, enc, mask_token, scale, pos, shuffle):
+        ctx.shuffle = shuffle
+        ctx.save_for_backward(mask_token, scale)
+        return ops.mae_restore_fwd(enc.contiguous(), mask_token, scale, pos.contiguous(), shuffle)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mask_token, scale = ctx.saved_tensors
+        need_enc, need_mask, need_scale, need_pos = ctx.needs_input_grad[:4]
+        denc, dmask, dscale, dpos = ops.mae_restore_bwd(dout.contiguous(), mask_token, scale,
+                                                        ctx.shuffle, need_enc, need_mask,
+                                                        need_scale, need_pos)
+        if dmask is not None:
+            dmask = dmask.view(mask_token.shape)
+        if dscale is not None:
+            dscale = dscale.view(scale.shape)
+        return denc, dmask, dscale, dpos, None
+
+
+def mae_restore_tokens(enc, mask_token, mask_token_scale, pos, shuffle):
+    """The decoder's input [B, L, E] in one launch: ``torch.gather(cat([enc, mask_token_scale *
+    mask_token.repeat(B, L - K, 1)], 1), 1, ids_restore) + pos`` for the encoded kept tokens enc
+    [B, K, E], the mask token [1, 1, E], its scale [1] (read on the device) and the positional
+    embedding pos [1, L, E]. The backward takes at most three launches, every sum in a fixed
+    order."""
+    if enc.dim() != 3 or pos.dim() != 3:
+        raise ValueError(f"mae_restore_tokens: enc [B, K, E] and pos [1, L, E] expected, got "
+                         f"{tuple(enc.shape)} and {tuple(pos.shape)}")
+    return _MaeRestoreFn.apply(enc, mask_token, mask_token_scale, pos, shuffle)
+
+
+class _MaeLossFn(torch.autograd.Function):
+    """Saved: pred and x, nothing else."""
+
+    @staticmethod
+    def forward(ctx, pred, x, patch_elems):
+        pred, x = pred.contiguous(), x.contiguous()
+        ctx.save_for_backward(pred, x)
+        ctx.patch_elems = patch_elems
+        return ops.mae_loss_fwd(pred, x, patch_elems)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, x = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.mae_loss_bwd(pred, x, ctx.patch_elems, g), None, None
+
+
+def mae_reconstruction_loss(pred, x, patch_elems):
+    """``MSELoss()(pred.view(B, L, ph, pw, C).permute(0, 4, 1, 2, 3).contiguous().view(B, C, H, W), x)``
+    for the token predictions pred [B, L, P * C] (P = ``patch_elems`` = ph * pw) and the image x
+    [B, C, H, W], without writing the permuted tensor: element (b, c, l P + p) of the reference's
+    "image" is pred[b, l, p C + c]. x takes no gradient."""
+    if x.dim() != 4:
+        raise ValueError(f"mae_reconstruction_loss: an image [B, C, H, W] expected, got "
+                         f"{tuple(x.shape)}")
+    return _MaeLossFn.apply(pred, x.detach(), int(patch_elems))
+
+
+class _MaeToImageFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, image_shape, patch_elems):
+        ctx.patch_elems = patch_elems
+        return ops.mae_to_image(pred.contiguous(), image_shape, patch_elems)
+
+    @staticmethod
+    def backward(ctx, dimage):
+        return ops.mae_from_image(dimage.contiguous(), ctx.patch_elems), None, None
+
+
+def mae_to_image(pred, image_shape):
+    """The reference's ``pred.view(B, L, ph, pw, C).permute(0, 4, 1, 2, 3).contiguous().view(B, C, H,
+    W)`` for pred [B, L, P * C] and ``image_shape`` (B, C, H, W): not a spatial un-patchify, element
+    (b, c) of the result holds pred[b, l, p C + c] at flat offset l P + p. With one channel it is a
+    view and nothing is launched."""
+    image_shape = tuple(int(v) for v in image_shape)
+    if pred.dim() != 3 or len(image_shape) != 4:
+        raise ValueError(f"mae_to_image: pred [B, L, P * C] and (B, C, H, W) expected, got "
+                         f"{tuple(pred.shape)} and {image_shape}")
+    B, C, H, W = image_shape
+    L = pred.shape[1]
+    if L < 1 or (H * W) % L:
+        raise ValueError(f"mae_to_image: {L} tokens do not divide an image of {H} x {W}")
+    B, C, L, P = ops._mae_image_shapes("mae_to_image", pred, image_shape, H * W // L)
+    if C == 1:
+        return pred.reshape(image_shape)
+    return _MaeToImageFn.apply(pred, image_shape, P)
+
+
 class _PairLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, kind, temperature, apply_relu):

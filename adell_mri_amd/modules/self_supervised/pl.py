@@ -33,9 +33,15 @@ teacher sees the whole image under ``no_grad``. ``step`` takes the smooth-L1 los
 from the teacher's raw output (functional.ijepa_block_loss, csrc/ijepa.hip: layer norm, row gather
 and loss in one pass, nothing of the teacher's size written) and never builds the targets;
 ``calculate_loss(predictions, targets)`` stays, composed, for callers that hold the two lists.
+
+``ViTMaskedAutoEncoderPL`` (pl.py:1434-1611) is the wrapper of ``ssl_method="mae"``: it HOLDS a
+``ViTMaskedAutoEncoder`` as ``model`` (no EMA, no ``SelfSLBasePL``). Each step takes the token
+predictions (``model.forward_tokens``) and the reconstruction loss through the reference's
+view / permute as an index map (functional.mae_reconstruction_loss, csrc/mae.hip): the image-shaped
+reconstruction is written only by ``forward``.
 """
 import warnings
-from typing import Callable
+from typing import Any, Callable
 
 import torch
 import torch.distributed as dist
@@ -49,6 +55,7 @@ from ..segmentation.unet import UNet
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from .dino import DINO
 from .ibot import iBOT
+from .autoencoders import ViTMaskedAutoEncoder
 from .jepa import IJEPA
 from .losses import (DinoLoss, NTXentLoss, VICRegLocalLoss, VICRegLoss, byol_loss,
                      simsiam_loss)
@@ -584,3 +591,87 @@ class IJEPAPL(IJEPA, SelfSLBasePL):
             conf["optimizer"], T_max=self.n_steps if self.n_steps is not None else self.n_epochs,
             start_decay=self.start_decay, n_warmup_steps=self.warmup_steps, eta_min=1e-6)
         return conf
+
+
+class ViTMaskedAutoEncoderPL(_Base):
+    """Masked-autoencoder pretraining of a ViT (pl.py:1434-1611): ``MSELoss()`` between the
+    reconstruction and the WHOLE image, masked and visible patches alike. Every step draws a new
+    shuffle from the model's one rng, validation and test included. AdamW with betas (0.9, 0.95);
+    with ``warmup_steps > 0`` the optimiser starts at lr 0.0 under a cosine schedule with warm-up
+    whose base lr is ``learning_rate``, otherwise ``configure_optimizers`` returns the bare
+    optimiser."""
+
+    if _Base is torch.nn.Module:
+        def log(self, *args, **kwargs):
+            return None
+
+        def save_hyperparameters(self, *args, **kwargs):
+            return None
+
+    def __init__(self, image_key: str, image_size, patch_size, in_channels: int,
+                 input_dim_size: int, encoder_args: dict[str, Any], decoder_args: dict[str, Any],
+                 n_epochs: int = 100, n_steps: int | None = None, embed_method: str = "linear",
+                 dropout_rate: float = 0.0, mask_fraction: float = 0.75,
+                 learning_rate: float = 1e-3, batch_size: int = 4, weight_decay: float = 1e-6,
+                 warmup_steps: int = 0, start_decay: int = 0,
+                 training_dataloader_call: Callable | None = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT):
+        super().__init__()
+        self.save_hyperparameters()
+        self.model = ViTMaskedAutoEncoder(
+            image_size=image_size, patch_size=patch_size, in_channels=in_channels,
+            input_dim_size=input_dim_size, encoder_args=encoder_args, decoder_args=decoder_args,
+            embed_method=embed_method, dropout_rate=dropout_rate, mask_fraction=mask_fraction)
+        self.criterion = torch.nn.MSELoss()     # what the steps compute; they use the fused form
+        self.image_key = image_key
+        self.batch_size = batch_size
+        self.learning_rate = learning_rate
+        self.weight_decay = weight_decay
+        self.warmup_steps = warmup_steps
+        self.training_dataloader_call = training_dataloader_call
+        self.n_steps = n_steps
+        self.n_epochs = n_epochs
+        self.start_decay = start_decay
+        self.optimizer_eps = optimizer_eps
+
+    def forward(self, x: torch.Tensor):
+        return self.model(x)
+
+    def step(self, batch, loss_str: str, **log_kwargs):
+        x = batch[self.image_key]
+        pred, _ = self.model.forward_tokens(x)
+        loss = HF.mae_reconstruction_loss(pred, x, self.model.patch_elems)
+        self.log(loss_str, loss, on_epoch=True, prog_bar=True, **log_kwargs)
+        return loss
+
+    def training_step(self, batch, batch_idx):
+        return self.step(batch, "train_loss", on_step=True)
+
+    def validation_step(self, batch, batch_idx):
+        return self.step(batch, "val_loss", on_step=False)
+
+    def test_step(self, batch, batch_idx):
+        return self.step(batch, "test_loss", on_step=False)
+
+    def configure_optimizers(self):
+        if self.n_steps:
+            n, interval = self.n_steps, "step"
+        else:
+            n, interval = self.n_epochs, "epoch"
+        initial_lr = 0.0 if self.warmup_steps > 0 else self.learning_rate
+        # parameters(): the positional embedding, held under two names, enters the flat buffer once
+        optimizer = FusedAdamW(self.parameters(), lr=initial_lr, weight_decay=self.weight_decay,
+                               betas=(0.9, 0.95), eps=self.optimizer_eps)
+        if self.warmup_steps > 0:
+            scheduler = {"scheduler": CosineAnnealingWithWarmupLR(
+                optimizer, T_max=n, start_decay=self.start_decay,
+                n_warmup_steps=self.warmup_steps, eta_min=1e-6),
+                "interval": interval, "frequency": 1}
+            scheduler["scheduler"].base_lrs = [self.learning_rate]
+            return {"optimizer": optimizer, "lr_scheduler": scheduler}
+        return optimizer
+
+    def train_dataloader(self):
+        if self.training_dataloader_call is None:
+            raise ValueError("training_dataloader_call must be provided for training")
+        return self.training_dataloader_call(self.batch_size)

@@ -3054,6 +3054,213 @@ def ijepa_loss_bwd(pred, h, rows, stats, g):
     return dpred
 
 
+# ---- masked autoencoder (csrc/mae.hip) --------------------------------------------------------
+class MaeShuffle:
+    """The per-item token shuffle of ``random_masking``, checked on the host -- the kernels read the
+    tables unchecked. ``ids_shuffle`` [B, L] integers, every row a permutation of 0..L-1, and
+    ``1 <= len_keep <= L`` (ValueError / IndexError otherwise, before anything touches the device).
+    On ``device``, int32: ``keep`` [B, K] = ids_shuffle[:, :K] (kept tokens, in shuffled order),
+    ``restore`` [B, L] = the inverse permutation (ids_restore), ``inv`` [B, L] = restore where it is
+    < K, else -1 (token -> its kept position); ``mask`` [B, L] float32, 0 keep / 1 remove. The four
+    travel to the device in one copy. ``host`` / ``restore_host`` are the int64 numpy originals."""
+
+    def __init__(self, ids_shuffle, len_keep, device):
+        if isinstance(ids_shuffle, torch.Tensor):
+            ids_shuffle = ids_shuffle.detach().cpu().numpy()
+        host = np.asarray(ids_shuffle)
+        if host.ndim != 2 or host.size < 1:
+            raise ValueError(f"mae shuffle: ids_shuffle [B, L] expected, got shape {host.shape}")
+        if not np.issubdtype(host.dtype, np.integer):
+            raise TypeError(f"mae shuffle: integer indices expected, got {host.dtype}")
+        host = host.astype(np.int64)
+        B, L = host.shape
+        if int(host.min()) < 0 or int(host.max()) >= L:
+            bad = int(host.max()) if int(host.max()) >= L else int(host.min())
+            raise IndexError(f"index {bad} is out of bounds for a sequence of {L} tokens")
+        if not np.array_equal(np.sort(host, axis=1), np.broadcast_to(np.arange(L), (B, L))):
+            raise ValueError("mae shuffle: every row of ids_shuffle must be a permutation of 0..L-1")
+        if int(len_keep) != len_keep or not 1 <= int(len_keep) <= L:
+            raise ValueError(f"mae shuffle: len_keep must be an integer in [1, {L}], got {len_keep}")
+        K = int(len_keep)
+        restore = np.argsort(host, axis=1, kind="stable")
+        self.host, self.restore_host = host, restore
+        self.B, self.L, self.K, self.device = B, L, K, torch.device(device)
+        mask = (restore >= K).astype(np.float32)
+        packed = np.concatenate([host[:, :K].reshape(-1), restore.reshape(-1),
+                                 np.where(restore < K, restore, -1).reshape(-1)]).astype(np.int32)
+        packed = np.concatenate([packed, mask.reshape(-1).view(np.int32)])
+        self._packed = torch.from_numpy(packed).to(self.device)
+        n = B * L
+        self.keep = self._packed[:B * K].view(B, K)
+        self.restore = self._packed[B * K:B * K + n].view(B, L)
+        self.inv = self._packed[B * K + n:B * K + 2 * n].view(B, L)
+        self.mask = self._packed[B * K + 2 * n:].view(torch.float32).view(B, L)
+
+    def check(self, what, B, device):
+        if B != self.B or torch.device(device) != self.device:
+            raise ValueError(f"{what}: a shuffle of {self.B} items on {self.device} for a batch of "
+                             f"{B} on {device}")
+
+
+def _mae_shuffle(what, shuffle, x):
+    if not isinstance(shuffle, MaeShuffle):
+        raise TypeError(f"{what}: an ops.MaeShuffle expected, got {type(shuffle).__name__}")
+    if x.dim() != 3:
+        raise ValueError(f"{what}: [B, tokens, E] expected, got {tuple(x.shape)}")
+    shuffle.check(what, x.shape[0], x.device)
+
+
+def mae_gather_rows(x, tab):
+    """out [B, No, E]: out[b, o] = x[b, tab[b, o]], zeros where tab[b, o] < 0, for x [B, Ni, E] and a
+    device int32 table [B, No] of a ``MaeShuffle`` (checked there; read unchecked here)."""
+    _require_cuda(x)
+    _ibot_3d("mae_gather_rows", x)
+    B, Ni, E = x.shape
+    if tab.dtype != torch.int32 or tab.dim() != 2 or tab.shape[0] != B or not tab.is_contiguous():
+        raise ValueError(f"mae_gather_rows: a dense int32 table [{B}, No] expected, got "
+                         f"{tab.dtype} {tuple(tab.shape)}")
+    No = tab.shape[1]
+    out = torch.empty((B, No, E), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_mae_gather_rows(_ptr(x), _ptr(tab), B, No, Ni, E, _ptr(out), _stream()))
+    return out
+
+
+def mae_keep_fwd(x, shuffle):
+    """x_masked [B, K, E] = torch.gather(x, 1, ids_keep) for x [B, L, E]."""
+    _mae_shuffle("mae_keep", shuffle, x)
+    if x.shape[1] != shuffle.L:
+        raise ValueError(f"mae_keep: {x.shape[1]} tokens for a shuffle of {shuffle.L}")
+    return mae_gather_rows(x, shuffle.keep)
+
+
+def mae_keep_bwd(dy, shuffle):
+    """dx [B, L, E], written whole by one launch: the gradient row of a kept token, zeros elsewhere."""
+    _mae_shuffle("mae_keep", shuffle, dy)
+    if dy.shape[1] != shuffle.K:
+        raise ValueError(f"mae_keep: a gradient of {dy.shape[1]} rows for {shuffle.K} kept tokens")
+    return mae_gather_rows(dy, shuffle.inv)
+
+
+def _mae_restore_shapes(what, rows, mask_token, scale, pos, shuffle, n_rows):
+    _mae_shuffle(what, shuffle, rows)
+    B, n, E = rows.shape
+    if n != n_rows:
+        raise ValueError(f"{what}: {n} rows for a shuffle with {n_rows}")
+    if mask_token.numel() != E or scale.numel() != 1:
+        raise ValueError(f"{what}: a mask token of {E} features and one scale expected, got "
+                         f"{tuple(mask_token.shape)} and {tuple(scale.shape)}")
+    if pos is not None and (pos.dim() != 3 or tuple(pos.shape) != (1, shuffle.L, E)):
+        raise ValueError(f"{what}: pos [1, {shuffle.L}, {E}] expected, got {tuple(pos.shape)}")
+    return B, E
+
+
+def mae_restore_fwd(enc, mask_token, scale, pos, shuffle):
+    """out [B, L, E]: the encoded kept tokens enc [B, K, E] back at their places, ``scale *
+    mask_token`` at the masked ones, plus pos [1, L, E]; scale [1] is read on the device."""
+    B, E = _mae_restore_shapes("mae_restore", enc, mask_token, scale, pos, shuffle, shuffle.K)
+    _require_cuda(enc, mask_token, scale, pos)
+    _ibot_3d("mae_restore", enc, pos)
+    mask_token, scale = mask_token.reshape(-1).contiguous(), scale.reshape(-1).contiguous()
+    out = torch.empty((B, shuffle.L, E), device=enc.device, dtype=torch.float32)
+    check(_lib.lib().adell_mae_restore_fwd(_ptr(enc), _ptr(mask_token), _ptr(scale), _ptr(pos),
+                                           _ptr(shuffle.restore), B, shuffle.L, shuffle.K, E,
+                                           _ptr(out), _stream()))
+    return out
+
+
+def mae_restore_bwd(dout, mask_token, scale, shuffle, need_enc=True, need_mask=True,
+                    need_scale=True, need_pos=True):
+    """(denc [B, K, E], dmask_token [1, 1, E], dscale [1], dpos [1, L, E]) of ``mae_restore_fwd`` in
+    at most three launches, every sum in a fixed order; a gradient that is not needed is None."""
+    B, E = _mae_restore_shapes("mae_restore", dout, mask_token, scale, None, shuffle, shuffle.L)
+    _require_cuda(dout, mask_token, scale)
+    _ibot_3d("mae_restore", dout)
+    dev, L, K = dout.device, shuffle.L, shuffle.K
+    mask_token, scale = mask_token.reshape(-1).contiguous(), scale.reshape(-1).contiguous()
+    denc = torch.empty((B, K, E), device=dev, dtype=torch.float32) if need_enc else None
+    dpos = torch.empty((1, L, E), device=dev, dtype=torch.float32) if need_pos else None
+    dmask = torch.empty((1, 1, E), device=dev, dtype=torch.float32) if need_mask else None
+    dscale = torch.empty((1,), device=dev, dtype=torch.float32) if need_scale else None
+    part, chunks = None, 0
+    if need_mask or need_scale:
+        chunks = _lib.lib().adell_mae_restore_bwd_chunks(B, L)
+        part = torch.empty((chunks, E), device=dev, dtype=torch.float64)
+    check(_lib.lib().adell_mae_restore_bwd(
+        _ptr(dout), _ptr(mask_token), _ptr(scale), _ptr(shuffle.keep), _ptr(shuffle.restore), B, L, K,
+        E, _ptr(denc), _ptr(dpos), _ptr(dmask), _ptr(dscale),
+        None if part is None else ctypes.c_void_p(part.data_ptr()), chunks, _stream()))
+    return denc, dmask, dscale, dpos
+
+
+def _mae_image_shapes(what, pred, image_shape, patch_elems):
+    """(B, C, L, P) of token rows pred [B, L, P * C] against an image [B, C, H, W]."""
+    if pred.dim() != 3 or len(image_shape) != 4:
+        raise ValueError(f"{what}: pred [B, L, P * C] and an image [B, C, H, W] expected, got "
+                         f"{tuple(pred.shape)} and {tuple(image_shape)}")
+    B, C, H, W = (int(v) for v in image_shape)
+    P = int(patch_elems)
+    if P < 1 or (H * W) % P:
+        raise ValueError(f"{what}: {P} elements per patch do not divide an image of {H} x {W}")
+    L = H * W // P
+    if tuple(pred.shape) != (B, L, P * C):
+        raise ValueError(f"{what}: pred [{B}, {L}, {P * C}] expected for an image {tuple(image_shape)} "
+                         f"and {P} elements per patch, got {tuple(pred.shape)}")
+    return B, C, L, P
+
+
+def mae_loss_fwd(pred, x, patch_elems):
+    """loss (0-d) = ``MSELoss()(image(pred), x)`` for pred [B, L, P * C] and x [B, C, H, W], where
+    image(pred)[b, c].flatten()[l * P + p] = pred[b, l, p * C + c]; the image of pred is not written."""
+    B, C, L, P = _mae_image_shapes("mae_loss", pred, x.shape, patch_elems)
+    _require_cuda(pred, x)
+    if not pred.is_contiguous() or not x.is_contiguous():
+        raise ValueError("mae_loss: dense pred and x expected")
+    buf = torch.empty((B * L + 1,), device=pred.device, dtype=torch.float32)
+    base = buf.data_ptr()
+    check(_lib.lib().adell_mae_loss_fwd(_ptr(pred), _ptr(x), B, C, L, P, ctypes.c_void_p(base),
+                                        ctypes.c_void_p(base + 4 * B * L), _stream()))
+    return buf[B * L]
+
+
+def mae_loss_bwd(pred, x, patch_elems, g):
+    """dpred = g * 2 * (pred - x_at) / (B * C * H * W); g is the incoming gradient (one element, on
+    the device)."""
+    B, C, L, P = _mae_image_shapes("mae_loss", pred, x.shape, patch_elems)
+    _require_cuda(pred, x, g)
+    g = g.reshape(-1).contiguous()
+    dpred = torch.empty_like(pred)
+    check(_lib.lib().adell_mae_loss_bwd(_ptr(pred), _ptr(x), _ptr(g), B, C, L, P, _ptr(dpred),
+                                        _stream()))
+    return dpred
+
+
+def mae_to_image(pred, image_shape, patch_elems):
+    """[B, C, H, W] with image[b, c].flatten()[l * P + p] = pred[b, l, p * C + c] (C > 1: a copy)."""
+    B, C, L, P = _mae_image_shapes("mae_to_image", pred, image_shape, patch_elems)
+    _require_cuda(pred)
+    _ibot_3d("mae_to_image", pred)
+    out = torch.empty(tuple(int(v) for v in image_shape), device=pred.device, dtype=torch.float32)
+    check(_lib.lib().adell_mae_to_image(_ptr(pred), B, C, L, P, _ptr(out), _stream()))
+    return out
+
+
+def mae_from_image(image, patch_elems):
+    """The inverse copy of ``mae_to_image`` (its gradient): [B, L, P * C] from [B, C, H, W]."""
+    if image.dim() != 4:
+        raise ValueError(f"mae_from_image: [B, C, H, W] expected, got {tuple(image.shape)}")
+    B, C, H, W = image.shape
+    P = int(patch_elems)
+    if P < 1 or (H * W) % P:
+        raise ValueError(f"mae_from_image: {P} elements per patch do not divide {H} x {W}")
+    _require_cuda(image)
+    if not image.is_contiguous():
+        raise ValueError("mae_from_image: a dense image expected")
+    L = H * W // P
+    out = torch.empty((B, L, P * C), device=image.device, dtype=torch.float32)
+    check(_lib.lib().adell_mae_from_image(_ptr(image), B, C, L, P, _ptr(out), _stream()))
+    return out
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

@@ -72,7 +72,10 @@ class StepRunner:
         self.sync_batchnorm = sync_batchnorm
         self.module = module
         if optimizer is None:
-            optimizer = module.configure_optimizers()["optimizer"]
+            # a dict with "optimizer", or the bare optimiser (ViTMaskedAutoEncoderPL without warm-up)
+            optimizer = module.configure_optimizers()
+            if isinstance(optimizer, dict):
+                optimizer = optimizer["optimizer"]
         self.optimizer = optimizer
         if (self.gradient_clip_val or self.accumulate_grad_batches > 1) and not (
                 hasattr(optimizer, "clip_grad_norm_") and hasattr(optimizer, "fold_grads")):

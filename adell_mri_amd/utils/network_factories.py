@@ -3,8 +3,9 @@
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
 constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
 ``DINOPL``, ``ssl_method="ibot"`` ``iBOTPL`` and ``ssl_method="ijepa"`` ``IJEPAPL`` on a ViT encoder
-(:799-956; ``TypeError`` for any other ``net_type``). Members outside the built path (the MONAI
-wrappers, the ViT masked autoencoder, Barlow Twins)
+(:799-956; ``TypeError`` for any other ``net_type``) and ``ssl_method="mae"``
+``ViTMaskedAutoEncoderPL`` (:851-867). Members outside the built path (the MONAI wrappers, Barlow
+Twins)
 raise ``NotImplementedError`` -- there is no eager-torch fallback.
 """
 from typing import Any, Callable
@@ -14,9 +15,10 @@ import torch
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
 from ..modules.self_supervised.pl import (DINOPL, IJEPAPL, SelfSLConvNeXtPL, SelfSLResNetPL,
-                                          SelfSLUNetPL, iBOTPL)
+                                          SelfSLUNetPL, ViTMaskedAutoEncoderPL, iBOTPL)
 
 OPTIMIZER_EPS_DEFAULT = 1e-8
+_MAE_STACK_KEYS = ("number_of_blocks", "hidden_dim", "n_heads", "mlp_structure")
 ALLOWED_NET_TYPES = {
     "segmentation": ["unet", "brunet", "unetpp", "unetr", "monai_unetr", "swin", "monai_swin"],
 }
@@ -135,7 +137,17 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
     "vit"``, the predictor's ``projection_head_args`` two blocks of ``n_encoder_features`` with 3
     heads by default, patch sizes [4, 4] ... [8, 8], one context and four target blocks,
     ``predictor_dim`` None, ``image_key="image"``, ``ValueError`` without ``ema`` (raised by
-    ``IJEPAPL``) -- and, as for iBOT, ``NotImplementedError`` without ``"backbone_args"``."""
+    ``IJEPAPL``) -- and, as for iBOT, ``NotImplementedError`` without ``"backbone_args"``.
+    ``"mae"`` builds ``ViTMaskedAutoEncoderPL`` (:851-867): ``encoder_args`` and ``decoder_args`` from
+    the network configuration, ``image_size``, ``patch_size`` and ``in_channels`` (default 1) read
+    from ``encoder_args``, ``input_dim_size = encoder_args.get("embed_dim", 96)``, ``mask_fraction``
+    0.75 by default, ``image_key="image"``, ``ema`` removed from the common parameters and no
+    ``net_type`` check. One difference on purpose: the reference's 224 x 224 / 16 x 16 default is
+    not mirrored and a stack without its size dies there with ``KeyError`` -- here a configuration
+    whose ``encoder_args`` or ``decoder_args`` is missing or lacks ``number_of_blocks``,
+    ``hidden_dim``, ``n_heads`` or ``mlp_structure``, or whose ``encoder_args`` lacks ``image_size``
+    or ``patch_size``, raises ``NotImplementedError`` naming the key. MAE has no collective of its
+    own and has run at world size 1 only."""
     common = {"training_dataloader_call": train_loader_call, "n_epochs": max_epochs,
               "n_steps": max_steps_optim, "warmup_steps": warmup_steps, "ema": ema,
               "batch_size": network_config.get("batch_size", 32),
@@ -212,8 +224,30 @@ def get_ssl_network(train_loader_call: Callable, max_epochs: int, max_steps_opti
                   "predictor_dim": network_config.get("predictor_dim", None),
                   "stop_gradient": stop_gradient, "optimizer_eps": optimizer_eps}
         return IJEPAPL(**{**common, **config})
-    if ssl_method in ("mae", "barlow"):
-        raise NotImplementedError(f"ssl_method {ssl_method!r} (ViT / Barlow-Twins wrappers) is "
+    if ssl_method == "mae":
+        for args_key, needed in (("encoder_args", _MAE_STACK_KEYS + ("image_size", "patch_size")),
+                                 ("decoder_args", _MAE_STACK_KEYS)):
+            if args_key not in network_config:
+                raise NotImplementedError(
+                    f"ssl_method 'mae': `{args_key}` must be given in the network configuration "
+                    "(the reference's built-in 224 x 224 default is not mirrored)")
+            for key in needed:
+                if key not in network_config[args_key]:
+                    raise NotImplementedError(
+                        f"ssl_method 'mae': `{args_key}` lacks `{key}` (the reference's defaults "
+                        "are not mirrored; its transformer stacks have none)")
+        encoder_args, decoder_args = network_config["encoder_args"], network_config["decoder_args"]
+        config = {"image_key": "image", "image_size": encoder_args["image_size"],
+                  "patch_size": encoder_args["patch_size"],
+                  "in_channels": encoder_args.get("in_channels", 1),
+                  "input_dim_size": encoder_args.get("embed_dim", 96),
+                  "encoder_args": encoder_args, "decoder_args": decoder_args,
+                  "mask_fraction": network_config.get("mask_fraction", 0.75),
+                  "optimizer_eps": optimizer_eps}
+        del common["ema"]
+        return ViTMaskedAutoEncoderPL(**{**common, **config})
+    if ssl_method == "barlow":
+        raise NotImplementedError(f"ssl_method {ssl_method!r} (Barlow-Twins wrapper) is "
                                   "outside the HIP path (SURVEY.md section 2: out of scope)")
     boilerplate = {"training_dataloader_call": train_loader_call,
                    "aug_image_key_1": "augmented_image_1",

@@ -948,6 +948,43 @@ int adell_ijepa_loss_fwd(const float* pred, const float* h, const int* rows, int
 int adell_ijepa_loss_bwd(const float* pred, const float* h, const int* rows, const float* stats,
                          const float* g, int B, int nt, int N, int E, float* dpred, void* stream);
 
+/* ViT masked autoencoder (self_supervised/autoencoders.py: random_masking, ViTMaskedAutoEncoder.forward;
+ * ViTMaskedAutoEncoderPL, pl.py:1434-1611; csrc/mae.hip). fp32, dense, one wave per row, no float
+ * atomics, results repeat bit for bit. Index tables are int32 on the device, one row PER ITEM, not
+ * sorted, and are NOT range-checked here: the caller checks them on the host.
+ * adell_mae_gather_rows: out [B][No][E], out[b][o] = in[b][tab[b][o]] of in [B][Ni][E], zeros where
+ * tab[b][o] < 0 (tab [B][No]). torch.gather(x, 1, ids_keep) with tab = ids_keep [B][K]; its gradient,
+ * written whole, with the inverse table [B][L] (token -> kept position or -1).
+ * adell_mae_restore_fwd: out [B][L][E]; out[b][l] = (r = restore[b][l]) < K ? enc[b][r] :
+ * scale[0] mask_token[:], plus pos[l] (enc [B][K][E], mask_token [E], pos [L][E]; scale on the device).
+ * The cat of mask tokens, the gather by ids_restore and the second positional embedding in one launch.
+ * _bwd, at most three launches: denc [B][K][E] = dout[b][keep[b][j]] and dpos [L][E] = sum_b dout[b][l]
+ * (b in order) in one; S[e] = the sum of dout over the masked rows (restore >= K) in fp64, per chunk of
+ * rows into part [chunks][E] (doubles; chunks = adell_mae_restore_bwd_chunks(B, L), passed back as
+ * part_rows and checked), then the chunks in order; dmask [E] = scale S, dscale [1] = sum_e
+ * mask_token[e] S[e]. denc, dpos, dmask, dscale may each be NULL (part only with dmask or dscale).
+ * adell_mae_loss_fwd: loss[0] = mean over B C L P of (pred[b][l][p C + c] - x[b][c][l P + p])^2:
+ * MSELoss()(pred.view(B, L, ph, pw, C).permute(0, 4, 1, 2, 3).view(B, C, H, W), x) with P = ph pw and
+ * L P = H W, the permuted tensor never written. part [B L] takes the row sums, which a one-wave second
+ * launch adds in a fixed order in fp64. _bwd: dpred = g[0] 2 (pred - x_at) / (B C L P).
+ * adell_mae_to_image: image[b][c][l P + p] = tokens[b][l][p C + c]; _from_image: the inverse copy. */
+int adell_mae_gather_rows(const float* in, const int* tab, int B, int No, int Ni, int E, float* out,
+                          void* stream);
+int adell_mae_restore_fwd(const float* enc, const float* mask_token, const float* scale,
+                          const float* pos, const int* restore, int B, int L, int K, int E, float* out,
+                          void* stream);
+int adell_mae_restore_bwd_chunks(int B, int L);
+int adell_mae_restore_bwd(const float* dout, const float* mask_token, const float* scale,
+                          const int* keep, const int* restore, int B, int L, int K, int E, float* denc,
+                          float* dpos, float* dmask, float* dscale, double* part, int part_rows,
+                          void* stream);
+int adell_mae_loss_fwd(const float* pred, const float* x, int B, int C, int L, int P, float* part,
+                       float* loss, void* stream);
+int adell_mae_loss_bwd(const float* pred, const float* x, const float* g, int B, int C, int L, int P,
+                       float* dpred, void* stream);
+int adell_mae_to_image(const float* tokens, int B, int C, int L, int P, float* image, void* stream);
+int adell_mae_from_image(const float* image, int B, int C, int L, int P, float* tokens, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
