@@ -242,6 +242,13 @@ SIGNATURES = {
     "adell_mae_loss_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "adell_mae_to_image": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "adell_mae_from_image": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_cls_loss_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_cls_loss_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "adell_cls_roc_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "adell_cls_roc_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "adell_cls_mixup": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "adell_cls_confusion_update": (_i, [_i, _vp, _vp, _vp, _l, _i, _vp, _vp]),
+    "adell_cls_auroc_pairs": (_i, [_vp, _vp, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

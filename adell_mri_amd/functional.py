@@ -2566,3 +2566,99 @@ def channel_max(x):
     if x.dim() == 4:
         return _ChannelMaxFn.apply(x.unsqueeze(2))
     return _ChannelMaxFn.apply(x)
+
+
+# ---- classification (csrc/classify.hip) -----------------------------------------------------------
+class _ClsLossFn(torch.autograd.Function):
+    """(item [B], reduced) of one of the losses on logits. Saved: the logits, the target, the
+    weight and the denominator of the reduction."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, kind, n_classes):
+        item, red, aux = ops.cls_loss_fwd(kind, logits, target, weight, n_classes)
+        ctx.save_for_backward(logits, target, aux)
+        ctx.weight, ctx.kind, ctx.n_classes = weight, kind, n_classes
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(aux)
+        return item, red, aux
+
+    @staticmethod
+    def backward(ctx, g_item, g_red, _):
+        logits, target, aux = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if g_red is not None:
+                dx = ops.cls_loss_bwd(ctx.kind, logits, target, ctx.weight, ctx.n_classes, g_red,
+                                      False, aux)
+            if g_item is not None:
+                di = ops.cls_loss_bwd(ctx.kind, logits, target, ctx.weight, ctx.n_classes, g_item,
+                                      True, aux)
+                dx = di if dx is None else dx + di
+        return dx, None, None, None, None
+
+
+def _cls_weight(weight, like):
+    if weight is None:
+        return None
+    return torch.as_tensor(weight).detach().to(device=like.device, dtype=torch.float32)
+
+
+def bce_with_logits(logits, target, weight=None, reduction="mean"):
+    """``torch.nn.functional.binary_cross_entropy_with_logits(logits, target, weight)`` for one logit
+    per item (logits [B] or [B, 1]); soft targets allowed; ``weight`` holds 1 or B elements and
+    multiplies the item loss (torch's ``weight``, not ``pos_weight``). ``reduction``: "mean" or
+    "none". The target takes no gradient."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"bce_with_logits: reduction must be 'mean' or 'none', got {reduction!r}")
+    item, red, _ = _ClsLossFn.apply(logits, target.detach(), _cls_weight(weight, logits), "bce", 1)
+    return red if reduction == "mean" else item.view(target.shape)
+
+
+def cross_entropy(logits, target, weight=None, reduction="mean"):
+    """``torch.nn.functional.cross_entropy(logits [B, K], target int64 [B], weight [K])``: "mean" is
+    sum(w[y] l) / sum(w[y]), "none" the weighted items. A label outside [0, K) is never used as an
+    index: that row's loss and gradient are NaN (torch raises instead)."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"cross_entropy: reduction must be 'mean' or 'none', got {reduction!r}")
+    item, red, _ = _ClsLossFn.apply(logits, target.detach(), _cls_weight(weight, logits), "ce",
+                                    int(logits.shape[-1]))
+    return red if reduction == "mean" else item
+
+
+def ordinal_sigmoidal_loss(pred, target, n_classes, weight=None):
+    """The ordinal sigmoidal (CORAL) loss of classification/losses.py:9-62 on pred [B, K - 1] and int64
+    labels [B]: the [B] vector -sum_j (logsig(p_j) t_j + (logsig(p_j) - p_j)(1 - t_j)), t_j = [y >= j],
+    times ``weight[y]`` when class weights are given. A label outside [0, K) is never used as an
+    index: that row's loss and gradient are NaN."""
+    item, _, _ = _ClsLossFn.apply(pred, target.detach(), _cls_weight(weight, pred), "ordinal",
+                                  int(n_classes))
+    return item
+
+
+class _ClsRocFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre_bias, target):
+        loss, aux = ops.cls_roc_fwd(pre_bias, target)
+        ctx.save_for_backward(pre_bias, target, aux)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pre_bias, target, aux = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return ops.cls_roc_bwd(pre_bias, target, g, aux), None
+
+
+def relative_order_consistency(pred, target):
+    """classification/losses.py:65-79: over every ordered pair i != j with y_i != y_j, the mean
+    BCE-with-logits of p_i - p_j against clamp(y_i - y_j, 0, 1); ``pred`` [B] or [B, 1], int64 labels.
+    NaN (value and gradient) when all labels are equal, as the reference's mean over no pairs."""
+    return _ClsRocFn.apply(pred, target.detach())
+
+
+def mixup_rows(x, factor, partner):
+    """x[b] * factor[b] + x[partner[b]] * (1 - factor[b]) over a batch x [B, ...], bit for bit torch's
+    three-operation expression; a row that is its own partner is returned as it is (a NaN or Inf in
+    it stays what it was). Inputs carry no gradient."""
+    return ops.cls_mixup(x.detach(), factor, partner)

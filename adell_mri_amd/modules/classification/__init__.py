@@ -1,0 +1,4 @@
+from .classification import (CatNet, GlobalPooling, OrdNet, ViTClassifier,  # noqa: F401
+                             label_to_ordinal, ordinal_prediction_to_class)
+from .losses import (BCEWithLogitsLoss, CrossEntropyLoss, OrdinalSigmoidalLoss,  # noqa: F401
+                     configure_loss_fn, ordinal_sigmoidal_loss, relative_order_consistency)

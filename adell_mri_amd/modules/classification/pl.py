@@ -1,0 +1,332 @@
+"""Classification training-step wrappers (mirror of adell_mri/modules/classification/pl.py):
+``ClassPLABC`` (:182-778), ``ClassNetPL`` (:781-928), ``OrdNetPL`` (:931-1174) and
+``ViTClassifierPL`` (:1762-1845), with the metric dicts of ``classification_metrics``.
+
+Kept: constructor arguments, the label casts of ``calculate_loss`` (:217-223), ``additional_params``
+and ``with_loss_params``, tuple losses averaged element-wise, the steps (``test_step`` returns
+``(loss, prediction)``; ``OrdNetPL``'s steps return ``loss + roc_loss``), ``predict_step`` without
+the Gaussian-process branch, and ``configure_optimizers`` (:623-702): the no-decay group (empty
+here: it holds the Gaussian-process parameters), the ``ordinal_bias`` group at a hundredth of the
+weight decay and the normal group, or the head / body split when ``weight_decay`` is a pair;
+``FusedAdamW`` with ``weight_decay=base_wd`` and the cosine schedule with warm-up.
+
+``loss_fn`` is called as it is: the classes of ``classification.losses`` (what
+``configure_loss_fn`` assigns) run the fused kernels, any other callable runs as given.
+
+Not mirrored: ``calibrate`` / ``predict_calibrated_step`` (conformal calibration), ``on_train_end``
+and ``predict_step_gp`` (Gaussian process), and the hyper-parameter logging of ``on_train_start``.
+Lightning is optional as in ``self_supervised/pl.py``.
+"""
+from abc import ABC
+from typing import Callable
+
+import torch
+
+from ... import classification_metrics as CM
+from ...optim import FusedAdamW
+from ..learning_rate import CosineAnnealingWithWarmupLR
+from .classification import CatNet, OrdNet, ViTClassifier, ordinal_prediction_to_class
+from .losses import BCEWithLogitsLoss
+
+try:  # pragma: no cover - lightning is not installed in the build image
+    import lightning.pytorch as pl
+
+    _Base = pl.LightningModule
+except Exception:  # noqa: BLE001
+    _Base = torch.nn.Module
+
+OPTIMIZER_EPS_DEFAULT = 1e-8
+
+get_metric_dict = CM.get_metric_dict
+get_ordinal_metric_dict = CM.get_ordinal_metric_dict
+
+
+class ClassPLABC(_Base, ABC):
+    """Abstract classification wrapper (pl.py:182-778)."""
+
+    if _Base is torch.nn.Module:
+        def log(self, *args, **kwargs):
+            return None
+
+        def save_hyperparameters(self, *args, **kwargs):
+            return None
+
+    def __init__(self):
+        super().__init__()
+        self.raise_nan_loss = False
+        self.calibrated = False
+        self.gaussian_process = False
+        self.net_type = "cat"
+        self.optimizer_eps = OPTIMIZER_EPS_DEFAULT
+
+    def calculate_loss(self, prediction, y, additional_params: dict | None = None,
+                       with_loss_params: bool = False):
+        y = y.to(device=prediction.device)
+        if self.n_classes > 2:
+            if len(y.shape) > 1:
+                y = y.squeeze(1)
+            y = y.to(torch.int64)
+        else:
+            y = y.float()
+        params = {}
+        if additional_params is not None:
+            params.update(additional_params)
+        if with_loss_params is True:
+            d = y.device
+            params.update({k: self.loss_params[k].to(d) for k in self.loss_params})
+        loss = self.loss_fn(prediction, y, **params)
+        if isinstance(loss, tuple):
+            return tuple(loss_element.mean() for loss_element in loss)
+        return loss.mean()
+
+    def on_batch_start(self, batch):
+        dev = batch[self.image_key].device
+        batch[self.label_key] = batch[self.label_key].to(dev)
+        return batch
+
+    def training_step(self, batch, batch_idx):
+        x, y = batch[self.image_key], batch[self.label_key]
+        if getattr(self, "training_batch_preproc", None) is not None:
+            x, y = self.training_batch_preproc(x, y)
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y, with_loss_params=True)
+        self.log("train_loss", loss, prog_bar=True)
+        return loss
+
+    def validation_step(self, batch, batch_idx):
+        x, y = batch[self.image_key], batch[self.label_key]
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y, with_loss_params=True)
+        self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True,
+                 batch_size=x.shape[0], sync_dist=True)
+        self.update_metrics(prediction, y, self.val_metrics)
+        return loss
+
+    def test_step(self, batch, batch_idx):
+        x, y = batch[self.image_key], batch[self.label_key]
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y)
+        self.log("test_loss", loss, on_epoch=True, on_step=False, prog_bar=True,
+                 batch_size=x.shape[0], sync_dist=True)
+        self.update_metrics(prediction, y, self.test_metrics, log=False)
+        return loss, prediction
+
+    def on_test_epoch_end(self):
+        self.log_metrics_end_epoch(self.test_metrics)
+
+    def predict_step(self, batch, batch_idx, dataloader_idx=0, *args, **kwargs):
+        x = batch[self.image_key]
+        prediction = self.forward(x, *args, **kwargs)
+        if "return_features" in kwargs:
+            return {"features": prediction}
+        return {"prediction": prediction}
+
+    def train_dataloader(self):
+        return self.training_dataloader_call()
+
+    def optimizer_groups(self):
+        """(parameter groups, base weight decay) of pl.py:632-683. The first group is the
+        reference's no-decay group of Gaussian-process parameters: always empty here, and kept so
+        that the group indices are the reference's."""
+        no_decay_params, reduced_decay_params, normal_decay_params = [], [], []
+        for n, p in self.named_parameters():
+            if not p.requires_grad:
+                continue
+            (reduced_decay_params if "ordinal_bias" in n else normal_decay_params).append(p)
+        if isinstance(self.weight_decay, (list, tuple)):
+            wd_body, wd_head = self.weight_decay
+            reduced = {id(p) for p in reduced_decay_params}
+            head_decay, body_decay = [], []
+            for n, p in self.named_parameters():
+                if not p.requires_grad or id(p) in reduced:
+                    continue
+                (head_decay if "classification" in n else body_decay).append(p)
+            return [{"params": no_decay_params, "weight_decay": 0},
+                    {"params": reduced_decay_params, "weight_decay": wd_body / 100},
+                    {"params": head_decay, "weight_decay": wd_head},
+                    {"params": body_decay, "weight_decay": wd_body}], wd_body / 100
+        wd = float(self.weight_decay)
+        return [{"params": no_decay_params, "weight_decay": 0},
+                {"params": reduced_decay_params, "weight_decay": wd / 100},
+                {"params": normal_decay_params, "weight_decay": wd}], wd / 100
+
+    def configure_optimizers(self) -> dict:
+        parameters, base_wd = self.optimizer_groups()
+        optimizer = FusedAdamW(parameters, lr=self.learning_rate, weight_decay=base_wd,
+                               eps=self.optimizer_eps)
+        lr_schedulers = CosineAnnealingWithWarmupLR(
+            optimizer, T_max=self.n_epochs, start_decay=self.start_decay,
+            n_warmup_steps=self.warmup_steps)
+        return {"optimizer": optimizer, "lr_scheduler": lr_schedulers, "monitor": "val_loss"}
+
+    def setup_metrics(self):
+        self.train_metrics = get_metric_dict(self.n_classes, [], prefix="")
+        self.val_metrics = get_metric_dict(self.n_classes, None, prefix="V_")
+        self.test_metrics = get_metric_dict(self.n_classes, None, prefix="T_", average="none")
+
+    def update_metrics(self, prediction, y, metrics, log=True):
+        """Softmax (more than two classes) or sigmoid of the logits, then one fused update of the
+        dict. The probabilities are a few numbers per item: plain torch."""
+        if self.n_classes > 2:
+            prediction = torch.softmax(prediction.detach(), 1)
+        else:
+            prediction = torch.sigmoid(prediction.detach())
+        if len(y.shape) > 1:
+            y = y.squeeze(1)
+        CM.update_many(metrics.values(), prediction, y)
+        if log is True:
+            for k in metrics:
+                self.log(k, metrics[k], on_epoch=True, on_step=False, prog_bar=True, sync_dist=True)
+
+    def log_metrics_end_epoch(self, metrics):
+        """pl.py:746-778: a vector metric is logged as ``{key}_{i}``. Returns what it logged."""
+        logged = {}
+        for k in metrics:
+            metric = metrics[k].compute()
+            if len(metric.shape) == 0:
+                metric = metric.reshape(1)
+            if len(metric) > 1:
+                for i in range(len(metric)):
+                    logged[f"{k}_{i}"] = metric[i]
+            else:
+                logged[k] = metric
+        for k, v in logged.items():
+            self.log(k, v, on_epoch=True, on_step=False, prog_bar=True, sync_dist=True)
+        return logged
+
+
+def _store(module, local, names):
+    for name in names:
+        setattr(module, name, local[name])
+
+
+_HYPERPARAMETERS = ("image_key", "label_key", "learning_rate", "batch_size", "weight_decay",
+                    "training_dataloader_call", "loss_fn", "loss_params", "n_epochs", "warmup_steps",
+                    "start_decay", "training_batch_preproc", "optimizer_eps", "args", "kwargs")
+_IGNORED = ["training_dataloader_call", "training_batch_preproc", "loss_fn"]
+
+
+class ClassNetPL(ClassPLABC):
+    """pl.py:781-928: holds a ``CatNet`` as ``network`` (``net_type[:3] == "cat"``); ``"vgg"`` raises
+    ``NotImplementedError``. The reference's default ``loss_fn`` is ``F.binary_cross_entropy`` on
+    logits, which no caller keeps; the default here is ``BCEWithLogitsLoss()``."""
+
+    def __init__(self, net_type: str = "cat", image_key: str = "image", label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__()
+        loss_fn = BCEWithLogitsLoss() if loss_fn is None else loss_fn
+        _store(self, locals(), _HYPERPARAMETERS)
+        self.net_type = net_type[:3]
+        self.save_hyperparameters(ignore=_IGNORED)
+        self.setup_network()
+        self.setup_metrics()
+        if hasattr(self.network, "forward_features"):
+            self.forward_features = self.network.forward_features
+
+    def setup_network(self):
+        if self.net_type == "cat":
+            self.network = CatNet(*self.args, **self.kwargs)
+        elif self.net_type == "vgg":
+            raise NotImplementedError("net_type 'vgg': the VGG classifier is not built")
+        else:
+            raise Exception("net_type '{}' not valid, has to be one of ['cat', 'vgg']".format(
+                self.net_type))
+        self.forward = self.network.forward
+        self.n_classes = self.network.n_classes
+
+
+class OrdNetPL(ClassPLABC):
+    """pl.py:931-1174: holds an ``OrdNet``; every step takes ``(loss, roc_loss)`` from the loss
+    (``OrdinalSigmoidalLoss`` with the pre-bias output) and returns their sum."""
+
+    def __init__(self, image_key: str = "image", label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__()
+        _store(self, locals(), _HYPERPARAMETERS)
+        self.net_type = "ord"
+        self.save_hyperparameters(ignore=_IGNORED)
+        self.setup_network()
+        if self.loss_fn is None:
+            from .losses import OrdinalSigmoidalLoss
+
+            self.loss_fn = OrdinalSigmoidalLoss(self.n_classes)
+        self.setup_metrics()
+        if hasattr(self.network, "forward_features"):
+            self.forward_features = self.network.forward_features
+
+    def setup_network(self):
+        self.network = OrdNet(*self.args, **self.kwargs)
+        self.forward = self.network.forward
+        self.n_classes = self.network.n_classes
+
+    def setup_metrics(self):
+        self.train_metrics = get_ordinal_metric_dict(self.n_classes, prefix="")
+        self.val_metrics = get_ordinal_metric_dict(self.n_classes, prefix="V_")
+        self.test_metrics = get_ordinal_metric_dict(self.n_classes, prefix="T_")
+
+    def update_metrics(self, prediction, y, metrics, log=True):
+        prediction = ordinal_prediction_to_class(torch.sigmoid(prediction.detach()))
+        if len(y.shape) > 1:
+            y = y.squeeze(1)
+        CM.update_many(metrics.values(), prediction, y)
+        if log is True:
+            for k in metrics:
+                self.log(k, metrics[k], on_epoch=True, on_step=False, prog_bar=True, sync_dist=True)
+
+    def _step(self, batch, preprocess=False):
+        x, y = batch[self.image_key], batch[self.label_key]
+        if preprocess and getattr(self, "training_batch_preproc", None) is not None:
+            x, y = self.training_batch_preproc(x, y)
+        prediction, pre_bias = self.forward(x, return_pre_bias=True)
+        prediction = torch.squeeze(prediction, 1)
+        loss, roc_loss = self.calculate_loss(prediction, y, additional_params={"pre_bias": pre_bias},
+                                             with_loss_params=True)
+        return x, y, prediction, loss, roc_loss
+
+    def training_step(self, batch, batch_idx):
+        _, _, _, loss, roc_loss = self._step(batch, preprocess=True)
+        self.log("train_loss", loss.detach(), prog_bar=True)
+        self.log("train_roc_loss", roc_loss.detach(), prog_bar=True)
+        return loss + roc_loss
+
+    def _eval_step(self, batch, name, metrics, log):
+        x, y, prediction, loss, roc_loss = self._step(batch)
+        kw = dict(on_epoch=True, on_step=False, prog_bar=True, batch_size=x.shape[0], sync_dist=True)
+        self.log(f"{name}_loss", loss, **kw)
+        self.log(f"{name}_roc_loss", roc_loss, **kw)
+        self.update_metrics(prediction, y, metrics, log=log)
+        return loss + roc_loss, prediction
+
+    def validation_step(self, batch, batch_idx):
+        return self._eval_step(batch, "val", self.val_metrics, True)[0]
+
+    def test_step(self, batch, batch_idx):
+        return self._eval_step(batch, "test", self.test_metrics, False)
+
+
+class ViTClassifierPL(ViTClassifier, ClassPLABC):
+    """pl.py:1762-1845: the ViT classifier IS the module (its parameters carry no ``network.``
+    prefix)."""
+
+    def __init__(self, image_key: str = "image", label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        loss_fn = BCEWithLogitsLoss() if loss_fn is None else loss_fn
+        _store(self, locals(), _HYPERPARAMETERS)
+        # ClassPLABC.__init__ is not reached through ViT's: its attributes
+        self.raise_nan_loss, self.calibrated, self.gaussian_process = False, False, False
+        self.net_type = "cat"
+        self.save_hyperparameters(ignore=_IGNORED)
+        self.setup_metrics()

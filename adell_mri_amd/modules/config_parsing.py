@@ -1,7 +1,7 @@
 """YAML -> constructor keyword arguments for the segmentation / SSL networks of the hot path.
 
-Restates ``parse_config_unet`` (adell_mri/modules/config_parsing.py:30-58) and
-``parse_config_ssl`` (:78-136) on this package's classes, so that the reference's sample
+Restates ``parse_config_unet`` (adell_mri/modules/config_parsing.py:30-58),
+``parse_config_cat`` (:61-64) and ``parse_config_ssl`` (:78-136) on this package's classes, so that the reference's sample
 configurations (``sample_configs/u-net-3d-resnet.yaml``, ``unetr.yaml``, ``unet-swin.yaml``,
 ``ssl-2d-convnext.yaml``, ``ssl-resnet.yaml``) can be consumed as they ship.
 
@@ -56,6 +56,12 @@ def parse_config_unet(config_file, n_keys, n_classes):
     network_config.setdefault("batch_size", 1)
     network_config["in_channels"] = n_keys * network_config["in_channels"]
     return network_config, loss_keys
+
+
+def parse_config_cat(config_file):
+    """config_parsing.py:61-64: the YAML mapping as it is (``get_classification_network`` pops
+    ``act_fn`` / ``norm_fn`` and splats the rest into the wrapper)."""
+    return _load(config_file)
 
 
 def parse_config_ssl(config_file, dropout_param, n_keys, is_vit=False):

@@ -3261,6 +3261,193 @@ def mae_from_image(image, patch_elems):
     return out
 
 
+# ---- classification (csrc/classify.hip) -------------------------------------------------------
+CLS_LOSS_KINDS = {"bce": 0, "ce": 1, "ordinal": 2}
+
+
+def _cls_on_device(*ts):
+    """Labels and counts are int64 here: only the device is checked (dtypes by each wrapper)."""
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise _lib.AdellHipError(
+                "adell_mri_amd kernels run on MI355X only: got a CPU tensor (no CPU fallback)")
+
+
+def _cls_loss_args(kind, logits, target, weight, n_classes):
+    """(kind id, logits [B, W], float target or None, int64 target or None, weight or None, nw, B, K)
+    checked on the host; K is the number of classes (1 for "bce")."""
+    kid = CLS_LOSS_KINDS[kind]
+    _cls_on_device(logits, target)
+    if logits.dtype != torch.float32:
+        raise TypeError(f"cls_loss: fp32 logits expected, got {logits.dtype}")
+    B = int(target.shape[0]) if target.dim() else 1
+    if kid == 0:
+        if logits.numel() != B or target.numel() != B:
+            raise ValueError(f"cls_loss (bce): one logit per target expected, got logits "
+                             f"{tuple(logits.shape)} and target {tuple(target.shape)}")
+        K, W = 1, 1
+        tf, ti = target.detach().reshape(B).to(torch.float32).contiguous(), None
+    else:
+        K = int(n_classes)
+        W = K if kid == 1 else K - 1
+        if logits.dim() != 2 or tuple(logits.shape) != (B, W) or target.dim() != 1:
+            raise ValueError(f"cls_loss ({kind}): logits [{B}, {W}] and labels [{B}] expected for "
+                             f"{K} classes, got {tuple(logits.shape)} and {tuple(target.shape)}")
+        if target.dtype != torch.int64:
+            raise TypeError(f"cls_loss ({kind}): int64 labels expected, got {target.dtype}")
+        tf, ti = None, target.detach().contiguous()
+    nw = 0
+    if weight is not None:
+        weight = weight.detach().to(device=logits.device, dtype=torch.float32).reshape(-1).contiguous()
+        nw = weight.numel()
+        if not (nw in (1, B) if kid == 0 else nw == K):
+            raise ValueError(f"cls_loss ({kind}): {nw} weights ("
+                             + ("1 or one per item" if kid == 0 else f"one per class, {K}") + " expected)")
+    return kid, logits.contiguous().reshape(B, W), tf, ti, weight, nw, B, K
+
+
+def cls_loss_fwd(kind, logits, target, weight=None, n_classes=None):
+    """(item [B], reduced 0-d, aux) of the loss ``kind`` in CLS_LOSS_KINDS on logits; one launch.
+    "bce": ``BCEWithLogitsLoss(weight)`` (item weights, 1 or B), reduced = mean; "ce":
+    ``CrossEntropyLoss(weight)`` (class weights), reduced = sum(item) / sum(w[y]); "ordinal":
+    ``ordinal_sigmoidal_loss`` on [B, K - 1] logits, reduced = mean. A label outside [0, K) gives a
+    NaN item (and gradient); it is never used as an index. ``aux`` (the denominator, a double on the
+    device) goes to ``cls_loss_bwd``."""
+    kid, x, tf, ti, w, nw, B, K = _cls_loss_args(kind, logits, target, weight, n_classes)
+    buf = torch.empty((B + 1,), device=x.device, dtype=torch.float32)
+    aux = torch.empty((1,), device=x.device, dtype=torch.float64)
+    base = buf.data_ptr()
+    check(_lib.lib().adell_cls_loss_fwd(kid, _ptr(x), _ptr(tf), _ptr(ti), _ptr(w), nw, B, K,
+                                        ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * B), _ptr(aux),
+                                        _stream()))
+    return buf[:B], buf[B], aux
+
+
+def cls_loss_bwd(kind, logits, target, weight, n_classes, g, per_item, aux):
+    """dlogits from the gradient of the reduced value (``g`` one element) or of the items (``g``
+    [B], ``per_item``); one launch."""
+    kid, x, tf, ti, w, nw, B, K = _cls_loss_args(kind, logits, target, weight, n_classes)
+    _cls_on_device(g)
+    g = g.detach().to(torch.float32).reshape(-1).contiguous()
+    if g.numel() != (B if per_item else 1):
+        raise ValueError(f"cls_loss_bwd: a gradient of {g.numel()} elements for {B} items")
+    dx = torch.empty_like(x)
+    check(_lib.lib().adell_cls_loss_bwd(kid, _ptr(x), _ptr(tf), _ptr(ti), _ptr(w), nw, _ptr(g),
+                                        int(bool(per_item)), _ptr(aux), B, K, _ptr(dx), _stream()))
+    return dx.view(logits.shape)
+
+
+def _cls_roc_args(pre_bias, target):
+    _cls_on_device(pre_bias, target)
+    B = int(target.shape[0])
+    if pre_bias.numel() != B or target.dim() != 1 or target.dtype != torch.int64:
+        raise ValueError(f"cls_roc: pre_bias of {B} elements and int64 labels [{B}] expected, got "
+                         f"{tuple(pre_bias.shape)} and {target.dtype} {tuple(target.shape)}")
+    if pre_bias.dtype != torch.float32:
+        raise TypeError(f"cls_roc: fp32 pre_bias expected, got {pre_bias.dtype}")
+    return pre_bias.contiguous().reshape(B), target.detach().contiguous(), B
+
+
+def cls_roc_fwd(pre_bias, target):
+    """(loss 0-d, aux): ``relative_order_consistency``; aux[0] = the number of ordered pairs M (a
+    double on the device). M = 0 gives NaN."""
+    p, y, B = _cls_roc_args(pre_bias, target)
+    rows = torch.empty((B + 1,), device=p.device, dtype=torch.float64)
+    loss = torch.empty((1,), device=p.device, dtype=torch.float32)
+    base = rows.data_ptr()
+    check(_lib.lib().adell_cls_roc_fwd(_ptr(p), _ptr(y), B, ctypes.c_void_p(base), _ptr(loss),
+                                       ctypes.c_void_p(base + 8 * B), _stream()))
+    return loss[0], rows[B:]
+
+
+def cls_roc_bwd(pre_bias, target, g, aux):
+    p, y, B = _cls_roc_args(pre_bias, target)
+    _cls_on_device(g)
+    g = g.detach().to(torch.float32).reshape(-1).contiguous()
+    dp = torch.empty_like(p)
+    check(_lib.lib().adell_cls_roc_bwd(_ptr(p), _ptr(y), _ptr(g), _ptr(aux), B, _ptr(dp), _stream()))
+    return dp.view(pre_bias.shape)
+
+
+def cls_mixup(x, factor, partner):
+    """out[b] = factor[b] * x[b] + (1 - factor[b]) * x[partner[b]] for x [B, ...] (fp32, dense; any
+    element offset), the three operations rounded one by one as torch's expression; a row with
+    ``partner[b] == b`` is copied. ``partner``: host integers in [0, B) (checked here)."""
+    _cls_on_device(x)
+    if x.dtype != torch.float32 or x.dim() < 1 or not x.is_contiguous():
+        raise ValueError(f"cls_mixup: a dense fp32 batch expected, got {x.dtype} {tuple(x.shape)} "
+                         f"strides {x.stride()}")
+    B = int(x.shape[0])
+    V = x.numel() // max(B, 1)
+    host = np.asarray(partner).reshape(-1)
+    if host.shape[0] != B or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f"cls_mixup: {B} integer partners expected, got {host.dtype} {host.shape}")
+    if B and (host.min() < 0 or host.max() >= B):
+        raise IndexError(f"cls_mixup: a partner outside [0, {B})")
+    factor = torch.as_tensor(factor, dtype=torch.float32, device=x.device).reshape(-1).contiguous()
+    if factor.numel() != B:
+        raise ValueError(f"cls_mixup: {B} factors expected, got {factor.numel()}")
+    out = torch.empty_like(x)
+    if B == 0 or V == 0:
+        return out
+    tab = torch.from_numpy(host.astype(np.int32)).to(x.device)
+    check(_lib.lib().adell_cls_mixup(_ptr(x), _ptr(factor), _ptr(tab), B, V, _ptr(out), _stream()))
+    return out
+
+
+def cls_confusion_update(preds, target, counts):
+    """counts (int64 [C * C + 1], on the device; row = label, column = prediction, last = samples
+    with a label or an integer prediction outside [0, C)) += the samples of one update. ``preds``:
+    fp32 [N, C] (argmax: first maximal index, a NaN wins), fp32 [N] probabilities (``p > 0.5``,
+    C = 2) or int64 [N] classes; ``target`` int64 [N]. No host synchronisation."""
+    _cls_on_device(preds, target, counts)
+    if counts.dtype != torch.int64 or counts.dim() != 1 or not counts.is_contiguous():
+        raise ValueError("cls_confusion_update: counts must be a dense int64 vector")
+    C = int(round(math.sqrt(counts.numel() - 1)))
+    if C < 2 or C * C + 1 != counts.numel():
+        raise ValueError(f"cls_confusion_update: counts of {counts.numel()} elements are no C * C + 1")
+    N = int(target.shape[0])
+    if target.dtype != torch.int64 or target.dim() != 1:
+        raise ValueError(f"cls_confusion_update: int64 labels [N] expected, got {target.dtype} "
+                         f"{tuple(target.shape)}")
+    target = target.contiguous()
+    pf = pi = None
+    if preds.dtype == torch.int64:
+        mode, pi = 2, preds.contiguous()
+        ok = tuple(preds.shape) == (N,)
+    elif preds.dtype == torch.float32 and preds.dim() == 2:
+        mode, pf = 0, preds.contiguous()
+        ok = tuple(preds.shape) == (N, C)
+    elif preds.dtype == torch.float32:
+        mode, pf = 1, preds.contiguous()
+        ok = tuple(preds.shape) == (N,) and C == 2
+    else:
+        raise TypeError(f"cls_confusion_update: fp32 or int64 predictions expected, got {preds.dtype}")
+    if not ok:
+        raise ValueError(f"cls_confusion_update: predictions {tuple(preds.shape)} do not match {N} "
+                         f"labels and {C} classes")
+    if N == 0:
+        return
+    check(_lib.lib().adell_cls_confusion_update(mode, _ptr(pf), _ptr(pi), _ptr(target), N, C,
+                                                _ptr(counts), _stream()))
+
+
+def cls_auroc_pairs(scores, target):
+    """int64 [3] on the device: (2 #{pos > neg} + #{pos == neg}, positives, negatives) over the
+    pairs of a positive (label 1) and a negative (label 0) sample; exact."""
+    _cls_on_device(scores, target)
+    N = int(target.shape[0])
+    if scores.dtype != torch.float32 or target.dtype != torch.int64 or tuple(scores.shape) != (N,) \
+            or target.dim() != 1:
+        raise ValueError(f"cls_auroc_pairs: fp32 scores [N] and int64 labels [N] expected, got "
+                         f"{scores.dtype} {tuple(scores.shape)} and {target.dtype} {tuple(target.shape)}")
+    out = torch.zeros((3,), device=scores.device, dtype=torch.int64)
+    if N:
+        check(_lib.lib().adell_cls_auroc_pairs(_ptr(scores.contiguous()), _ptr(target.contiguous()), N,
+                                               _ptr(out), _stream()))
+    return out
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

@@ -331,7 +331,10 @@ def _evaluate(module, batches, step_name, loss_key, metrics_attr):
         with torch.no_grad():
             total, count = None, 0
             for i, batch in enumerate(batches):
-                loss = getattr(module, step_name)(batch, i).detach().double().reshape(())
+                loss = getattr(module, step_name)(batch, i)
+                if isinstance(loss, tuple):       # a classification test_step: (loss, prediction)
+                    loss = loss[0]
+                loss = loss.detach().double().reshape(())
                 bs = _batch_size(module, batch)
                 total = loss * bs if total is None else total + loss * bs
                 count += bs
@@ -350,7 +353,9 @@ def _evaluate(module, batches, step_name, loss_key, metrics_attr):
         keys = list(metrics.keys())
         for k, bad in zip(keys, host[1 + len(keys):]):
             if bad > 0:
-                raise RuntimeError(f"{k}: " + bad_target_message(metrics[k].num_classes))
+                own = getattr(metrics[k], "bad_target_message", None)
+                raise RuntimeError(f"{k}: " + (own() if own is not None
+                                               else bad_target_message(metrics[k].num_classes)))
         out = {loss_key: host[0]}
         out.update(zip(keys, host[1:1 + len(keys)]))
         if picai is not None and len(picai):

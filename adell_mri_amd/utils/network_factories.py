@@ -1,5 +1,6 @@
-"""Network factories of the hot path: ``get_segmentation_network``
-(adell_mri/utils/network_factories.py:493-701) and ``get_ssl_network`` (:705-1028) on this
+"""Network factories of the hot path: ``get_classification_network``
+(adell_mri/utils/network_factories.py:136-305), ``get_segmentation_network`` (:493-701) and
+``get_ssl_network`` (:705-1028) on this
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
 constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
 ``DINOPL``, ``ssl_method="ibot"`` ``iBOTPL`` and ``ssl_method="ijepa"`` ``IJEPAPL`` on a ViT encoder
@@ -12,6 +13,8 @@ from typing import Any, Callable
 
 import torch
 
+from ..modules.classification.pl import ClassNetPL, OrdNetPL, ViTClassifierPL
+from ..modules.layers.adn_fn import get_adn_fn
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
 from ..modules.self_supervised.pl import (DINOPL, IJEPAPL, SelfSLConvNeXtPL, SelfSLResNetPL,
@@ -20,6 +23,7 @@ from ..modules.self_supervised.pl import (DINOPL, IJEPAPL, SelfSLConvNeXtPL, Sel
 OPTIMIZER_EPS_DEFAULT = 1e-8
 _MAE_STACK_KEYS = ("number_of_blocks", "hidden_dim", "n_heads", "mlp_structure")
 ALLOWED_NET_TYPES = {
+    "classification": ["unet", "vit", "factorized_vit", "cat", "ord", "vgg"],
     "segmentation": ["unet", "brunet", "unetpp", "unetr", "monai_unetr", "swin", "monai_swin"],
 }
 
@@ -29,6 +33,57 @@ def _first_given(*sizes):
         if size is not None:
             return size
     return None
+
+
+def get_classification_network(
+        net_type: str, network_config: dict[str, Any], dropout_param: float, seed: int,
+        n_classes: int, keys: list[str], clinical_feature_keys: list[str],
+        train_loader_call: Callable, max_epochs: int, warmup_steps: int, start_decay: int,
+        crop_size: int, clinical_feature_means: torch.Tensor = None,
+        clinical_feature_stds: torch.Tensor = None, label_smoothing: float | None = None,
+        mixup_alpha: float | None = None, partial_mixup: float | None = None,
+        optimizer_eps: float = OPTIMIZER_EPS_DEFAULT):
+    """network_factories.py:136-305: ``"cat"`` builds ``ClassNetPL``, ``"ord"`` ``OrdNetPL`` and
+    ``"vit"`` ``ViTClassifierPL``, with the reference's keyword plumbing (``act_fn`` / ``norm_fn``
+    popped from ``network_config`` into the 3-D ``adn_fn``, the ``BatchPreprocessing`` of the three
+    mixup arguments as ``training_batch_preproc``). An unknown ``net_type`` is the reference's
+    ``ValueError``; ``"unet"``, ``"factorized_vit"`` and ``"vgg"``, and a non-empty
+    ``clinical_feature_keys`` (the hybrid / tabular classifier), raise ``NotImplementedError``."""
+    from .batch_preprocessing import BatchPreprocessing
+
+    if net_type not in ALLOWED_NET_TYPES["classification"]:
+        raise ValueError(f"net_type '{net_type}' not valid, has to be one of "
+                         f"{ALLOWED_NET_TYPES['classification']}")
+    if net_type in ("unet", "factorized_vit", "vgg"):
+        raise NotImplementedError(f"net_type '{net_type}' is not built for classification "
+                                  "(built: 'cat', 'ord', 'vit')")
+    if len(clinical_feature_keys) > 0:
+        raise NotImplementedError("clinical_feature_keys: the hybrid (image + tabular) classifier is "
+                                  "not built")
+    network_config = dict(network_config)
+    act_fn = network_config.pop("act_fn", "swish")
+    norm_fn = network_config.pop("norm_fn", "batch")
+    adn_fn = get_adn_fn(3, norm_fn, act_fn=act_fn, dropout_param=dropout_param)
+    batch_preprocessing = BatchPreprocessing(label_smoothing, mixup_alpha, partial_mixup, seed)
+    boilerplate_args = {
+        "in_channels": len(keys), "n_classes": n_classes,
+        "training_dataloader_call": train_loader_call, "image_key": "image", "label_key": "label",
+        "n_epochs": max_epochs, "warmup_steps": warmup_steps,
+        "training_batch_preproc": batch_preprocessing, "start_decay": start_decay,
+        "optimizer_eps": optimizer_eps,
+    }
+    if net_type == "vit":
+        network_config["image_size"] = tuple(int(x) for x in crop_size)
+        return ViTClassifierPL(
+            adn_fn=get_adn_fn(1, "identity", act_fn="gelu", dropout_param=dropout_param),
+            **boilerplate_args, **network_config)
+    if net_type == "ord":
+        for k in ["net_type", "in_channels", "n_classes", "adn_fn"]:
+            network_config.pop(k, None)
+        return OrdNetPL(adn_fn=adn_fn, **boilerplate_args, **network_config)
+    for k in ["in_channels", "n_classes", "adn_fn"]:
+        network_config.pop(k, None)
+    return ClassNetPL(net_type=net_type, adn_fn=adn_fn, **boilerplate_args, **network_config)
 
 
 def get_segmentation_network(

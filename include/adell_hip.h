@@ -985,6 +985,43 @@ int adell_mae_loss_bwd(const float* pred, const float* x, const float* g, int B,
 int adell_mae_to_image(const float* tokens, int B, int C, int L, int P, float* image, void* stream);
 int adell_mae_from_image(const float* image, int B, int C, int L, int P, float* tokens, void* stream);
 
+/* Classification (modules/classification/losses.py, pl.py; utils/batch_preprocessing.py;
+ * csrc/classify.hip). fp32, dense, one wave per row, floating-point sums in a fixed order in fp64, no
+ * float atomics: results repeat bit for bit. The counts are int64 and use integer atomics.
+ * adell_cls_loss_fwd, one launch: kind 0 BCE with logits (x [B][1], float targets tf [B], soft targets
+ * allowed, l = max(x, 0) - x t + log1p(exp(-|x|)); w: NULL, or 1 or B item weights), kind 1 cross
+ * entropy (x [B][K], int64 labels ti [B], w: NULL or [K] class weights), kind 2 the ordinal sigmoidal
+ * (CORAL) loss (x [B][K - 1], t_j = [y >= j], l = -sum_j (logsig(x_j) t_j + (logsig(x_j) - x_j)
+ * (1 - t_j)), w: NULL or [K]). item [B] = weight * l; red [1] = sum(item) / aux[0] with aux[0] (a double,
+ * kept for the backward) = sum of w[y] for kind 1 and B otherwise. A label outside [0, K) is never used
+ * as an index: that row's item and gradient are NaN. _bwd, one launch: dx = c_b dl_b/dx with
+ * c_b = g[0] weight_b / aux[0] (per_item = 0) or g[b] weight_b (per_item = 1; aux may be NULL).
+ * adell_cls_roc_fwd (relative_order_consistency): over the M ordered pairs i != j with y_i != y_j the
+ * mean of BCE-with-logits(p_i - p_j, [y_i > y_j]); rows [B] doubles take the row sums, aux[0] = M;
+ * M = 0 gives NaN. _bwd: dp [B] in one launch, row i collecting its (i, .) and (., i) terms.
+ * adell_cls_mixup: out[b][:] = factor[b] x[b][:] + (1 - factor[b]) x[partner[b]][:] over [B][V], the two
+ * products and the sum rounded one by one; a row with partner[b] == b is copied. partner in [0, B) is
+ * the caller's to check. Any alignment, any V.
+ * adell_cls_confusion_update: counts [C][C] (row: label, column: prediction) += the samples, and
+ * counts[C C] += those whose label or integer prediction lies outside [0, C). mode 0: pf [N][C], argmax
+ * (first maximal index, a NaN wins); mode 1: pf [N], class [p > 0.5], C = 2; mode 2: pi [N] classes.
+ * adell_cls_auroc_pairs: out[0] += 2 #{s_pos > s_neg} + #{s_pos == s_neg} over the pairs of a positive
+ * (y = 1) and a negative (y = 0), out[1] += positives, out[2] += negatives; exact, O(P Nneg). */
+int adell_cls_loss_fwd(int kind, const float* x, const float* tf, const long long* ti, const float* w,
+                       int nw, int B, int K, float* item, float* red, double* aux, void* stream);
+int adell_cls_loss_bwd(int kind, const float* x, const float* tf, const long long* ti, const float* w,
+                       int nw, const float* g, int per_item, const double* aux, int B, int K, float* dx,
+                       void* stream);
+int adell_cls_roc_fwd(const float* p, const long long* y, int B, double* rows, float* loss, double* aux,
+                      void* stream);
+int adell_cls_roc_bwd(const float* p, const long long* y, const float* g, const double* aux, int B,
+                      float* dp, void* stream);
+int adell_cls_mixup(const float* x, const float* factor, const int* partner, int B, long V, float* out,
+                    void* stream);
+int adell_cls_confusion_update(int mode, const float* pf, const long long* pi, const long long* y, long N,
+                               int C, long long* counts, void* stream);
+int adell_cls_auroc_pairs(const float* scores, const long long* y, int N, long long* out, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
