@@ -338,7 +338,7 @@ SIGNATURES = {
     "adell_gemm_f32_workspace_floats": (_l, [_i, _i, _i]),
     "adell_gemm_f32": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp, _vp]),
     "adell_absmax_f32": (_i, [_vp, _l, _vp, _vp]),
-    "adell_gemm_f16x3_applicable": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i]),
+    "adell_gemm_plan": (_i, [_i] * 6 + [_l, _l, _i, _i, _vp]),
     "adell_gemm_f16x3_workspace_floats": (_l, [_i, _i, _i]),
     "adell_gemm_f16x3": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp, _vp,
                               _vp, _vp]),

@@ -123,6 +123,29 @@ int adell_dw_wgrad_mfma_plan(int N, int C, int D, int H, int W, int KD, int KH, 
                              int ya, AdellDwPlan* p);
 static inline int adell_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// Launch plans of the two GEMM families (adell_gemm_plan, include/adell_hip.h: the ADELL_GEMM_* routes,
+// the `aligned` bits and the out[] layouts). Each launcher, its shape-only workspace query and the plan
+// query call the one plan function of the family, so a condition is written once: adell_gemm_f32_plan
+// (gemm.hip), adell_gemm_h_plan (gemm_f16x3.hip), which asks adell_gemm_rows_plan (gemm_rows.hip) first.
+struct AdellGemmF32Plan {
+  int route, splits, ksteps_per_split, reduce;
+  int R, NB;                 // tall_lds: chunk rows, outputs per thread
+  long blocks, workspace;    // grid x (tile routes: tiles x splits); floats of workspace
+};
+struct AdellGemmHPlan {
+  int route, epi;                                         // epi: the ADELL_GEMM_EPI_* asked for
+  int slices, R, tiles_per_block;                         // rows: column slices, pack rows per block
+  int wide, splits, stages_per_split, fold_v, fold_s;     // tile
+  int many_rows, cu;                                      // the streaming regime; CUs (rows' tile limit)
+  long blocks, workspace;
+};
+AdellGemmF32Plan adell_gemm_f32_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb,
+                                     int aligned);
+AdellGemmHPlan adell_gemm_h_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb, int aligned,
+                                 int epilogue);
+bool adell_gemm_rows_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb, int aligned,
+                          int epilogue, AdellGemmHPlan* p);
+
 static inline int adell_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int adell_ilog2(int v) {
   int r = 0;

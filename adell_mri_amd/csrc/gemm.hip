@@ -17,6 +17,7 @@
 // Skinny problems are split along k (deterministic: each split writes its own slab, a
 // second kernel sums the slabs in fixed order and applies bias / residual).
 #include "common.h"
+#include <algorithm>
 
 struct GemmArgs {
   const float* A;
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void adell_gemm_reduce_flat_kernel(GemmArgs a)
 //                 order by adell_gemm_reduce_kernel (deterministic).
 constexpr int GEMM_SMALL = 32;
 
-constexpr int GEMM_ROWS_K = 64, GEMM_ROWS_N = 64;   // rows kernel: K <= 64, N <= 64, N K <= 512
+constexpr int GEMM_ROWS_K = 64, GEMM_ROWS_N = 64;   // rows kernel: K, N up to 64, N K up to 512
 constexpr int GEMM_ROWS_W = 512 + 4 * GEMM_ROWS_N;    // weight image: N rows of K + 4 floats
 
 template <bool BKC>
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(256) void adell_gemm_tall_small_kernel(GemmArgs a) 
 }
 
 // The same product for dense operands (lda == M, ldb == N, 16-byte aligned) and power-of-two M, N
-// up to 64 with M N <= 512: a block walks a contiguous range of rows in chunks; a chunk of both
+// up to 64 with M N up to 512: a block walks a contiguous range of rows in chunks; a chunk of both
 // operands is copied to LDS as one flat stream of 16-byte pieces (the kernel above reads 4-byte
 // pieces, a few per lane in flight: 1.3 TB/s on 8 x 2 over 8.4 M rows, and 64 x 8 fell to the
 // 128-wide MFMA tiles at 0.9 TB/s); thread = (m, NB outputs n, row group g) sums the rows
@@ -435,46 +436,47 @@ __global__ __launch_bounds__(256) void adell_gemm_tall_lds_kernel(GemmArgs a, in
   }
 }
 
-// chunk rows / outputs per thread / blocks of the LDS-staged form, or 0 when it does not apply
-static int adell_gemm_tall_lds_plan(int M, int N, int K, long lda, long ldb, const float* A,
-                                    const float* B, int* R, int* NB) {
-  auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-  if (!pow2(M) || !pow2(N) || M > 64 || N > 64 || M * N > 512 || M * N < 8 || K < 16384 || (K & 3)) return 0;
-  if (A != nullptr && (lda != M || ldb != N || (((uintptr_t)A | (uintptr_t)B) & 15))) return 0;
-  int nb = N < 8 ? N : 8;
-  while (M * (N / nb) > 256) nb *= 2;           // (M N <= 512, nb <= 8: never needed beyond 8)
-  if (nb > 8) return 0;
-  int r = GEMM_TALL_LDS_FLOATS / (M + N);
-  r &= ~63;
-  if (r < 64) return 0;
-  *R = r;
-  *NB = nb;
-  long b = ((long)K + r - 1) / r;               // chunks
-  b = (b + 3) / 4;                              // at least four chunks per block
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-static int adell_gemm_tall_blocks(int M, int N, int K) {
-  if (M > GEMM_SMALL || N > GEMM_SMALL || K < 16384) return 0;
-  long b = K / 512;
-  if (b > 1024) b = 1024;
-  if (b < 2) b = 2;
-  return (int)b;
-}
-
-struct GemmPlan {
-  int skinny;  // 32 x 128 tile instead of 128 x 128
-  int BM, BN, splits, ksteps_per_split;
-};
-
-static GemmPlan adell_gemm_plan(int M, int N, int K) {
-  GemmPlan p;
-  p.skinny = M <= 32;
-  p.BM = p.skinny ? 32 : 128;
-  p.BN = 128;
-  const long tiles = (long)adell_cdiv(M, p.BM) * adell_cdiv(N, p.BN);
+// ---- host side ----------------------------------------------------------------------------------
+// The launch plan of the fp32 family: every route condition of adell_gemm_f32 is written here and
+// nowhere else (routes, `aligned` bits and the out[] layout: adell_gemm_plan, include/adell_hip.h).
+AdellGemmF32Plan adell_gemm_f32_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb,
+                                     int aligned) {
+  AdellGemmF32Plan p = {};
+  const long MN = (long)M * N;
+  // (measured on SWIN-UNet's shapes: 10x / 5x for 8 -> 2 / 2 -> 8 features at 8.4 M rows; from
+  // N K = 256 on the MFMA tiles are as fast or faster, 32 x 8 at 2 M rows 180 vs 250 us)
+  // (round 5: without the 64-bit division per output the thread-per-output kernel wins up to
+  // N K = 512 -- 2 097 152 x 8 x 32: 249 us on the tiles)
+  if (a_kc && K <= GEMM_ROWS_K && N <= GEMM_ROWS_N && (long)N * K <= 512 && M >= 65536) {
+    p.route = ADELL_GEMM_ROWS_SMALL;
+    p.splits = 1;
+    p.blocks = std::min((MN + 255) / 256, 8192L);
+    return p;
+  }
+  if (!a_kc && !b_kc && K >= 16384) {   // the weight gradient of those layers: K = rows
+    // LDS-staged form: power-of-two M, N, whole 16-byte pieces, dense 16-byte aligned operands
+    int nb = N < 8 ? N : 8;
+    const bool lds = adell_is_pow2(M) && adell_is_pow2(N) && M <= 64 && N <= 64 && MN <= 512 && MN >= 8 &&
+                     (K & 3) == 0 && lda == M && ldb == N && (aligned & ADELL_GEMM_ALIGNED_A) &&
+                     (aligned & ADELL_GEMM_ALIGNED_B) && M * (N / nb) <= 256;   // (nb <= 8: M N <= 512)
+    if (lds) {
+      p.route = ADELL_GEMM_TALL_LDS;
+      p.R = (GEMM_TALL_LDS_FLOATS / (M + N)) & ~63;      // (M + N <= 128: at least 64 rows)
+      p.NB = nb;
+      p.blocks = std::clamp((((long)K + p.R - 1) / p.R + 3) / 4, 1L, 1024L);   // >= four chunks per block
+    } else if (M <= GEMM_SMALL && N <= GEMM_SMALL) {
+      p.route = ADELL_GEMM_TALL_SMALL;
+      p.blocks = std::clamp((long)K / 512, 2L, 1024L);
+    }
+    if (p.blocks) {                     // one partial [M][N] per block, folded in block order
+      p.splits = (int)p.blocks;
+      p.reduce = ADELL_GEMM_REDUCE_TREE;
+      p.workspace = p.blocks * MN;
+      return p;
+    }
+  }
+  p.route = M <= 32 ? ADELL_GEMM_TILE_SKINNY : ADELL_GEMM_TILE_SQUARE;   // 32 x 128 or 128 x 128 tiles
+  const long tiles = (long)adell_cdiv(M, M <= 32 ? 32 : 128) * adell_cdiv(N, 128);
   const int ksteps = adell_cdiv(K, GEMM_BK);
   long s = adell_cdiv(512, tiles);
   // very long reductions over a small output (per-voxel weight gradients: k = voxels): more,
@@ -482,40 +484,55 @@ static GemmPlan adell_gemm_plan(int M, int N, int K) {
   const long by_len = adell_cdiv(ksteps, 256);
   if (s < by_len) s = by_len;
   if (s > ksteps / 4) s = ksteps / 4;
-  const long slab_cap = (16L << 20) / ((long)M * N);
+  const long slab_cap = (16L << 20) / MN;
   if (s > slab_cap) s = slab_cap;
   if (s > 65535) s = 65535;
   if (s < 1) s = 1;
   p.ksteps_per_split = adell_cdiv(ksteps, (int)s);
   p.splits = adell_cdiv(ksteps, p.ksteps_per_split);
+  // few slabs: one thread per output walks them; more: 16 lanes per output
+  p.reduce = p.splits == 1 ? ADELL_GEMM_REDUCE_NONE : p.splits <= 8 ? ADELL_GEMM_REDUCE_FLAT : ADELL_GEMM_REDUCE_TREE;
+  p.blocks = tiles * p.splits;
+  p.workspace = p.splits > 1 ? p.splits * MN : 0;
   return p;
 }
 
+// the layout and the operands' alignment pick the route at launch: room for any of them
 extern "C" long adell_gemm_f32_workspace_floats(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const GemmPlan p = adell_gemm_plan(M, N, K);
-  long need = p.splits > 1 ? (long)p.splits * M * N : 0;
-  // (the layout decides at launch whether the tall small-output kernel runs: room for either)
-  long tall = (long)adell_gemm_tall_blocks(M, N, K) * M * N;
-  int r_ = 0, nb_ = 0;
-  const long tall2 = (long)adell_gemm_tall_lds_plan(M, N, K, 0, 0, nullptr, nullptr, &r_, &nb_) * M * N;
-  if (tall2 > tall) tall = tall2;
-  return need > tall ? need : tall;
+  long need = 0;
+  for (int l = 0; l < 4; ++l)
+    for (int al : {0, ADELL_GEMM_ALIGNED_ALL})
+      need = std::max(need, adell_gemm_f32_plan(M, N, K, l >> 1, l & 1, (l >> 1) ? K : M, (l & 1) ? K : N,
+                                                al).workspace);
+  return need;
 }
 
-template <int WM, int WN, int TM, int TN>
-static int adell_gemm_launch(const GemmArgs& a, int a_kc, int b_kc, dim3 grid, hipStream_t st) {
-  if (a_kc && b_kc)
-    hipLaunchKernelGGL((adell_gemm_f32_kernel<WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, a);
-  else if (a_kc && !b_kc)
-    hipLaunchKernelGGL((adell_gemm_f32_kernel<WM, WN, TM, TN, true, false>), grid, dim3(256), 0, st, a);
-  else if (!a_kc && !b_kc)
-    hipLaunchKernelGGL((adell_gemm_f32_kernel<WM, WN, TM, TN, false, false>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((adell_gemm_f32_kernel<WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, a);
-  ADELL_CHECK_HIP(hipGetLastError());
+extern "C" int adell_gemm_plan(int family, int M, int N, int K, int a_kc, int b_kc, long lda, long ldb,
+                               int aligned, int epilogue, long* out) {
+  ADELL_REQUIRE(out && M > 0 && N > 0 && K > 0, "gemm_plan: bad arguments");
+  ADELL_REQUIRE(family == ADELL_GEMM_F32 || family == ADELL_GEMM_F16X3, "gemm_plan: unknown family %d", family);
+  ADELL_REQUIRE(epilogue >= ADELL_GEMM_EPI_NONE && epilogue <= ADELL_GEMM_EPI_DACT,
+                "gemm_plan: unknown epilogue %d", epilogue);
+  if (family == ADELL_GEMM_F32) {
+    const AdellGemmF32Plan p = adell_gemm_f32_plan(M, N, K, a_kc, b_kc, lda, ldb, aligned);
+    const long v[] = {p.route, p.splits, p.ksteps_per_split, p.reduce, p.R, p.NB, p.blocks, p.workspace};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+  } else {
+    const AdellGemmHPlan p = adell_gemm_h_plan(M, N, K, a_kc, b_kc, lda, ldb, aligned, epilogue);
+    const long v[] = {p.route, p.epi, p.slices, p.R, p.blocks, p.tiles_per_block, p.wide, p.splits,
+                      p.stages_per_split, p.fold_v, p.fold_s, p.workspace, p.many_rows, p.cu};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+  }
   return ADELL_OK;
 }
+
+using GemmKernel = void (*)(GemmArgs);
+#define GEMM_LAYOUTS(...)                                                             \
+  {{adell_gemm_f32_kernel<__VA_ARGS__, false, false>, adell_gemm_f32_kernel<__VA_ARGS__, false, true>}, \
+   {adell_gemm_f32_kernel<__VA_ARGS__, true, false>, adell_gemm_f32_kernel<__VA_ARGS__, true, true>}}
+// [skinny][a_kc][b_kc]
+static const GemmKernel kGemmTile[2][2][2] = {GEMM_LAYOUTS(2, 2, 2, 2), GEMM_LAYOUTS(1, 4, 1, 1)};
 
 // C[M][N] (row stride ldc) = A x B (+ bias[N]) (+ residual, row stride ldr).
 // a_kc != 0: A element (m, k) at A[m*lda + k], else at A[k*lda + m];
@@ -529,62 +546,45 @@ extern "C" int adell_gemm_f32(int M, int N, int K, const float* A, long lda, int
   ADELL_REQUIRE(A && B && C, "gemm: null pointer");
   ADELL_REQUIRE(lda >= (a_kc ? K : M) && ldb >= (b_kc ? K : N) && ldc >= N, "gemm: bad strides");
   ADELL_REQUIRE(!residual || ldr >= N, "gemm: bad residual stride");
-  const GemmPlan p = adell_gemm_plan(M, N, K);
-  int tallR = 0, tallNB = 0;
-  const int tall_lds = (!a_kc && !b_kc) ? adell_gemm_tall_lds_plan(M, N, K, lda, ldb, A, B, &tallR, &tallNB) : 0;
-  const int tall = tall_lds ? tall_lds : ((!a_kc && !b_kc) ? adell_gemm_tall_blocks(M, N, K) : 0);
-  // (measured on SWIN-UNet's shapes: 10x / 5x for 8 -> 2 / 2 -> 8 features at 8.4 M rows; from
-  // N K = 256 on the MFMA tiles are as fast or faster, 32 x 8 at 2 M rows 180 vs 250 us)
-  // (round 5: without the 64-bit division per output the thread-per-output kernel wins up to
-  // N K = 512 -- 2 097 152 x 8 x 32: 249 us on the tiles)
-  const bool rows_small = a_kc && K <= GEMM_ROWS_K && N <= GEMM_ROWS_N && (long)N * K <= 512 && M >= 65536;
-  ADELL_REQUIRE(rows_small || (tall ? workspace != nullptr : (p.splits == 1 || workspace)),
-                "gemm: workspace required for this shape");
+  const AdellGemmF32Plan p = adell_gemm_f32_plan(
+      M, N, K, a_kc, b_kc, lda, ldb,
+      (adell_aligned16(A) ? ADELL_GEMM_ALIGNED_A : 0) | (adell_aligned16(B) ? ADELL_GEMM_ALIGNED_B : 0));
+  ADELL_REQUIRE(p.workspace == 0 || workspace, "gemm: workspace required for this shape");
   GemmArgs a;
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.residual = residual; a.slab = workspace;
   a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr;
   a.splits = p.splits;
   a.ksteps_per_split = p.ksteps_per_split;
-  a.a_vec = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
-  a.b_vec = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
+  a.a_vec = adell_aligned16(A) && (lda % 4 == 0);
+  a.b_vec = adell_aligned16(B) && (ldb % 4 == 0);
   hipStream_t st = (hipStream_t)stream;
-  if (rows_small) {
-    long blocks = ((long)M * N + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (b_kc)
-      hipLaunchKernelGGL(adell_gemm_rows_small_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(adell_gemm_rows_small_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  }
-  if (tall) {
-    a.splits = tall;
-    if (tall_lds)
-      hipLaunchKernelGGL(adell_gemm_tall_lds_kernel, dim3((unsigned)tall), dim3(256), 0, st, a, tallR, tallNB);
-    else
-      hipLaunchKernelGGL(adell_gemm_tall_small_kernel, dim3((unsigned)tall), dim3(256), 0, st, a);
-    const long blocks = ((long)M * N + 63) / 64;
-    hipLaunchKernelGGL(adell_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, a);
-    ADELL_CHECK_HIP(hipGetLastError());
-    return ADELL_OK;
-  }
-  dim3 grid(adell_cdiv(M, p.BM), adell_cdiv(N, p.BN), p.splits);
-  ADELL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm: grid too large");
-  int rc = p.skinny ? adell_gemm_launch<1, 4, 1, 1>(a, a_kc, b_kc, grid, st)
-                    : adell_gemm_launch<2, 2, 2, 2>(a, a_kc, b_kc, grid, st);
-  if (rc != ADELL_OK) return rc;
-  if (p.splits > 1) {
-    if (p.splits <= 8) {
-      long blocks = ((long)M * N + 255) / 256;
-      if (blocks > 8192) blocks = 8192;
-      hipLaunchKernelGGL(adell_gemm_reduce_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    } else {
-      const long blocks = ((long)M * N + 63) / 64;
-      hipLaunchKernelGGL(adell_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, a);
+  const dim3 blocks((unsigned)p.blocks), threads(256);
+  switch (p.route) {
+    case ADELL_GEMM_ROWS_SMALL:
+      hipLaunchKernelGGL(b_kc ? adell_gemm_rows_small_kernel<true> : adell_gemm_rows_small_kernel<false>,
+                         blocks, threads, 0, st, a);
+      break;
+    case ADELL_GEMM_TALL_LDS:
+      hipLaunchKernelGGL(adell_gemm_tall_lds_kernel, blocks, threads, 0, st, a, p.R, p.NB);
+      break;
+    case ADELL_GEMM_TALL_SMALL:
+      hipLaunchKernelGGL(adell_gemm_tall_small_kernel, blocks, threads, 0, st, a);
+      break;
+    default: {
+      const int skinny = p.route == ADELL_GEMM_TILE_SKINNY;
+      const dim3 grid(adell_cdiv(M, skinny ? 32 : 128), adell_cdiv(N, 128), p.splits);
+      ADELL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm: grid too large");
+      hipLaunchKernelGGL(kGemmTile[skinny][a_kc != 0][b_kc != 0], grid, threads, 0, st, a);
     }
-    ADELL_CHECK_HIP(hipGetLastError());
   }
+  ADELL_CHECK_HIP(hipGetLastError());
+  const long MN = (long)M * N;
+  if (p.reduce == ADELL_GEMM_REDUCE_FLAT)
+    hipLaunchKernelGGL(adell_gemm_reduce_flat_kernel, dim3((unsigned)std::min((MN + 255) / 256, 8192L)),
+                       threads, 0, st, a);
+  else if (p.reduce == ADELL_GEMM_REDUCE_TREE)
+    hipLaunchKernelGGL(adell_gemm_reduce_kernel, dim3((unsigned)((MN + 63) / 64)), dim3(1024), 0, st, a);
+  ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }

@@ -26,6 +26,7 @@
 // writing the four 4-k half-slots of its rows -- the transpose costs no extra pass.
 // Skinny problems split K (deterministic: slabs + fixed-order fold with bias / residual).
 #include "common.h"
+#include <algorithm>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -501,20 +502,6 @@ __global__ __launch_bounds__(G == 16 ? 1024 : 256) void adell_gemm_f16x3_fold_ke
   }
 }
 
-template <int V>
-static void adell_gemm_f16x3_fold(const GemmHArgs& a, hipStream_t st) {
-  const long units = ((long)a.M * a.N + V - 1) / V;
-  if (a.splits >= 32)
-    hipLaunchKernelGGL((adell_gemm_f16x3_fold_kernel<V, 16>), dim3((unsigned)((units + 63) / 64)),
-                       dim3(1024), 0, st, a);
-  else if (a.splits >= 8)
-    hipLaunchKernelGGL((adell_gemm_f16x3_fold_kernel<V, 4>), dim3((unsigned)((units + 63) / 64)),
-                       dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((adell_gemm_f16x3_fold_kernel<V, 1>), dim3((unsigned)((units + 255) / 256)),
-                       dim3(256), 0, st, a);
-}
-
 // absmax (float bits, atomicMax into a zero-initialised word) of n floats
 __global__ __launch_bounds__(256) void adell_absmax_f32_kernel(const float* __restrict__ x, long n,
                                                                unsigned* __restrict__ out) {
@@ -542,22 +529,38 @@ __global__ __launch_bounds__(256) void adell_absmax_f32_kernel(const float* __re
 }
 
 // the streaming kernel for many-row Linear layers (gemm_rows.hip)
-bool adell_gemm_rows_ok(int M, int N, int K, const float* A, long lda, int a_kc, const float* B, long ldb,
-                        int act, bool epi, bool dact);
-long adell_gemm_rows_workspace_floats(int M, int N, int K);
-int adell_gemm_rows_run(int M, int N, int K, const float* A, long lda, const float* B, long ldb, int b_kc,
-                        float* C, long ldc, const float* bias, const float* residual, long ldr,
-                        float* workspace, hipStream_t st, int act, float act_p, float* act_out,
-                        const float* dact_in);
+int adell_gemm_rows_run(const AdellGemmHPlan& p, int M, int N, int K, const float* A, long lda,
+                        const float* B, long ldb, int b_kc, float* C, long ldc, const float* bias,
+                        const float* residual, long ldr, float* workspace, hipStream_t st, float act_p,
+                        float* act_out);
 
-namespace {
-
-struct GemmHPlan {
-  int splits, stages_per_split;
-};
-
-GemmHPlan gemm_h_plan(int M, int N, int K) {
-  GemmHPlan p;
+// The launch plan of the f16x3 family: every route condition of adell_gemm_f16x3(_act) is written here
+// (and, for the streaming kernel, in adell_gemm_rows_plan) and nowhere else. Routes, `aligned` bits
+// and the out[] layout: adell_gemm_plan, include/adell_hip.h.
+AdellGemmHPlan adell_gemm_h_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb, int aligned,
+                                 int epilogue) {
+  AdellGemmHPlan p = {};
+  p.route = ADELL_GEMM_H_REFUSED;
+  p.epi = epilogue;
+  p.cu = adell_cu_count();
+  // the streaming regime: >= 32 on both output sides and >= 64 k rows along M or K, where this family
+  // wins below the callers' 64 x 64 size rule too (524 288 x 32 x 128: 178 -> 66 us on the rows
+  // kernel; its dW 188 -> 103 us)
+  p.many_rows = std::min(M, N) >= 32 && std::max(M, K) >= 65536;
+  // 16-byte aligned operands, whole 16-byte groups along each operand's contiguous axis
+  const bool ok = (aligned & ADELL_GEMM_ALIGNED_A) && (aligned & ADELL_GEMM_ALIGNED_B) && !((lda | ldb) & 3) &&
+                  !(K & 3) && (a_kc || !(M & 3)) && (b_kc || !(N & 3));
+  if (ok && adell_gemm_rows_plan(M, N, K, a_kc, b_kc, lda, ldb, aligned, epilogue, &p)) {
+    p.route = ADELL_GEMM_H_ROWS;
+    return p;
+  }
+  // the tiles. A refused plan keeps their geometry -- what the shape would launch with operands that
+  // qualify --, so the shape-only workspace query has room whatever the operands turn out to be
+  // wide epilogue: the tile leaves through LDS in 16-byte rows; the only one with an activation
+  const int out16 = ADELL_GEMM_ALIGNED_C | ADELL_GEMM_ALIGNED_BIAS | ADELL_GEMM_ALIGNED_RESIDUAL |
+                    ADELL_GEMM_ALIGNED_WORKSPACE;
+  p.wide = N % 4 == 0 && (aligned & out16) == out16;
+  if (ok && (p.wide || epilogue == ADELL_GEMM_EPI_NONE)) p.route = ADELL_GEMM_H_TILE;
   const long tiles = (long)adell_cdiv(M, BM) * adell_cdiv(N, BN);
   const int stages = adell_cdiv(K, BK);
   // two resident blocks per CU, and never one block more than that: 3 tiles x 171 shares = 513 blocks
@@ -570,22 +573,15 @@ GemmHPlan gemm_h_plan(int M, int N, int K) {
   if (s < 1) s = 1;
   p.stages_per_split = adell_cdiv(stages, (int)s);
   p.splits = adell_cdiv(stages, p.stages_per_split);
+  p.blocks = tiles * p.splits;
+  if (p.splits > 1) {
+    // the fold: 16-byte pieces when the rows and the slabs allow; thread groups by the slab count
+    p.fold_v = (N % 4 == 0 && (aligned & ADELL_GEMM_ALIGNED_WORKSPACE)) ? 4 : 1;
+    p.fold_s = p.splits >= 32 ? 16 : p.splits >= 8 ? 4 : 1;
+    p.workspace = (long)p.splits * M * N;
+  }
   return p;
 }
-
-bool gemm_h_ok(int M, int N, int K, const float* A, long lda, int a_kc, const float* B, long ldb,
-               int b_kc) {
-  if (M <= 0 || N <= 0 || K <= 0) return false;
-  if (((uintptr_t)A | (uintptr_t)B) & 15) return false;
-  if ((lda | ldb) & 3) return false;
-  // whole 16-byte groups along each operand's contiguous axis
-  if (K & 3) return (false);
-  if (!a_kc && (M & 3)) return false;
-  if (!b_kc && (N & 3)) return false;
-  return true;
-}
-
-}  // namespace
 
 // absmax of n floats as float bits into *out (zero-initialised by the caller): the operand scale
 // words of adell_gemm_f16x3.
@@ -601,25 +597,29 @@ extern "C" int adell_absmax_f32(const float* x, long n, uint32_t* out, void* str
   return ADELL_OK;
 }
 
-// 1 when adell_gemm_f16x3 takes the problem (16-byte aligned operands, leading dimensions and K
-// multiples of 4, outer-contiguous operands with a multiple-of-4 outer extent).
-extern "C" int adell_gemm_f16x3_applicable(int M, int N, int K, const float* A, long lda, int a_kc,
-                                           const float* B, long ldb, int b_kc) {
-  return gemm_h_ok(M, N, K, A, lda, a_kc, B, ldb, b_kc) ? 1 : 0;
-}
-
+// the layout and the epilogue pick the route at launch (a dact_in call leaves the streaming kernel for
+// the tiles): room for any of them
 extern "C" long adell_gemm_f16x3_workspace_floats(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const GemmHPlan p = gemm_h_plan(M, N, K);
-  long need = p.splits > 1 ? (long)p.splits * M * N : 0;
-  // the streaming kernel packs its weight operand into the workspace (shape-eligible problems only;
-  // the pointer conditions are checked at the call)
-  if (adell_gemm_rows_ok(M, N, K, nullptr, 0, 1, nullptr, 0, ADELL_ACT_GELU, false, false)) {
-    const long rows = adell_gemm_rows_workspace_floats(M, N, K);
-    need = need > rows ? need : rows;
-  }
+  long need = 0;
+  for (int l = 0; l < 4; ++l)
+    for (int epi : {ADELL_GEMM_EPI_NONE, ADELL_GEMM_EPI_DACT})
+      need = std::max(need, adell_gemm_h_plan(M, N, K, l >> 1, l & 1, (l >> 1) ? K : M, (l & 1) ? K : N,
+                                              ADELL_GEMM_ALIGNED_ALL, epi).workspace);
   return need;
 }
+
+using GemmHLaunch = int (*)(dim3, dim3, size_t, hipStream_t, const GemmHArgs&);
+#define GEMM_H_TILE(akc, bkc)                                          \
+  {adell_launch<adell_gemm_f16x3_kernel<akc, bkc, false>, GemmHArgs>, \
+   adell_launch<adell_gemm_f16x3_kernel<akc, bkc, true>, GemmHArgs>}
+// [a_kc][b_kc][wide]
+static const GemmHLaunch kGemmHTile[2][2][2] = {{GEMM_H_TILE(false, false), GEMM_H_TILE(false, true)},
+                                                {GEMM_H_TILE(true, false), GEMM_H_TILE(true, true)}};
+using GemmHFold = void (*)(GemmHArgs);
+#define GEMM_H_FOLD(V) \
+  {adell_gemm_f16x3_fold_kernel<V, 1>, adell_gemm_f16x3_fold_kernel<V, 4>, adell_gemm_f16x3_fold_kernel<V, 16>}
+static const GemmHFold kGemmHFold[2][3] = {GEMM_H_FOLD(1), GEMM_H_FOLD(4)};   // [width 4][S = 1, 4, 16]
 
 // Same contract as adell_gemm_f32 + a_absmax / b_absmax: both NULL (operand scales chosen per block
 // and 64-k stage inside the kernel), or device words holding the float bits of the absmax of the
@@ -636,16 +636,25 @@ static int gemm_h_run(int M, int N, int K, const float* A, long lda, int a_kc,
                 "gemm_f16x3: give both absmax words or neither");
   ADELL_REQUIRE(lda >= (a_kc ? K : M) && ldb >= (b_kc ? K : N) && ldc >= N, "gemm_f16x3: bad strides");
   ADELL_REQUIRE(!residual || ldr >= N, "gemm_f16x3: bad residual stride");
-  if (!gemm_h_ok(M, N, K, A, lda, a_kc, B, ldb, b_kc)) {
-    adell_set_error("gemm_f16x3: operands need 16-byte alignment, leading dimensions / K multiples of 4");
+  const int aligned = (adell_aligned16(A) ? ADELL_GEMM_ALIGNED_A : 0) |
+                      (adell_aligned16(B) ? ADELL_GEMM_ALIGNED_B : 0) |
+                      (adell_aligned16(C) && ldc % 4 == 0 ? ADELL_GEMM_ALIGNED_C : 0) |
+                      (adell_aligned16(bias) ? ADELL_GEMM_ALIGNED_BIAS : 0) |
+                      (adell_aligned16(residual) && (!residual || ldr % 4 == 0) ? ADELL_GEMM_ALIGNED_RESIDUAL : 0) |
+                      (adell_aligned16(workspace) ? ADELL_GEMM_ALIGNED_WORKSPACE : 0);
+  const int epilogue = dact_in ? ADELL_GEMM_EPI_DACT : !act_out ? ADELL_GEMM_EPI_NONE
+                       : act == ADELL_ACT_GELU ? ADELL_GEMM_EPI_ACT_GELU : ADELL_GEMM_EPI_ACT;
+  const AdellGemmHPlan p = adell_gemm_h_plan(M, N, K, a_kc, b_kc, lda, ldb, aligned, epilogue);
+  if (p.route == ADELL_GEMM_H_REFUSED) {
+    adell_set_error("gemm_f16x3: operands need 16-byte alignment, leading dimensions / K multiples of 4 "
+                    "(an activation epilogue: N and every output-side operand too)");
     return ADELL_E_UNSUPPORTED;
   }
-  if (workspace && (((uintptr_t)workspace) & 15) == 0 && (((uintptr_t)C) & 3) == 0 &&
-      adell_gemm_rows_ok(M, N, K, A, lda, a_kc, B, ldb, act, act_out || dact_in, dact_in != nullptr))
-    return adell_gemm_rows_run(M, N, K, A, lda, B, ldb, b_kc, C, ldc, bias, residual, ldr, workspace,
-                               (hipStream_t)stream, act, act_p, act_out, dact_in);
-  const GemmHPlan p = gemm_h_plan(M, N, K);
-  ADELL_REQUIRE(p.splits == 1 || workspace, "gemm_f16x3: workspace required for this shape");
+  ADELL_REQUIRE(p.workspace == 0 || workspace, "gemm_f16x3: workspace required for this shape");
+  hipStream_t st = (hipStream_t)stream;
+  if (p.route == ADELL_GEMM_H_ROWS)
+    return adell_gemm_rows_run(p, M, N, K, A, lda, B, ldb, b_kc, C, ldc, bias, residual, ldr, workspace, st,
+                               act_p, act_out);
   GemmHArgs a;
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.residual = residual; a.slab = workspace;
   a.amaxA = a_absmax; a.amaxB = b_absmax;
@@ -654,40 +663,17 @@ static int gemm_h_run(int M, int N, int K, const float* A, long lda, int a_kc,
   a.splits = p.splits;
   a.stages_per_split = p.stages_per_split;
   a.act = act; a.act_p = act_p; a.act_out = act_out; a.dact_in = dact_in;
-  const bool epi = act_out || dact_in;
-  hipStream_t st = (hipStream_t)stream;
   dim3 grid(adell_cdiv(M, BM), adell_cdiv(N, BN), p.splits);
   ADELL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "gemm_f16x3: grid too large");
   constexpr size_t kLds = 2 * kTileBytes + 8 * sizeof(float);
-  const dim3 block(256);
-  int rc;
-  const bool wide = N % 4 == 0 && ldc % 4 == 0 && (!residual || ldr % 4 == 0) &&
-                    ((((uintptr_t)C) | ((uintptr_t)bias) | ((uintptr_t)residual) |
-                      ((uintptr_t)workspace)) & 15) == 0;
-  ADELL_REQUIRE(wide || !epi, "gemm_f16x3_act: operands do not qualify for the wide epilogue");
-  if (wide) {
-    if (a_kc && b_kc)
-      rc = adell_launch<adell_gemm_f16x3_kernel<true, true, true>>(grid, block, kLds, st, a);
-    else if (a_kc && !b_kc)
-      rc = adell_launch<adell_gemm_f16x3_kernel<true, false, true>>(grid, block, kLds, st, a);
-    else if (!a_kc && !b_kc)
-      rc = adell_launch<adell_gemm_f16x3_kernel<false, false, true>>(grid, block, kLds, st, a);
-    else
-      rc = adell_launch<adell_gemm_f16x3_kernel<false, true, true>>(grid, block, kLds, st, a);
-  } else if (a_kc && b_kc)
-    rc = adell_launch<adell_gemm_f16x3_kernel<true, true>>(grid, block, kLds, st, a);
-  else if (a_kc && !b_kc)
-    rc = adell_launch<adell_gemm_f16x3_kernel<true, false>>(grid, block, kLds, st, a);
-  else if (!a_kc && !b_kc)
-    rc = adell_launch<adell_gemm_f16x3_kernel<false, false>>(grid, block, kLds, st, a);
-  else
-    rc = adell_launch<adell_gemm_f16x3_kernel<false, true>>(grid, block, kLds, st, a);
+  const int rc = kGemmHTile[a_kc != 0][b_kc != 0][p.wide](grid, dim3(256), kLds, st, a);
   if (rc != ADELL_OK) return rc;
   if (p.splits > 1) {
-    if (N % 4 == 0 && (((uintptr_t)a.slab) & 15) == 0)
-      adell_gemm_f16x3_fold<4>(a, st);
-    else
-      adell_gemm_f16x3_fold<1>(a, st);
+    // a block of 1024 (S = 16) or 256 threads: S groups of threads, each thread fold_v outputs
+    const int threads = p.fold_s == 16 ? 1024 : 256;
+    const long units = ((long)M * N + p.fold_v - 1) / p.fold_v, per_block = threads / p.fold_s;
+    hipLaunchKernelGGL(kGemmHFold[p.fold_v == 4][(p.fold_s > 1) + (p.fold_s > 4)],
+                       dim3((unsigned)((units + per_block - 1) / per_block)), dim3(threads), 0, st, a);
     ADELL_CHECK_HIP(hipGetLastError());
   }
   return ADELL_OK;

@@ -1,5 +1,5 @@
 // Streaming form of the f16x3 GEMM (gemm_f16x3.hip) for Linear layers over MANY rows with a SMALL
-// weight: C[M][N] = A[M][K] W (+ bias) (+ residual) (x act' / + act output), A K-contiguous, M in the
+// weight: C[M][N] = A[M][K] W (+ bias) (+ residual) (+ act output), A K-contiguous, M in the
 // tens of thousands to millions, K x N a few 10^4 .. 10^6 -- ConvNeXt's point-wise MLP
 // (res_blocks.py:588-604: 262 144 x 96 -> 384 -> 96 at BASELINE config 4), the token-wise Linear
 // layers of ViT / SWIN (linear_blocks.py:85-103, vit.py:531-536) and their backward-data products.
@@ -57,7 +57,6 @@ struct RowsArgs {
   const float* bias;
   const float* residual;
   float* act_out;
-  const float* dact_in;
   int M, N, K;
   long lda, ldc, ldr;
   int nslices, kstages, tiles, tiles_per_block;
@@ -183,8 +182,8 @@ __global__ __launch_bounds__(256) void adell_gemm_rows_pack_kernel(const float* 
 }
 
 // ---- the streaming kernel -------------------------------------------------------------------------
-// EPI 0: C = acc + bias (+ residual);  1: also act_out = act(C);  2: C = (acc + bias ...) * act'(dact_in).
-// ACT: the activation of EPI 1 / 2 (compile time: one inlined activation at the 64 store sites).
+// EPI 0: C = acc + bias (+ residual);  1: also act_out = act(C).
+// ACT: the activation of EPI 1 (compile time: one inlined activation at the 64 store sites).
 template <int EPI, int ACT>
 __global__ __launch_bounds__(64 * (RB_CW + 4), (RB_CW + 4) / 4) void adell_gemm_rows_f16x3_kernel(RowsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -359,7 +358,6 @@ __global__ __launch_bounds__(64 * (RB_CW + 4), (RB_CW + 4) / 4) void adell_gemm_
     const bool full = rw + 32 <= a.M;
     float* cb = a.C + (size_t)rw * a.ldc + n0;
     const float* rb = a.residual ? a.residual + (size_t)rw * a.ldr + n0 : nullptr;
-    const float* db = EPI == 2 ? a.dact_in + (size_t)rw * a.ldc + n0 : nullptr;
     float* ob = EPI == 1 ? a.act_out + (size_t)rw * a.ldc + n0 : nullptr;
     const unsigned ldc = (unsigned)a.ldc, ldr = (unsigned)a.ldr;
     // Address of (register r, tile j) = [uniform row pointer of r] + [ONE per-lane element offset] + 32 j:
@@ -386,16 +384,6 @@ __global__ __launch_bounds__(64 * (RB_CW + 4), (RB_CW + 4) / 4) void adell_gemm_
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[j][r] += t[r];
         }
-        if constexpr (EPI == 2) {
-          float t[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int ru = (r & 3) + 8 * (r >> 2);
-            t[r] = (full || ru < rows_left) ? (db + (size_t)ru * ldc + 32 * j)[lo_c] : 0.f;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[j][r] *= adell_act_grad(ACT, t[r], a.act_p);
-        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ru = (r & 3) + 8 * (r >> 2);            // wave-uniform part of the row
@@ -410,66 +398,59 @@ __global__ __launch_bounds__(64 * (RB_CW + 4), (RB_CW + 4) / 4) void adell_gemm_
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-// Whether the streaming kernel takes this problem (gemm_f16x3.hip asks before it plans its tiles):
-// A K-contiguous, K a multiple of 32, many rows, a weight small enough to pack per call, and an
-// epilogue it has an instance of (no activation, or GELU for the activation pair).
-bool adell_gemm_rows_ok(int M, int N, int K, const float* A, long lda, int a_kc, const float* B, long ldb,
-                        int act, bool epi, bool dact) {
+// Whether the streaming kernel takes this problem, and its launch geometry (adell_gemm_h_plan asks
+// before it plans its tiles): A K-contiguous, K a multiple of 32, many rows, a weight small enough to
+// pack per call into a 16-byte aligned workspace, 16-byte rows of both operands, and an epilogue it
+// has an instance of (none, or the GELU pair).
+bool adell_gemm_rows_plan(int M, int N, int K, int a_kc, int b_kc, long lda, long ldb, int aligned,
+                          int epilogue, AdellGemmHPlan* p) {
   if (g_adell_tune.gemm_norows) return false;
   if (!a_kc || (K % RB_K) != 0 || K > 8192 || N < 32 || M < 2048) return false;
   if ((long)K * N > (4L << 20)) return false;                 // pack per call: <= 16 MB of weight
-  if ((((uintptr_t)A) & 15) || (lda & 3) || (ldb & 3) || (((uintptr_t)B) & 15)) return false;
-  if (epi && act != ADELL_ACT_GELU) return false;
-  // (the act' epilogue -- C * act'(saved) -- reads a second [M][N] tensor with 4-byte loads from the
+  const int need = ADELL_GEMM_ALIGNED_A | ADELL_GEMM_ALIGNED_B | ADELL_GEMM_ALIGNED_WORKSPACE;
+  if ((aligned & need) != need || (lda & 3) || (ldb & 3)) return false;
+  if (epilogue == ADELL_GEMM_EPI_ACT) return false;
+  // the act' epilogue -- C * act'(saved) -- would read a second [M][N] tensor with 4-byte loads from the
   // accumulator layout: measured slower than the tile kernel's LDS-transposed epilogue, 591 vs 473 us
-  // at 262 144 x 96 -> 384; the instance stays for completeness, the dispatch does not pick it)
-  if (dact) return false;
+  // at 262 144 x 96 -> 384, so there is no such instance and every dact_in call runs on the tiles
+  if (epilogue == ADELL_GEMM_EPI_DACT) return false;
   // enough tiles for the persistent grid: at least one per CU
-  const long tiles = (long)adell_cdiv(M, RB_M) * adell_cdiv(N, RB_N);
-  return tiles >= (long)adell_cu_count();
-}
-
-// floats of workspace: the packed image + the column scales
-long adell_gemm_rows_workspace_floats(int M, int N, int K) {
-  (void)M;
-  const long slices = adell_cdiv(N, RB_N);
-  return slices * RB_N * (long)K + slices * RB_N;
-}
-
-int adell_gemm_rows_run(int M, int N, int K, const float* A, long lda, const float* B, long ldb, int b_kc,
-                        float* C, long ldc, const float* bias, const float* residual, long ldr,
-                        float* workspace, hipStream_t st, int act, float act_p, float* act_out,
-                        const float* dact_in) {
-  ADELL_REQUIRE(workspace && (((uintptr_t)workspace) & 15) == 0, "gemm_rows: workspace required (16-byte aligned)");
-  RowsArgs a;
   const int slices = adell_cdiv(N, RB_N);
-  char* img = reinterpret_cast<char*>(workspace);
-  float* bscale = workspace + (size_t)slices * RB_N * K;
+  const long tiles = (long)adell_cdiv(M, RB_M) * slices;
+  if (tiles < (long)adell_cu_count()) return false;
+  p->slices = slices;
   // rows per pack block: the tile [R][K + 4] fp32 stays within 64 KB of LDS (K <= 8192: R >= 1);
   // outer-contiguous weights want many rows per block (their rows are the contiguous axis)
-  int R = b_kc ? 8 : 32;
-  while (R > 1 && (size_t)R * (K + 4) * 4 > 64 * 1024) R >>= 1;
-  const size_t plds = (size_t)R * (K + 4) * 4 + 32 * sizeof(unsigned);
-  const int rc = adell_launch<adell_gemm_rows_pack_kernel>(dim3((unsigned)(slices * RB_N / R)), dim3(256),
-                                                           plds, st, B, ldb, b_kc, N, K, R, img, bscale);
+  p->R = b_kc ? 8 : 32;
+  while (p->R > 1 && (size_t)p->R * (K + 4) * 4 > 64 * 1024) p->R >>= 1;
+  p->tiles_per_block = (int)((tiles + adell_cu_count() - 1) / adell_cu_count());
+  p->blocks = (tiles + p->tiles_per_block - 1) / p->tiles_per_block;
+  p->workspace = (long)p->slices * RB_N * ((long)K + 1);      // the packed image + the column scales
+  return true;
+}
+
+int adell_gemm_rows_run(const AdellGemmHPlan& p, int M, int N, int K, const float* A, long lda,
+                        const float* B, long ldb, int b_kc, float* C, long ldc, const float* bias,
+                        const float* residual, long ldr, float* workspace, hipStream_t st, float act_p,
+                        float* act_out) {
+  RowsArgs a;
+  char* img = reinterpret_cast<char*>(workspace);
+  float* bscale = workspace + (size_t)p.slices * RB_N * K;
+  const size_t plds = (size_t)p.R * (K + 4) * 4 + 32 * sizeof(unsigned);
+  const int rc = adell_launch<adell_gemm_rows_pack_kernel>(dim3((unsigned)(p.slices * RB_N / p.R)), dim3(256),
+                                                           plds, st, B, ldb, b_kc, N, K, p.R, img, bscale);
   if (rc != ADELL_OK) return rc;
   a.A = A; a.Bimg = img; a.bscale = bscale; a.C = C; a.bias = bias; a.residual = residual;
-  a.act_out = act_out; a.dact_in = dact_in;
+  a.act_out = act_out;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr;
-  a.nslices = slices; a.kstages = K / RB_K;
-  const long tiles = (long)adell_cdiv(M, RB_M) * slices;
+  a.nslices = p.slices; a.kstages = K / RB_K;
+  const long tiles = (long)adell_cdiv(M, RB_M) * p.slices;
   ADELL_REQUIRE(tiles < 0x7fffffffL, "gemm_rows: too many tiles");
   a.tiles = (int)tiles;
-  int blocks = adell_cu_count();
-  if (blocks > tiles) blocks = (int)tiles;
-  a.tiles_per_block = (int)((tiles + blocks - 1) / blocks);
-  blocks = (int)((tiles + a.tiles_per_block - 1) / a.tiles_per_block);
+  a.tiles_per_block = p.tiles_per_block;
   a.act_p = act_p;
-  const dim3 grid((unsigned)blocks), block(64 * (RB_CW + 4));
-  (void)act;
-  if (act_out)
+  const dim3 grid((unsigned)p.blocks), block(64 * (RB_CW + 4));
+  if (p.epi == ADELL_GEMM_EPI_ACT_GELU)
     return adell_launch<adell_gemm_rows_f16x3_kernel<1, ADELL_ACT_GELU>>(grid, block, RB_LDS, st, a);
-  if (dact_in)
-    return adell_launch<adell_gemm_rows_f16x3_kernel<2, ADELL_ACT_GELU>>(grid, block, RB_LDS, st, a);
   return adell_launch<adell_gemm_rows_f16x3_kernel<0, ADELL_ACT_IDENTITY>>(grid, block, RB_LDS, st, a);
 }

@@ -7,6 +7,7 @@ are the only places that care about strides. Everything is enqueued on
 """
 import collections
 import ctypes
+import functools
 import math
 import os
 
@@ -2272,23 +2273,26 @@ def winattn_bwd(q, k, v, v_ts, v_hs, rel, mask, o, dout, lse, W, H, T, A, Dv, sc
     return ds
 
 
+def _gemm_launch(kernel, ws_query, call, M, N, K, a_kc, b_kc, device, mn_tensors, tag=""):
+    """Workspace by the family's shape-only query, then ``call(workspace)`` under the kernel timer
+    (algorithmic bytes: each operand once and ``mn_tensors`` tensors of [M, N])."""
+    nws = ws_query(M, N, K)
+    ws = _workspace(nws * 4, device) if nws else None
+    _timed(kernel, 2.0 * M * N * K, lambda: check(call(_ptr(ws))),
+           lambda: f"{M}x{N}x{K} {'kc' if a_kc else 'outer'}/{'kc' if b_kc else 'outer'}{tag}",
+           4.0 * (M * K + K * N + M * N * mn_tensors))
+
+
 def gemm(M, N, K, A, lda, a_kc, B, ldb, b_kc, out=None, bias=None, residual=None):
     """out[M, N] = A x B (+ bias) (+ residual) on the fp32 MFMA GEMM (csrc/gemm.hip).
     a_kc: A(m,k) = A[m*lda + k] else A[k*lda + m]; b_kc: B(k,n) = B[n*ldb + k] else B[k*ldb + n]."""
     _require_cuda(A, B, bias, residual)
     if out is None:
         out = torch.empty((M, N), device=A.device, dtype=torch.float32)
-    nws = _lib.lib().adell_gemm_f32_workspace_floats(M, N, K)
-    ws = _workspace(nws * 4, A.device) if nws else None
-    ldr = 0 if residual is None else N
-
-    def run():
-        check(_lib.lib().adell_gemm_f32(M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb, int(b_kc),
-                                        _ptr(out), N, _ptr(bias), _ptr(residual), ldr, _ptr(ws),
-                                        _stream()))
-    _timed("adell_gemm_f32_kernel", 2.0 * M * N * K, run,
-           lambda: f"{M}x{N}x{K} {'kc' if a_kc else 'outer'}/{'kc' if b_kc else 'outer'}",
-           4.0 * (M * K + K * N + M * N * (2 if residual is not None else 1)))
+    h, ldr = _lib.lib(), 0 if residual is None else N
+    _gemm_launch("adell_gemm_f32_kernel", h.adell_gemm_f32_workspace_floats, lambda ws: h.adell_gemm_f32(
+        M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb, int(b_kc), _ptr(out), N, _ptr(bias), _ptr(residual),
+        ldr, ws, _stream()), M, N, K, a_kc, b_kc, A.device, 1 + (residual is not None))
     return out
 
 
@@ -2302,20 +2306,54 @@ def absmax_word(x):
     return word
 
 
+# launch plans of the two GEMM families (adell_gemm_plan, include/adell_hip.h: routes and fields)
+GemmF32Plan = collections.namedtuple(
+    "GemmF32Plan", "route splits ksteps_per_split reduce chunk_rows per_thread blocks workspace")
+GemmF16x3Plan = collections.namedtuple(
+    "GemmF16x3Plan", "route epilogue slices pack_rows blocks tiles_per_block wide splits stages_per_split "
+    "fold_v fold_s workspace many_rows cu")
+GEMM_ROUTES = {"f32": ("rows_small", "tall_lds", "tall_small", "tile_skinny", "tile_square"),
+               "f16x3": ("refused", "rows", "tile")}
+GEMM_REDUCES, GEMM_EPILOGUES = ("none", "flat", "tree"), ("none", "act_gelu", "act", "dact")
+GEMM_OPERANDS = ("a", "b", "c", "bias", "residual", "workspace")
+
+
+def gemm_plan(family, M, N, K, a_kc=True, b_kc=True, lda=None, ldb=None, unaligned=(), epilogue="none"):
+    """What ``gemm`` (``family`` "f32") or ``gemm_f16x3`` / ``gemm_f16x3_act`` ("f16x3") would launch
+    under the current tuning switches. ``lda`` / ``ldb``: dense by default; ``unaligned``: the
+    GEMM_OPERANDS that are not 16-byte aligned (c / residual: or whose row stride is not a multiple of
+    4); ``epilogue``: one of GEMM_EPILOGUES. Host only: no GPU needed."""
+    out = (ctypes.c_long * 16)()
+    aligned = sum(1 << i for i, name in enumerate(GEMM_OPERANDS) if name not in unaligned)
+    check(_lib.lib().adell_gemm_plan(
+        family == "f16x3", M, N, K, bool(a_kc), bool(b_kc), (K if a_kc else M) if lda is None else lda,
+        (K if b_kc else N) if ldb is None else ldb, aligned, GEMM_EPILOGUES.index(epilogue), out))
+    if family == "f16x3":
+        return GemmF16x3Plan(GEMM_ROUTES[family][out[0]], GEMM_EPILOGUES[out[1]], *out[2:14])
+    return GemmF32Plan(GEMM_ROUTES[family][out[0]], out[1], out[2], GEMM_REDUCES[out[3]], *out[4:8])
+
+
+@functools.lru_cache(maxsize=None)
+def _gemm_f16x3_facts(M, N, K, a_kc, b_kc, lda, ldb, unaligned):
+    """(the streaming regime, the f16x3 family refuses it, the fp32 family streams it) off the two plans.
+    None of the three depends on a tuning switch, so a shape is asked once (Linear layers ask per call)."""
+    h = gemm_plan("f16x3", M, N, K, a_kc, b_kc, lda, ldb, unaligned)
+    return (bool(h.many_rows), h.route == "refused",
+            gemm_plan("f32", M, N, K, a_kc, b_kc, lda, ldb).route == "rows_small")
+
+
 def gemm_f16x3_ok(M, N, K, A, lda, a_kc, B, ldb, b_kc):
+    """Policy only (the three FLAGS entries) on top of what the plans say: not where the fp32 family
+    streams the problem (rows_small), not what the f16x3 family refuses."""
     if not FLAGS["gemm_f16x3"] or K < FLAGS["gemm_f16x3_min_k"]:
         return False
-    if min(M, N) < FLAGS["gemm_f16x3_min_mn"]:
-        # below the threshold only the streaming regime: >= 32 on both output sides and >= 64 k rows
-        # along M or K (524 288 x 32 x 128: 178 -> 66 us on the rows kernel; its dW 188 -> 103 us)
-        if FLAGS["gemm_f16x3_min_mn"] != 64 or min(M, N) < 32 or max(M, K) < 65536:
-            return False
-    # a handful of features over >= 64 k rows: the thread-per-output kernel of adell_gemm_f32
-    # (csrc/gemm.hip, rows_small) streams them; 128-wide MFMA tiles run 2 097 152 x 32 x 8 at 1.3 TB/s
-    if a_kc and K <= 64 and N <= 64 and N * K <= 512 and M >= 65536:
+    many_rows, refused, rows_small = _gemm_f16x3_facts(
+        M, N, K, bool(a_kc), bool(b_kc), lda, ldb,
+        tuple(name for name, t in (("a", A), ("b", B)) if t.data_ptr() % 16))
+    # below the default size rule only the streaming regime
+    if min(M, N) < FLAGS["gemm_f16x3_min_mn"] and (FLAGS["gemm_f16x3_min_mn"] != 64 or not many_rows):
         return False
-    return bool(_lib.lib().adell_gemm_f16x3_applicable(M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb,
-                                                       int(b_kc)))
+    return not rows_small and not refused
 
 
 def gemm_f16x3(M, N, K, A, lda, a_kc, B, ldb, b_kc, a_amax=None, b_amax=None, out=None, bias=None,
@@ -2329,18 +2367,11 @@ def gemm_f16x3(M, N, K, A, lda, a_kc, B, ldb, b_kc, a_amax=None, b_amax=None, ou
         raise _lib.AdellHipError("gemm_f16x3: both absmax words (device tensors) or neither")
     if out is None:
         out = torch.empty((M, N), device=A.device, dtype=torch.float32)
-    nws = _lib.lib().adell_gemm_f16x3_workspace_floats(M, N, K)
-    ws = _workspace(nws * 4, A.device) if nws else None
-    ldr = 0 if residual is None else N
-
-    def run():
-        check(_lib.lib().adell_gemm_f16x3(M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb, int(b_kc),
-                                          _ptr(out), N, _ptr(bias), _ptr(residual), ldr,
-                                          _ptr(a_amax), _ptr(b_amax), _ptr(ws), _stream()))
-    # algorithmic bytes: each operand and the output once (+ the residual)
-    _timed("adell_gemm_f16x3_kernel", 2.0 * M * N * K, run,
-           lambda: f"{M}x{N}x{K} {'kc' if a_kc else 'outer'}/{'kc' if b_kc else 'outer'}",
-           4.0 * (M * K + K * N + M * N * (2 if residual is not None else 1)))
+    h, ldr = _lib.lib(), 0 if residual is None else N
+    _gemm_launch("adell_gemm_f16x3_kernel", h.adell_gemm_f16x3_workspace_floats, lambda ws: h.adell_gemm_f16x3(
+        M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb, int(b_kc), _ptr(out), N, _ptr(bias), _ptr(residual),
+        ldr, _ptr(a_amax), _ptr(b_amax), ws, _stream()), M, N, K, a_kc, b_kc, A.device,
+        1 + (residual is not None))
     return out
 
 
@@ -2352,19 +2383,11 @@ def gemm_f16x3_act(M, N, K, A, lda, a_kc, B, ldb, b_kc, act, act_p=0.0, bias=Non
     _require_cuda(A, B, bias, residual, dact_in)
     out = torch.empty((M, N), device=A.device, dtype=torch.float32)
     act_out = torch.empty_like(out) if want_act else None
-    nws = _lib.lib().adell_gemm_f16x3_workspace_floats(M, N, K)
-    ws = _workspace(nws * 4, A.device) if nws else None
-    ldr = 0 if residual is None else N
-
-    def run():
-        check(_lib.lib().adell_gemm_f16x3_act(M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb,
-                                              int(b_kc), _ptr(out), N, _ptr(bias), _ptr(residual),
-                                              ldr, None, None, _ptr(ws), _lib.ACT_IDS[act],
-                                              float(act_p), _ptr(act_out), _ptr(dact_in), _stream()))
-    extra = (1 if residual is not None else 0) + (1 if want_act else 0) + (1 if dact_in is not None else 0)
-    _timed("adell_gemm_f16x3_kernel", 2.0 * M * N * K, run,
-           lambda: f"{M}x{N}x{K} {'kc' if a_kc else 'outer'}/{'kc' if b_kc else 'outer'} act",
-           4.0 * (M * K + K * N + M * N * (1 + extra)))
+    h, ldr = _lib.lib(), 0 if residual is None else N
+    _gemm_launch("adell_gemm_f16x3_kernel", h.adell_gemm_f16x3_workspace_floats, lambda ws: h.adell_gemm_f16x3_act(
+        M, N, K, _ptr(A), lda, int(a_kc), _ptr(B), ldb, int(b_kc), _ptr(out), N, _ptr(bias), _ptr(residual),
+        ldr, None, None, ws, _lib.ACT_IDS[act], float(act_p), _ptr(act_out), _ptr(dact_in), _stream()),
+        M, N, K, a_kc, b_kc, A.device, 1 + (residual is not None) + want_act + (dact_in is not None), " act")
     return out, act_out
 
 

@@ -1289,13 +1289,11 @@ int adell_gemm_f32(int M, int N, int K, const float* A, long lda, int a_kc, cons
  * MLPs (res_blocks.py:559-566), the ViT / SWIN projections (linear_blocks.py) and the projection
  * heads (res_net.py:278-324). a_absmax / b_absmax: both NULL (operand scales chosen inside the
  * kernel per block and 64-k stage), or device words with the float bits of the absmax of the A / B
- * tensors (adell_absmax_f32 into a zero-initialised word): one scale per tensor. _applicable: 1 when the
- * operands qualify (16-byte alignment; leading dimensions, K and the outer extent of an
- * outer-contiguous operand multiples of 4); otherwise the call returns ADELL_E_UNSUPPORTED and the
- * caller uses adell_gemm_f32. */
+ * tensors (adell_absmax_f32 into a zero-initialised word): one scale per tensor. Operands that do
+ * not qualify (route ADELL_GEMM_H_REFUSED of adell_gemm_plan below) make the call return
+ * ADELL_E_UNSUPPORTED; the caller asks the plan first and uses adell_gemm_f32.
+ * workspace: adell_gemm_f16x3_workspace_floats(M, N, K) floats (NULL when that is 0). */
 int adell_absmax_f32(const float* x, long n, uint32_t* out, void* stream);
-int adell_gemm_f16x3_applicable(int M, int N, int K, const float* A, long lda, int a_kc,
-                                const float* B, long ldb, int b_kc);
 long adell_gemm_f16x3_workspace_floats(int M, int N, int K);
 int adell_gemm_f16x3(int M, int N, int K, const float* A, long lda, int a_kc, const float* B,
                      long ldb, int b_kc, float* C, long ldc, const float* bias,
@@ -1313,6 +1311,77 @@ int adell_gemm_f16x3_act(int M, int N, int K, const float* A, long lda, int a_kc
                          const float* residual, long ldr, const uint32_t* a_absmax,
                          const uint32_t* b_absmax, float* workspace, int act, float act_p,
                          float* act_out, const float* dact_in, void* stream);
+/* Launch plan of a GEMM, host only (no launch, no tensor read, no device needed): what adell_gemm_f32
+ * (family ADELL_GEMM_F32) or adell_gemm_f16x3 / adell_gemm_f16x3_act (ADELL_GEMM_F16X3) would run
+ * under the current tuning switches, decided by the same function the launchers and the two
+ * *_workspace_floats queries call (those take the largest workspace over the layouts, alignments and
+ * epilogues a shape can arrive in).
+ * aligned: ADELL_GEMM_ALIGNED_* bits; set the bit of a tensor the call does not have. A, B, BIAS,
+ *   WORKSPACE: the pointer is 16-byte aligned; C, RESIDUAL: that and a leading dimension that is a
+ *   multiple of 4. The fp32 family looks at A and B only.
+ * epilogue (f16x3 family): ADELL_GEMM_EPI_NONE (adell_gemm_f16x3), _ACT_GELU / _ACT (act_out of
+ *   adell_gemm_f16x3_act with GELU / any other activation), _DACT (dact_in).
+ * fp32 routes, in the order they are tried:
+ *   ROWS_SMALL   a_kc, K <= 64, N <= 64, N K <= 512, M >= 65536: a thread per output (four when N
+ *                allows), weights in LDS: adell_gemm_rows_small_kernel<b_kc>. No workspace.
+ *   TALL_LDS     both operands outer-contiguous, K >= 16384 and K % 4 == 0, M and N powers of two up to
+ *                64 with 8 <= M N <= 512, lda == M, ldb == N, A and B 16-byte aligned: chunks of both
+ *                operands staged in LDS, one partial per block: adell_gemm_tall_lds_kernel +
+ *                adell_gemm_reduce_kernel.
+ *   TALL_SMALL   both operands outer-contiguous, K >= 16384, M <= 32, N <= 32 (whatever TALL_LDS left):
+ *                adell_gemm_tall_small_kernel + adell_gemm_reduce_kernel.
+ *   TILE_SKINNY  M <= 32: 32 x 128 MFMA tiles; TILE_SQUARE: 128 x 128 tiles
+ *                (adell_gemm_f32_kernel<.., a_kc, b_kc>). Split along k while there are fewer than 512
+ *                tiles (at least 4 k-steps of 16 per split, at most 256 k-steps, slabs up to 64 MB);
+ *                2 .. 8 splits are summed by adell_gemm_reduce_flat_kernel (REDUCE_FLAT), more by
+ *                adell_gemm_reduce_kernel (REDUCE_TREE).
+ *   out[8]: [0] route; [1] splits (tall routes: partials = blocks); [2] k-steps per split; [3]
+ *   ADELL_GEMM_REDUCE_*; [4] chunk rows, [5] outputs per thread (TALL_LDS); [6] blocks of the first
+ *   kernel; [7] workspace floats of this route.
+ * f16x3 routes, in the order they are tried:
+ *   REFUSED      A or B not 16-byte aligned, lda, ldb or K not a multiple of 4, an outer-contiguous
+ *                operand whose outer extent (M, N) is not; or an activation epilogue without the wide
+ *                epilogue's conditions. The fields are those of TILE: what the shape would launch.
+ *   ROWS         a_kc, K % 32 == 0, K <= 8192, N >= 32, M >= 2048, K N <= 4 Mi, a 16-byte aligned
+ *                workspace, epilogue NONE or ACT_GELU (never DACT: measured slower than the tiles), not
+ *                under the tuning switch "gemm_norows", and at least one (256-row tile, 128-column
+ *                slice) pair per CU: adell_gemm_rows_pack_kernel + adell_gemm_rows_f16x3_kernel.
+ *   TILE         everything else: 128 x 128 tiles, adell_gemm_f16x3_kernel<a_kc, b_kc, wide>. wide: N % 4
+ *                == 0 and C, bias, residual, workspace aligned (required by an activation epilogue).
+ *                Split along K while there are fewer than 512 tiles (at least 4 stages of 64 per
+ *                split, slabs up to 64 MB) and folded by adell_gemm_f16x3_fold_kernel<V, S>: V = 4 when
+ *                N % 4 == 0 and the workspace is aligned, else 1; S = 1, 4 (>= 8 splits), 16 (>= 32).
+ *   out[14]: [0] route; [1] epilogue; ROWS: [2] column slices, [3] pack rows per block, [4] blocks,
+ *   [5] tiles per block; TILE: [4] blocks, [6] wide, [7] splits, [8] stages per split, [9] fold V,
+ *   [10] fold S (0 without a fold); [11] workspace floats of this route; [12] the streaming regime
+ *   (min(M, N) >= 32 and max(M, K) >= 65536: this family pays off below the callers' size rule too);
+ *   [13] the CU count ROWS compares its tile count against. */
+#define ADELL_GEMM_F32 0
+#define ADELL_GEMM_F16X3 1
+#define ADELL_GEMM_ROWS_SMALL 0
+#define ADELL_GEMM_TALL_LDS 1
+#define ADELL_GEMM_TALL_SMALL 2
+#define ADELL_GEMM_TILE_SKINNY 3
+#define ADELL_GEMM_TILE_SQUARE 4
+#define ADELL_GEMM_REDUCE_NONE 0
+#define ADELL_GEMM_REDUCE_FLAT 1
+#define ADELL_GEMM_REDUCE_TREE 2
+#define ADELL_GEMM_H_REFUSED 0
+#define ADELL_GEMM_H_ROWS 1
+#define ADELL_GEMM_H_TILE 2
+#define ADELL_GEMM_EPI_NONE 0
+#define ADELL_GEMM_EPI_ACT_GELU 1
+#define ADELL_GEMM_EPI_ACT 2
+#define ADELL_GEMM_EPI_DACT 3
+#define ADELL_GEMM_ALIGNED_A 1
+#define ADELL_GEMM_ALIGNED_B 2
+#define ADELL_GEMM_ALIGNED_C 4
+#define ADELL_GEMM_ALIGNED_BIAS 8
+#define ADELL_GEMM_ALIGNED_RESIDUAL 16
+#define ADELL_GEMM_ALIGNED_WORKSPACE 32
+#define ADELL_GEMM_ALIGNED_ALL 63
+int adell_gemm_plan(int family, int M, int N, int K, int a_kc, int b_kc, long lda, long ldb,
+                    int aligned, int epilogue, long* out);
 
 /* Element-wise segmentation losses beyond the fused binary dice + focal pair, on probabilities
  * p[B][V][C] (NDHWC; C = 1 for the binary family) against targets of the same layout:

@@ -1,10 +1,11 @@
-"""f16x3 GEMM (csrc/gemm_f16x3.hip): the three operand layouts of a Linear layer (forward X W^T,
-backward-data dY W, backward-weight dY^T X), ragged tiles, split-K, bias / residual epilogue and
-extreme operand scales, against fp64; HF.linear takes it when ops.FLAGS["gemm_f16x3"] is set (the
-default, for outputs of at least 64 x 64: ops.FLAGS["gemm_f16x3_min_mn"]) and falls back to the
-fp32-MFMA GEMM when the operands do not qualify."""
+"""f16x3 GEMM (csrc/gemm_f16x3.hip): split-K determinism, extreme operand scales and the streaming
+kernel against fp64 (every route in every operand layout: tests/test_gemm_plans.py); HF.linear takes
+it when ops.FLAGS["gemm_f16x3"] is set (the default, for outputs of at least 64 x 64:
+ops.FLAGS["gemm_f16x3_min_mn"]) and falls back to the fp32-MFMA GEMM when the operands do not qualify."""
 import pytest
 import torch
+
+import test_gemm_plans as table
 
 pytestmark = pytest.mark.gpu
 
@@ -22,31 +23,16 @@ def _rel(a, b):
     return float((a.detach().cpu().double() - b).abs().max() / b.abs().max())
 
 
-@pytest.mark.parametrize("M,N,K", [(128, 128, 32), (256, 384, 96), (100, 36, 64), (4, 8, 4),
-                                   (1000, 132, 260), (64, 3072, 768), (4096, 96, 384)])
+@pytest.mark.parametrize("M,N,K", [(c.M, c.N, c.K) for c in table.CASES
+                                   if c.family == "f16x3" and "former" in c.opt])
 @pytest.mark.parametrize("a_kc,b_kc", [(True, True), (True, False), (False, False), (False, True)])
 @pytest.mark.parametrize("words", [False, True])
 def test_layouts_against_fp64(cuda, M, N, K, a_kc, b_kc, words):
-    from adell_mri_amd import ops
-
-    g = torch.Generator().manual_seed(M + N + K)
-    A = torch.randn(M, K, generator=g)
-    B = torch.randn(K, N, generator=g)
-    bias = torch.randn(N, generator=g)
-    res = torch.randn(M, N, generator=g)
-    want = A.double() @ B.double() + bias.double() + res.double()
-    Ad = (A if a_kc else A.t()).contiguous().to(cuda)
-    Bd = (B.t() if b_kc else B).contiguous().to(cuda)
-    lda, ldb = (K if a_kc else M), (K if b_kc else N)
-    if not ops.gemm_f16x3_ok(M, N, K, Ad, lda, a_kc, Bd, ldb, b_kc):
-        assert (not a_kc and M % 4) or (not b_kc and N % 4) or K % 4
-        pytest.skip("operands do not qualify (checked: the reason is an extent that is not a multiple of 4)")
-    # operand scales: chosen per block and stage inside the kernel, or per tensor from absmax words
-    wa, wb = (ops.absmax_word(Ad), ops.absmax_word(Bd)) if words else (None, None)
-    got = ops.gemm_f16x3(M, N, K, Ad, lda, a_kc, Bd, ldb, b_kc, wa, wb, bias=bias.to(cuda),
-                         residual=res.to(cuda))
-    scale = (A.double().abs() @ B.double().abs()).max()
-    assert float((got.cpu().double() - want).abs().max() / scale) < 2e-6
+    """One layout and one operand-scale setting (chosen per block and stage inside the kernel, or per
+    tensor from absmax words) of the shape's row in the case table of tests/test_gemm_plans.py: the
+    route the row pins, then the product with bias and residual against fp64 at the family's bar."""
+    layout = next(k for k, v in table.LAYOUTS.items() if v == (a_kc, b_kc))
+    table.check_f16x3_case(table.case_of("f16x3", M, N, K), cuda, [layout], (words,))
 
 
 def test_split_k_is_deterministic_and_exact_enough(cuda):
@@ -270,8 +256,9 @@ def test_rows_kernel_against_fp64_and_the_tile_kernel(cuda, M, N, K, b_kc):
 
 
 def test_rows_kernel_activation_pair(cuda):
-    """Linear -> GELU with both tensors from one launch, and the backward of the pair (C * act'(saved))
-    on the streaming kernel, against torch fp64 and the tile kernel's epilogue."""
+    """Linear -> GELU with both tensors from one launch of the streaming kernel, against torch fp64 and
+    the tile kernel's epilogue; the backward of the pair (C * act'(saved)) on the same shape, which
+    every plan sends to the tile kernel (the streaming kernel has no such instance)."""
     from adell_mri_amd import _lib, ops
 
     M, K, N = 50000, 96, 384
