@@ -249,6 +249,12 @@ SIGNATURES = {
     "adell_cls_mixup": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
     "adell_cls_confusion_update": (_i, [_i, _vp, _vp, _vp, _l, _i, _vp, _vp]),
     "adell_cls_auroc_pairs": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "adell_mil_volume_to_slices": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mil_slices_to_volume": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "adell_mil_pool_fwd": (_i, [_i] + [_vp] * 5 + [_i] * 4 + [_vp] * 5),
+    "adell_mil_pool_bwd": (_i, [_i] + [_vp] * 9 + [_i] * 4 + [_vp] * 7),
+    "adell_mil_slice_tokens_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "adell_mil_slice_tokens_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -2662,3 +2662,110 @@ def mixup_rows(x, factor, partner):
     three-operation expression; a row that is its own partner is returned as it is (a NaN or Inf in
     it stays what it was). Inputs carry no gradient."""
     return ops.cls_mixup(x.detach(), factor, partner)
+
+
+# ---- multiple-instance classification (csrc/mil.hip) ----------------------------------------------
+class _VolumeToSlicesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.n_slices = int(x.shape[-1])
+        return ops.mil_volume_to_slices(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.mil_slices_to_volume(dy.contiguous(), ctx.n_slices)
+
+
+def volume_to_slices(x):
+    """``einops.rearrange(x, "b c h w s -> (b s) c h w")`` for a dense volume [B, C, H, W, S]: item
+    b * S + s of the result is slice s of item b. For fixed (b, c) a [H W, S] -> [S, H W] transpose,
+    tiled through LDS so that both global sides are contiguous; the backward is the inverse copy.
+    Both are bit-equal to torch's ``permute().contiguous()``. The slice axis is always the LAST
+    one, as in the reference's live ``v_module`` (its ``dim`` argument is only read by the dead
+    ``v_module_old``). A non-dense input is refused, not copied."""
+    return _VolumeToSlicesFn.apply(x)
+
+
+class _MilGatedPoolFn(torch.autograd.Function):
+    """Saved: the inputs, A, and the arg-max ("max") or the row statistics ("vocabulary")."""
+
+    @staticmethod
+    def forward(ctx, feat, hv, hu, w, b, mode):
+        pooled, A, saved = ops.mil_pool_fwd(mode, feat, hv, hu, w, b)
+        ctx.mode = mode
+        ctx.has = (feat is not None, hv is not None, saved is not None)
+        keep = [t for t in (feat, hv, hu, w, saved) if t is not None]
+        ctx.save_for_backward(A, *keep)
+        ctx.set_materialize_grads(False)
+        if pooled is None:
+            pooled = A.new_empty((A.shape[0], 0))
+            ctx.mark_non_differentiable(pooled)
+        return pooled, A
+
+    @staticmethod
+    def backward(ctx, g, gA):
+        A, *rest = ctx.saved_tensors
+        rest = list(rest)
+        has_feat, has_gate, has_saved = ctx.has
+        feat = rest.pop(0) if has_feat else None
+        hv, hu, w = (rest.pop(0), rest.pop(0), rest.pop(0)) if has_gate else (None, None, None)
+        saved = rest.pop(0) if has_saved else None
+        if not has_feat:
+            g = None
+        if not has_gate:
+            gA = None       # A = 1 / S is a constant
+        if g is None and gA is None:
+            return None, None, None, None, None, None
+        dfeat, dhv, dhu, dw, db = ops.mil_pool_bwd(ctx.mode, feat, hv, hu, w, A, saved, g, gA)
+        if dw is not None:
+            dw = dw.view(w.shape)
+        return dfeat, dhv, dhu, dw, db, None
+
+
+def mil_gated_pool(feat, hv=None, hu=None, w=None, b=None, mode="mean"):
+    """(pooled [B, F], A [B, S, 1]) of ``MultipleInstanceClassifier.get_prediction`` in ONE launch:
+    A = softmax over the slices of ``W(tanh(V x) * sigmoid(U x))`` from hv = V(x), hu = U(x)
+    [B, S, N], the row w ([N] or [1, N]) and the bias b [1] of ``W`` (without them A = 1 / S and no
+    gate input is read), and pooled = sum_s feat A ("mean"), max_s feat A ("max": lowest slice on
+    a tie, a NaN propagates as in ``torch.max``) or sum_s softmax(feat, -1) A ("vocabulary") for
+    feat [B, S, F]. Neither the gate product nor feat * A is written; "max" keeps its int32
+    arg-max, "vocabulary" the row max and log-sum, not the softmax matrix. The backward (two
+    launches, one without the gate) returns dfeat, dhv, dhu, dw and db and honours a gradient that
+    arrives on A; db is whatever the fixed-order sum gives (zero up to rounding)."""
+    if mode not in ops.MIL_MODES:
+        raise ValueError(f"mil_gated_pool: mode must be one of {sorted(ops.MIL_MODES)}, got {mode!r}")
+    if feat is None:
+        raise ValueError("mil_gated_pool: feat [B, S, F] expected (mil_attention gives A alone)")
+    cont = [None if t is None else t.contiguous() for t in (feat, hv, hu, w, b)]
+    return _MilGatedPoolFn.apply(*cont, mode)
+
+
+def mil_attention(hv, hu, w, b):
+    """A [B, S, 1] alone (``MILAttention.calculate_attention`` behind its two Linear layers): the
+    same kernel as ``mil_gated_pool`` without features."""
+    cont = [t.contiguous() for t in (hv, hu, w, b)]
+    return _MilGatedPoolFn.apply(None, *cont, "mean")[1]
+
+
+class _SliceTokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pos, class_token):
+        ctx.n_slices = int(x.shape[1])
+        ctx.has_class_token = class_token is not None
+        return ops.mil_slice_tokens_fwd(x, pos, class_token)
+
+    @staticmethod
+    def backward(ctx, dout):
+        need = ctx.needs_input_grad
+        return ops.mil_slice_tokens_bwd(dout.contiguous(), ctx.n_slices, ctx.has_class_token,
+                                        need[0], need[1], need[2] and ctx.has_class_token)
+
+
+def slice_tokens(x, pos=None, class_token=None):
+    """The token rows of ``TransformableTransformer``: ``cat([class_token.expand(B, 1, E), x + pos],
+    1)`` for x [B, S, E], pos [1, S, 1] (one scalar per slice, broadcast over the features; None:
+    nothing added) and class_token [1, 1, E] (None: no row in front); one launch, bit-equal to
+    torch's add and cat. The backward writes dx whole in one launch with dpos and dclass_token,
+    their sums over the batch in order in fp64."""
+    return _SliceTokensFn.apply(x.contiguous(), None if pos is None else pos.contiguous(),
+                                None if class_token is None else class_token.contiguous())

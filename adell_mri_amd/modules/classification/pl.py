@@ -1,6 +1,7 @@
 """Classification training-step wrappers (mirror of adell_mri/modules/classification/pl.py):
-``ClassPLABC`` (:182-778), ``ClassNetPL`` (:781-928), ``OrdNetPL`` (:931-1174) and
-``ViTClassifierPL`` (:1762-1845), with the metric dicts of ``classification_metrics``.
+``ClassPLABC`` (:182-778), ``ClassNetPL`` (:781-928), ``OrdNetPL`` (:931-1174),
+``ViTClassifierPL`` (:1762-1845), ``TransformableTransformerPL`` (:1934-2021) and
+``MultipleInstanceClassifierPL`` (:2024-2111), with the metric dicts of ``classification_metrics``.
 
 Kept: constructor arguments, the label casts of ``calculate_loss`` (:217-223), ``additional_params``
 and ``with_loss_params``, tuple losses averaged element-wise, the steps (``test_step`` returns
@@ -27,6 +28,7 @@ from ...optim import FusedAdamW
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from .classification import CatNet, OrdNet, ViTClassifier, ordinal_prediction_to_class
 from .losses import BCEWithLogitsLoss
+from .multiple_instance_learning import MultipleInstanceClassifier, TransformableTransformer
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as pl
@@ -330,3 +332,55 @@ class ViTClassifierPL(ViTClassifier, ClassPLABC):
         self.net_type = "cat"
         self.save_hyperparameters(ignore=_IGNORED)
         self.setup_metrics()
+
+
+class _SliceClassifierPL(ClassPLABC):
+    """What the two multiple-instance wrappers share: the classifier IS the module (its parameters
+    carry no ``network.`` prefix, the 2-D module's sit under ``module.``). Parameters with
+    ``requires_grad=False`` -- a frozen ``module`` -- stay out of the optimiser's groups
+    (``optimizer_groups``). The default ``loss_fn`` is ``BCEWithLogitsLoss()``, as for
+    ``ClassNetPL``."""
+
+    def _setup_wrapper(self, local):
+        local["loss_fn"] = BCEWithLogitsLoss() if local["loss_fn"] is None else local["loss_fn"]
+        _store(self, local, _HYPERPARAMETERS)
+        # ClassPLABC.__init__ is not reached through the classifier's: its attributes
+        self.raise_nan_loss, self.calibrated, self.gaussian_process = False, False, False
+        self.net_type = "cat"
+        self.save_hyperparameters(ignore=["module"] + _IGNORED)
+        self.setup_metrics()
+
+    def predict_step(self, batch, batch_idx, dataloader_idx=0, *args, **kwargs):
+        x = batch[self.image_key]
+        output = self.forward(x, *args, **kwargs)
+        if kwargs.get("return_attention", False):
+            prediction, attention = output
+            return {"prediction": prediction, "attention": attention}
+        return {"prediction": output}
+
+
+class TransformableTransformerPL(TransformableTransformer, _SliceClassifierPL):
+    """pl.py:1934-2021. ``predict_step(..., return_attention=True)`` also returns the last block's
+    attention."""
+
+    def __init__(self, image_key: str = "image", label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._setup_wrapper(locals())
+
+
+class MultipleInstanceClassifierPL(MultipleInstanceClassifier, _SliceClassifierPL):
+    """pl.py:2024-2111. ``predict_step(..., return_attention=True)`` also returns A [B, S, 1]."""
+
+    def __init__(self, image_key: str = "image", label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._setup_wrapper(locals())

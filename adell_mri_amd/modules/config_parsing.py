@@ -1,7 +1,8 @@
 """YAML -> constructor keyword arguments for the segmentation / SSL networks of the hot path.
 
 Restates ``parse_config_unet`` (adell_mri/modules/config_parsing.py:30-58),
-``parse_config_cat`` (:61-64) and ``parse_config_ssl`` (:78-136) on this package's classes, so that the reference's sample
+``parse_config_cat`` (:61-64), ``parse_config_ssl`` (:78-136) and ``parse_config_2d_classifier_3d``
+(:139-172) on this package's classes, so that the reference's sample
 configurations (``sample_configs/u-net-3d-resnet.yaml``, ``unetr.yaml``, ``unet-swin.yaml``,
 ``ssl-2d-convnext.yaml``, ``ssl-resnet.yaml``) can be consumed as they ship.
 
@@ -62,6 +63,27 @@ def parse_config_cat(config_file):
     """config_parsing.py:61-64: the YAML mapping as it is (``get_classification_network`` pops
     ``act_fn`` / ``norm_fn`` and splats the rest into the wrapper)."""
     return _load(config_file)
+
+
+def parse_config_2d_classifier_3d(config_file, dropout_param, mil_method="standard"):
+    """config_parsing.py:139-172, the YAML of the multiple-instance classifiers
+    (``MultipleInstanceClassifierPL`` / ``TransformableTransformerPL``) -> (network_config,
+    network_config_correct): ``batch_size`` defaulted to 1, a ``classification_adn_fn`` mapping
+    turned into its 1-D factory, ``adn_fn`` built from ``norm_fn`` / ``act_fn`` (defaults "layer" /
+    "gelu") with ``dropout_param``; the second dictionary is the first without those two keys.
+    ``mil_method`` is accepted and unused, as in the reference."""
+    network_config = _load(config_file)
+    network_config.setdefault("batch_size", 1)
+    norm_fn = network_config.get("norm_fn", "layer")
+    act_fn = network_config.get("act_fn", "gelu")
+    if "classification_adn_fn" in network_config:
+        network_config["classification_adn_fn"] = get_adn_fn(
+            1, **network_config["classification_adn_fn"])
+    network_config["adn_fn"] = get_adn_fn(1, norm_fn=norm_fn, act_fn=act_fn,
+                                          dropout_param=dropout_param)
+    network_config_correct = {k: v for k, v in network_config.items()
+                              if k not in ("norm_fn", "act_fn")}
+    return network_config, network_config_correct
 
 
 def parse_config_ssl(config_file, dropout_param, n_keys, is_vit=False):

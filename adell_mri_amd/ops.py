@@ -3471,6 +3471,190 @@ def cls_auroc_pairs(scores, target):
     return out
 
 
+# ---- multiple-instance classification (csrc/mil.hip) -------------------------------------------
+MIL_MODES = {"mean": 0, "max": 1, "vocabulary": 2}
+
+
+def _mil_dense(what, *ts):
+    """fp32 device tensors, dense row-major (a view with gaps or a permuted one is refused here,
+    whatever ADELL_CHECK_DENSE says: these kernels index from the shape alone)."""
+    _require_cuda(*ts)
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise _lib.AdellHipError(f"{what}: non-dense tensor handed to a kernel: shape "
+                                     f"{tuple(t.shape)}, strides {t.stride()}")
+
+
+def mil_volume_to_slices(x):
+    """[B, C, H, W, S] -> [B * S, C, H, W], item b * S + s holding slice s of item b
+    (``"b c h w s -> (b s) c h w"``); a copy, one launch."""
+    if x.dim() != 5:
+        raise ValueError(f"mil_volume_to_slices: a volume [B, C, H, W, S] expected, got "
+                         f"{tuple(x.shape)}")
+    _mil_dense("mil_volume_to_slices", x)
+    B, C, H, W, S = (int(v) for v in x.shape)
+    out = torch.empty((B * S, C, H, W), device=x.device, dtype=torch.float32)
+    if out.numel():
+        check(_lib.lib().adell_mil_volume_to_slices(_ptr(x), B, C, H * W, S, _ptr(out), _stream()))
+    return out
+
+
+def mil_slices_to_volume(y, n_slices):
+    """The inverse copy: [B * S, C, H, W] -> [B, C, H, W, S]."""
+    S = int(n_slices)
+    if y.dim() != 4 or S < 1 or y.shape[0] % S:
+        raise ValueError(f"mil_slices_to_volume: slices [B * {S}, C, H, W] expected, got "
+                         f"{tuple(y.shape)}")
+    _mil_dense("mil_slices_to_volume", y)
+    BS, C, H, W = (int(v) for v in y.shape)
+    out = torch.empty((BS // S, C, H, W, S), device=y.device, dtype=torch.float32)
+    if out.numel():
+        check(_lib.lib().adell_mil_slices_to_volume(_ptr(y), BS // S, C, H * W, S, _ptr(out),
+                                                    _stream()))
+    return out
+
+
+def _mil_pool_args(what, mode, feat, hv, hu, w, b, with_bias=True):
+    """(mode id, B, S, N, F) checked on the host; ``feat`` or the gate inputs may be None (the
+    backward has no use for the bias: ``with_bias=False``)."""
+    if mode not in MIL_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(MIL_MODES)}, got {mode!r}")
+    gate = (hv, hu, w, b) if with_bias else (hv, hu, w)
+    if any(t is None for t in gate) and not all(t is None for t in gate):
+        raise ValueError(f"{what}: hv, hu, w and b go together (all or none)")
+    if hv is None and feat is None:
+        raise ValueError(f"{what}: neither gate inputs nor features")
+    lead = feat if feat is not None else hv
+    if lead.dim() != 3:
+        raise ValueError(f"{what}: [B, S, features] expected, got {tuple(lead.shape)}")
+    B, S = int(lead.shape[0]), int(lead.shape[1])
+    F = int(feat.shape[2]) if feat is not None else 0
+    N = 0
+    if hv is not None:
+        N = int(hv.shape[-1])
+        if tuple(hv.shape) != (B, S, N) or tuple(hu.shape) != (B, S, N) or w.numel() != N \
+                or (with_bias and b.numel() != 1):
+            raise ValueError(f"{what}: hv and hu [{B}, {S}, N], w [N] and b [1] expected, got "
+                             f"{tuple(hv.shape)}, {tuple(hu.shape)}, {tuple(w.shape)}"
+                             + (f", {tuple(b.shape)}" if with_bias else ""))
+    if B < 1 or S < 1 or (feat is not None and F < 1) or (hv is not None and N < 1):
+        raise ValueError(f"{what}: empty input {tuple(lead.shape)}")
+    _mil_dense(what, feat, hv, hu, w, b)
+    return MIL_MODES[mode], B, S, N, F
+
+
+def mil_pool_fwd(mode, feat, hv=None, hu=None, w=None, b=None):
+    """(pooled [B, F] or None, A [B, S, 1], saved) in one launch: A the gated-attention softmax over
+    the slices of hv, hu [B, S, N] with the row w [N] and bias b [1] (1 / S without them), pooled
+    by ``mode`` in MIL_MODES from feat [B, S, F] (None: only A). ``saved``: the int32 arg-max
+    [B, F] ("max"), the row (max, log-sum) [B, S, 2] ("vocabulary"), else None."""
+    mid, B, S, N, F = _mil_pool_args("mil_pool_fwd", mode, feat, hv, hu, w, b)
+    dev = (feat if feat is not None else hv).device
+    A = torch.empty((B, S, 1), device=dev, dtype=torch.float32)
+    pooled = torch.empty((B, F), device=dev, dtype=torch.float32) if F else None
+    arg = rowstat = None
+    if F and mid == 1:
+        arg = torch.empty((B, F), device=dev, dtype=torch.int32)
+    if F and mid == 2:
+        rowstat = torch.empty((B, S, 2), device=dev, dtype=torch.float32)
+    check(_lib.lib().adell_mil_pool_fwd(
+        mid, _ptr(hv), _ptr(hu), _ptr(w), _ptr(b), _ptr(feat), B, S, N, F, _ptr(A), _ptr(pooled),
+        None if arg is None else ctypes.c_void_p(arg.data_ptr()), _ptr(rowstat), _stream()))
+    return pooled, A, (arg if mid == 1 else rowstat)
+
+
+def mil_pool_bwd(mode, feat, hv, hu, w, A, saved, g, gA):
+    """(dfeat, dhv, dhu, dw, db) of ``mil_pool_fwd`` from the gradient g [B, F] of pooled and gA
+    [B, S, 1] (or None) of A; two launches, one without the gate. A gradient whose input was None
+    is None."""
+    mid, B, S, N, F = _mil_pool_args("mil_pool_bwd", mode, feat, hv, hu, w, None, with_bias=False)
+    dev = A.device
+    if F:
+        g = (torch.zeros((B, F), device=dev, dtype=torch.float32) if g is None
+             else g.to(torch.float32).contiguous())
+        if tuple(g.shape) != (B, F):
+            raise ValueError(f"mil_pool_bwd: a gradient [{B}, {F}] expected, got {tuple(g.shape)}")
+    else:
+        g = None
+    if gA is not None:
+        gA = gA.to(torch.float32).contiguous()
+        if gA.numel() != B * S:
+            raise ValueError(f"mil_pool_bwd: a gradient of A with {B * S} elements expected, got "
+                             f"{tuple(gA.shape)}")
+    if tuple(A.shape) != (B, S, 1):
+        raise ValueError(f"mil_pool_bwd: A [{B}, {S}, 1] expected, got {tuple(A.shape)}")
+    _mil_dense("mil_pool_bwd", A, g, gA)
+    arg = saved if mid == 1 else None
+    rowstat = saved if mid == 2 else None
+    if F and mid == 1 and (arg is None or arg.dtype != torch.int32 or tuple(arg.shape) != (B, F)
+                           or not arg.is_cuda or not arg.is_contiguous()):
+        raise ValueError(f"mil_pool_bwd: the int32 arg-max [{B}, {F}] of the forward expected")
+    if F and mid == 2 and (rowstat is None or tuple(rowstat.shape) != (B, S, 2)):
+        raise ValueError(f"mil_pool_bwd: the row statistics [{B}, {S}, 2] of the forward expected")
+    _mil_dense("mil_pool_bwd", rowstat)
+    dfeat = torch.empty_like(feat) if F else None
+    dhv = dhu = dw = db = part = None
+    if hv is not None:
+        dhv, dhu = torch.empty_like(hv), torch.empty_like(hu)
+        dwb = torch.empty((N + 1,), device=dev, dtype=torch.float32)
+        dw, db = dwb[:N], dwb[N:]
+        part = torch.empty((B, N + 1), device=dev, dtype=torch.float64)
+    check(_lib.lib().adell_mil_pool_bwd(
+        mid, _ptr(hv), _ptr(hu), _ptr(w), _ptr(feat), _ptr(A),
+        None if arg is None else ctypes.c_void_p(arg.data_ptr()), _ptr(rowstat), _ptr(g), _ptr(gA),
+        B, S, N, F, _ptr(dfeat), _ptr(dhv), _ptr(dhu),
+        None if dw is None else ctypes.c_void_p(dw.data_ptr()),
+        None if db is None else ctypes.c_void_p(db.data_ptr()),
+        None if part is None else ctypes.c_void_p(part.data_ptr()), _stream()))
+    return dfeat, dhv, dhu, dw, db
+
+
+def _mil_token_args(what, x, pos, class_token):
+    if x.dim() != 3:
+        raise ValueError(f"{what}: x [B, S, E] expected, got {tuple(x.shape)}")
+    B, S, E = (int(v) for v in x.shape)
+    if pos is not None and tuple(pos.shape) != (1, S, 1):
+        raise ValueError(f"{what}: pos [1, {S}, 1] (one scalar per slice) expected, got "
+                         f"{tuple(pos.shape)}")
+    if class_token is not None and tuple(class_token.shape) != (1, 1, E):
+        raise ValueError(f"{what}: class_token [1, 1, {E}] expected, got {tuple(class_token.shape)}")
+    if B < 1 or S < 1 or E < 1:
+        raise ValueError(f"{what}: empty input {tuple(x.shape)}")
+    return B, S, E
+
+
+def mil_slice_tokens_fwd(x, pos=None, class_token=None):
+    """out [B, S (+ 1), E]: row 0 the class token (when given), row (1 +) s = x[b, s] + pos[s];
+    one launch."""
+    B, S, E = _mil_token_args("mil_slice_tokens", x, pos, class_token)
+    _mil_dense("mil_slice_tokens", x, pos, class_token)
+    ct = 0 if class_token is None else 1
+    out = torch.empty((B, S + ct, E), device=x.device, dtype=torch.float32)
+    check(_lib.lib().adell_mil_slice_tokens_fwd(_ptr(x), _ptr(pos), _ptr(class_token), B, S, E,
+                                                _ptr(out), _stream()))
+    return out
+
+
+def mil_slice_tokens_bwd(dout, n_slices, has_class_token, need_x=True, need_pos=True,
+                         need_class_token=True):
+    """(dx [B, S, E], dpos [1, S, 1], dclass_token [1, 1, E]) in one launch, the two sums over the
+    batch in order in fp64; a gradient that is not needed is None."""
+    ct, S = int(bool(has_class_token)), int(n_slices)
+    if dout.dim() != 3 or dout.shape[1] != S + ct:
+        raise ValueError(f"mil_slice_tokens_bwd: a gradient [B, {S + ct}, E] expected, got "
+                         f"{tuple(dout.shape)}")
+    _mil_dense("mil_slice_tokens_bwd", dout)
+    B, _, E = (int(v) for v in dout.shape)
+    dev = dout.device
+    dx = torch.empty((B, S, E), device=dev, dtype=torch.float32) if need_x else None
+    dpos = torch.empty((1, S, 1), device=dev, dtype=torch.float32) if need_pos else None
+    dcls = (torch.empty((1, 1, E), device=dev, dtype=torch.float32)
+            if need_class_token and ct else None)
+    check(_lib.lib().adell_mil_slice_tokens_bwd(_ptr(dout), B, S, E, ct, _ptr(dx), _ptr(dpos),
+                                                _ptr(dcls), _stream()))
+    return dx, dpos, dcls
+
+
 PAIR_LOSS_KINDS = {"simsiam": 0, "byol": 1, "ntxent": 2}
 
 

@@ -1022,6 +1022,40 @@ int adell_cls_confusion_update(int mode, const float* pf, const long long* pi, c
                                int C, long long* counts, void* stream);
 int adell_cls_auroc_pairs(const float* scores, const long long* y, int N, long long* out, void* stream);
 
+/* Multiple-instance classification (modules/classification/classification/multiple_instance_learning.py;
+ * csrc/mil.hip). fp32, dense, floating-point sums in a fixed order, no float atomics: results repeat bit
+ * for bit.
+ * adell_mil_volume_to_slices: "b c h w s -> (b s) c h w" with P = H W: slices[(b S + s) C + c][p] =
+ * vol[b C + c][p][s], a tiled transpose through LDS, both global sides contiguous. _slices_to_volume is
+ * the inverse copy (its gradient).
+ * adell_mil_pool_fwd, one launch, a block per item and 64 features: score[b][s] = sum_n w[n] tanh(hv[b][s][n])
+ * sigmoid(hu[b][s][n]) + bias[0], A [B][S] = softmax over s (max-subtracted); hv == NULL: A = 1 / S and
+ * hu, w, bias are not read. pooled [B][F] by mode: ADELL_MIL_MEAN sum_s feat[b][s][f] A[b][s];
+ * ADELL_MIL_MAX the maximum over s of the same products, arg [B][F] its slice (the lowest on a tie; a NaN
+ * wins); ADELL_MIL_VOCABULARY sum_s softmax_F(feat[b][s])[f] A[b][s] with rowstat [B][S][2] = (row max,
+ * log of the row's sum of exponentials). F = 0: only A (feat, pooled, arg, rowstat unused). S <= 8192.
+ * adell_mil_pool_bwd: g [B][F] the gradient of pooled, gA [B][S] (or NULL) the one that arrived on A;
+ * writes dfeat [B][S][F] and, with hv, dhv, dhu [B][S][N], dw [N], db [1] (the fixed-order sum of
+ * dscore: zero up to rounding); part: B (N + 1) doubles of workspace. Two launches, one without hv.
+ * adell_mil_slice_tokens_fwd: out [B][S + ct][E], row 0 = class_token [E] (ct = 1; NULL: ct = 0), row
+ * ct + s = x[b][s] + pos[s] (pos [S], one scalar per slice; NULL: a copy); one launch. _bwd, one launch:
+ * dx [B][S][E] copied whole, dpos[s] = sum_b sum_e and dclass_token[e] = sum_b in fp64, b in order; a
+ * NULL output is not computed. */
+enum { ADELL_MIL_MEAN = 0, ADELL_MIL_MAX = 1, ADELL_MIL_VOCABULARY = 2 };
+int adell_mil_volume_to_slices(const float* vol, int B, int C, int P, int S, float* slices, void* stream);
+int adell_mil_slices_to_volume(const float* slices, int B, int C, int P, int S, float* vol, void* stream);
+int adell_mil_pool_fwd(int mode, const float* hv, const float* hu, const float* w, const float* bias,
+                       const float* feat, int B, int S, int N, int F, float* A, float* pooled, int* arg,
+                       float* rowstat, void* stream);
+int adell_mil_pool_bwd(int mode, const float* hv, const float* hu, const float* w, const float* feat,
+                       const float* A, const int* arg, const float* rowstat, const float* g,
+                       const float* gA, int B, int S, int N, int F, float* dfeat, float* dhv, float* dhu,
+                       float* dw, float* db, double* part, void* stream);
+int adell_mil_slice_tokens_fwd(const float* x, const float* pos, const float* class_token, int B, int S,
+                               int E, float* out, void* stream);
+int adell_mil_slice_tokens_bwd(const float* dout, int B, int S, int E, int has_class_token, float* dx,
+                               float* dpos, float* dclass_token, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
