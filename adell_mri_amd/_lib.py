@@ -112,6 +112,10 @@ SIGNATURES = {
     "adell_conv3d_bwd_weight_f16x3_plan": (_i, [ctypes.POINTER(ConvDesc), _vp]),
     "adell_conv3d_bwd_weight_f16x3_rows": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 10
                                            + [ctypes.c_size_t, _vp]),
+    "adell_conv3d_bwd_weight_f16x3_share": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 8
+                                            + [ctypes.c_size_t, _vp, _i]),
+    "adell_conv3d_bwd_weight_f16x3_rows_share": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 10
+                                                 + [ctypes.c_size_t, _vp, _i]),
     "adell_conv3d_fwd_f16x3_rows": (_i, [ctypes.POINTER(ConvDesc)] + [_vp] * 10 + [_i, _vp, _vp]),
     "adell_norm_act_fwd_mask": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 9),
     "adell_norm_act_bwd_from_dt": (_i, [ctypes.POINTER(NormActDesc)] + [_vp] * 5 + [_i, _i, _i, _vp, _vp,
@@ -327,6 +331,8 @@ SIGNATURES = {
     "adell_dw_wgrad_mfma_ok": (_i, [_i] * 8 + [_vp, _vp]),
     "adell_dwconv3d_plan": (_i, [_i] * 11 + [_vp]),
     "adell_wgrad_zring_plan": (_i, [_i] * 16 + [_vp]),
+    "adell_wgrad_zring_share_plan": (_i, [ctypes.POINTER(ConvDesc), _i, _vp]),
+    "adell_wgrad_zring_occupancy": (_i, [ctypes.POINTER(ConvDesc), _i]),
     "adell_rowscale_fwd": (_i, [_vp] * 5 + [_i, _i, _vp]),
     "adell_rowscale_bwd": (_i, [_vp] * 8 + [_i, _i, _vp]),
     "adell_window_ndhwc": (_i, [_vp, _vp] + [_i] * 11 + [_vp]),

@@ -73,13 +73,16 @@ extern long g_adell_plan_epoch;
 
 // LDS per CU on gfx950 (MI355X): the most LDS one block may take.
 constexpr int kAdellLdsPerCu = 160 * 1024;
+// A block's LDS is allocated in units of 320 dwords there: what a request of `bytes` takes of a CU.
+constexpr size_t kAdellLdsGranule = 320 * 4;
+constexpr size_t adell_lds_alloc(size_t bytes) {
+  return (bytes + kAdellLdsGranule - 1) / kAdellLdsGranule * kAdellLdsGranule;
+}
 
-// Launch of a kernel whose dynamic LDS may exceed the runtime's 64 KiB default. The first call for
-// each Kern raises its limit, once per process (a thread-safe function-local static), to the CU's
-// LDS less the kernel's static LDS; every call launches and checks the launch. Errors name Kern
-// through __PRETTY_FUNCTION__.
-template <auto Kern, typename... Args>
-static int adell_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+// The dynamic-LDS limit of Kern raised, once per process (a thread-safe function-local static), to
+// the CU's LDS less the kernel's static LDS; the result of that one attempt.
+template <auto Kern>
+static hipError_t adell_raise_lds_limit() {
   static const hipError_t attr = [] {
     hipFuncAttributes fa;
     const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kern));
@@ -88,6 +91,15 @@ static int adell_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                kAdellLdsPerCu - (int)fa.sharedSizeBytes);
   }();
+  return attr;
+}
+
+// Launch of a kernel whose dynamic LDS may exceed the runtime's 64 KiB default. The first call for
+// each Kern raises its limit (adell_raise_lds_limit); every call launches and checks the launch.
+// Errors name Kern through __PRETTY_FUNCTION__.
+template <auto Kern, typename... Args>
+static int adell_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  const hipError_t attr = adell_raise_lds_limit<Kern>();
   if (attr != hipSuccess) {
     adell_set_error("%s: raising the dynamic LDS limit -> %s", __PRETTY_FUNCTION__,
                     hipGetErrorString(attr));

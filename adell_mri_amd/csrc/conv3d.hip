@@ -431,6 +431,17 @@ static bool adell_item_below_4g(const ConvArgs& a) {
   return (size_t)a.D * a.H * a.W * (a.C0 > a.C1 ? a.C0 : a.C1) < ((size_t)1 << 30);
 }
 
+// LDS plans of the specialised 3x3x3 stride-1 instances: SPEC = 3 stages a 10 x 10 x 10 halo and
+// seven weight rows of 32 columns; SPEC = 1 (8 x 8 x 4 bricks, cfg 0 / 1) a 10 x 10 x 6 halo and a kz
+// plane of up to 64 columns (the general formula of adell_plan_tile_f16 at those extents). The larger
+// of the two is what a kernel that shares a CU with these blocks has to leave free
+// (adell_wgrad_zring_share_lds, conv_wgrad_zring.hip).
+constexpr size_t kConvSpec3Lds = (size_t)1000 * 64 + (size_t)7 * 32 * 64 + 64;
+constexpr size_t kConvSpec1LdsMax = (size_t)600 * 64 + (size_t)9 * 64 * 64 + 64;
+size_t adell_conv_f16_spec_lds_max() {
+  return kConvSpec3Lds > kConvSpec1LdsMax ? kConvSpec3Lds : kConvSpec1LdsMax;
+}
+
 // Tile, brick, weight group and LDS bytes of the plan: the heuristic brick, a measured rule's, or
 // (when its halo does not fit LDS, i.e. stride 2) the small-brick configuration of the same channel
 // width.
@@ -534,7 +545,7 @@ static int adell_plan_tile_f16(const ConvArgs& a, int N, ConvPlanF16* p) {
     t.BM = 512;
     t.lTZ = 3;
     p->brick = adell_brick(a, t);   // 10 x 10 x 10 halo
-    lds = (size_t)1000 * 64 + (size_t)7 * 32 * 64 + 64;
+    lds = kConvSpec3Lds;
   }
   // transposed-conv forward (1 tap, F * Cs columns with a pixel-shuffle store): one block takes a
   // 64-voxel brick and up to 256 columns (cfg 5), so the input brick is staged once instead of

@@ -597,11 +597,12 @@ static int adell_wgrad_plane_launch(const adell_conv3d_desc& d, const WgradRoute
   return r.inst->launch(a, r.grid, p.lds, st);
 }
 
-// xk0 / xk1 non-null = that source holds split rows (adell_conv3d_bwd_weight_f16x3_rows)
+// xk0 / xk1 non-null = that source holds split rows (adell_conv3d_bwd_weight_f16x3_rows); share: the
+// caller's ADELL_WGRAD_SHARE_* hint, which only the z-ring launch reads
 static int adell_wgrad_f16_run(const adell_conv3d_desc& d, const float* x0, const float* x1,
                                const float* dy, float* out, float* db, const uint32_t* xmax_in,
                                const uint32_t* ymax_in, void* ws, size_t ws_bytes, hipStream_t st,
-                               const int* xk0 = nullptr, const int* xk1 = nullptr) {
+                               const int* xk0, const int* xk1, int share) {
   WgradRoute r;
   const int prc = adell_wgrad_route(d, &r);
   ADELL_REQUIRE((!xk0 && !xk1) || r.rows_ok,
@@ -636,7 +637,8 @@ static int adell_wgrad_f16_run(const adell_conv3d_desc& d, const float* x0, cons
   float* dbs = db ? wsdb : nullptr;
   int rc;
   if (r.route == ADELL_WGRAD_ZRING32 || r.route == ADELL_WGRAD_ZRING16)
-    rc = adell_wgrad_zring_launch(d, r.zr, x0, x1, dy, slabs, dbs, xmax, ymax, st, xk0, xk1);
+    rc = adell_wgrad_zring_launch(d, r.zr, x0, x1, dy, slabs, dbs, xmax, ymax, st, xk0, xk1,
+                                  share);
   else if (r.route == ADELL_WGRAD_S2)
     rc = adell_wgrad_s2_launch(d, r.s2, x0, dy, slabs, dbs, xmax, ymax, st);
   else
@@ -687,7 +689,28 @@ extern "C" int adell_conv3d_bwd_weight_f16x3(const adell_conv3d_desc* d, const f
   ADELL_REQUIRE(d && x0 && dy && dw, "conv_bwd_weight_f16x3: null pointer");
   ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3: C1 > 0 needs x1");
   return adell_wgrad_f16_run(*d, x0, x1, dy, dw, db, x_absmax, dy_absmax, workspace,
-                             workspace_bytes, (hipStream_t)stream);
+                             workspace_bytes, (hipStream_t)stream, nullptr, nullptr,
+                             ADELL_WGRAD_SHARE_NONE);
+}
+
+// The same call with a share hint (ADELL_WGRAD_SHARE_*, include/adell_hip.h): a per-call fact about
+// the streams around this launch, not a tuning switch -- the plan, the workspace and the bits do not
+// depend on it.
+static bool adell_wgrad_share_ok(int share) {
+  return share == ADELL_WGRAD_SHARE_NONE || share == ADELL_WGRAD_SHARE_AUTO ||
+         share == ADELL_WGRAD_SHARE_ALWAYS;
+}
+
+extern "C" int adell_conv3d_bwd_weight_f16x3_share(const adell_conv3d_desc* d, const float* x0,
+                                                   const float* x1, const float* dy, float* dw,
+                                                   float* db, const uint32_t* x_absmax,
+                                                   const uint32_t* dy_absmax, void* workspace,
+                                                   size_t workspace_bytes, void* stream, int share) {
+  ADELL_REQUIRE(d && x0 && dy && dw, "conv_bwd_weight_f16x3_share: null pointer");
+  ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3_share: C1 > 0 needs x1");
+  ADELL_REQUIRE(adell_wgrad_share_ok(share), "conv_bwd_weight_f16x3_share: unknown hint %d", share);
+  return adell_wgrad_f16_run(*d, x0, x1, dy, dw, db, x_absmax, dy_absmax, workspace,
+                             workspace_bytes, (hipStream_t)stream, nullptr, nullptr, share);
 }
 
 // The same with split-row sources of X (adell_norm_act_fwd_split; include/adell_hip.h): xk0 / xk1
@@ -708,5 +731,23 @@ extern "C" int adell_conv3d_bwd_weight_f16x3_rows(const adell_conv3d_desc* d, co
   ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3_rows: C1 > 0 needs x1");
   ADELL_REQUIRE(xk0 || xk1, "conv_bwd_weight_f16x3_rows: no split-row source");
   return adell_wgrad_f16_run(*d, (const float*)x0, (const float*)x1, dy, dw, db, x_absmax,
-                             dy_absmax, workspace, workspace_bytes, (hipStream_t)stream, xk0, xk1);
+                             dy_absmax, workspace, workspace_bytes, (hipStream_t)stream, xk0, xk1,
+                             ADELL_WGRAD_SHARE_NONE);
+}
+
+extern "C" int adell_conv3d_bwd_weight_f16x3_rows_share(const adell_conv3d_desc* d, const void* x0,
+                                                        const int* xk0, const void* x1,
+                                                        const int* xk1, const float* dy, float* dw,
+                                                        float* db, const uint32_t* x_absmax,
+                                                        const uint32_t* dy_absmax, void* workspace,
+                                                        size_t workspace_bytes, void* stream,
+                                                        int share) {
+  ADELL_REQUIRE(d && x0 && dy && dw, "conv_bwd_weight_f16x3_rows_share: null pointer");
+  ADELL_REQUIRE(d->C1 == 0 || x1, "conv_bwd_weight_f16x3_rows_share: C1 > 0 needs x1");
+  ADELL_REQUIRE(xk0 || xk1, "conv_bwd_weight_f16x3_rows_share: no split-row source");
+  ADELL_REQUIRE(adell_wgrad_share_ok(share), "conv_bwd_weight_f16x3_rows_share: unknown hint %d",
+                share);
+  return adell_wgrad_f16_run(*d, (const float*)x0, (const float*)x1, dy, dw, db, x_absmax,
+                             dy_absmax, workspace, workspace_bytes, (hipStream_t)stream, xk0, xk1,
+                             share);
 }

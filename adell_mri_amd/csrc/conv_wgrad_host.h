@@ -12,11 +12,21 @@ struct WgradZrPlan {
 };
 // true + plan when the z-ring kernel serves the problem
 bool adell_wgrad_zring_plan_desc(const adell_conv3d_desc& d, WgradZrPlan& p);
-// slabs: [R][27][Cin][Cout], wsdb: [R][Cout] or null; xk0 / xk1 non-null = that source holds split rows
+// Residency of a z-ring launch under a share hint (ADELL_WGRAD_SHARE_*, include/adell_hip.h): the
+// blocks per CU it is sized for, the dynamic LDS it requests, the LDS of a CU it leaves to others.
+struct WgradZrShare {
+  int per_cu;
+  size_t lds, room;
+};
+WgradZrShare adell_wgrad_zring_share(const adell_conv3d_desc& d, const WgradZrPlan& p, int share);
+// the most LDS a specialised 3x3x3 stride-1 implicit-GEMM block asks for (conv3d.hip)
+size_t adell_conv_f16_spec_lds_max();
+// slabs: [R][27][Cin][Cout], wsdb: [R][Cout] or null; xk0 / xk1 non-null = that source holds split
+// rows; share: the caller's hint (the launch is the same grid and the same bits either way)
 int adell_wgrad_zring_launch(const adell_conv3d_desc& d, const WgradZrPlan& p, const float* x0,
                              const float* x1, const float* dy, float* slabs, float* wsdb,
                              const unsigned* xmax, const unsigned* ymax, hipStream_t st,
-                             const int* xk0, const int* xk1);
+                             const int* xk0, const int* xk1, int share);
 
 // the 32 -> 32 stride-2 downsampling layer (conv_wgrad_s2.hip)
 struct WgradS2Plan {

@@ -702,10 +702,86 @@ extern "C" int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1
   return 1;
 }
 
+// Residency under a share hint. Alone, two blocks of the 32 x 32 form (three of the 16 x 16 form) hold
+// a CU for the whole launch -- a block is a region that lives as long as the launch does -- and once
+// another stream's short-lived blocks have retired nothing of theirs becomes resident again before
+// the regions finish: the two streams take turns. A launch that takes the hint asks for more dynamic
+// LDS than it uses, the smallest allocation of which two no longer fit a CU, so one block per CU
+// runs and half the register file and the rest of the LDS stay with the other stream. Same grid,
+// regions, units, slabs and fold: the same bits. The hint is taken only when
+//   - the 32 x 32 form runs (the 16 x 16 form's three blocks are not what holds the step's CUs),
+//   - the launch has more blocks than CUs (ADELL_WGRAD_SHARE_AUTO; fewer sit one to a CU anyway),
+//   - a block marches at least kZrShareMinSteps planes (ADELL_WGRAD_SHARE_AUTO). Measured on the
+//     2 x 128^3 U-Net step, rules alternating in one process (tools/wgrad_share_rules.py): no hint
+//     32.12 ms, the hint on the 128-plane launches alone 31.70, on every launch 32.03, on the
+//     64-plane and shorter ones alone 32.34 -- beside the short launches the main stream runs short
+//     MFMA-bound kernels, which gain nothing from the room, while a lone block's exposed staging
+//     and the second round of blocks cost the z-ring more than at 128 planes (docs/LABBOOK.md), and
+//   - the largest specialised implicit-GEMM block (adell_conv_f16_spec_lds_max) still fits beside
+//     the request, both rounded up to the allocation unit.
+constexpr long kZrShareMinSteps = 96;
+static size_t adell_wgrad_zring_lds(int t16) {
+  return t16 ? 2 * (ZR_SLOTS * (size_t)Z16_XPLANE + 2 * (size_t)Z16_YPLANE)
+             : ZR_SLOTS * (size_t)ZR_PLANE + 2 * (size_t)ZR_YBUF;
+}
+
+WgradZrShare adell_wgrad_zring_share(const adell_conv3d_desc& d, const WgradZrPlan& p, int share) {
+  WgradZrShare s = {p.t16 ? 3 : 2, adell_wgrad_zring_lds(p.t16), 0};
+  const long blocks = (long)p.R * p.nci * p.nco;
+  const long nunits = (long)d.N * p.ntx * p.nty * p.nseg;
+  const long steps = (nunits + p.R - 1) / p.R * p.seglen;   // planes the busiest block marches
+  if (!p.t16 && (share == ADELL_WGRAD_SHARE_ALWAYS ||
+                 (share == ADELL_WGRAD_SHARE_AUTO && blocks > adell_cu_count() &&
+                  steps >= kZrShareMinSteps))) {
+    size_t want = adell_lds_alloc(kAdellLdsPerCu / 2 + 1);
+    if (want < s.lds) want = s.lds;
+    if (2 * adell_lds_alloc(want) > (size_t)kAdellLdsPerCu &&
+        adell_lds_alloc(want) + adell_lds_alloc(adell_conv_f16_spec_lds_max()) <= (size_t)kAdellLdsPerCu) {
+      s.per_cu = 1;
+      s.lds = want;
+    }
+  }
+  s.room = kAdellLdsPerCu - s.per_cu * adell_lds_alloc(s.lds);
+  return s;
+}
+
+// The exported query (include/adell_hip.h): plan[8] as above, then the residency under `share`.
+extern "C" int adell_wgrad_zring_share_plan(const adell_conv3d_desc* d, int share, int* out) {
+  WgradZrPlan p;
+  if (!d || !out || !adell_wgrad_zring_plan_desc(*d, p)) return 0;
+  const WgradZrShare s = adell_wgrad_zring_share(*d, p, share);
+  const int v[11] = {p.ntx, p.nty, p.nseg, p.seglen, p.nci, p.nco, p.R, p.t16,
+                     s.per_cu, (int)s.lds, (int)s.room};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return 1;
+}
+
+// Blocks per CU the runtime's occupancy calculator gives the launch of d under `share` (no launch);
+// a negative ADELL_E_* when no z-ring kernel serves d or the runtime refuses.
+extern "C" int adell_wgrad_zring_occupancy(const adell_conv3d_desc* d, int share) {
+  ADELL_REQUIRE(d, "wgrad_zring_occupancy: null pointer");
+  WgradZrPlan p;
+  if (!adell_wgrad_zring_plan_desc(*d, p)) {
+    adell_set_error("wgrad_zring_occupancy: the z-ring kernel does not serve this problem");
+    return ADELL_E_UNSUPPORTED;
+  }
+  const WgradZrShare s = adell_wgrad_zring_share(*d, p, share);
+  int n = 0;
+  if (p.t16) {
+    ADELL_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, adell_conv_wgrad_zring16_kernel,
+                                                                 256, s.lds));
+  } else {
+    ADELL_CHECK_HIP(adell_raise_lds_limit<adell_conv_wgrad_zring_kernel>());
+    ADELL_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, adell_conv_wgrad_zring_kernel,
+                                                                 256, s.lds));
+  }
+  return n;
+}
+
 int adell_wgrad_zring_launch(const adell_conv3d_desc& d, const WgradZrPlan& p, const float* x0,
                              const float* x1, const float* dy, float* slabs, float* wsdb,
                              const unsigned* xmax, const unsigned* ymax, hipStream_t st,
-                             const int* xk0, const int* xk1) {
+                             const int* xk0, const int* xk1, int share) {
   WgradZrArgs a = {};
   a.x0 = x0; a.x1 = x1; a.dy = dy; a.ws = slabs; a.wsdb = wsdb; a.xmax = xmax; a.ymax = ymax;
   a.xk0 = xk0; a.xk1 = xk1;
@@ -716,12 +792,11 @@ int adell_wgrad_zring_launch(const adell_conv3d_desc& d, const WgradZrPlan& p, c
   a.nci = p.nci; a.nco = p.nco; a.R = p.R;
   a.dbg = g_adell_tune.zr_dbg;
   const dim3 grid((unsigned)p.R, (unsigned)(p.nci * p.nco));
+  const size_t lds = adell_wgrad_zring_share(d, p, share).lds;  // (no hint: what the kernel uses)
   if (p.t16) {
-    const size_t lds16 = 2 * (ZR_SLOTS * (size_t)Z16_XPLANE + 2 * (size_t)Z16_YPLANE);
-    hipLaunchKernelGGL(adell_conv_wgrad_zring16_kernel, grid, dim3(256), lds16, st, a);
+    hipLaunchKernelGGL(adell_conv_wgrad_zring16_kernel, grid, dim3(256), lds, st, a);
     ADELL_CHECK_HIP(hipGetLastError());
     return ADELL_OK;
   }
-  const size_t lds = ZR_SLOTS * (size_t)ZR_PLANE + 2 * (size_t)ZR_YBUF;
   return adell_launch<adell_conv_wgrad_zring_kernel>(grid, dim3(256), lds, st, a);
 }

@@ -43,6 +43,10 @@ FLAGS = {"s2class_always": bool(os.environ.get("ADELL_S2CLASS_ALWAYS")),
          # weight gradients of the convolutions / linear layers on a second HIP stream (side_run);
          # ADELL_WGRAD_STREAM=0 keeps every launch on the caller's stream
          "wgrad_stream": os.environ.get("ADELL_WGRAD_STREAM", "1") != "0",
+         # a conv weight gradient that runs on the side stream tells the library so (the share hint
+         # of ops.conv3d_bwd_weight: one z-ring block per CU, the other half of the CU stays with the
+         # main stream's kernels); ADELL_NO_WGRAD_SHARE=1: no hint, two blocks per CU (A/B)
+         "no_wgrad_share": bool(os.environ.get("ADELL_NO_WGRAD_SHARE")),
          # an ADN output whose only reader is a 3x3x3 stride-1 conv is written as SPLIT ROWS (the
          # conv kernels' LDS row image: ops.SplitRows) instead of fp32; ADELL_NO_ROWS=1: always fp32
          "no_rows": bool(os.environ.get("ADELL_NO_ROWS")),
@@ -762,7 +766,7 @@ class _Conv3dFn(torch.autograd.Function):
         want_db = has_bias and need[3]
         wroute = conv3d_wgrad_route(call.route, need[2], want_db)
 
-        def weight_grads():
+        def weight_grads(on_side=False):
             db = None
             if wroute == "conv1_small":
                 dw, db = ops.conv1_small_bwd_weight(x0, x1, dy, want_db)
@@ -773,7 +777,8 @@ class _Conv3dFn(torch.autograd.Function):
                 dw = ops.conv3d_bwd_weight(x0, dy, k, stride, padding, x1=x1, want_db=want_db,
                                            f16x3=wroute == "igemm_f16x3",
                                            x_amax=None if amax is None else amax[0:1],
-                                           dy_amax=dy_amax, rows0=ctx.rows[0], rows1=ctx.rows[1])
+                                           dy_amax=dy_amax, rows0=ctx.rows[0], rows1=ctx.rows[1],
+                                           share=on_side and not FLAGS["no_wgrad_share"])
                 if want_db:
                     dw, db = dw
             elif wroute == "bias_only":
@@ -783,7 +788,7 @@ class _Conv3dFn(torch.autograd.Function):
             return (dw.view(weight.shape) if need[2] else None), db
 
         if wroute is not None:
-            dw, db = (side_run(weight_grads, (x0, x1, dy))
+            dw, db = (side_run(lambda: weight_grads(on_side=True), (x0, x1, dy))
                       if _side_ok(wref.obj, ctx.bias_ref.obj) else weight_grads())
         if add0 is not None and dx0 is not None:   # a route without the fused add
             dx0 = dx0 + add0

@@ -786,12 +786,34 @@ def conv3d_bwd_weight_plan(N, in_size, C0, C1, Cout, kernel, stride, padding):
                      tuple(o[13:16]), tuple(o[16:24]) if route.startswith("zring") else None, o[24])
 
 
+# what the z-ring weight gradient does with a share hint (adell_wgrad_zring_share_plan): zring: the
+# eight ints of adell_wgrad_zring_plan; blocks_per_cu: resident blocks the launch is sized for (1: the
+# hint was accepted); lds: dynamic LDS bytes it requests; room: LDS bytes of a CU left to another
+# kernel's blocks beside them
+WgradSharePlan = collections.namedtuple("WgradSharePlan", "zring blocks_per_cu lds room")
+
+
+def conv3d_bwd_weight_share_plan(N, in_size, C0, C1, Cout, kernel, stride, padding, share):
+    """The z-ring launch of conv3d_bwd_weight(f16x3=True, share=share); None when another kernel
+    serves the problem. Host only: no GPU needed."""
+    d = make_conv_desc(N, tuple(in_size), C0, C1, Cout, kernel, stride, padding)
+    out = (ctypes.c_int * 11)()
+    if not _lib.lib().adell_wgrad_zring_share_plan(ctypes.byref(d), int(share), out):
+        return None
+    o = list(out)
+    return WgradSharePlan(tuple(o[:8]), o[8], o[9], o[10])
+
+
 def conv3d_bwd_weight(x0, dy, kernel, stride, padding, x1=None, want_db=False, f16x3=False,
-                      x_amax=None, dy_amax=None, rows0=None, rows1=None):
+                      x_amax=None, dy_amax=None, rows0=None, rows1=None, share=False):
     """dW in torch's canonical [Cout, Cin, kD, kH, kW] layout (and db when want_db).
     f16x3: error-compensated f16 MFMA instead of the fp32 MFMA. ``rows0`` / ``rows1``
     (SplitRows): that source holds split rows (converted back when the kernel that serves the
-    problem cannot read them: ROWS_FALLBACKS)."""
+    problem cannot read them: ROWS_FALLBACKS). ``share`` (f16x3 only): the launch runs beside
+    another stream's kernels -- the z-ring kernel then leaves half of every CU to them
+    (ADELL_WGRAD_SHARE_* of include/adell_hip.h; ``conv3d_bwd_weight_share_plan`` says what a hint
+    does to a problem); the same bits either way. True: where the library expects it to pay (_AUTO);
+    2: wherever the kernel form allows it (_ALWAYS)."""
     _require_cuda(x0, x1, dy)
     if rows0 is not None or rows1 is not None:
         ok = f16x3 and conv3d_bwd_weight_rows_ok(
@@ -824,17 +846,23 @@ def conv3d_bwd_weight(x0, dy, kernel, stride, padding, x1=None, want_db=False, f
     ws = _workspace(nbytes, x0.device)
     dw = torch.empty((Cout, C0 + C1, *k), device=x0.device, dtype=torch.float32)
     db = torch.empty((Cout,), device=x0.device, dtype=torch.float32) if want_db else None
+    # (no hint: the plain entry points, launch for launch what they always ran)
+    hint = (int(share),) if share and f16x3 else ()
     if rows0 is not None or rows1 is not None:
         # (x_amax: the forward's by-product covers the fp32 source only, as this call needs it)
-        check(_timed(name, _conv_flops(d), lambda: L.adell_conv3d_bwd_weight_f16x3_rows(
+        rows_fn = (L.adell_conv3d_bwd_weight_f16x3_rows_share if hint
+                   else L.adell_conv3d_bwd_weight_f16x3_rows)
+        check(_timed(name, _conv_flops(d), lambda: rows_fn(
             ctypes.byref(d), _ptr(x0), None if rows0 is None else _ptr(rows0.xk), _ptr(x1),
             None if rows1 is None else _ptr(rows1.xk), _ptr(dy), _ptr(dw), _ptr(db), _ptr(x_amax),
-            _ptr(dy_amax), _ptr(ws), ws.numel() * 4, _stream()), _conv_tag(d, "wgrad"),
+            _ptr(dy_amax), _ptr(ws), ws.numel() * 4, _stream(), *hint), _conv_tag(d, "wgrad"),
                      _conv_bytes(d)))
     elif f16x3:
+        if hint:
+            fn = L.adell_conv3d_bwd_weight_f16x3_share
         check(_timed(name, _conv_flops(d), lambda: fn(
             ctypes.byref(d), _ptr(x0), _ptr(x1), _ptr(dy), _ptr(dw), _ptr(db), _ptr(x_amax),
-            _ptr(dy_amax), _ptr(ws), ws.numel() * 4, _stream()), _conv_tag(d, "wgrad"),
+            _ptr(dy_amax), _ptr(ws), ws.numel() * 4, _stream(), *hint), _conv_tag(d, "wgrad"),
                      _conv_bytes(d)))
     else:
         check(_timed(name, _conv_flops(d), lambda: fn(

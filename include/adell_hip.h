@@ -265,6 +265,34 @@ int adell_conv3d_bwd_weight_f16x3_rows(const adell_conv3d_desc* d, const void* x
                                        float* db, const uint32_t* x_absmax,
                                        const uint32_t* dy_absmax, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* The two calls above with a share hint: what the caller knows about the streams around this one
+ * launch (a per-call fact, not an adell_set_tuning switch: no plan, workspace or row count depends on
+ * it, the plan epoch does not move, and dw / db are bit-identical under every hint).
+ *   ADELL_WGRAD_SHARE_NONE    the plain calls, launch for launch;
+ *   ADELL_WGRAD_SHARE_AUTO    other streams have kernels to run beside this launch: the 32 x 32 z-ring
+ *                             kernel, whose two blocks per CU otherwise hold every CU until the launch
+ *                             ends, requests enough dynamic LDS that ONE block per CU runs and an
+ *                             implicit-GEMM block or the norm / activation kernels' waves fit beside
+ *                             it. The library refuses the hint (and launches as the plain call) on
+ *                             every other route, for the 16 x 16 z-ring form, for launches with no
+ *                             more blocks than CUs, and for launches whose blocks march fewer than
+ *                             96 planes (beside those it measured no gain or a loss);
+ *   ADELL_WGRAD_SHARE_ALWAYS  the same without the two size conditions (tests, measurements).
+ * adell_wgrad_zring_share_plan says what a hint does to a problem. */
+#define ADELL_WGRAD_SHARE_NONE 0
+#define ADELL_WGRAD_SHARE_AUTO 1
+#define ADELL_WGRAD_SHARE_ALWAYS 2
+int adell_conv3d_bwd_weight_f16x3_share(const adell_conv3d_desc* d, const float* x0,
+                                        const float* x1, const float* dy, float* dw, float* db,
+                                        const uint32_t* x_absmax, const uint32_t* dy_absmax,
+                                        void* workspace, size_t workspace_bytes, void* stream,
+                                        int share);
+int adell_conv3d_bwd_weight_f16x3_rows_share(const adell_conv3d_desc* d, const void* x0,
+                                             const int* xk0, const void* x1, const int* xk1,
+                                             const float* dy, float* dw, float* db,
+                                             const uint32_t* x_absmax, const uint32_t* dy_absmax,
+                                             void* workspace, size_t workspace_bytes, void* stream,
+                                             int share);
 /* Launch plan of adell_conv3d_bwd_weight_f16x3 (and _rows), host only (no launch, no tensor read, no
  * device needed): what the call would run under the current tuning switches, from the same plan the
  * launch, the workspace query and _rows_ok read. Returns ADELL_OK, or ADELL_E_UNSUPPORTED when no
@@ -1550,6 +1578,16 @@ int adell_dwconv3d_plan(int pass, int N, int C, int D, int H, int W, int KD, int
  * when adell_conv3d_bwd_weight_f16x3 runs the layer on the per-plane kernel instead. */
 int adell_wgrad_zring_plan(int N, int D, int H, int W, int C0, int C1, int Cout, int KD, int KH,
                            int KW, int SD, int SH, int SW, int Do, int Ho, int Wo, int* plan);
+/* The same for a descriptor under a share hint (ADELL_WGRAD_SHARE_*), host only: returns 1 and fills
+ * out[11] = {the plan[8] above -- no hint changes it --, [8] resident blocks per CU the launch is sized
+ * for (1: the hint is accepted; else 2, or 3 for the 16 x 16 form), [9] dynamic LDS bytes it requests,
+ * [10] LDS bytes of a CU those blocks leave to another kernel's}, or 0 when the z-ring kernel does not
+ * serve d. An accepted request is the smallest LDS allocation of which two exceed a CU's LDS; it is
+ * accepted only while the largest specialised implicit-GEMM block (78 400 B) fits in [10]. */
+int adell_wgrad_zring_share_plan(const adell_conv3d_desc* d, int share, int* out);
+/* Blocks per CU the runtime's occupancy calculator gives that launch (needs a device, runs no kernel);
+ * a negative ADELL_E_* when the z-ring kernel does not serve d. */
+int adell_wgrad_zring_occupancy(const adell_conv3d_desc* d, int share);
 
 /* Layer scale folded into a Linear layer's parameters (ConvNeXtBlock3d, res_blocks.py:588-604:
  * gamma * (h W^T + b) = h (gamma W)^T + gamma b): W2[c][k] = gamma[c] W[c][k], b2[c] = gamma[c] b[c]
