@@ -259,6 +259,17 @@ SIGNATURES = {
     "adell_mil_pool_bwd": (_i, [_i] + [_vp] * 9 + [_i] * 4 + [_vp] * 7),
     "adell_mil_slice_tokens_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "adell_mil_slice_tokens_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_det_table_blocks": (_l, [_l]),
+    "adell_det_positive_table": (_i, [_vp] + [_i] * 9 + [_f] + [_vp] * 4),
+    "adell_det_loss_partials": (_l, [_l]),
+    "adell_det_loss_fwd": (_i, [_vp] * 7 + [_f] * 3 + [_i] * 9 + [_vp] * 4),
+    "adell_det_loss_bwd": (_i, [_vp] * 7 + [_f] * 3 + [_i] * 9 + [_vp] * 5),
+    "adell_det_nms_max": (_i, []),
+    "adell_det_nms": (_i, [_vp, _i, _f, _vp, _vp, _vp]),
+    "adell_det_decode": (_i, [_vp] * 4 + [_i] + [_vp] * 3 + [_f] * 3 + [_i] * 6 + [_vp] * 5),
+    "adell_det_match": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "adell_det_encode": (_i, [_vp] * 4 + [ctypes.c_double] * 4 + [_i] * 6 + [_vp, _vp]),
+    "adell_adamw_amsgrad_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _l, _f, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -170,13 +170,23 @@ _KINDS = {
 
 
 class _Binary(ClassMetric):
+    """``threshold``: a probability counts as class 1 when ``p > threshold``. The default 0.5 is the
+    update kernel's own comparison; another value thresholds the probabilities first."""
+
     kind = None
 
-    def __init__(self, beta: float = 1.0):
+    def __init__(self, beta: float = 1.0, threshold: float = 0.5):
         super().__init__(2)
         if not beta > 0:
             raise ValueError(f"{type(self).__name__}: beta must be positive, got {beta}")
         self.beta = float(beta)
+        self.threshold = float(threshold)
+
+    def _prepare(self, preds):
+        if self.threshold != 0.5 and preds.is_floating_point() and (
+                preds.dim() == 1 or (preds.dim() == 2 and preds.shape[1] == 1)):
+            return (preds.detach().reshape(-1) > self.threshold).to(torch.int64)
+        return super()._prepare(preds)
 
     def _value(self, M):
         return _KINDS[self.kind](*_class_counts(M), self.beta ** 2)[1]
@@ -197,8 +207,8 @@ class BinaryPrecision(_Binary):
 class BinaryFBetaScore(_Binary):
     kind = "fbeta"
 
-    def __init__(self, beta: float):
-        super().__init__(beta)
+    def __init__(self, beta: float, threshold: float = 0.5):
+        super().__init__(beta, threshold)
 
 
 class _Multiclass(ClassMetric):
@@ -403,7 +413,7 @@ def update_many(metrics, preds, target):
     shared = {}
     for m in metrics:
         if isinstance(m, ClassMetric):
-            key = (m.num_classes, m.ordinal)
+            key = (m.num_classes, m.ordinal, getattr(m, "threshold", 0.5))
             if key not in shared:
                 shared[key] = _confusion_delta(m._prepare(preds), target, m.num_classes)
             m._add(shared[key])

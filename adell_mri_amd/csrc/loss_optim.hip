@@ -415,6 +415,44 @@ extern "C" int adell_adam_step(float* param, const float* grad, float* exp_avg,
                            weight_decay, step, grad_scale, stream);
 }
 
+// torch.optim.AdamW(amsgrad=True): vmax = max(vmax, v) kept beside v, the denominator from vmax.
+__global__ __launch_bounds__(256) void adell_adamw_amsgrad_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    float* __restrict__ vmax, long n, float lr, float b1, float b2, float eps, float wd, float bc1,
+    float bc2_sqrt, float grad_scale) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+    const float gi = g[i] * grad_scale;
+    float pi = p[i] * (1.0f - lr * wd);
+    const float mi = b1 * m[i] + (1.0f - b1) * gi;
+    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    const float vm = fmaxf(vmax[i], vi);
+    m[i] = mi;
+    v[i] = vi;
+    vmax[i] = vm;
+    const float denom = sqrtf(vm) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    p[i] = pi;
+  }
+}
+
+extern "C" int adell_adamw_amsgrad_step(float* param, const float* grad, float* exp_avg,
+                                        float* exp_avg_sq, float* max_exp_avg_sq, long n, float lr,
+                                        float beta1, float beta2, float eps, float weight_decay,
+                                        long step, float grad_scale, void* stream) {
+  ADELL_REQUIRE(param && grad && exp_avg && exp_avg_sq && max_exp_avg_sq,
+                "adamw_amsgrad_step: null pointer");
+  ADELL_REQUIRE(n > 0 && step >= 1, "adamw_amsgrad_step: bad n / step");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(adell_adamw_amsgrad_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, lr,
+                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
+  ADELL_CHECK_HIP(hipGetLastError());
+  return ADELL_OK;
+}
+
 __global__ __launch_bounds__(256) void adell_ema_kernel(float* __restrict__ shadow,
                                                         const float* __restrict__ p, long n,
                                                         float one_minus_decay) {

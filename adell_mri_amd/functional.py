@@ -2774,3 +2774,84 @@ def slice_tokens(x, pos=None, class_token=None):
     their sums over the batch in order in fp64."""
     return _SliceTokensFn.apply(x.contiguous(), None if pos is None else pos.contiguous(),
                                 None if class_token is None else class_token.contiguous())
+
+
+# ---- 3-D object detection (csrc/detect.hip) --------------------------------------------------------
+class _DetectionLossFn(torch.autograd.Function):
+    """Saved: the three heads (the network's own outputs, no copy), the table and its count."""
+
+    @staticmethod
+    def forward(ctx, centre, size, obj, target, anchors, corr, iou_threshold, first_channel):
+        table, count = ops.det_positive_table(target, obj.shape[1], iou_threshold, first_channel)
+        out, rows = ops.det_loss_fwd(centre, size, obj, target, anchors, table, count, corr, first_channel)
+        ctx.save_for_backward(centre, size, obj, target, anchors, table, count)
+        ctx.corr, ctx.first_channel = corr, first_channel
+        ctx.mark_non_differentiable(out, rows, table, count)
+        return out[0], out, rows, table, count
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        centre, size, obj, target, anchors, table, count = ctx.saved_tensors
+        dc, ds, do = ops.det_loss_bwd(centre, size, obj, target, anchors, table, count, ctx.corr,
+                                      g.contiguous().view(1), ctx.first_channel)
+        return dc, ds, do, None, None, None, None, None
+
+
+def detection_loss(centre, size, objectness, target, anchors, correction_factor, iou_threshold=0.5,
+                   first_channel=1, return_parts=False):
+    """The loss of ``YOLONet3dPL.step`` with ``complete_iou_loss`` and ``F.binary_cross_entropy`` from
+    the heads as the network returns them -- centre and size [B, 3 A, H, W, D] (anchor a: channels
+    [3 a, 3 a + 3)), objectness [B, A, H, W, D] -- and the anchor map ``target`` [B, first_channel +
+    7 A, H, W, D], all read in place: the positive cells (target objectness > ``iou_threshold``) are
+    tabulated on the device in ``torch.where``'s order, their boxes decoded (cell index added,
+    ``correction_factor`` (three host floats), ``exp(size) * anchor / 2``), complete IoU taken, and the
+    objectness cross-entropy summed against a target of ``iou`` at the positives and 0 elsewhere:
+    ``bce_mean + 0.1 * (mean(1 - iou) + mean(cpd) + mean(ar))``. Fixed-order fp64 sums: two runs are
+    bit-equal. The positive count never leaves the device. With no positive cell the result is NaN,
+    as the reference's means of empty tensors, and the objectness gradient is the cross-entropy's.
+    The backward returns gradients for the three heads, including the cross-entropy's gradient
+    through its TARGET (``iou`` is not detached in the reference). ``return_parts``: also (parts [5] = loss, bce, mean(1 - iou),
+    mean(cpd), mean(ar); rows [4, cells] = iou, cpd, ar, bce correction per positive; table; count)."""
+    corr = tuple(float(v) for v in correction_factor)
+    if len(corr) != 3:
+        raise ValueError(f"detection_loss: three correction factors expected, got {corr}")
+    anchors = anchors.detach().reshape(-1).to(torch.float32).contiguous()
+    loss, parts, rows, table, count = _DetectionLossFn.apply(
+        centre, size, objectness, target, anchors, corr, float(iou_threshold), int(first_channel))
+    if return_parts:
+        return loss, parts, rows, table, count
+    return loss
+
+
+def detection_nms(boxes, scores, score_threshold, iou_threshold=0.5):
+    """``nms_nd(..., suppress=True)`` on the device: the indices into ``boxes`` [n, 6] that survive,
+    in descending score order. Scores are thresholded and sorted by torch on the device (a stable
+    sort of the reference's flipped ascending order), the pairwise mask and the sweep are HIP;
+    the candidate count is read once on the host."""
+    idx = torch.nonzero(scores > score_threshold).flatten()
+    # argsort(scores).flip(0) of the reference: ascending stable order reversed
+    order = torch.argsort(scores[idx], stable=True).flip(0)
+    idx = idx[order]
+    if idx.numel() == 0:
+        return idx
+    if idx.numel() > ops.det_nms_max():
+        raise ValueError(f"detection_nms: {idx.numel()} candidates above the score threshold, at most "
+                         f"{ops.det_nms_max()}")
+    keep = ops.det_nms_keep(boxes[idx].to(torch.float32).contiguous(), iou_threshold)
+    return idx[keep.bool()]
+
+
+def detection_decode(centre, size, objectness, class_pred, anchors, correction_factor=None):
+    """``YOLONet3d.recover_boxes`` before its NMS / top-1000 tail for a whole batch, from the heads in
+    place: per image the cells with objectness > 0.5 in ``torch.where``'s order -> a list of
+    (boxes [n, 6], scores [n], classes [n, C] or [n]); ``class_pred`` None: the classes are the
+    objectness values (the reference's ``n_classes == 2``). Four launches, one host read (the
+    per-image row ranges)."""
+    A = objectness.shape[1]
+    corr = (1.0, 1.0, 1.0) if correction_factor is None else tuple(float(v) for v in correction_factor)
+    anchors = anchors.detach().reshape(-1).to(torch.float32).contiguous()
+    table, count = ops.det_positive_table(objectness, A, 0.5, 0, 1)
+    boxes, scores, classes, starts = ops.det_decode(centre, size, objectness, class_pred, anchors, table,
+                                                    count, corr)
+    st = starts.tolist()
+    return [(boxes[lo:hi], scores[lo:hi], classes[lo:hi]) for lo, hi in zip(st[:-1], st[1:])]

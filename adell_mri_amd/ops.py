@@ -3935,3 +3935,228 @@ def resize_linear(x, size):
     check(_lib.lib().adell_interp_linear_fwd(_ptr(x), _ptr(y), N, C, Di, Hi, Wi, Do, Ho, Wo,
                                              Do / Di, Ho / Hi, Wo / Wi, 0, _stream()))
     return y
+
+
+# ---- 3-D object detection (csrc/detect.hip) -----------------------------------------------------
+def _det_layout(what, *ts):
+    """0 when every tensor is dense row-major, 1 when every one is dense channels-last (the layout
+    the conv kernels produce: [B, C, H, W, D] logical, [B, H, W, D, C] in memory); anything else --
+    a view with gaps, a mix -- is refused, whatever ADELL_CHECK_DENSE says."""
+    ts = [t for t in ts if t is not None]
+    if all(t.is_contiguous() for t in ts):
+        return 0
+    if all(t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d) for t in ts):
+        return 1
+    raise _lib.AdellHipError(f"{what}: non-dense tensor (or a mix of layouts) handed to a kernel: "
+                             + ", ".join(f"shape {tuple(t.shape)} strides {t.stride()}" for t in ts))
+
+
+def _det_dense(what, *ts, dtype=torch.float32, layouts=False):
+    """Device tensors of ``dtype``, dense row-major (``layouts``: or dense channels-last, checked by
+    ``_det_layout``): these kernels index from the shape alone."""
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels run on MI355X only: got a CPU "
+                                     "tensor (no CPU fallback)")
+        if t.dtype != dtype:
+            raise _lib.AdellHipError(f"{what}: {dtype} expected, got {t.dtype}")
+        if not t.is_contiguous() and not (
+                layouts and t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d)):
+            raise _lib.AdellHipError(f"{what}: non-dense tensor handed to a kernel: shape "
+                                     f"{tuple(t.shape)}, strides {t.stride()}")
+
+
+def _det_grid(what, obj_like, n_anchors, per_anchor):
+    if obj_like.dim() != 5:
+        raise ValueError(f"{what}: a [B, C, H, W, D] map expected, got {tuple(obj_like.shape)}")
+    B, C, H, W, D = (int(v) for v in obj_like.shape)
+    A = int(n_anchors)
+    if A < 1 or B < 1 or H * W * D < 1:
+        raise ValueError(f"{what}: empty grid {tuple(obj_like.shape)} with {A} anchors")
+    return B, C, H, W, D, A
+
+
+def det_positive_table(target, n_anchors, threshold, first_channel=1, per_anchor=7):
+    """(table int32 [B A H W D, 5], count int32 [1]): the rows (b, h, w, d, a) of the cells of
+    ``target`` [B, first_channel + per_anchor * A, H, W, D] whose objectness channel
+    (``first_channel + per_anchor * a``) is > ``threshold``, in ``torch.where``'s order on the stacked
+    [B, H, W, D, A] view; rows beyond ``count`` are not written. Three launches, no host read."""
+    what = "det_positive_table"
+    _det_dense(what, target, layouts=True)
+    B, C, H, W, D, A = _det_grid(what, target, n_anchors, per_anchor)
+    if per_anchor not in (1, 7) or first_channel < 0 or first_channel + per_anchor * A > C:
+        raise ValueError(f"{what}: {C} channels cannot hold {A} anchors of {per_anchor} from channel "
+                         f"{first_channel}")
+    cells = B * A * H * W * D
+    table = torch.empty((cells, 5), device=target.device, dtype=torch.int32)
+    count = torch.empty((1,), device=target.device, dtype=torch.int32)
+    scratch = torch.empty((int(_lib.lib().adell_det_table_blocks(cells)),), device=target.device,
+                          dtype=torch.int32)
+    check(_lib.lib().adell_det_positive_table(_ptr(target), B, A, H, W, D, C, int(first_channel),
+                                              int(per_anchor), _det_layout(what, target),
+                                              float(threshold), _ptr(scratch),
+                                              _ptr(table), _ptr(count), _stream()))
+    return table, count
+
+
+def _det_heads(what, centre, size, obj, target, anchors, table, count, first_channel):
+    _det_dense(what, centre, size, obj, target, layouts=True)
+    _det_dense(what, anchors)
+    _det_dense(what, table, count, dtype=torch.int32)
+    B, A, H, W, D = (int(v) for v in obj.shape) if obj.dim() == 5 else (0,) * 5
+    if obj.dim() != 5 or tuple(centre.shape) != (B, 3 * A, H, W, D) or tuple(size.shape) != tuple(centre.shape):
+        raise ValueError(f"{what}: centre and size [B, 3 A, H, W, D] and objectness [B, A, H, W, D] "
+                         f"expected, got {tuple(centre.shape)}, {tuple(size.shape)}, {tuple(obj.shape)}")
+    if anchors.numel() != 3 * A:
+        raise ValueError(f"{what}: {A} anchors of 3 sizes expected, got {tuple(anchors.shape)}")
+    if tuple(table.shape) != (B * A * H * W * D, 5) or count.numel() != 1:
+        raise ValueError(f"{what}: the table of det_positive_table for this grid expected, got "
+                         f"{tuple(table.shape)}")
+    Ct = 0
+    if target is not None:
+        Ct = int(target.shape[1])
+        if target.dim() != 5 or tuple(target.shape) != (B, Ct, H, W, D) or first_channel < 0 \
+                or first_channel + 7 * A > Ct:
+            raise ValueError(f"{what}: target [B, {first_channel} + 7 A, H, W, D] expected, got "
+                             f"{tuple(target.shape)}")
+    return B, A, H, W, D, Ct, _det_layout(what, target), _det_layout(what, centre, size, obj)
+
+
+def det_loss_fwd(centre, size, obj, target, anchors, table, count, corr, first_channel=1):
+    """(out [5] = loss, bce mean, mean(1 - iou), mean(cpd), mean(ar); rows [4, cells] = iou, cpd, ar
+    and the cross-entropy correction of every positive, valid up to ``count``). Two launches."""
+    what = "det_loss_fwd"
+    B, A, H, W, D, Ct, cl_t, cl_h = _det_heads(what, centre, size, obj, target, anchors, table, count,
+                                               first_channel)
+    cells = B * A * H * W * D
+    dev = obj.device
+    partial = torch.empty((int(_lib.lib().adell_det_loss_partials(cells)),), device=dev, dtype=torch.float64)
+    rows = torch.empty((4, cells), device=dev, dtype=torch.float32)
+    out = torch.empty((5,), device=dev, dtype=torch.float32)
+    check(_lib.lib().adell_det_loss_fwd(_ptr(centre), _ptr(size), _ptr(obj), _ptr(target), _ptr(anchors),
+                                        _ptr(table), _ptr(count), float(corr[0]), float(corr[1]),
+                                        float(corr[2]), B, A, H, W, D, Ct, int(first_channel),
+                                        cl_t, cl_h, _ptr(partial), _ptr(rows), _ptr(out), _stream()))
+    return out, rows
+
+
+def det_loss_bwd(centre, size, obj, target, anchors, table, count, corr, grad_out, first_channel=1):
+    """(dcentre, dsize, dobj) of ``det_loss_fwd``'s loss times ``grad_out`` [1] (device); written
+    whole, two launches."""
+    what = "det_loss_bwd"
+    B, A, H, W, D, Ct, cl_t, cl_h = _det_heads(what, centre, size, obj, target, anchors, table, count,
+                                               first_channel)
+    _det_dense(what, grad_out)
+    if grad_out.numel() != 1:
+        raise ValueError(f"{what}: a scalar gradient expected, got {tuple(grad_out.shape)}")
+    # the gradients take the heads' layout: the dense pass walks memory, not indices
+    fmt = torch.channels_last_3d if cl_h else torch.contiguous_format
+    dcentre, dsize, dobj = (torch.empty(t.shape, device=t.device, dtype=t.dtype, memory_format=fmt)
+                            for t in (centre, size, obj))
+    check(_lib.lib().adell_det_loss_bwd(_ptr(centre), _ptr(size), _ptr(obj), _ptr(target), _ptr(anchors),
+                                        _ptr(table), _ptr(count), float(corr[0]), float(corr[1]),
+                                        float(corr[2]), B, A, H, W, D, Ct, int(first_channel),
+                                        cl_t, cl_h, _ptr(grad_out), _ptr(dcentre),
+                                        _ptr(dsize), _ptr(dobj), _stream()))
+    return dcentre, dsize, dobj
+
+
+def det_nms_max():
+    return int(_lib.lib().adell_det_nms_max())
+
+
+def det_nms_keep(boxes, iou_threshold):
+    """keep int32 [n] (1: survives) of the greedy sweep over ``boxes`` [n, 6], which are sorted by
+    descending score: candidate j > i goes when i is kept, ``check_overlap(i, j)`` and
+    ``calculate_iou(i, j) > iou_threshold``. Two launches."""
+    what = "det_nms_keep"
+    _det_dense(what, boxes)
+    if boxes.dim() != 2 or boxes.shape[1] != 6:
+        raise ValueError(f"{what}: boxes [n, 6] expected, got {tuple(boxes.shape)}")
+    n = int(boxes.shape[0])
+    if n > det_nms_max():
+        raise ValueError(f"{what}: {n} candidates, at most {det_nms_max()}")
+    keep = torch.empty((n,), device=boxes.device, dtype=torch.int32)
+    if n:
+        mask = torch.empty((n * ((n + 63) // 64),), device=boxes.device, dtype=torch.int64)
+        check(_lib.lib().adell_det_nms(_ptr(boxes), n, float(iou_threshold), _ptr(mask), _ptr(keep),
+                                       _stream()))
+    return keep
+
+
+def det_decode(centre, size, obj, cls, anchors, table, count, corr):
+    """(boxes [cells, 6], scores [cells], classes [cells, NC] or [cells], starts int32 [B + 1]) of the
+    cells in ``table`` (objectness > 0.5, ``det_positive_table(obj, A, 0.5, 0, 1)``); rows beyond
+    ``starts[B]`` are not written. ``cls`` None: the classes are the objectness. One launch."""
+    what = "det_decode"
+    B, A, H, W, D, _, _, cl_h = _det_heads(what, centre, size, obj, None, anchors, table, count, 0)
+    NC = 0
+    if cls is not None:
+        _det_dense(what, cls, layouts=True)
+        cl_h = _det_layout(what, centre, size, obj, cls)
+        NC = int(cls.shape[1])
+        if tuple(cls.shape) != (B, NC, H, W, D) or NC < 1:
+            raise ValueError(f"{what}: class head [B, C, H, W, D] expected, got {tuple(cls.shape)}")
+    cells, dev = B * A * H * W * D, obj.device
+    boxes = torch.empty((cells, 6), device=dev, dtype=torch.float32)
+    scores = torch.empty((cells,), device=dev, dtype=torch.float32)
+    classes = torch.empty((cells, NC) if NC else (cells,), device=dev, dtype=torch.float32)
+    starts = torch.empty((B + 1,), device=dev, dtype=torch.int32)
+    check(_lib.lib().adell_det_decode(_ptr(centre), _ptr(size), _ptr(obj), _ptr(cls), NC, _ptr(anchors),
+                                      _ptr(table), _ptr(count), float(corr[0]), float(corr[1]),
+                                      float(corr[2]), B, A, H, W, D, cl_h, _ptr(boxes), _ptr(scores),
+                                      _ptr(classes), _ptr(starts), _stream()))
+    return boxes, scores, classes, starts
+
+
+def det_match(targets, target_image, preds, pred_start):
+    """(best int32 [T], iou [T]): for target box t of image ``target_image[t]`` the prediction among
+    ``preds[pred_start[img]:pred_start[img + 1]]`` with the highest IoU of the overlapping ones, its
+    index within the image (lowest on a tie; 0 with IoU 0 when none overlaps; -1 without predictions)."""
+    what = "det_match"
+    _det_dense(what, targets, preds)
+    _det_dense(what, target_image, pred_start, dtype=torch.int32)
+    T = int(targets.shape[0])
+    if targets.dim() != 2 or targets.shape[1] != 6 or preds.dim() != 2 or preds.shape[1] != 6 \
+            or target_image.numel() != T:
+        raise ValueError(f"{what}: targets [T, 6], their images [T] and predictions [P, 6] expected")
+    best = torch.empty((T,), device=targets.device, dtype=torch.int32)
+    iou = torch.empty((T,), device=targets.device, dtype=torch.float32)
+    if T:
+        check(_lib.lib().adell_det_match(_ptr(targets), _ptr(target_image), T, _ptr(preds),
+                                         _ptr(pred_start), _ptr(best), _ptr(iou), _stream()))
+    return best, iou
+
+
+def det_encode(boxes, classes, counts, half, rel, thresh, output_sh):
+    """The anchor maps [B, 1 + 7 A, *output_sh] (fp64) of padded boxes [B, N, 6], classes [B, N] and
+    counts [B] (int32): ``BBToAdjustedAnchors.__call__`` per item. ``half`` [A, 3] fp64 = anchor /
+    rel_sh / 2, ``rel`` the three input / output ratios the boxes are divided by. One launch."""
+    what = "det_encode"
+    _det_dense(what, boxes, classes, half, dtype=torch.float64)
+    _det_dense(what, counts, dtype=torch.int32)
+    if boxes.dim() != 3 or boxes.shape[2] != 6 or tuple(classes.shape) != tuple(boxes.shape[:2]) \
+            or counts.numel() != boxes.shape[0] or half.dim() != 2 or half.shape[1] != 3:
+        raise ValueError(f"{what}: boxes [B, N, 6], classes [B, N], counts [B], half [A, 3] expected, got "
+                         f"{tuple(boxes.shape)}, {tuple(classes.shape)}, {tuple(counts.shape)}, "
+                         f"{tuple(half.shape)}")
+    B, N, A = int(boxes.shape[0]), int(boxes.shape[1]), int(half.shape[0])
+    H, W, D = (int(v) for v in output_sh)
+    out = torch.empty((B, 1 + 7 * A, H, W, D), device=counts.device, dtype=torch.float64)
+    check(_lib.lib().adell_det_encode(_ptr(boxes) if N else None, _ptr(classes) if N else None,
+                                      _ptr(counts), _ptr(half), float(rel[0]), float(rel[1]),
+                                      float(rel[2]), float(thresh), B, N, A, H, W, D, _ptr(out),
+                                      _stream()))
+    return out
+
+
+def adamw_amsgrad_step(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps,
+                       weight_decay, step, grad_scale=1.0):
+    """torch.optim.AdamW(amsgrad=True) over one flat run; one launch."""
+    _require_cuda(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq)
+    check(_lib.lib().adell_adamw_amsgrad_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                              _ptr(max_exp_avg_sq), param.numel(), lr, beta1, beta2,
+                                              eps, weight_decay, int(step), grad_scale, _stream()))
+    _weights_changed()

@@ -436,22 +436,42 @@ class FusedSGD(_FusedBase):
 
 
 class FusedAdamW(_FusedBase):
-    decoupled = True
-    _state_names = ("exp_avg", "exp_avg_sq")
+    """``amsgrad=True`` (``torch.optim.AdamW(amsgrad=True)``, the detection wrapper's optimiser) keeps
+    ``max_exp_avg_sq`` beside the two moments and takes the denominator from it: its own kernel entry;
+    the state_dict carries the extra buffer under torch's name."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    decoupled = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 amsgrad=False):
+        self.amsgrad = bool(amsgrad)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      grad_scale=1.0))
+                                      amsgrad=bool(amsgrad), grad_scale=1.0))
+
+    @property
+    def _state_names(self):
+        return ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ())
 
     def _param_state(self, st, i, o, n, shape):
-        return {"step": torch.tensor(float(st["steps"][i])),
-                "exp_avg": st["exp_avg"][o:o + n].view(shape).clone(),
-                "exp_avg_sq": st["exp_avg_sq"][o:o + n].view(shape).clone()}
+        out = {"step": torch.tensor(float(st["steps"][i]))}
+        for name in self._state_names:
+            out[name] = st[name][o:o + n].view(shape).clone()
+        return out
 
     def _load_param_state(self, gi, st, i, o, n, ent):
-        self._buffer(gi, "exp_avg")[o:o + n].copy_(ent["exp_avg"].reshape(-1))
-        self._buffer(gi, "exp_avg_sq")[o:o + n].copy_(ent["exp_avg_sq"].reshape(-1))
+        for name in self._state_names:
+            self._buffer(gi, name)[o:o + n].copy_(ent[name].reshape(-1))
         st["steps"][i] = int(float(ent["step"]))
+
+    def load_state_dict(self, state_dict):
+        """``amsgrad`` is fixed at construction (it decides which buffers exist): a checkpoint saved
+        with the other setting is refused instead of silently dropping or inventing
+        ``max_exp_avg_sq``."""
+        for saved in state_dict["param_groups"]:
+            if bool(saved.get("amsgrad", False)) != self.amsgrad:
+                raise ValueError(f"{type(self).__name__}(amsgrad={self.amsgrad}) cannot load a state "
+                                 f"saved with amsgrad={bool(saved.get('amsgrad', False))}")
+        super().load_state_dict(state_dict)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -460,11 +480,18 @@ class FusedAdamW(_FusedBase):
         for gi, g in enumerate(self.param_groups):
             flat, st = self._flat(gi), self._flat_state[gi]
             m, v = self._buffer(gi, "exp_avg"), self._buffer(gi, "exp_avg_sq")
+            vmax = self._buffer(gi, "max_exp_avg_sq") if self.amsgrad else None
             active = flat.has_grad()
             st["steps"][active] += 1
             # the bias correction depends on a parameter's own step count (torch keeps one per
             # parameter): one launch per run of equal counts (normally ONE run)
             for i, lo, hi in flat.runs(active, st["steps"]):
+                if vmax is not None:
+                    ops.adamw_amsgrad_step(flat.data[lo:hi], flat.grad[lo:hi], m[lo:hi], v[lo:hi],
+                                           vmax[lo:hi], g["lr"], g["betas"][0], g["betas"][1],
+                                           g["eps"], g["weight_decay"], int(st["steps"][i]),
+                                           g.get("grad_scale", 1.0))
+                    continue
                 ops.adamw_step(flat.data[lo:hi], flat.grad[lo:hi], m[lo:hi], v[lo:hi], g["lr"],
                                g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
                                int(st["steps"][i]), g.get("grad_scale", 1.0),

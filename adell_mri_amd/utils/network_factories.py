@@ -11,10 +11,14 @@ raise ``NotImplementedError`` -- there is no eager-torch fallback.
 """
 from typing import Any, Callable
 
+import numpy as np
 import torch
+import torch.nn.functional as F
 
 from ..modules.classification.pl import ClassNetPL, OrdNetPL, ViTClassifierPL
 from ..modules.layers.adn_fn import get_adn_fn
+from ..modules.object_detection.losses import complete_iou_loss
+from ..modules.object_detection.pl import YOLONet3dPL
 from ..modules.segmentation.pl import (BrUNetPL, SWINUNetPL, UNETRPL, UNetPL,
                                        UNetPlusPlusPL)
 from ..modules.self_supervised.pl import (DINOPL, IJEPAPL, SelfSLConvNeXtPL, SelfSLResNetPL,
@@ -84,6 +88,57 @@ def get_classification_network(
     for k in ["in_channels", "n_classes", "adn_fn"]:
         network_config.pop(k, None)
     return ClassNetPL(net_type=net_type, adn_fn=adn_fn, **boilerplate_args, **network_config)
+
+
+def get_detection_network(
+        network_config: dict[str, Any], dropout_param: float, loss_gamma: float, loss_comb: float,
+        class_weights: torch.Tensor, train_loader_call: Callable, iou_threshold: float, n_classes: int,
+        anchor_array: np.ndarray, n_epochs: int, warmup_steps: int, boxes_key: str, box_class_key: str,
+        dev: str, optimizer_eps: float = OPTIMIZER_EPS_DEFAULT):
+    """network_factories.py:406-489: ``YOLONet3dPL`` with ``complete_iou_loss`` as the box loss, the
+    batch-norm ``adn_fn`` of ``activation_fn`` (default "swish"), ``label_key="bb_map"``, the
+    classification loss ``F.binary_cross_entropy`` / ``F.cross_entropy`` by ``n_classes`` and the
+    objectness loss ``F.binary_cross_entropy``; ``"classification_loss_fn"`` / ``"object_loss_fn"``
+    keys pick from ``loss_factory`` instead, ``batch_size`` defaults to 1, every other key goes to the
+    constructor. As in the reference ``dev`` is not handed on (the network is built on "cuda" unless
+    ``network_config`` carries ``dev``), and with an ``object_loss_fn`` key and all three of
+    ``loss_gamma`` / ``loss_comb`` / ``class_weights`` given it reads ``get_loss_param_dict``, which
+    this package does not have: ``NotImplementedError``."""
+    from .utils import loss_factory
+
+    act_fn = network_config["activation_fn"] if "activation_fn" in network_config else "swish"
+    if "classification_loss_fn" in network_config:
+        k = "binary" if n_classes == 2 else "categorical"
+        classification_loss_fn = loss_factory[k][network_config["classification_loss_fn"]]
+    else:
+        classification_loss_fn = F.binary_cross_entropy if n_classes == 2 else F.cross_entropy
+    if "object_loss_fn" in network_config:
+        object_loss_fn = loss_factory["binary"][network_config["object_loss_fn"]]
+    else:
+        object_loss_fn = F.binary_cross_entropy
+    net_cfg = {k: network_config[k] for k in network_config
+               if k not in ["activation_fn", "classification_loss_fn", "object_loss_fn"]}
+    if "batch_size" not in net_cfg:
+        net_cfg["batch_size"] = 1
+    classification_loss_params = {}
+    if (loss_gamma is None) or (loss_comb is None) or (class_weights is None):
+        object_loss_params = {}
+    elif "object_loss_fn" not in network_config:
+        # the reference reads an unbound ``object_loss_key`` here: UnboundLocalError
+        raise UnboundLocalError("get_detection_network: loss parameters need an 'object_loss_fn' key "
+                                "(the reference fails here too)")
+    else:
+        raise NotImplementedError("get_detection_network: object loss parameters "
+                                  "(get_loss_param_dict) are not built")
+    adn_fn = get_adn_fn(3, norm_fn="batch", act_fn=act_fn, dropout_param=dropout_param)
+    return YOLONet3dPL(
+        training_dataloader_call=train_loader_call, image_key="image", label_key="bb_map",
+        boxes_key=boxes_key, box_label_key=box_class_key, anchor_sizes=anchor_array, adn_fn=adn_fn,
+        iou_threshold=iou_threshold, classification_loss_fn=classification_loss_fn,
+        object_loss_fn=object_loss_fn, reg_loss_fn=complete_iou_loss,
+        object_loss_params=object_loss_params,
+        classification_loss_params=classification_loss_params, n_epochs=n_epochs,
+        warmup_steps=warmup_steps, n_classes=n_classes, optimizer_eps=optimizer_eps, **net_cfg)
 
 
 def get_segmentation_network(

@@ -1084,6 +1084,61 @@ int adell_mil_slice_tokens_fwd(const float* x, const float* pos, const float* cl
 int adell_mil_slice_tokens_bwd(const float* dout, int B, int S, int E, int has_class_token, float* dx,
                                float* dpos, float* dclass_token, void* stream);
 
+/* 3-D object detection (csrc/detect.hip; adell_mri/modules/object_detection). Heads and target map are
+ * read in place, [B][C][H W D] or channels last [B][H W D][C] (the *_cl / channels_last flags; the three
+ * heads and the class head share one): anchor a of a logical [B, k A, ...] tensor is channels [k a, k a + k). target [B][Ct][H W D]
+ * holds, from channel c0 on, 7 channels per anchor: objectness, centre 3, size 3.
+ * adell_det_positive_table: int32 rows (b, h, w, d, a) of the cells with target objectness > threshold in
+ *   torch.where's order on the stacked [B, H, W, D, A] view, capacity B A H W D rows; count [1] stays on
+ *   the device; block_scratch: adell_det_table_blocks(B A H W D) ints. cs: channels per anchor of the
+ *   map, 7 for the target map, 1 when the map is the objectness head itself (box decoding, c0 = 0).
+ * adell_det_loss_fwd: out[5] = loss, bce mean, mean(1 - iou), mean(cpd), mean(ar) of YOLONet3dPL's step
+ *   with complete_iou_loss and binary_cross_entropy (NaN with no positive); rows [4][B A H W D] = iou,
+ *   cpd, ar and the cross-entropy correction per positive; partial: adell_det_loss_partials(B A H W D)
+ *   doubles. cf0..2: the correction factor. adell_det_loss_bwd: grad_out[1] on the device; dcentre,
+ *   dsize, dobj written whole.
+ * adell_det_nms: boxes [n][6] sorted by descending score, n <= adell_det_nms_max(); mask: n ceil(n / 64)
+ *   64-bit words; keep[n] = 1 for a candidate that survives the greedy sweep. */
+long adell_det_table_blocks(long cells);
+int adell_det_positive_table(const float* target, int B, int A, int H, int W, int D, int Ct, int c0,
+                             int cs, int channels_last, float threshold, int* block_scratch, int* table,
+                             int* count, void* stream);
+long adell_det_loss_partials(long cells);
+int adell_det_loss_fwd(const float* centre, const float* size, const float* obj, const float* target,
+                       const float* anchors, const int* table, const int* count, float cf0, float cf1,
+                       float cf2, int B, int A, int H, int W, int D, int Ct, int c0, int target_cl,
+                       int heads_cl, double* partial, float* rows, float* out, void* stream);
+int adell_det_loss_bwd(const float* centre, const float* size, const float* obj, const float* target,
+                       const float* anchors, const int* table, const int* count, float cf0, float cf1,
+                       float cf2, int B, int A, int H, int W, int D, int Ct, int c0, int target_cl,
+                       int heads_cl, const float* grad_out, float* dcentre, float* dsize, float* dobj,
+                       void* stream);
+int adell_det_nms_max(void);
+int adell_det_nms(const float* boxes, int n, float iou_threshold, unsigned long long* mask, int* keep,
+                  void* stream);
+/* adell_det_decode: YOLONet3d.recover_boxes for a batch from the table of objectness > 0.5 (cs = 1):
+ *   boxes [n][6], scores [n], classes [n][NC] (cls [B][NC][H W D]; NULL: classes [n] = the objectness),
+ *   starts [B + 1] = first row of every image and n.
+ * adell_det_match: per target box t of image target_image[t] the prediction of that image
+ *   (preds[pred_start[img] .. pred_start[img + 1])) with the highest IoU among the overlapping ones, the
+ *   lowest index on a tie (0 and IoU 0 when none overlaps, -1 when the image has no prediction).
+ * adell_det_encode: BBToAdjustedAnchors for a batch in fp64: boxes [B][N][6], classes [B][N],
+ *   counts [B], half [A][3] = anchor / rel_sh / 2, rel0..2 the boxes' input / output shape ratio ->
+ *   out [B][1 + 7 A][H W D]. */
+int adell_det_decode(const float* centre, const float* size, const float* obj, const float* cls, int NC,
+                     const float* anchors, const int* table, const int* count, float cf0, float cf1,
+                     float cf2, int B, int A, int H, int W, int D, int heads_cl, float* boxes,
+                     float* scores, float* classes, int* starts, void* stream);
+int adell_det_match(const float* targets, const int* target_image, int T, const float* preds,
+                    const int* pred_start, int* best, float* best_iou, void* stream);
+int adell_det_encode(const double* boxes, const double* classes, const int* counts, const double* half,
+                     double rel0, double rel1, double rel2, double thresh, int B, int N, int A, int H,
+                     int W, int D, double* out, void* stream);
+/* torch.optim.AdamW(amsgrad=True): adell_adamw_step with max_exp_avg_sq kept and used in the denominator. */
+int adell_adamw_amsgrad_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                             float* max_exp_avg_sq, long n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, long step, float grad_scale, void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
