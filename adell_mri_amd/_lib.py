@@ -270,6 +270,16 @@ SIGNATURES = {
     "adell_det_match": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "adell_det_encode": (_i, [_vp] * 4 + [ctypes.c_double] * 4 + [_i] * 6 + [_vp, _vp]),
     "adell_adamw_amsgrad_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _l, _f, _vp]),
+    "adell_eca_gates_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _vp]),
+    "adell_eca_gates_bwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
+    "adell_eca_apply_fwd": (_i, [_vp, _vp, _i, _vp, _i, _l, _i, _vp]),
+    "adell_eca_apply_bwd_workspace_doubles": (_l, [_i, _l, _i]),
+    "adell_eca_apply_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _l, _i, _vp]),
+    "adell_diffusion_noise": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _vp]),
+    "adell_diffusion_reverse_step": (_i, [_vp] * 5 + [_l] + [_f] * 7 + [_i, _vp]),
+    "adell_mse_workspace_bytes": (_l, []),
+    "adell_mse_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp]),
+    "adell_mse_bwd": (_i, [_vp, _vp, _vp, _l, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -14,6 +14,7 @@ Statistics produced by the conv epilogue ride on the output tensor as
 import collections
 import ctypes
 import itertools
+import math
 import os
 import weakref
 
@@ -2855,3 +2856,230 @@ def detection_decode(centre, size, objectness, class_pred, anchors, correction_f
                                                     count, corr)
     st = starts.tolist()
     return [(boxes[lo:hi], scores[lo:hi], classes[lo:hi]) for lo, hi in zip(st[:-1], st[1:])]
+
+
+# ---- DDPM diffusion (csrc/diffusion.hip) ---------------------------------------------------------
+def _eca_site_params(site):
+    """The eight parameter tensors of an ``EfficientConditioningAttentionBlock(op_type="linear")`` in
+    the kernels' order."""
+    return (site.class_to_channels.weight, site.class_to_channels.bias, site.op[1].weight,
+            site.op[1].bias, site.op[2].weight, site.op[2].bias, site.op[4].weight, site.op[4].bias)
+
+
+class _EcaGatesFn(torch.autograd.Function):
+    """Outputs: one [Ng, C] logits tensor per site. Inputs: t, the class-embedding rows (or None),
+    LayerNorm's eps, the site count, then eight parameters per site."""
+
+    @staticmethod
+    def forward(ctx, t, cls, eps, n_sites, *flat):
+        params = [tuple(flat[8 * i:8 * i + 8]) for i in range(n_sites)]
+        zs, (emb, recs) = ops.eca_gates_fwd(t, cls, params, eps)
+        ctx.save_for_backward(emb, *recs, *flat)
+        ctx.n_sites = n_sites
+        ctx.set_materialize_grads(False)
+        return tuple(zs)
+
+    @staticmethod
+    def backward(ctx, *gzs):
+        n = ctx.n_sites
+        emb, recs, flat = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + n], ctx.saved_tensors[1 + n:]
+        params = [tuple(flat[8 * i:8 * i + 8]) for i in range(n)]
+        gzs = [None if g is None else g.contiguous() for g in gzs]
+        grads, de = ops.eca_gates_bwd(params, (emb, list(recs)), gzs, ctx.needs_input_grad[1])
+        return (None, de, None, None) + tuple(g for site in grads for g in site)
+
+
+def timestep_embedding(t, channels, max_period=10000):
+    """``get_timestep_embedding`` (modules/diffusion/unet.py) in torch ops, its arithmetic in fp64 and
+    the result rounded to fp32 once, as the gate kernel evaluates it: cos half, sin half, zero pad
+    for an odd ``channels``; ``channels == 1`` gives zeros. ``t`` [G] or [G, 1] -> [G, channels]."""
+    t = t.reshape(-1).to(torch.float32).double()
+    half = channels // 2
+    k = torch.arange(half, dtype=torch.float64, device=t.device)
+    args = t[:, None] * torch.exp(-math.log(max_period) * k / max(half, 1))[None, :]
+    emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
+    if channels % 2 == 1:
+        emb = torch.nn.functional.pad(emb, (0, 1, 0, 0))
+    return emb.float()
+
+
+def _eca_gates_composed(t, sites, cls_embedding):
+    """The same logits from the package's Linear / LayerNorm / activation kernels, site by site."""
+    T = sites[0].class_dimension
+    emb = cls_embedding if t is None else timestep_embedding(t, T)
+    if t is not None and cls_embedding is not None:
+        emb = emb + cls_embedding
+    out = []
+    for site in sites:
+        w0, b0, w1, b1, lg, lb, w2, b2 = _eca_site_params(site)
+        h = elementwise(linear(emb, w0, b0), "silu")
+        h = layer_norm(linear(h, w1, b1), lg, lb, site.op[2].eps)
+        out.append(linear(elementwise(h, "silu"), w2, b2))
+    return out
+
+
+def eca_gates(t, sites, cls_embedding=None):
+    """Pre-sigmoid gate logits ``z_site`` [G, C_site] of every ``EfficientConditioningAttentionBlock``
+    (``op_type="linear"``) in ``sites`` for the timesteps ``t`` ([G] or [G, 1], a fraction or an
+    integer step count; moved to the parameters' device): the sinusoidal embedding of
+    ``get_timestep_embedding`` (evaluated in fp64, rounded to fp32 once), ``+ cls_embedding[g]``
+    ([G, t_dim], the rows ``Embedding(cls)``; with one timestep and several class rows the timestep
+    serves them all), then per site ``class_to_channels`` -> SiLU -> Linear -> LayerNorm -> SiLU ->
+    Linear. ``t`` None: the embedding is ``cls_embedding`` alone (a stand-alone block's conditioning
+    vector). One grouped launch forward, two backward, for all sites; the backward returns the
+    gradients of every site's eight parameters and of ``cls_embedding``, summed over G in a fixed
+    order. ``t`` gets no gradient.
+
+    Up to 32 sites of at most 1024 channels and ``t_dim <= 1024`` take the grouped kernels. Anything
+    beyond composes the same values from ``functional.linear`` / ``layer_norm`` / ``elementwise``,
+    site by site (several launches per site; the embedding in torch ops)."""
+    sites = list(sites)
+    if not sites:
+        return []
+    params = [_eca_site_params(s) for s in sites]
+    dev = params[0][0].device
+    if t is not None:
+        t = t.to(dev).reshape(-1).to(torch.float32)
+    T = int(params[0][0].shape[1])
+    if any(int(p[0].shape[1]) != T for p in params):
+        raise ValueError("eca_gates: the sites read one embedding, their class_dimension must agree")
+    eps = {float(s.op[2].eps) for s in sites}
+    widest = max(int(p[0].shape[0]) for p in params)
+    if (len(sites) > ops.ECA_MAX_SITES or widest > ops.ECA_MAX_DIM or T > ops.ECA_MAX_DIM
+            or len(eps) > 1):
+        ops._dif_layout("eca_gates", t, cls_embedding)
+        return _eca_gates_composed(t, sites, cls_embedding)
+    cls = None if cls_embedding is None else cls_embedding.contiguous()
+    flat = [p for site in params for p in site]
+    return list(_EcaGatesFn.apply(t, cls, eps.pop(), len(sites), *flat))
+
+
+def _as_channels_last(what, x):
+    """``x`` itself when its memory is dense channels-last; a dense row-major tensor is copied to
+    that layout (the conv kernels never produce one); a view with gaps is refused."""
+    if x.dim() not in (4, 5):
+        raise ValueError(f"{what}: [N, C, H, W] or [N, C, D, H, W] expected, got {tuple(x.shape)}")
+    fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
+    if x.is_contiguous(memory_format=fmt):
+        return x
+    if x.is_cuda and not x.is_contiguous():
+        raise ops.AdellHipError(f"{what}: non-dense tensor handed to a kernel: shape {tuple(x.shape)}, "
+                                f"strides {x.stride()}")
+    return x.contiguous(memory_format=fmt)
+
+
+class _EcaApplyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, z):
+        ctx.save_for_backward(x, z)
+        return ops.eca_apply_fwd(x, z)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, z = ctx.saved_tensors
+        dy = _as_channels_last("eca_apply backward", dy)
+        return ops.eca_apply_bwd(x, z, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def eca_apply(x, z):
+    """``x * sigmoid(z)`` for an activation ``x`` [N, C, *spatial] (2 or 3 spatial axes, channels-last
+    memory as the conv kernels leave it) and gate logits ``z`` [Ng, C] with Ng in {1, N}: one gate
+    row is broadcast over the batch inside the kernel. One launch forward. Backward: one pass over
+    ``x`` and ``dy`` writes ``dx = dy * s`` and fp64 partial sums of ``dy * x``, a small second
+    kernel folds them in a fixed order into ``dz = s (1 - s) sum`` (over the items too when Ng is
+    1) -- three full-size tensor passes where ``scale_per_item_channel`` makes four."""
+    x = _as_channels_last("eca_apply", x)
+    return _EcaApplyFn.apply(x, z)
+
+
+def diffusion_noise(x, epsilon, alpha_bar, t):
+    """``sqrt(alpha_bar[t_n]) * x + sqrt(1 - alpha_bar[t_n]) * epsilon`` per item in one launch
+    (``Diffusion.noise_images``). ``alpha_bar`` fp32 [noise_steps] and ``t`` int64 [N] live on the
+    device and are read by the kernel; a ``t`` outside ``[0, noise_steps)`` is never used as an index
+    and makes that item NaN. No autograd: ``x`` and ``epsilon`` are data."""
+    return ops.diffusion_noise(x.detach(), epsilon.detach(), alpha_bar, t)
+
+
+DIFFUSION_STEP_KINDS = ("ddpm", "ddim", "alpha_deblending")
+
+
+def diffusion_step_coefficients(kind, t, tables, eta=1.0, clip=True):
+    """Host fp64 scalars of one reverse step: ((sb, sa, c_x0, c_x, c_e, c_n), flags) such that
+    ``out = c_x x + c_e e + c_x0 x0 + c_n noise`` with ``x0 = (x - sb e) / sa`` (clamped to [-1, 1]
+    under the CLIP flag) restates ``ddpm_reverse_step`` / ``ddim_reverse_step`` /
+    ``alpha_deblending_step`` of the reference. ``tables``: host sequences "beta", "alpha",
+    "alpha_bar"."""
+    if kind not in DIFFUSION_STEP_KINDS:
+        raise ValueError(f"diffusion_reverse_step: kind must be one of {DIFFUSION_STEP_KINDS}, got {kind!r}")
+    t = int(t)
+    n = len(tables["alpha_bar"])
+    if not 0 <= t < n:
+        raise ValueError(f"diffusion_reverse_step: t = {t} outside [0, {n})")
+    ab = float(tables["alpha_bar"][t])
+    abp = float(tables["alpha_bar"][t - 1]) if t > 0 else 1.0        # alpha_bar_prev = 1 at t = 0
+    beta, alpha = float(tables["beta"][t]), float(tables["alpha"][t])
+    sb, sa = math.sqrt(1.0 - ab), math.sqrt(ab)
+    if kind == "ddpm":
+        bb = 1.0 - ab
+        c_n = 0.0
+        if t > 0 and eta > 0:
+            c_n = math.sqrt((1.0 - abp) / (1.0 - ab) * beta) * eta
+        flags = ops.DIFFUSION_X0 | (ops.DIFFUSION_CLIP if clip is True else 0)
+        return (sb, sa, math.sqrt(abp) * beta / bb, math.sqrt(alpha) * (1.0 - abp) / bb, 0.0, c_n), flags
+    if kind == "ddim":
+        var = math.sqrt((1.0 - abp) / (1.0 - ab)) * math.sqrt(1.0 - ab / abp) * eta
+        return (sb, sa, math.sqrt(abp), 0.0, math.sqrt(max(1.0 - abp - var ** 2, 0.0)), var), \
+            ops.DIFFUSION_X0
+    return (sb, sa, 0.0, 1.0, ab - abp, 0.0), 0
+
+
+def diffusion_reverse_step(kind, x, eps, t, tables, noise=None, eps_uncond=None, scale=0.0, eta=1.0,
+                           clip=True):
+    """One reverse-diffusion step in one launch. ``kind``: "ddpm", "ddim" or "alpha_deblending",
+    as ``Diffusion.ddpm_reverse_step`` / ``ddim_reverse_step`` / ``alpha_deblending_step`` write them
+    (``alpha_bar_prev = 1`` at ``t = 0``; the [-1, 1] clamp of ``x_orig`` in DDPM only, under
+    ``clip``; ``clamp(1 - alpha_bar_prev - var^2, min=0)`` in DDIM; DDPM adds no noise when ``t == 0``
+    or ``eta <= 0``). With ``eps_uncond`` the guidance blend ``eps_uncond + scale * (eps -
+    eps_uncond)`` is folded into the same launch. ``t`` is a Python int; the scalar coefficients are
+    computed here in fp64 from ``tables``, host copies of "beta", "alpha" and "alpha_bar", so the
+    step reads nothing back from the device. ``noise`` is required where the step's noise
+    coefficient is not zero. All tensors share one dense layout."""
+    coef, flags = diffusion_step_coefficients(kind, t, tables, eta, clip)
+    if coef[5] != 0.0 and noise is None:
+        raise ValueError(f"diffusion_reverse_step: the {kind} step at t = {t}, eta = {eta} adds noise; "
+                         "pass it")
+    if coef[5] == 0.0:
+        noise = None
+    return ops.diffusion_reverse_step(x.detach(), eps.detach(),
+                                      None if eps_uncond is None else eps_uncond.detach(),
+                                      noise, coef, scale, flags)
+
+
+class _MseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        ctx.save_for_backward(pred, target)
+        return ops.mse_fwd(pred, target)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        return ops.mse_bwd(pred, target, g.contiguous()), None
+
+
+def mse_loss(pred, target):
+    """``torch.nn.MSELoss()``: the mean of ``(pred - target)^2`` over all elements, a 0-d device
+    tensor. Forward: one launch, fp64 partial sums per block folded in index order by the block
+    that finishes last. Backward: one launch (gradient of ``pred`` only: the target is data). The
+    MAE reconstruction loss's kernels (``mae_reconstruction_loss``) index patch tokens and need a
+    copy to be reached from an image, so this is a kernel of its own. A ``target`` in the other
+    dense layout than ``pred`` (row-major noise against a channels-last prediction) is copied to
+    the prediction's layout first."""
+    target = target.detach()
+    if pred.is_cuda and target.is_cuda and pred.dim() in (4, 5) and pred.shape == target.shape:
+        fmt = torch.channels_last_3d if pred.dim() == 5 else torch.channels_last
+        if pred.is_contiguous(memory_format=fmt) and not pred.is_contiguous():
+            target = target.contiguous(memory_format=fmt)
+        elif pred.is_contiguous() and not target.is_contiguous():
+            target = target.contiguous()
+    return _MseFn.apply(pred, target).reshape(())

@@ -4160,3 +4160,209 @@ def adamw_amsgrad_step(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, bet
                                               _ptr(max_exp_avg_sq), param.numel(), lr, beta1, beta2,
                                               eps, weight_decay, int(step), grad_scale, _stream()))
     _weights_changed()
+
+
+# ---- DDPM diffusion (csrc/diffusion.hip) ---------------------------------------------------------
+ECA_MAX_SITES = 32        # gate blocks per grouped launch
+ECA_MAX_DIM = 1024        # widest site / embedding of the grouped gate kernels
+DIFFUSION_X0, DIFFUSION_CLIP = 1, 2
+_ECA_PARAMS = 8           # class_to_channels.{weight,bias}, op.1.*, op.2.*, op.4.*
+
+
+def _dif_layout(what, *ts):
+    """0 when every tensor is dense row-major, 1 when every one is dense channels-last (4-D or 5-D, the
+    layout the conv kernels leave); a view with gaps or a mix of layouts is refused whatever
+    ADELL_CHECK_DENSE says, and so are CPU tensors and other dtypes."""
+    ts = [t for t in ts if t is not None]
+    for t in ts:
+        if not t.is_cuda:
+            raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels run on MI355X only: got a CPU "
+                                     "tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels are fp32; got {t.dtype}")
+    if all(t.is_contiguous() for t in ts):
+        return 0
+    if all((t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d))
+           or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)) for t in ts):
+        return 1
+    raise _lib.AdellHipError(f"{what}: non-dense tensor (or a mix of layouts) handed to a kernel: "
+                             + ", ".join(f"shape {tuple(t.shape)} strides {t.stride()}" for t in ts))
+
+
+def _dif_channels_last(what, x):
+    """(N, V, C) of an activation [N, C, *spatial] whose memory is dense [N, *spatial, C]."""
+    if not x.is_cuda:
+        raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels run on MI355X only: got a CPU tensor "
+                                 "(no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels are fp32; got {x.dtype}")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"{what}: [N, C, H, W] or [N, C, D, H, W] expected, got {tuple(x.shape)}")
+    fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
+    if not x.is_contiguous(memory_format=fmt):
+        raise _lib.AdellHipError(f"{what}: the activation must be dense channels-last memory (the "
+                                 f"layout the conv kernels leave): shape {tuple(x.shape)}, strides "
+                                 f"{x.stride()}")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if N < 1 or C < 1 or x.numel() == 0:
+        raise ValueError(f"{what}: empty activation {tuple(x.shape)}")
+    return N, x.numel() // (N * C), C
+
+
+def _eca_gate_rows(what, x_shape_n, z, C):
+    if z.dim() != 2 or z.shape[1] != C or z.shape[0] not in (1, x_shape_n):
+        raise ValueError(f"{what}: gate logits [1 or {x_shape_n}, {C}] expected, got {tuple(z.shape)}")
+    _dif_layout(what, z)
+    return int(z.shape[0])
+
+
+def eca_gates_fwd(t, cls, params, eps):
+    """Gate logits of every site in one launch. ``t`` [Gt] fp32 (None: no sinusoidal part), ``cls`` [Ng, T] or None, ``params``
+    one tuple of the eight parameter tensors per site, ``eps`` LayerNorm's. Returns (z per site
+    [Ng, C], saved) with saved = (emb [Ng, T], the sites' records)."""
+    what = "eca_gates_fwd"
+    n_sites = len(params)
+    if not 1 <= n_sites <= ECA_MAX_SITES:
+        raise ValueError(f"{what}: 1..{ECA_MAX_SITES} sites per call, got {n_sites}")
+    _dif_layout(what, t, cls, *[p for site in params for p in site])
+    T = int(params[0][0].shape[1])
+    if t is None and cls is None:
+        raise ValueError(f"{what}: neither timesteps nor class rows")
+    Gt = int(t.numel()) if t is not None else 0
+    Ng = int(cls.shape[0]) if cls is not None else Gt
+    if cls is not None and (cls.dim() != 2 or cls.shape[1] != T):
+        raise ValueError(f"{what}: class embedding [{Ng}, {T}] expected, got {tuple(cls.shape)}")
+    if t is not None and Gt not in (1, Ng):
+        raise ValueError(f"{what}: {Gt} timesteps for {Ng} class rows (1 or {Ng})")
+    dev = params[0][0].device
+    emb = torch.empty((Ng, T), device=dev, dtype=torch.float32)
+    zs, recs, words = [], [], []
+    for site in params:
+        w0, b0, w1, b1, lg, lb, w2, b2 = site
+        C = int(w0.shape[0])
+        shapes = [(C, T), (C,), (C, C), (C,), (C,), (C,), (C, C), (C,)]
+        if len(site) != _ECA_PARAMS or [tuple(p.shape) for p in site] != shapes:
+            raise ValueError(f"{what}: a site's parameters must have shapes {shapes}, got "
+                             f"{[tuple(p.shape) for p in site]}")
+        z = torch.empty((Ng, C), device=dev, dtype=torch.float32)
+        rec = torch.empty((Ng, 8 * C + 4), device=dev, dtype=torch.float32)
+        zs.append(z)
+        recs.append(rec)
+        words += [C] + [p.data_ptr() for p in site] + [z.data_ptr(), rec.data_ptr()]
+    table = (ctypes.c_longlong * len(words))(*words)
+    check(_lib.lib().adell_eca_gates_fwd(table, n_sites, _ptr(t), Gt, _ptr(cls), Ng, T, float(eps),
+                                         _ptr(emb), _stream()))
+    return zs, (emb, recs)
+
+
+def eca_gates_bwd(params, saved, gzs, need_cls):
+    """Gradients of ``eca_gates_fwd`` in two launches: (one tuple of eight parameter gradients per
+    site, the gradient [Ng, T] of the class embedding or None). ``gzs``: per site the gradient of its
+    logits, or None where none arrived."""
+    what = "eca_gates_bwd"
+    emb, recs = saved
+    Ng, T = int(emb.shape[0]), int(emb.shape[1])
+    _dif_layout(what, emb, *recs, *[g for g in gzs if g is not None])
+    words, grads = [], []
+    for site, rec, gz in zip(params, recs, gzs):
+        C = int(site[0].shape[0])
+        if gz is not None and tuple(gz.shape) != (Ng, C):
+            raise ValueError(f"{what}: a gradient [{Ng}, {C}] expected, got {tuple(gz.shape)}")
+        d = tuple(torch.empty_like(p) for p in site)
+        grads.append(d)
+        words += ([C] + [p.data_ptr() for p in site] + [gz.data_ptr() if gz is not None else 0,
+                                                          rec.data_ptr()] + [g.data_ptr() for g in d])
+    de = torch.empty_like(emb) if need_cls else None
+    table = (ctypes.c_longlong * len(words))(*words)
+    check(_lib.lib().adell_eca_gates_bwd(table, len(params), _ptr(emb), _ptr(de), Ng, T, _stream()))
+    return grads, de
+
+
+def eca_apply_fwd(x, z):
+    """x [N, C, *spatial] (channels-last memory) times sigmoid(z) with z [1 or N, C]; one launch."""
+    N, V, C = _dif_channels_last("eca_apply", x)
+    Ng = _eca_gate_rows("eca_apply", N, z, C)
+    y = torch.empty_like(x)
+    check(_lib.lib().adell_eca_apply_fwd(_ptr(x), _ptr(z), Ng, _ptr(y), N, V, C, _stream()))
+    return y
+
+
+def eca_apply_bwd(x, z, dy, need_x=True, need_z=True):
+    """(dx, dz) of ``eca_apply_fwd``: one pass over x and dy, then the fold of its partial sums."""
+    what = "eca_apply_bwd"
+    N, V, C = _dif_channels_last(what, x)
+    Ng = _eca_gate_rows(what, N, z, C)
+    if dy.shape != x.shape:
+        raise ValueError(f"{what}: gradient {tuple(dy.shape)} for an activation {tuple(x.shape)}")
+    _dif_channels_last(what, dy)
+    dx = torch.empty_like(x) if need_x else None
+    dz = part = None
+    if need_z:
+        dz = torch.empty_like(z)
+        n = _lib.lib().adell_eca_apply_bwd_workspace_doubles(N, V, C)
+        part = torch.empty(n, device=x.device, dtype=torch.float64)
+    if dx is None and dz is None:
+        return None, None
+    check(_lib.lib().adell_eca_apply_bwd(_ptr(x), _ptr(dy), _ptr(z), Ng, _ptr(dx), _ptr(dz),
+                                         _ptr(part), N, V, C, _stream()))
+    return dx, dz
+
+
+def diffusion_noise(x, epsilon, alpha_bar, t):
+    """sqrt(alpha_bar[t_n]) x + sqrt(1 - alpha_bar[t_n]) epsilon per item; ``alpha_bar`` [S] fp32 and
+    ``t`` [N] int64 on the device; one launch."""
+    what = "diffusion_noise"
+    _dif_layout(what, x, epsilon)
+    _dif_layout(what, alpha_bar)
+    if x.shape != epsilon.shape or x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"{what}: x {tuple(x.shape)} and epsilon {tuple(epsilon.shape)} differ")
+    N = int(x.shape[0])
+    if not t.is_cuda:
+        raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels run on MI355X only: got CPU timesteps")
+    if t.dtype != torch.int64 or t.numel() != N or not t.is_contiguous():
+        raise _lib.AdellHipError(f"{what}: t must be a dense int64 tensor of {N} timesteps, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+    y = torch.empty_like(x)
+    check(_lib.lib().adell_diffusion_noise(_ptr(x), _ptr(epsilon), _ptr(alpha_bar),
+                                           int(alpha_bar.numel()), _ptr(t), _ptr(y), N,
+                                           x.numel() // N, _stream()))
+    return y
+
+
+def diffusion_reverse_step(x, eps, eps_uncond, noise, coef, scale, flags):
+    """out = c_x x + c_e e + c_x0 x0 + c_n noise (adell_diffusion_reverse_step); ``coef`` = (sb, sa,
+    c_x0, c_x, c_e, c_n); one launch."""
+    what = "diffusion_reverse_step"
+    _dif_layout(what, x, eps, eps_uncond, noise)
+    for other in (eps, eps_uncond, noise):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"{what}: shapes differ: {tuple(x.shape)} and {tuple(other.shape)}")
+    out = torch.empty_like(eps)
+    sb, sa, c_x0, c_x, c_e, c_n = (float(v) for v in coef)
+    check(_lib.lib().adell_diffusion_reverse_step(_ptr(x), _ptr(eps), _ptr(eps_uncond), _ptr(noise),
+                                                  _ptr(out), x.numel(), sb, sa, c_x0, c_x, c_e, c_n,
+                                                  float(scale), int(flags), _stream()))
+    return out
+
+
+def mse_fwd(pred, target):
+    """mean((pred - target)^2) as a one-element device tensor; one launch (and its counter's memset)."""
+    what = "mse_loss"
+    _dif_layout(what, pred, target)
+    if pred.shape != target.shape or pred.numel() == 0:
+        raise ValueError(f"{what}: prediction {tuple(pred.shape)} and target {tuple(target.shape)}")
+    ws = torch.empty(_lib.lib().adell_mse_workspace_bytes() // 8, device=pred.device, dtype=torch.float64)
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    check(_lib.lib().adell_mse_fwd(_ptr(pred), _ptr(target), pred.numel(), _ptr(ws), _ptr(loss),
+                                   _stream()))
+    return loss
+
+
+def mse_bwd(pred, target, g):
+    """g 2 (pred - target) / n with g a one-element device tensor; one launch."""
+    _dif_layout("mse_loss", pred, target)
+    _dif_layout("mse_loss", g)
+    dpred = torch.empty_like(pred)
+    check(_lib.lib().adell_mse_bwd(_ptr(pred), _ptr(target), _ptr(g), pred.numel(), _ptr(dpred),
+                                   _stream()))
+    return dpred

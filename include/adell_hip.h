@@ -1139,6 +1139,52 @@ int adell_adamw_amsgrad_step(float* param, const float* grad, float* exp_avg, fl
                              float* max_exp_avg_sq, long n, float lr, float beta1, float beta2, float eps,
                              float weight_decay, long step, float grad_scale, void* stream);
 
+/* DDPM diffusion (modules/diffusion/unet.py, diffusion_process.py, modules/layers/class_attention.py;
+ * csrc/diffusion.hip). fp32, dense, floating-point sums in a fixed order with fp64 accumulation, no
+ * float atomics: results repeat bit for bit.
+ * adell_eca_gates_fwd, ONE launch for n_sites <= 32 gate blocks (op_type="linear") that read the same
+ * embedding. table (HOST memory), 11 words per site: C (1..1024), the eight parameters
+ * class_to_channels.weight [C][T], .bias, op.1.weight [C][C], op.1.bias, op.2.weight, op.2.bias,
+ * op.4.weight [C][C], op.4.bias, the logits z [Ng][C] (output) and the site's record of Ng (8 C + 4)
+ * floats (output, the backward's input). Row g of the embedding emb [Ng][T] (output): the sinusoidal
+ * embedding of t[Gt == 1 ? 0 : g] (cos half, sin half, zero pad for odd T, T <= 1024; evaluated in
+ * fp64; t NULL: zeros) plus cls[g] (cls [Ng][T] or NULL). z = Linear(SiLU(LayerNorm(Linear(SiLU(Linear(emb))))))
+ * before the sigmoid; eps: LayerNorm's.
+ * adell_eca_gates_bwd, TWO launches: table of 19 words per site: C, the eight parameters, gz [Ng][C]
+ * (NULL: zeros), the forward's record, the eight parameter gradients (outputs, summed over the Ng rows
+ * in order). de [Ng][T] (NULL: not computed): the gradient of cls, summed over the sites in order.
+ * adell_eca_apply_fwd: y = x sigmoid(z[Ng == 1 ? 0 : n][c]) for x, y [N][V][C] (NDHWC), z [Ng][C], Ng in
+ * {1, N}, C <= 16384; one launch. adell_eca_apply_bwd: dx = dy s (NULL: skipped) in the one pass over x
+ * and dy that also leaves fp64 partial sums of dy x in part (adell_eca_apply_bwd_workspace_doubles(N,
+ * V, C) doubles), then dz [Ng][C] = s (1 - s) sum (over the items too when Ng == 1) by a small second
+ * kernel; dz and part NULL together: dx alone.
+ * adell_diffusion_noise: y = sqrt(ab[t[n]]) x + sqrt(1 - ab[t[n]]) eps for N items of M elements;
+ * alpha_bar [S] and t [N] (int64) on the device; an item whose t is outside [0, S) is NaN.
+ * adell_diffusion_reverse_step: e = eps_uncond + scale (eps - eps_uncond) (eps_uncond NULL: e = eps);
+ * out = c_x x + c_e e [+ c_x0 x0 with ADELL_DIFFUSION_X0: x0 = (x - sb e) / sa, clamped to [-1, 1] with
+ * ADELL_DIFFUSION_CLIP] [+ c_n noise, noise NULL: none]; n elements, one launch.
+ * adell_mse_fwd: loss[0] = mean((pred - target)^2), one launch; ws: adell_mse_workspace_bytes() bytes,
+ * 16-byte aligned. adell_mse_bwd: dpred = g[0] 2 (pred - target) / n, g on the device. */
+enum { ADELL_DIFFUSION_X0 = 1, ADELL_DIFFUSION_CLIP = 2 };
+int adell_eca_gates_fwd(const long long* table, int n_sites, const float* t, int Gt, const float* cls,
+                        int Ng, int T, float eps, float* emb, void* stream);
+int adell_eca_gates_bwd(const long long* table, int n_sites, const float* emb, float* de, int Ng, int T,
+                        void* stream);
+int adell_eca_apply_fwd(const float* x, const float* z, int Ng, float* y, int N, long V, int C,
+                        void* stream);
+long adell_eca_apply_bwd_workspace_doubles(int N, long V, int C);
+int adell_eca_apply_bwd(const float* x, const float* dy, const float* z, int Ng, float* dx, float* dz,
+                        double* part, int N, long V, int C, void* stream);
+int adell_diffusion_noise(const float* x, const float* eps, const float* alpha_bar, int S,
+                          const long long* t, float* y, int N, long M, void* stream);
+int adell_diffusion_reverse_step(const float* x, const float* eps, const float* eps_uncond,
+                                 const float* noise, float* out, long n, float sb, float sa, float c_x0,
+                                 float c_x, float c_e, float c_n, float scale, int flags, void* stream);
+long adell_mse_workspace_bytes(void);
+int adell_mse_fwd(const float* pred, const float* target, long n, void* ws, float* loss, void* stream);
+int adell_mse_bwd(const float* pred, const float* target, const float* g, long n, float* dpred,
+                  void* stream);
+
 /* Cosine-similarity losses between two [B][D] embedding batches, the non-VICReg choices of
  * SelfSLBasePL.init_loss (self_supervised/pl.py:202-212): kind 0 simsiam_loss, kind 1 byol_loss
  * (self_supervised/losses/functional.py:138-164), kind 2 NTXentLoss (losses/ntxent.py:11-46;
