@@ -280,6 +280,17 @@ SIGNATURES = {
     "adell_mse_workspace_bytes": (_l, []),
     "adell_mse_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp]),
     "adell_mse_bwd": (_i, [_vp, _vp, _vp, _l, _vp, _vp]),
+    "adell_gp_route": (_i, [_i, _i, _i]),
+    "adell_gp_phi_fwd": (_i, [_vp] * 6 + [_i] * 4 + [_f, _f] + [_vp] * 5),
+    "adell_gp_phi_bwd": (_i, [_vp] * 11 + [_i] * 4 + [_f, _f] + [_vp] * 6),
+    "adell_gp_cos": (_i, [_vp, _vp, _vp, _l, _i, _f, _vp, _vp]),
+    "adell_gp_precision_update": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "adell_gp_variance": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "adell_gp_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_ensemble_pool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "adell_ensemble_pool_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "adell_ensemble_average_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "adell_ensemble_average_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -3083,3 +3083,114 @@ def mse_loss(pred, target):
         elif pred.is_contiguous() and not target.is_contiguous():
             target = target.contiguous()
     return _MseFn.apply(pred, target).reshape(())
+
+
+# ---- ensemble classifiers and the Gaussian-process head (csrc/ensemble.hip) ---------------------------
+gp_route = ops.gp_route
+
+
+class _GpPhiFn(torch.autograd.Function):
+    """(logits, phi) of the fused route: one launch forward, at most two backward. W and b are
+    buffers: no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, W, b, weights, scale, eps):
+        phi, logits, mean, rstd = ops.gp_phi_fwd(x, gamma, beta, W, b, weights, scale, eps)
+        ctx.save_for_backward(x, gamma, beta, W, b, weights, phi, mean, rstd)
+        ctx.consts = (scale, eps)
+        ctx.set_materialize_grads(False)
+        return logits, phi
+
+    @staticmethod
+    def backward(ctx, dlogits, dphi):
+        x, gamma, beta, W, b, weights, phi, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgamma, dbeta, dweights = ops.gp_phi_bwd(
+            x, gamma, beta, W, b, weights, phi, mean, rstd, dlogits, dphi, *ctx.consts,
+            need_x=need[0], need_norm=need[1] or need[2], need_weights=need[5])
+        return dx, dgamma, dbeta, None, None, dweights, None, None
+
+
+class _GpCosFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, b, scale):
+        ctx.save_for_backward(t, b)
+        ctx.scale = scale
+        return ops.gp_cos(t, b, scale)
+
+    @staticmethod
+    def backward(ctx, dphi):
+        t, b = ctx.saved_tensors
+        return ops.gp_cos(t, b, ctx.scale, dphi=dphi.contiguous()), None, None
+
+
+def gp_phi(x, gamma, beta, W, b, weights, scale, eps=1e-5, route=None):
+    """(logits [N, o], phi [N, r]) of the Gaussian-process layer on rows x [N, i]: x^ = LayerNorm(x)
+    (``gamma`` / ``beta`` None: x), phi = scale cos(b - W x^), logits = phi weights^T. ``route``:
+    None asks ``gp_route``; "fused" is one launch, "composed" the layer norm and the two GEMMs of
+    ``layer_norm`` / ``linear`` around the cos epilogue."""
+    if x.dim() != 2:
+        raise NotImplementedError(f"gp_phi: rows [N, in_channels] expected, got {tuple(x.shape)}: "
+                                  "inputs of rank above 2 are not built")
+    R, I = int(W.shape[-2]), int(W.shape[-1])
+    route = gp_route(x.shape[0], I, R) if route is None else route
+    x = x.contiguous()
+    if route == "fused":
+        return _GpPhiFn.apply(x, gamma, beta, W, b, weights, float(scale), float(eps))
+    if route != "composed":
+        raise ValueError(f"gp_phi: route {route!r} is neither 'fused' nor 'composed'")
+    xh = x if gamma is None else layer_norm(x, gamma, beta, eps)
+    phi = _GpCosFn.apply(linear(xh, W.reshape(R, I)), b, float(scale))
+    return linear(phi, weights), phi
+
+
+class _EnsemblePoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *members):
+        out, arg = ops.ensemble_pool_fwd(members)
+        ctx.save_for_backward(arg)
+        ctx.shapes = [tuple(m.shape) for m in members]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        return tuple(ops.ensemble_pool_bwd(g, arg, ctx.shapes, ctx.needs_input_grad))
+
+
+def ensemble_pool(members):
+    """``torch.concat([m.flatten(start_dim=2).max(-1).values (or m itself when [B, C]) for m in
+    members], 1)``: one launch each way for up to ``ops.ENSEMBLE_MAX`` members; more are composed
+    from ``channel_max`` and the concat copy."""
+    members = [m.contiguous() if m.dim() == 2 else
+               m.contiguous(memory_format=torch.channels_last if m.dim() == 4
+                            else torch.channels_last_3d) for m in members]
+    if len(members) <= ops.ENSEMBLE_MAX:
+        return _EnsemblePoolFn.apply(*members)
+    pooled = [m if m.dim() == 2 else channel_max(m) for m in members]
+    B = pooled[0].shape[0]
+    return _CatFn.apply(*[p.reshape(B, -1, 1, 1, 1) for p in pooled]).reshape(B, -1)
+
+
+class _EnsembleAverageFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *logits):
+        y = ops.ensemble_average_fwd(logits)
+        ctx.save_for_backward(y)
+        ctx.K = len(logits)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return tuple(ops.ensemble_average_bwd(y, dy, ctx.K, ctx.needs_input_grad))
+
+
+def ensemble_average(logits):
+    """sigmoid (one column) or softmax over dim 1 of ``sum(logits) / len(logits)`` for logit tensors
+    [B, C]; one launch each way, up to ``ops.ENSEMBLE_MAX`` members."""
+    logits = [x.contiguous() for x in logits]
+    if len(logits) > ops.ENSEMBLE_MAX:
+        raise NotImplementedError(f"ensemble_average: {len(logits)} members, at most "
+                                  f"{ops.ENSEMBLE_MAX} are built")
+    return _EnsembleAverageFn.apply(*logits)

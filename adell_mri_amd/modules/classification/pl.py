@@ -14,8 +14,14 @@ weight decay and the normal group, or the head / body split when ``weight_decay`
 ``loss_fn`` is called as it is: the classes of ``classification.losses`` (what
 ``configure_loss_fn`` assigns) run the fused kernels, any other callable runs as given.
 
+``GenericEnsemblePL`` (:1504-1631) and ``AveragingEnsemblePL`` (:1634-1759) read a list of
+``image_keys``; the generic one carries the Gaussian-process hooks (``fit_gaussian_process`` /
+``on_train_end``, ``predict_step_gp``), and ``optimizer_groups`` puts the trainable parameters of
+any ``GaussianProcessLayer`` into the no-decay group.
+
 Not mirrored: ``calibrate`` / ``predict_calibrated_step`` (conformal calibration), ``on_train_end``
-and ``predict_step_gp`` (Gaussian process), and the hyper-parameter logging of ``on_train_start``.
+and ``predict_step_gp`` of the single-network wrappers (their Gaussian-process head is not built),
+and the hyper-parameter logging of ``on_train_start``.
 Lightning is optional as in ``self_supervised/pl.py``.
 """
 from abc import ABC
@@ -26,7 +32,9 @@ import torch
 from ... import classification_metrics as CM
 from ...optim import FusedAdamW
 from ..learning_rate import CosineAnnealingWithWarmupLR
+from ..layers.gaussian_process import GaussianProcessLayer
 from .classification import CatNet, OrdNet, ViTClassifier, ordinal_prediction_to_class
+from .ensemble import AveragingEnsemble, GenericEnsemble
 from .losses import BCEWithLogitsLoss
 from .multiple_instance_learning import MultipleInstanceClassifier, TransformableTransformer
 
@@ -128,16 +136,22 @@ class ClassPLABC(_Base, ABC):
 
     def optimizer_groups(self):
         """(parameter groups, base weight decay) of pl.py:632-683. The first group is the
-        reference's no-decay group of Gaussian-process parameters: always empty here, and kept so
-        that the group indices are the reference's."""
+        reference's no-decay group: the trainable parameters of every ``GaussianProcessLayer``
+        (empty for a wrapper without one, and kept so that the group indices are the
+        reference's)."""
+        gp_ids = {id(p) for m in self.modules() if isinstance(m, GaussianProcessLayer)
+                  for p in m.parameters() if p.requires_grad}
         no_decay_params, reduced_decay_params, normal_decay_params = [], [], []
         for n, p in self.named_parameters():
             if not p.requires_grad:
                 continue
+            if id(p) in gp_ids:
+                no_decay_params.append(p)
+                continue
             (reduced_decay_params if "ordinal_bias" in n else normal_decay_params).append(p)
         if isinstance(self.weight_decay, (list, tuple)):
             wd_body, wd_head = self.weight_decay
-            reduced = {id(p) for p in reduced_decay_params}
+            reduced = {id(p) for p in reduced_decay_params} | gp_ids
             head_decay, body_decay = [], []
             for n, p in self.named_parameters():
                 if not p.requires_grad or id(p) in reduced:
@@ -382,5 +396,160 @@ class MultipleInstanceClassifierPL(MultipleInstanceClassifier, _SliceClassifierP
                  loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
                  start_decay: int = None, training_batch_preproc: Callable = None,
                  optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._setup_wrapper(locals())
+
+
+_ENSEMBLE_HYPERPARAMETERS = ("image_keys", "label_key", "learning_rate", "batch_size",
+                             "weight_decay", "training_dataloader_call", "loss_fn", "loss_params",
+                             "n_epochs", "warmup_steps", "start_decay", "optimizer_eps", "args",
+                             "kwargs")
+
+
+class _EnsemblePL(ClassPLABC):
+    """What the two ensemble wrappers share (pl.py:1504-1759): the ensemble IS the module, the steps
+    read ``[batch[k] for k in image_keys]``, the loss takes no ``loss_params``, and ``test_step``
+    returns ``(loss, prediction)`` as the base's does. The default ``loss_fn`` is
+    ``BCEWithLogitsLoss()``, as for ``ClassNetPL``."""
+
+    def _setup_wrapper(self, local):
+        local["loss_fn"] = BCEWithLogitsLoss() if local["loss_fn"] is None else local["loss_fn"]
+        _store(self, local, _ENSEMBLE_HYPERPARAMETERS)
+        # ``gaussian_process`` is the generic ensemble's own argument; the averaging one has none
+        self.raise_nan_loss, self.calibrated = False, False
+        self.gaussian_process = bool(getattr(self, "gaussian_process", False))
+        self.net_type = "cat"
+        self.save_hyperparameters(ignore=["networks"] + _IGNORED)
+        self.setup_metrics()
+
+    def _inputs(self, batch):
+        return [batch[k] for k in self.image_keys], batch[self.label_key]
+
+    def training_step(self, batch, batch_idx):
+        x, y = self._inputs(batch)
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y)
+        self.log("train_loss", loss.detach())
+        return loss
+
+    def validation_step(self, batch, batch_idx):
+        x, y = self._inputs(batch)
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y)
+        self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True,
+                 batch_size=x[0].shape[0])
+        self.update_metrics(prediction, y, self.val_metrics)
+        return loss
+
+    def test_step(self, batch, batch_idx):
+        x, y = self._inputs(batch)
+        prediction = torch.squeeze(self.forward(x), 1)
+        loss = self.calculate_loss(prediction, y)
+        self.update_metrics(prediction, y, self.test_metrics, log=False)
+        return loss, prediction
+
+    def predict_step(self, batch, batch_idx, dataloader_idx=0, *args, **kwargs):
+        x = [batch[k] for k in self.image_keys]
+        prediction = torch.squeeze(self.forward(x, *args, **kwargs), 1)
+        return {"prediction": prediction}
+
+
+class GenericEnsemblePL(GenericEnsemble, _EnsemblePL):
+    """pl.py:1504-1631, with the Gaussian-process hooks of ``ClassPLABC`` (:433-458, :487-595)
+    written for this wrapper -- the reference's read ``self.network``, which it does not have:
+    ``fit_gaussian_process`` / ``on_train_end``, ``predict_step_gp`` and the dispatch of
+    ``predict_step``."""
+
+    def __init__(self, image_keys: list[str] = ["image"], label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, optimizer_eps: float = OPTIMIZER_EPS_DEFAULT,
+                 *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._setup_wrapper(locals())
+
+    def classification_probabilities(self, logits):
+        """pl.py:387-410 for a categorical head: sigmoid (two classes) or softmax over the class
+        axis, the LAST one (the reference names axis 1, which on samples [S, N, C] is the items')."""
+        if self.n_classes == 2:
+            return torch.sigmoid(logits)
+        return torch.softmax(logits, dim=-1)
+
+    def fit_gaussian_process(self, batches):
+        """What the reference's ``on_train_end`` does: in ``eval()`` mode and without autograd the
+        precision matrix is reset, updated from every batch (one launch per batch, no host read)
+        and inverted (``get_cov``). Single-rank: the precision is not reduced over ranks."""
+        if not self.gaussian_process:
+            raise RuntimeError("Gaussian process is not enabled for this model")
+        head = self.gaussian_process_head
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                head.reset_inv_cov()
+                for batch in batches:
+                    rows = self.forward_head_features([batch[k] for k in self.image_keys])
+                    logits, phi = head.forward_with_phi(rows)
+                    head.update_inv_cov_from_phi(phi, self.classification_probabilities(logits))
+                head.get_cov()
+        finally:
+            self.train(was_training)
+
+    def on_train_end(self):
+        if self.gaussian_process:
+            self.fit_gaussian_process(self.training_dataloader_call(False))
+
+    def predict_step(self, batch, batch_idx, dataloader_idx=0, *args, **kwargs):
+        if self.gaussian_process:
+            if "return_features" in kwargs:
+                raise NotImplementedError(
+                    "return_features=True not implemented for Gaussian process models")
+            return self.predict_step_gp(batch, batch_idx, *args, **kwargs)
+        return super().predict_step(batch, batch_idx, dataloader_idx, *args, **kwargs)
+
+    def predict_step_gp(self, batch, batch_idx, n_samples=100, generator=None, eps=None):
+        """The reference's keys (pl.py:514-595). ``eps`` [2, n_samples, N, o]: the standard normal
+        draws of ``gp_samples`` and of the samples behind ``epistemic_uncertainty_pred`` (default:
+        ``torch.randn`` on the device with ``generator``). The network runs once: in ``eval()``
+        mode ``prediction`` is the head's mean. Nothing is read on the host."""
+        if not self.gaussian_process:
+            raise RuntimeError("Gaussian process is not enabled for this model")
+        head = getattr(self, "gaussian_process_head", None)
+        if head is None or not hasattr(head, "cov"):
+            raise RuntimeError("Gaussian process is not fitted. Call on_fit_end() first.")
+        x = [batch[k] for k in self.image_keys]
+        with torch.no_grad():
+            rows = self.forward_head_features(x)
+            gp_mean, var = head.parameters_with_variance(rows)
+            if eps is None:
+                eps = torch.randn((2, n_samples, *gp_mean.shape), device=gp_mean.device,
+                                  dtype=torch.float32, generator=generator)
+            gp_samples, predictive_mean, predictive_std = head.sample_statistics(
+                rows, n_samples, eps=eps[0], parameters=(gp_mean, var))
+            mean_samples = head.sample_statistics(rows, n_samples, eps=eps[1],
+                                                  parameters=(gp_mean, var))[0]
+            return {
+                "prediction": gp_mean,
+                "gp_mean": gp_mean,
+                "gp_samples": gp_samples,
+                "predictive_mean": predictive_mean,
+                "predictive_std": predictive_std,
+                "epistemic_uncertainty": var[:, None].expand(-1, head.n_outputs),
+                "predictive_std_pred": self.classification_probabilities(gp_samples).std(dim=0),
+                "epistemic_uncertainty_pred":
+                    self.classification_probabilities(mean_samples).std(dim=0),
+            }
+
+
+class AveragingEnsemblePL(AveragingEnsemble, _EnsemblePL):
+    """pl.py:1634-1759."""
+
+    def __init__(self, image_keys: list[str] = ["image"], label_key: str = "label",
+                 learning_rate: float = 0.001, batch_size: int = 4, weight_decay: float = 0.0,
+                 training_dataloader_call: Callable = None, loss_fn: Callable = None,
+                 loss_params: dict = {}, n_epochs: int = 100, warmup_steps: int = 0,
+                 start_decay: int = None, optimizer_eps: float = OPTIMIZER_EPS_DEFAULT,
+                 *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._setup_wrapper(locals())

@@ -4366,3 +4366,289 @@ def mse_bwd(pred, target, g):
     check(_lib.lib().adell_mse_bwd(_ptr(pred), _ptr(target), _ptr(g), pred.numel(), _ptr(dpred),
                                    _stream()))
     return dpred
+
+
+# ---- ensemble classifiers and the Gaussian-process head (csrc/ensemble.hip) ---------------------------
+GP_ROUTES = {0: "fused", 1: "composed"}
+ENSEMBLE_MAX = 8        # ADELL_ENSEMBLE_MAX: members of one ensemble_pool / ensemble_average launch
+
+
+def gp_route(n, i, r):
+    """The route of a Gaussian-process layer over ``n`` rows of ``i`` inputs with ``r`` random
+    features, by the library's own host function (no device needed): "fused" (gp_phi_fwd / _bwd) or
+    "composed" (layer norm, GEMM and gp_cos)."""
+    rc = _lib.lib().adell_gp_route(int(n), int(i), int(r))
+    check(min(rc, 0))
+    return GP_ROUTES[rc]
+
+
+def _ens_rows(what, *ts):
+    """Dense row-major fp32 device tensors, whatever ADELL_CHECK_DENSE says (as ``_mil_dense`` and
+    ``_dif_layout`` refuse for their kernels); the addresses themselves are taken by ``_ptr``."""
+    for t in ts:
+        if t is None:
+            continue
+        _require_cuda(t)
+        if not t.is_contiguous():
+            raise _lib.AdellHipError(f"{what}: non-dense tensor handed to a kernel: shape "
+                                     f"{tuple(t.shape)}, strides {t.stride()}")
+
+
+def _gp_args(what, x, gamma, beta, W, b, weights):
+    if x.dim() != 2:
+        raise NotImplementedError(f"{what}: rows [N, in_channels] expected, got {tuple(x.shape)}: "
+                                  "inputs of rank above 2 are not built")
+    N, I = (int(v) for v in x.shape)
+    R = int(W.shape[-2])
+    if W.numel() != R * I or b.numel() != R or N < 1:
+        raise ValueError(f"{what}: x [N, {I}], W [1, r, {I}] and b [1, r] expected, got "
+                         f"{tuple(x.shape)}, {tuple(W.shape)}, {tuple(b.shape)}")
+    if (gamma is None) != (beta is None) or (gamma is not None and (gamma.numel() != I
+                                                                    or beta.numel() != I)):
+        raise ValueError(f"{what}: the norm's weight and bias [{I}] go together")
+    O = 0
+    if weights is not None:
+        O = int(weights.shape[0])
+        if tuple(weights.shape) != (O, R):
+            raise ValueError(f"{what}: weights [o, {R}] expected, got {tuple(weights.shape)}")
+    _ens_rows(what, x, gamma, beta, W, b, weights)
+    return N, I, R, O
+
+
+def gp_phi_fwd(x, gamma, beta, W, b, weights, scale, eps=1e-5):
+    """(phi [N, r], logits [N, o] or None, mean [N], rstd [N]) in one launch (the fused route)."""
+    N, I, R, O = _gp_args("gp_phi_fwd", x, gamma, beta, W, b, weights)
+    dev = x.device
+    phi = torch.empty((N, R), device=dev, dtype=torch.float32)
+    logits = torch.empty((N, O), device=dev, dtype=torch.float32) if O else None
+    mean = rstd = None
+    if gamma is not None:
+        stats = torch.empty((2, N), device=dev, dtype=torch.float32)
+        mean, rstd = stats[0], stats[1]
+    check(_lib.lib().adell_gp_phi_fwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b),
+                                      _ptr(weights), N, I, R, O, float(scale), float(eps), _ptr(phi),
+                                      _ptr(logits), _ptr(mean), _ptr(rstd), _stream()))
+    return phi, logits, mean, rstd
+
+
+def gp_phi_bwd(x, gamma, beta, W, b, weights, phi, mean, rstd, dlogits, dphi, scale, eps=1e-5,
+               need_x=True, need_norm=True, need_weights=True):
+    """(dx, dgamma, dbeta, dweights) of ``gp_phi_fwd`` from dlogits [N, o] and / or dphi [N, r]; at
+    most two launches. A gradient that is not needed (or has no input) is None."""
+    what = "gp_phi_bwd"
+    N, I, R, O = _gp_args(what, x, gamma, beta, W, b, weights)
+    if dlogits is None and dphi is None:
+        return None, None, None, None
+    dev = x.device
+    if dlogits is not None:
+        dlogits = dlogits.to(torch.float32).contiguous()
+        if tuple(dlogits.shape) != (N, O):
+            raise ValueError(f"{what}: a gradient [{N}, {O}] expected, got {tuple(dlogits.shape)}")
+    if dphi is not None:
+        dphi = dphi.to(torch.float32).contiguous()
+        if tuple(dphi.shape) != (N, R):
+            raise ValueError(f"{what}: a gradient of phi [{N}, {R}] expected, got {tuple(dphi.shape)}")
+    _ens_rows(what, phi, mean, rstd, dlogits, dphi)
+    need_norm = need_norm and gamma is not None
+    need_weights = need_weights and dlogits is not None
+    dx = torch.empty((N, I), device=dev, dtype=torch.float32) if need_x else None
+    dxhat = dgamma = dbeta = dweights = None
+    if need_norm:
+        dxhat = torch.empty((N, I), device=dev, dtype=torch.float32)
+        dgb = torch.empty((2, I), device=dev, dtype=torch.float32)
+        dgamma, dbeta = dgb[0], dgb[1]
+    if need_weights:
+        dweights = torch.empty((O, R), device=dev, dtype=torch.float32)
+    if dx is None and dgamma is None and dweights is None:
+        return None, None, None, None
+    check(_lib.lib().adell_gp_phi_bwd(
+        _ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b), _ptr(weights), _ptr(phi), _ptr(mean),
+        _ptr(rstd), _ptr(dlogits), _ptr(dphi), N, I, R, O, float(scale), float(eps), _ptr(dx),
+        _ptr(dxhat), _ptr(dgamma), _ptr(dbeta), _ptr(dweights), _stream()))
+    return dx, dgamma, dbeta, dweights
+
+
+def gp_cos(t, b, scale, dphi=None):
+    """The composed route's epilogue over t = x^ W^T [rows, r]: scale cos(b - t), or with ``dphi`` the
+    gradient of t, scale sin(b - t) dphi; one launch."""
+    what = "gp_cos"
+    R = int(t.shape[-1])
+    if b.numel() != R or t.numel() == 0 or (dphi is not None and dphi.shape != t.shape):
+        raise ValueError(f"{what}: t [rows, r], b [1, r] (and dphi like t) expected, got "
+                         f"{tuple(t.shape)}, {tuple(b.shape)}")
+    _ens_rows(what, t, b, dphi)
+    out = torch.empty_like(t)
+    check(_lib.lib().adell_gp_cos(_ptr(t), _ptr(b), _ptr(dphi), t.numel() // R, R, float(scale),
+                                  _ptr(out), _stream()))
+    return out
+
+
+def gp_precision_update(inv_cov, phi, probabilities, use_momentum=False, m=0.999):
+    """In place on ``inv_cov`` [1, r, r] (or [r, r]): += sum_n c_n phi_n phi_n^T, or the momentum form,
+    with c_n = sum over the row of p (1 - p) of ``probabilities`` [N] or [N, C]; one launch, no host
+    read. The result is exactly symmetric."""
+    what = "gp_precision_update"
+    if phi.dim() != 2:
+        raise NotImplementedError(f"{what}: phi [N, r] expected, got {tuple(phi.shape)}")
+    N, R = (int(v) for v in phi.shape)
+    p = probabilities.to(torch.float32)
+    if p.dim() == 1:
+        p = p[:, None]
+    if p.dim() != 2 or p.shape[0] != N or p.shape[1] < 1:
+        raise ValueError(f"{what}: probabilities [{N}] or [{N}, C] expected, got "
+                         f"{tuple(probabilities.shape)}")
+    if inv_cov.numel() != R * R or inv_cov.shape[-1] != R:
+        raise ValueError(f"{what}: a precision matrix [1, {R}, {R}] expected, got "
+                         f"{tuple(inv_cov.shape)}")
+    _ens_rows(what, inv_cov, phi, p)
+    check(_lib.lib().adell_gp_precision_update(_ptr(phi), _ptr(p), N, R, int(p.shape[1]),
+                                               int(bool(use_momentum)), float(m), _ptr(inv_cov),
+                                               _stream()))
+    return inv_cov
+
+
+def gp_variance(phi, cov):
+    """var [N] = phi_n^T cov phi_n; one launch."""
+    what = "gp_variance"
+    if phi.dim() != 2:
+        raise NotImplementedError(f"{what}: phi [N, r] expected, got {tuple(phi.shape)}")
+    N, R = (int(v) for v in phi.shape)
+    if cov.numel() != R * R or cov.shape[-1] != R:
+        raise ValueError(f"{what}: a covariance [1, {R}, {R}] expected, got {tuple(cov.shape)}")
+    _ens_rows(what, phi, cov)
+    var = torch.empty((N,), device=phi.device, dtype=torch.float32)
+    check(_lib.lib().adell_gp_variance(_ptr(phi), _ptr(cov), N, R, _ptr(var), _stream()))
+    return var
+
+
+def gp_sample(mean, var, eps):
+    """(samples [S, N, o], their mean [N, o], their unbiased std [N, o]) from mean [N, o], var [N] and
+    eps [S, N, o]: mean + sqrt(max(var, 0)) eps; one launch."""
+    what = "gp_sample"
+    if mean.dim() != 2 or eps.dim() != 3 or tuple(eps.shape[1:]) != tuple(mean.shape) \
+            or var.numel() != mean.shape[0] or eps.shape[0] < 1:
+        raise ValueError(f"{what}: mean [N, o], var [N] and eps [S, N, o] expected, got "
+                         f"{tuple(mean.shape)}, {tuple(var.shape)}, {tuple(eps.shape)}")
+    _ens_rows(what, mean, var, eps)
+    S, N, O = (int(v) for v in eps.shape)
+    samples = torch.empty_like(eps)
+    stats = torch.empty((2, N, O), device=mean.device, dtype=torch.float32)
+    check(_lib.lib().adell_gp_sample(_ptr(mean), _ptr(var), _ptr(eps), S, N, O, _ptr(samples),
+                                     _ptr(stats[0]), _ptr(stats[1]), _stream()))
+    return samples, stats[0], stats[1]
+
+
+def _ens_member(what, x):
+    """A member's output as the kernel reads it: ([B, V, C] channels-last memory, C, V)."""
+    _require_cuda(x)
+    if x.dim() == 2:
+        if not x.is_contiguous():
+            raise _lib.AdellHipError(f"{what}: non-dense tensor handed to a kernel: shape "
+                                     f"{tuple(x.shape)}, strides {x.stride()}")
+        return x, int(x.shape[1]), 1
+    if x.dim() == 4:
+        x = x.unsqueeze(2)
+    if x.dim() != 5:
+        raise ValueError(f"{what}: members [B, C], [B, C, H, W] or [B, C, D, H, W] expected, got "
+                         f"{tuple(x.shape)}")
+    if not x.is_contiguous(memory_format=torch.channels_last_3d):
+        raise _lib.AdellHipError(f"{what}: non-dense tensor handed to a kernel (channels-last "
+                                 f"memory expected): shape {tuple(x.shape)}, strides {x.stride()}")
+    return x, int(x.shape[1]), int(x.shape[2] * x.shape[3] * x.shape[4])
+
+
+def _ens_pointers(tensors):
+    """Host array of the tensors' device addresses (``_ptr``: the dense-layout check of every other
+    kernel argument); None stays a null pointer."""
+    ptrs = [_ptr(t) for t in tensors]
+    return (ctypes.c_void_p * len(ptrs))(*[None if p is None else p.value for p in ptrs])
+
+
+def _ens_arrays(tensors, C, V):
+    K = len(C)
+    return _ens_pointers(tensors), (ctypes.c_int * K)(*C), (ctypes.c_long * K)(*V)
+
+
+def ensemble_pool_fwd(members):
+    """(out [B, sum C_k], arg int32 [B, sum C_k]) of up to ENSEMBLE_MAX members [B, C_k, *spatial]
+    (channels-last memory; max over the voxels, lowest index on a tie) or [B, C_k] (copied); one
+    launch, no per-member pooled tensor and no cat."""
+    what = "ensemble_pool_fwd"
+    if not 1 <= len(members) <= ENSEMBLE_MAX:
+        raise ValueError(f"{what}: {len(members)} members, 1 to {ENSEMBLE_MAX} go in one launch")
+    xs, C, V = zip(*[_ens_member(what, x) for x in members])
+    B = int(xs[0].shape[0])
+    if any(x.shape[0] != B for x in xs) or B < 1:
+        raise ValueError(f"{what}: the members' batch sizes differ: {[tuple(x.shape) for x in xs]}")
+    Ct = sum(C)
+    out = torch.empty((B, Ct), device=xs[0].device, dtype=torch.float32)
+    arg = torch.empty((B, Ct), device=xs[0].device, dtype=torch.int32)
+    px, pc, pv = _ens_arrays(xs, C, V)
+    check(_lib.lib().adell_ensemble_pool_fwd(px, pc, pv, len(xs), B, _ptr(out), _ptr(arg),
+                                             _stream()))
+    return out, arg
+
+
+def ensemble_pool_bwd(g, arg, shapes, needs=None):
+    """The members' dense gradients (channels-last memory, the forward's logical shapes) from g
+    [B, sum C_k] and the forward's arg-max; one launch. ``needs[k]`` False: None."""
+    what = "ensemble_pool_bwd"
+    K = len(shapes)
+    needs = [True] * K if needs is None else list(needs)
+    B = int(shapes[0][0])
+    C = [int(s[1]) for s in shapes]
+    V = [int(math.prod(s[2:])) for s in shapes]
+    g = g.to(torch.float32).contiguous()
+    if tuple(g.shape) != (B, sum(C)) or tuple(arg.shape) != tuple(g.shape) \
+            or arg.dtype != torch.int32 or not arg.is_cuda or not arg.is_contiguous():
+        raise ValueError(f"{what}: g and the int32 arg-max [{B}, {sum(C)}] expected, got "
+                         f"{tuple(g.shape)} and {arg.dtype} {tuple(arg.shape)}")
+    _ens_rows(what, g)
+    dxs = []
+    for s, need in zip(shapes, needs):
+        if not need:
+            dxs.append(None)
+        elif len(s) == 2:
+            dxs.append(torch.empty(tuple(s), device=g.device, dtype=torch.float32))
+        else:
+            dxs.append(torch.empty((s[0], *s[2:], s[1]), device=g.device, dtype=torch.float32)
+                       .permute(0, len(s) - 1, *range(1, len(s) - 1)))
+    pd, pc, pv = _ens_arrays(dxs, C, V)
+    check(_lib.lib().adell_ensemble_pool_bwd(_ptr(g), _ptr(arg), pc, pv, K, B,
+                                             pd, _stream()))
+    return dxs
+
+
+def _ens_logits(what, logits):
+    if not 1 <= len(logits) <= ENSEMBLE_MAX:
+        raise ValueError(f"{what}: {len(logits)} members, 1 to {ENSEMBLE_MAX} go in one launch")
+    shape = tuple(logits[0].shape)
+    if len(shape) != 2 or any(tuple(x.shape) != shape for x in logits) or 0 in shape:
+        raise ValueError(f"{what}: members [B, C] of one shape expected, got "
+                         f"{[tuple(x.shape) for x in logits]}")
+    _ens_rows(what, *logits)
+    return int(shape[0]), int(shape[1])
+
+
+def ensemble_average_fwd(logits):
+    """sigmoid (C = 1) or softmax of the mean of up to ENSEMBLE_MAX logit tensors [B, C]; one launch."""
+    B, C = _ens_logits("ensemble_average_fwd", logits)
+    y = torch.empty((B, C), device=logits[0].device, dtype=torch.float32)
+    px = _ens_pointers(logits)
+    check(_lib.lib().adell_ensemble_average_fwd(px, len(logits), B, C, _ptr(y), _stream()))
+    return y
+
+
+def ensemble_average_bwd(y, dy, K, needs=None):
+    """The K members' gradients (every one the gradient of the mean / K) from y and dy; one launch."""
+    what = "ensemble_average_bwd"
+    dy = dy.to(torch.float32).contiguous()
+    if dy.shape != y.shape or y.dim() != 2:
+        raise ValueError(f"{what}: y and dy [B, C] expected, got {tuple(y.shape)}, {tuple(dy.shape)}")
+    _ens_rows(what, y, dy)
+    needs = [True] * K if needs is None else list(needs)
+    dxs = [torch.empty_like(y) if need else None for need in needs]
+    pd = _ens_pointers(dxs)
+    check(_lib.lib().adell_ensemble_average_bwd(_ptr(y), _ptr(dy), K, int(y.shape[0]),
+                                                int(y.shape[1]), pd, _stream()))
+    return dxs

@@ -1711,6 +1711,61 @@ long adell_gibbs_workspace(int N, int D, int H, int W, int C);
 int adell_gibbs_lowpass(const float* x, float* out, int N, int D, int H, int W, int C,
                         const float* radius, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Ensemble classifiers and the Gaussian-process (SNGP) head (csrc/ensemble.hip; the reference's
+ * modules/classification/classification/ensemble.py and modules/layers/gaussian_process.py). fp32,
+ * dense row-major tensors, every sum in a fixed order in fp64, no atomics: bit-reproducible.
+ * ---------------------------------------------------------------------- */
+#define ADELL_GP_FUSED 0     /* adell_gp_phi_fwd / _bwd */
+#define ADELL_GP_COMPOSED 1  /* layer norm, GEMM and adell_gp_cos */
+#define ADELL_ENSEMBLE_MAX 8 /* members of one adell_ensemble_* launch */
+/* Host only: the route of a Gaussian-process layer over n rows of i inputs with r random features
+ * (the fused kernels keep i + r floats in LDS: i <= 1024 and r <= 4096), or ADELL_E_BADARG. */
+int adell_gp_route(int n, int i, int r);
+/* One launch: x^ = LayerNorm(x) over the row (gamma, beta [i]; both NULL: x^ = x), z = b - W x^
+ * (W [r][i], b [r]), phi [N][r] = scale cos(z), logits [N][o] = phi weights^T (weights [o][r];
+ * logits NULL: phi only). mean, rstd [N]: the row statistics, written with the norm. */
+int adell_gp_phi_fwd(const float* x, const float* gamma, const float* beta, const float* W,
+                     const float* b, const float* weights, int N, int I, int R, int O, float scale,
+                     float eps, float* phi, float* logits, float* mean, float* rstd, void* stream);
+/* At most two launches: from dlogits [N][o] and / or dphi [N][r] (either may be NULL) dx [N][i], and
+ * dgamma, dbeta [i], dweights [o][r] summed over the rows in order (each may be NULL). dxhat [N][i]:
+ * the gradient of x^, needed with dgamma (without the norm it is dx itself and may be NULL). */
+int adell_gp_phi_bwd(const float* x, const float* gamma, const float* beta, const float* W,
+                     const float* b, const float* weights, const float* phi, const float* mean,
+                     const float* rstd, const float* dlogits, const float* dphi, int N, int I, int R,
+                     int O, float scale, float eps, float* dx, float* dxhat, float* dgamma,
+                     float* dbeta, float* dweights, void* stream);
+/* The epilogue of the composed route over t = x^ W^T [rows][r]: dphi NULL: out = scale cos(b - t);
+ * else the gradient of t, out = scale sin(b - t) dphi. */
+int adell_gp_cos(const float* t, const float* b, const float* dphi, long rows, int R, float scale,
+                 float* out, void* stream);
+/* One launch, in place on P [r][r]: U = sum_n c_n phi_n phi_n^T (n in order), c_n = sum over the row
+ * of prob [N][Cp] of p (1 - p); P += U, or P = m P + (1 - m) U with use_momentum. The upper triangle
+ * is computed and mirrored: P comes out exactly symmetric. */
+int adell_gp_precision_update(const float* phi, const float* prob, int N, int R, int Cp,
+                              int use_momentum, float m, float* P, void* stream);
+/* var[n] = phi_n^T cov phi_n (cov [r][r]). */
+int adell_gp_variance(const float* phi, const float* cov, int N, int R, float* var, void* stream);
+/* samples [S][N][o] = mean [N][o] + sqrt(max(var[n], 0)) eps [S][N][o]; smean, sstd [N][o]: their
+ * mean and unbiased standard deviation over S (S = 1: NaN). */
+int adell_gp_sample(const float* mean, const float* var, const float* eps, int S, int N, int O,
+                    float* samples, float* smean, float* sstd, void* stream);
+/* K <= ADELL_ENSEMBLE_MAX members x[k] [B][V[k]][C[k]] (channels last; V = 1: a vector) max-pooled over
+ * their voxels into out [B][sum C] at their channel offset; arg: the int32 voxel index, the lowest on
+ * a tie, the first NaN wins. x, C, V (and dx) are HOST arrays of K entries: the device pointers
+ * travel in the launch's arguments. Backward: dx[k] (NULL: not wanted) = g scattered to the arg-max. */
+int adell_ensemble_pool_fwd(const float* const* x, const int* C, const long* V, int K, int B,
+                            float* out, int* arg, void* stream);
+int adell_ensemble_pool_bwd(const float* g, const int* arg, const int* C, const long* V, int K, int B,
+                            float* const* dx, void* stream);
+/* y [B][C] = sigmoid (C = 1) or softmax over C of the mean of the K <= ADELL_ENSEMBLE_MAX logit
+ * tensors x[k] [B][C] (host array of device pointers); backward: every dx[k] (NULL: not wanted) = the
+ * gradient of the mean / K. */
+int adell_ensemble_average_fwd(const float* const* x, int K, int B, int C, float* y, void* stream);
+int adell_ensemble_average_bwd(const float* y, const float* dy, int K, int B, int C, float* const* dx,
+                               void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
