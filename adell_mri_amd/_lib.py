@@ -291,6 +291,10 @@ SIGNATURES = {
     "adell_ensemble_pool_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "adell_ensemble_average_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "adell_ensemble_average_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "adell_be_expand": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _l, _i, _vp]),
+    "adell_be_members_sum": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i, _l, _i, _vp]),
+    "adell_be_tgrad_workspace_doubles": (_l, [_i, _l, _i, _i]),
+    "adell_be_tgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _l, _i, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

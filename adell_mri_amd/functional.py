@@ -3194,3 +3194,151 @@ def ensemble_average(logits):
         raise NotImplementedError(f"ensemble_average: {len(logits)} members, at most "
                                   f"{ops.ENSEMBLE_MAX} are built")
     return _EnsembleAverageFn.apply(*logits)
+
+
+# ---- batch-ensemble layers (csrc/batch_ensemble.hip) -----------------------------------------------------
+# The eval mean's "batched" route puts members side by side in one batch; a chunk of members is sized
+# so that the expanded batch stays inside this many bytes (docs/LABBOOK.md, "Batch ensembles").
+BE_BATCH_BUDGET_BYTES = 256 << 20
+BE_ROUTES = ("batched", "loop")
+
+
+def _be_dense(what, x):
+    """Rows [B, C] as they are (dense), activations as dense channels-last memory."""
+    if x.dim() == 2:
+        return x.contiguous()
+    return _as_channels_last(what, x)
+
+
+def be_indices(idx, n, batch, device):
+    """The int32 [batch] device tensor ``be_scale`` reads, from host indices (a sequence or a numpy
+    array of ``batch`` entries). A negative entry wraps as torch indexing does; one outside
+    ``[-n, n)`` raises ``IndexError`` here, on the host, before any kernel. One upload, without a
+    host synchronisation."""
+    host = np.asarray(idx)
+    if host.ndim != 1 or host.dtype.kind not in "iu":
+        raise TypeError(f"be_indices: a sequence of integers expected, got {idx!r}")
+    assert len(host) == batch, "len(idx) must be == X.shape[0]"
+    host = host.astype(np.int64)
+    bad = (host < -n) | (host >= n)
+    if bad.any():
+        raise IndexError(f"index {int(host[bad][0])} is out of bounds for dimension 0 with size {n}")
+    staged = torch.from_numpy(np.where(host < 0, host + n, host).astype(np.int32))
+    if torch.device(device).type != "cuda":
+        return staged.to(device)
+    # through pinned memory: the copy is queued behind the stream and the host does not wait
+    return staged.pin_memory().to(device, non_blocking=True)
+
+
+class _BeScaleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, table, idx):
+        ctx.save_for_backward(x, table, idx)
+        return ops.be_expand(x, table, idx)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, table, idx = ctx.saved_tensors
+        dy = _be_dense("be_scale backward", dy)
+        dx, dt = ops.be_tgrad(dy, x, int(table.shape[0]), table=table, idx=idx,
+                              need_x=ctx.needs_input_grad[0], need_t=ctx.needs_input_grad[1])
+        return dx, dt, None
+
+
+def be_scale(x, table, idx=None):
+    """``y[b, c, v] = x[b, c, v] * table[idx[b], c]`` for an activation ``x`` [B, C, *spatial]
+    (channels-last memory) or rows [B, C], a table [n, C] and ``idx`` an int32 [B] device tensor
+    (``be_indices``); ``idx=None``: row 0 for every item, broadcast inside the kernel. One launch
+    forward. Backward: one pass over ``x`` and ``dy`` writes ``dx = dy * table[idx[b]]`` and fp64
+    partial sums of ``dy * x``, a small fold sums them into ``dtable`` per member over the items that
+    drew it, in item order (a member nobody drew: an exact 0 row). An index outside ``[0, n)`` in a
+    hand-made ``idx`` is never read through: its item comes out NaN."""
+    return _BeScaleFn.apply(_be_dense("be_scale", x), table, idx)
+
+
+class _BeExpandFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pre, m0, m1):
+        ctx.save_for_backward(x, pre)
+        ctx.members = (m0, m1)
+        return ops.be_expand(x, pre, None, m0, m1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, pre = ctx.saved_tensors
+        m0, m1 = ctx.members
+        dy = _be_dense("be_members_expand backward", dy)
+        dx = ops.be_members_sum(dy, pre, m0, m1) if ctx.needs_input_grad[0] else None
+        dpre = None
+        if ctx.needs_input_grad[1]:
+            dpre = ops.be_tgrad(dy, x, int(pre.shape[0]), m0, m1)[1]
+        return dx, dpre, None, None
+
+
+def be_members_expand(x, pre, m0, m1):
+    """``out[(m - m0) * B + b] = x[b] * pre[m]`` for the members ``m0 <= m < m1``: ``x`` is read once
+    and ``m1 - m0`` copies are written, one launch. Differentiable: the input gradient is a members
+    sum with table ``pre``, the table gradient the fixed-order fp64 reduction of ``be_scale``."""
+    return _BeExpandFn.apply(_be_dense("be_members_expand", x), pre, int(m0), int(m1))
+
+
+class _BeMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, post, acc, m0, m1, n):
+        ctx.save_for_backward(y, post)
+        ctx.members = (m0, m1, n)
+        return ops.be_members_sum(y, post, m0, m1, acc, 1.0 / n if m1 == n else None)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, post = ctx.saved_tensors
+        m0, m1, n = ctx.members
+        scale = 1.0 / n if m1 == n else 1.0
+        dout = _be_dense("be_members_mean backward", dout)
+        dy = ops.be_expand(dout, post, None, m0, m1, scale) if ctx.needs_input_grad[0] else None
+        dpost = None
+        if ctx.needs_input_grad[1]:
+            dpost = ops.be_tgrad(y, dout, n, m0, m1, scale)[1]
+        dacc = None
+        if ctx.needs_input_grad[2]:
+            dacc = dout if m1 != n else ops.be_expand(dout, None, None, 0, 1, scale)
+        return dy, dpost, dacc, None, None, None
+
+
+def be_members_mean(y, post, m0, m1, n, acc=None):
+    """``out[b] = acc[b] + sum_{m0 <= m < m1} post[m] * y[(m - m0) * B + b]``, a single fma chain in
+    member order (from 0 without ``acc``), times ``1 / n`` once, in the call whose ``m1 == n``: the
+    mean over ``n`` members does not depend on how they were cut into calls, bit for bit. One launch
+    per call, no stack and no mean. Differentiable through the same kernels."""
+    if tuple(post.shape)[0] != n:
+        raise ValueError(f"be_members_mean: a table of {n} rows expected, got {tuple(post.shape)}")
+    acc = None if acc is None else _be_dense("be_members_mean", acc)
+    return _BeMeanFn.apply(_be_dense("be_members_mean", y), post, acc, int(m0), int(m1),
+                           int(n))
+
+
+def _be_mixes_items(mod):
+    """True when ``mod`` holds a batch norm that takes its statistics from the batch it is given."""
+    for m in mod.modules():
+        if isinstance(m, torch.nn.modules.batchnorm._NormBase) and not isinstance(
+                m, torch.nn.modules.instancenorm._InstanceNorm):
+            if m.training or not m.track_running_stats or m.running_mean is None:
+                return True
+    return False
+
+
+def be_chunk(n, B, item_bytes):
+    """Members per launch of the "batched" route: as many as keep the expanded batch inside
+    ``BE_BATCH_BUDGET_BYTES``, at least one."""
+    return max(1, min(int(n), BE_BATCH_BUDGET_BYTES // max(1, int(B) * int(item_bytes))))
+
+
+def be_route(n, B, item_bytes, mod):
+    """The route of the eval mean over ``n`` members of a batch of ``B`` items of ``item_bytes`` each
+    through ``mod``: "batched" (members side by side in one batch, ``mod`` run once per chunk) or
+    "loop" (one member at a time). Batching is exact only where ``mod`` treats the items of a batch
+    independently: a batch norm on batch statistics inside ``mod`` forces "loop"; so does a batch of
+    which not even two members fit the byte budget."""
+    if _be_mixes_items(mod) or n < 2:
+        return "loop"
+    return "batched" if be_chunk(n, B, item_bytes) >= 2 else "loop"

@@ -6,9 +6,11 @@ adell_mri/modules/classification/classification/classification.py): ``CatNet`` (
 Module trees, attribute names and ``state_dict`` keys are the reference's (``res_net.*`` with
 ``feature_extraction`` the same module, ``classification_layer.0.op.*`` for ``CatNet`` and
 ``ViTClassifier``, ``classification_layer.op.*`` plus ``ordinal_bias`` / ``ordinal_bias_scale`` for
-``OrdNet``). Not built, each raising ``NotImplementedError`` that names the argument: the
-Gaussian-process head (``gaussian_process=True``), batch ensembles (``batch_ensemble=True``) and
-SeqPool (``use_class_token="seqpool"``).
+``OrdNet``). ``batch_ensemble=n`` (a member count) goes to the ResNet backbone, whose stages then
+run inside ``BatchEnsembleWrapper``s; ``forward(X, batch_idx=...)`` picks the members. Not built,
+each raising ``NotImplementedError`` that names the argument: the Gaussian-process head
+(``gaussian_process=True``), a bare ``batch_ensemble=True`` (the reference's annotation says bool,
+its layers need the member count and fail on a bool) and SeqPool (``use_class_token="seqpool"``).
 
 One deviation: with a ``feature_extraction`` module given, ``CatNet`` reads the module's
 ``output_features`` when it has one, and otherwise runs the reference's probe tensor on the module's
@@ -93,8 +95,12 @@ class CatNet(torch.nn.Module):
         super().__init__()
         if gaussian_process:
             raise NotImplementedError("gaussian_process=True: the Gaussian-process head is not built")
-        if batch_ensemble:
-            raise NotImplementedError("batch_ensemble=True: batch-ensemble layers are not built")
+        if isinstance(batch_ensemble, bool) and batch_ensemble:
+            raise NotImplementedError("batch_ensemble=True: give the number of members; the "
+                                      "batch-ensemble layers cannot size their tables from a flag")
+        if batch_ensemble and feature_extraction is not None:
+            raise NotImplementedError("batch_ensemble with a given feature_extraction: the members "
+                                      "live in the ResNet backbone this class builds")
         self.spatial_dim = spatial_dimensions
         self.in_channels = in_channels
         self.n_classes = n_classes
@@ -118,7 +124,7 @@ class CatNet(torch.nn.Module):
             self.res_net = ResNetBackbone(
                 self.spatial_dim, self.in_channels, self.resnet_structure, adn_fn=self.adn_fn,
                 maxpool_structure=self.maxpool_structure, res_type=self.res_type,
-                batch_ensemble=0, skip_last_activation=self.skip_last_activation)
+                batch_ensemble=int(self.batch_ensemble), skip_last_activation=self.skip_last_activation)
             self.feature_extraction = self.res_net
             self.last_size = self.resnet_structure[-1][0]
         else:
@@ -178,6 +184,7 @@ class OrdNet(CatNet):
 
     def forward(self, X: torch.Tensor, return_features: bool = False,
                 return_pre_bias: bool = False, return_only_pre_bias: bool = False):
+        # (no batch_idx, as the reference's signature: an ordinal net draws or averages its members)
         features = self.gp(self.feature_extraction(X))
         if return_features is True:
             return features

@@ -1,0 +1,1 @@
+from .batch_ensemble import BatchEnsemble, BatchEnsembleWrapper  # noqa: F401

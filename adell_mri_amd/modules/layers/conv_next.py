@@ -28,9 +28,12 @@ class ConvNeXtBackbone(torch.nn.Module):
                  first_layer_stride=4, padding=None, adn_fn: torch.nn.Module = torch.nn.Identity,
                  batch_ensemble: int = 0):
         super().__init__()
-        if spatial_dim not in (2, 3) or batch_ensemble > 0:
-            raise NotImplementedError("HIP ConvNeXtBackbone covers spatial_dim 2 / 3, "
-                                      "batch_ensemble=0")
+        if batch_ensemble > 0:
+            raise NotImplementedError(
+                "batch_ensemble > 0: the reference's ConvNeXtBackbone hands idx= to a Sequential "
+                "(a TypeError) and never calls its be_operations; ResNetBackbone has batch ensembles")
+        if spatial_dim not in (2, 3):
+            raise NotImplementedError("HIP ConvNeXtBackbone covers spatial_dim 2 / 3")
         if maxpool_structure is None:
             maxpool_structure = [2] * len(structure)
         self.spatial_dim, self.in_channels = spatial_dim, in_channels

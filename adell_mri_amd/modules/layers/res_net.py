@@ -3,13 +3,16 @@ of adell_mri/modules/layers/res_net.py:27-396) for ``res_type="resnet"`` in 3-D:
 same constructors, module tree / state_dict keys (``input_layer``, ``first_pooling``,
 ``operations``, ``pooling_operations``, ``op.linear_N``) and forward variants. Convs
 (7^3 stem, k=5 / k=3 bottleneck blocks), pooling, ADN and Linear layers are the HIP
-leaves.
+leaves. ``batch_ensemble=n`` (res_net.py:191-208): the last block of every stage skips its
+activation and ``be_operations[i]``, a ``BatchEnsembleWrapper`` without a module of its own, is
+called around the stage.
 """
 from typing import List, OrderedDict, Tuple, Union
 
 import torch
 
 from ... import functional as HF
+from .batch_ensemble import BatchEnsembleWrapper
 from .conv import Conv2d, Conv3d, MaxPool2d, MaxPool3d
 from .linear_blocks import LayerNorm, Linear
 from .res_blocks import ResidualBlock2d, ResidualBlock3d
@@ -39,9 +42,9 @@ class ResNetBackbone(torch.nn.Module):
                  res_type: str = "resnet", batch_ensemble: int = 0,
                  skip_last_activation: bool = False):
         super().__init__()
-        if spatial_dim not in (2, 3) or res_type != "resnet" or batch_ensemble > 0:
+        if spatial_dim not in (2, 3) or res_type != "resnet":
             raise NotImplementedError("HIP ResNetBackbone covers spatial_dim 2 / 3, "
-                                      "res_type='resnet', batch_ensemble=0")
+                                      "res_type='resnet'")
         if maxpool_structure is None:
             maxpool_structure = [2] * len(structure)
         self.spatial_dim, self.in_channels, self.structure = spatial_dim, in_channels, structure
@@ -55,41 +58,49 @@ class ResNetBackbone(torch.nn.Module):
             conv(in_channels, stem, 7, padding="same"), adn_fn(stem),
             conv(stem, stem, 3, padding="same"), adn_fn(stem))
         self.first_pooling = pool_op(2, 2)
-        stages, pools, width_in = [], [], stem
+        stages, be_ops, pools, width_in = [], [], [], stem
         for (width, inner, kernel, n_blocks), pool in zip(structure, maxpool_structure):
             # at least two blocks per stage, the first one changes the width
             widths = [width_in] + [width] * max(n_blocks - 1, 1)
-            stages.append(torch.nn.Sequential(
-                *[block(w, kernel, inner, width, adn_fn) for w in widths]))
+            if batch_ensemble > 0:
+                # the stage ends without its activation: the wrapper's ADN follows the post scale
+                blocks = [block(w, kernel, inner, width, adn_fn) for w in widths[:-1]]
+                blocks.append(block(widths[-1], kernel, inner, width, adn_fn, skip_activation=True))
+                be_ops.append(BatchEnsembleWrapper(None, batch_ensemble, width_in, width, adn_fn))
+            else:
+                blocks = [block(w, kernel, inner, width, adn_fn) for w in widths]
+                be_ops.append(None)
+            stages.append(torch.nn.Sequential(*blocks))
             pools.append(pool_op(pool, pool))
             width_in = width
         self.operations = torch.nn.ModuleList(stages)
-        self.be_operations = torch.nn.ModuleList([None] * len(stages))  # batch-ensemble slots: unused
+        self.be_operations = torch.nn.ModuleList(be_ops)   # batch-ensemble slots, None without
         self.pooling_operations = torch.nn.ModuleList(pools)
         self.output_features = structure[-1][0]
 
-    def _walk(self, X):
+    def _walk(self, X, batch_idx=None):
         """Yields (level output, pooled level output): the stem first, then the stages."""
         X = self.input_layer(X)
         pooled = self.first_pooling(X)
         yield X, pooled
-        for stage, pool in zip(self.operations, self.pooling_operations):
-            X = stage(pooled)
+        for stage, be_op, pool in zip(self.operations, self.be_operations, self.pooling_operations):
+            X = be_op(pooled, batch_idx, mod=stage) if self.batch_ensemble > 0 else stage(pooled)
             pooled = pool(X)
             yield X, pooled
 
     def forward_intermediate(self, X, after_pool: bool = False, batch_idx: int = None):
         """Every level including the stem."""
-        return [pooled if after_pool else features for features, pooled in self._walk(X)]
+        return [pooled if after_pool else features
+                for features, pooled in self._walk(X, batch_idx)]
 
     def forward_with_intermediate(self, X, after_pool: bool = False, batch_idx: int = None):
         """(output, the residual stages' tensors) -- the stem is not listed."""
-        levels = list(self._walk(X))
+        levels = list(self._walk(X, batch_idx))
         return levels[-1][1], [pooled if after_pool else features
                                for features, pooled in levels[1:]]
 
     def forward_regular(self, X, batch_idx: int = None):
-        for _, X in self._walk(X):
+        for _, X in self._walk(X, batch_idx):
             pass
         return X
 

@@ -4652,3 +4652,114 @@ def ensemble_average_bwd(y, dy, K, needs=None):
     check(_lib.lib().adell_ensemble_average_bwd(_ptr(y), _ptr(dy), K, int(y.shape[0]),
                                                 int(y.shape[1]), pd, _stream()))
     return dxs
+
+
+# ---- batch-ensemble layers (csrc/batch_ensemble.hip) -----------------------------------------------------
+def _be_activation(what, x):
+    """(B, V, C) of rows [B, C] (V = 1, dense) or of an activation [B, C, *spatial] whose memory is
+    dense channels-last; anything else is refused whatever ADELL_CHECK_DENSE says."""
+    if x.dim() == 2:
+        _ens_rows(what, x)
+        if x.dtype != torch.float32:
+            raise _lib.AdellHipError(f"{what}: adell_mri_amd kernels are fp32; got {x.dtype}")
+        if x.numel() == 0:
+            raise ValueError(f"{what}: empty rows {tuple(x.shape)}")
+        return int(x.shape[0]), 1, int(x.shape[1])
+    return _dif_channels_last(what, x)
+
+
+def _be_table(what, table, C):
+    if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1:
+        raise ValueError(f"{what}: a table [n, {C}] expected, got {tuple(table.shape)}")
+    _dif_layout(what, table)
+    return int(table.shape[0])
+
+
+def _be_idx(what, idx, B):
+    if idx is None:
+        return
+    if (not idx.is_cuda or idx.dtype != torch.int32 or tuple(idx.shape) != (B,)
+            or not idx.is_contiguous()):
+        raise ValueError(f"{what}: item indices are a dense int32 [{B}] device tensor, got "
+                         f"{idx.dtype} {tuple(idx.shape)} on {idx.device}")
+
+
+def _be_members(what, m0, m1, n):
+    if not 0 <= m0 < m1 <= n:
+        raise ValueError(f"{what}: members [{m0}, {m1}) of {n}")
+    return m1 - m0
+
+
+def _be_like(x, rows):
+    """An uninitialised tensor of ``rows`` items in ``x``'s layout."""
+    shape = (rows,) + tuple(x.shape[1:])
+    if x.dim() == 2:
+        return torch.empty(shape, device=x.device, dtype=torch.float32)
+    fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
+    return torch.empty(shape, device=x.device, dtype=torch.float32, memory_format=fmt)
+
+
+def be_expand(x, table, idx=None, m0=0, m1=1, scale=1.0):
+    """out[(m - m0) B + b] = x[b] * table[m] * scale for m0 <= m < m1, or with ``idx`` (int32 [B] on
+    the device, one copy) x[b] * table[idx[b]]; ``table`` None: the scale alone. One launch."""
+    what = "be_expand"
+    B, V, C = _be_activation(what, x)
+    n = _be_table(what, table, C) if table is not None else 1
+    _be_idx(what, idx, B)
+    K = 1 if idx is not None else _be_members(what, m0, m1, n)
+    out = _be_like(x, K * B)
+    check(_lib.lib().adell_be_expand(_ptr(x), _ptr(table), _ptr(idx), int(m0), K, n, float(scale),
+                                     _ptr(out), B, V, C, _stream()))
+    return out
+
+
+def be_members_sum(y, table, m0, m1, acc=None, scale=None):
+    """out[b] = acc[b] + sum_m table[m] y[(m - m0) B + b] as one fma chain in member order, times
+    ``scale`` when one is given. One launch."""
+    what = "be_members_sum"
+    rows, V, C = _be_activation(what, y)
+    n = _be_table(what, table, C)
+    K = _be_members(what, m0, m1, n)
+    if rows % K:
+        raise ValueError(f"{what}: {rows} rows for {K} members")
+    B = rows // K
+    out = _be_like(y, B)
+    if acc is not None:
+        if tuple(acc.shape) != tuple(out.shape):
+            raise ValueError(f"{what}: the running sum must be {tuple(out.shape)}, got "
+                             f"{tuple(acc.shape)}")
+        _be_activation(what, acc)
+    check(_lib.lib().adell_be_members_sum(_ptr(y), _ptr(table), _ptr(acc), int(m0), K, n,
+                                          float(scale if scale is not None else 1.0),
+                                          int(scale is not None), _ptr(out), B, V, C, _stream()))
+    return out
+
+
+def be_tgrad(p, q, n, m0=0, m1=0, scale=1.0, table=None, idx=None, need_x=False, need_t=True):
+    """(dx, dtable [n, C]). ``m1 > m0``: p holds the members [m0, m1) side by side over the items of q,
+    dtable[m] = scale sum_b sum_v p[(m - m0) B + b] q[b]. ``m1 == m0`` (the training scale's
+    backward, p = dy, q = x): dx = p table[idx] in the same pass and dtable[m] the sum over the items
+    that drew m, in item order. One pass and a fold."""
+    what = "be_tgrad"
+    B, V, C = _be_activation(what, q)
+    K = m1 - m0
+    rows, Vp, Cp = _be_activation(what, p)
+    if (rows, Vp, Cp) != (max(K, 1) * B, V, C) or p.dim() != q.dim():
+        raise ValueError(f"{what}: {tuple(p.shape)} against {tuple(q.shape)} for {max(K, 1)} members")
+    if K > 0:
+        _be_members(what, m0, m1, n)
+    if table is not None and _be_table(what, table, C) != n:
+        raise ValueError(f"{what}: a table of {n} rows expected")
+    _be_idx(what, idx, B)
+    dx = _be_like(q, B) if need_x else None
+    dt = part = None
+    if need_t:
+        dt = torch.empty((n, C), device=q.device, dtype=torch.float32)
+        words = _lib.lib().adell_be_tgrad_workspace_doubles(B, V, C, max(K, 1))
+        check(min(words, 0))
+        part = torch.empty(words, device=q.device, dtype=torch.float64)
+    if dx is None and dt is None:
+        return None, None
+    check(_lib.lib().adell_be_tgrad(_ptr(p), _ptr(q), _ptr(table), _ptr(idx), int(m0), K, n,
+                                    float(scale), _ptr(dx), _ptr(dt), _ptr(part), B, V, C, _stream()))
+    return dx, dt

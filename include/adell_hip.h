@@ -1766,6 +1766,35 @@ int adell_ensemble_average_fwd(const float* const* x, int K, int B, int C, float
 int adell_ensemble_average_bwd(const float* y, const float* dy, int K, int B, int C, float* const* dx,
                                void* stream);
 
+/* ------------------------------------------------------------------------
+ * Batch-ensemble layers (csrc/batch_ensemble.hip; the reference's modules/layers/batch_ensemble.py,
+ * arXiv:2002.06715). Activations [B][V][C] (NDHWC memory; V = 1: rows [B][C]), tables [n][C]. fp32,
+ * every sum in a fixed order in fp64, no atomics: bit-reproducible. B K <= 65535 rows per launch.
+ * ---------------------------------------------------------------------- */
+/* One launch: out[k B + b] = x[b] * table[row] * scale for k < K; x is read once. idx (int32 [B] on the
+ * device, K = 1): row = idx[b], the training scale; idx NULL: row = m0 + k, the members [m0, m0 + K)
+ * side by side. table NULL: all ones. An index outside [0, n) makes its item NaN and is never read
+ * through. */
+int adell_be_expand(const float* x, const float* table, const int* idx, int m0, int K, int n, float scale,
+                    float* out, int B, long V, int C, void* stream);
+/* One launch: out[b] = acc[b] (NULL: 0) + sum over k < K of table[m0 + k] y[k B + b], one fma chain in
+ * member order; with `scaled` the chain's end is multiplied by scale. Cutting the members into several
+ * calls (acc = the previous out) gives the same bits as one call. */
+int adell_be_members_sum(const float* y, const float* table, const float* acc, int m0, int K, int n,
+                         float scale, int scaled, float* out, int B, long V, int C, void* stream);
+/* Doubles of the partial-sum workspace of adell_be_tgrad (K = 0 counts as one copy). */
+long adell_be_tgrad_workspace_doubles(int B, long V, int C, int K);
+/* At most two launches. One pass over p [max(K, 1) B rows] and q [B rows] leaves fp64 partial sums of
+ * p[k B + b] q[b] over tiles of voxels in part; the fold writes all n rows of dtable.
+ *   K = 0, the training scale's backward (p = dy, q = x): dx[b] = p[b] table[idx[b]] in the same pass
+ *     (NULL: skipped) and dtable[m] = scale * the sum over the items with idx[b] == m in ascending
+ *     order (idx NULL: every item is member 0's); a member nobody drew gets an exact 0.
+ *   K > 0, members side by side: dtable[m0 + k] = scale * the sum over b; other rows 0. dx must be NULL.
+ * dtable NULL (with part NULL): dx alone, one launch. */
+int adell_be_tgrad(const float* p, const float* q, const float* table, const int* idx, int m0, int K,
+                   int n, float scale, float* dx, float* dtable, double* part, int B, long V, int C,
+                   void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
