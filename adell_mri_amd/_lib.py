@@ -51,6 +51,22 @@ class AdnSite(ctypes.Structure):
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
+DECONF_MAX_HEADS = 8     # ADELL_DECONF_MAX_HEADS
+
+
+class DeconfHeads(ctypes.Structure):
+    """adell_deconf_heads (include/adell_hip.h): the linear confounder heads of one launch."""
+    _fields_ = [("n_heads", ctypes.c_int32), ("n_cont", ctypes.c_int32),
+                ("K", ctypes.c_int32 * DECONF_MAX_HEADS), ("W", _vp * DECONF_MAX_HEADS),
+                ("b", _vp * DECONF_MAX_HEADS), ("Wc", _vp), ("bc", _vp)]
+
+
+class DeconfHeadGrads(ctypes.Structure):
+    """adell_deconf_head_grads: where the heads' gradients go (NULL: not wanted)."""
+    _fields_ = [("dW", _vp * DECONF_MAX_HEADS), ("db", _vp * DECONF_MAX_HEADS), ("dWc", _vp),
+                ("dbc", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/adell_hip.h declares.
 SIGNATURES = {
     "adell_abi_version": (_i, []),
@@ -295,6 +311,18 @@ SIGNATURES = {
     "adell_be_members_sum": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i, _l, _i, _vp]),
     "adell_be_tgrad_workspace_doubles": (_l, [_i, _l, _i, _i]),
     "adell_be_tgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _l, _i, _vp]),
+    "adell_deconf_split_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "adell_deconf_split_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "adell_deconf_corr_workspace_doubles": (_l, [_i, _i, _i]),
+    "adell_deconf_corr_saved_doubles": (_l, [_i, _i, _i]),
+    "adell_deconf_corr_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "adell_deconf_corr_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "adell_deconf_route": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int), _i]),
+    "adell_deconf_heads_workspace_doubles": (_l, [_i]),
+    "adell_deconf_heads_fwd": (_i, [ctypes.POINTER(DeconfHeads), _vp, _vp, _vp, _i, _i, _i, _f, _vp,
+                                    _vp, _vp]),
+    "adell_deconf_heads_bwd": (_i, [ctypes.POINTER(DeconfHeads), ctypes.POINTER(DeconfHeadGrads), _vp,
+                                    _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

@@ -3342,3 +3342,143 @@ def be_route(n, B, item_bytes, mod):
     if _be_mixes_items(mod) or n < 2:
         return "loop"
     return "batched" if be_chunk(n, B, item_bytes) >= 2 else "loop"
+
+
+# ---- deconfounded classification (csrc/deconfound.hip) ---------------------------------------------------
+class _SplitColumnsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, n):
+        ctx.geom = (int(features.shape[0]), int(features.shape[1]), n, features.device)
+        ctx.set_materialize_grads(False)
+        return ops.deconf_split_fwd(features, n)
+
+    @staticmethod
+    def backward(ctx, da, db):
+        B, F, n, dev = ctx.geom
+        if da is None and db is None:
+            return None, None
+        da = None if da is None else da.contiguous()
+        db = None if db is None else db.contiguous()
+        return ops.deconf_split_bwd(da, db, B, F, n, dev), None
+
+
+def split_columns(features, n):
+    """``(features[:, :n], features[:, n:])`` of dense rows [B, F] as two dense tensors, one launch.
+    Backward: one launch writes the whole [B, F] gradient from whichever halves have one (zeros for
+    the other), no ``cat``. This is how a column slice reaches ``functional.linear``: a strided view
+    is refused at the kernel boundary."""
+    return _SplitColumnsFn.apply(features.contiguous(), int(n))
+
+
+class _DeconfCorrFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, n_conf):
+        loss, saved = ops.deconf_corr_fwd(features, n_conf)
+        ctx.save_for_backward(features, saved)
+        ctx.n_conf = n_conf
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        features, saved = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        g = g.to(torch.float32).reshape(1).contiguous()
+        return ops.deconf_corr_bwd(features, ctx.n_conf, saved, g), None
+
+
+def deconf_correlation_loss(features, n_conf):
+    """``DeconfoundedNetPL.correlation_loss``: columns ``[0, n_conf)`` of ``features`` [B, F] against
+    columns ``[n_conf, F)``, both centred over the batch, ``r = clamp(<a, b> / clamp(|a| |b|,
+    min=1e-8), -1, 1)``, the mean of ``r^2`` over the pairs; a 0-d tensor. One launch forward, one
+    backward; the ``[B, n_conf, F - n_conf]`` product is never written (kept: mean and norm per
+    column, the ratio per pair, in fp64). Clamp gradients are torch's (passed on the closed
+    interval). One deviation: the gradient of ``sqrt`` at an exactly zero centred norm is 0, where
+    the reference's whole gradient becomes NaN: a constant column has ``r = 0`` with every partner
+    and receives an exact 0 gradient."""
+    return _DeconfCorrFn.apply(features.contiguous(), int(n_conf))
+
+
+def deconf_route(n_conf, cat_classes=(), n_cont=0, structure=()):
+    """The route of the confounder heads' loss: "fused" (``deconf_heads_loss`` in one launch) for
+    linear heads within ``n_conf <= 1024``, at most 8 categorical heads of at most 64 classes and at
+    most 64 regression outputs; "composed" (``split_columns``, the heads' own forward,
+    ``cross_entropy`` and ``mse_loss``) beyond a limit or with a non-empty ``structure``."""
+    if len(structure or ()) > 0:
+        return "composed"
+    return ops.deconf_route(n_conf, cat_classes, n_cont)
+
+
+class _DeconfHeadsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, n_conf, n_cat, has_cont, cat_targets, cont_target, conf_mult, *params):
+        cat_heads = [(params[2 * h], params[2 * h + 1]) for h in range(n_cat)]
+        cont_head = (params[2 * n_cat], params[2 * n_cat + 1]) if has_cont else None
+        out = ops.deconf_heads_fwd(features, n_conf, cat_heads, cat_targets, cont_head, cont_target,
+                                   conf_mult)
+        ctx.save_for_backward(features, cat_targets, cont_target, *params)
+        ctx.cfg = (n_conf, n_cat, has_cont, conf_mult)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_cat, g_cont):
+        features, cat_targets, cont_target, *params = ctx.saved_tensors
+        n_conf, n_cat, has_cont, conf_mult = ctx.cfg
+        none = (None,) * (7 + len(params))
+        if g_cat is None and g_cont is None:
+            return none
+        cat_heads = [(params[2 * h], params[2 * h + 1]) for h in range(n_cat)]
+        cont_head = (params[2 * n_cat], params[2 * n_cat + 1]) if has_cont else None
+        g_cat = None if g_cat is None or not n_cat else g_cat.to(torch.float32).reshape(1).contiguous()
+        g_cont = (None if g_cont is None or not has_cont
+                  else g_cont.to(torch.float32).reshape(1).contiguous())
+        dx, dcat, dcont = ops.deconf_heads_bwd(
+            features, n_conf, cat_heads, cat_targets, cont_head, cont_target, conf_mult, g_cat, g_cont,
+            need_x=ctx.needs_input_grad[0], need_w=any(ctx.needs_input_grad[7:]))
+        grads = []
+        for pair in dcat + ([dcont] if dcont is not None else []):
+            grads += list(pair)
+        if not grads:
+            grads = [None] * len(params)
+        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[7:])]
+        return (dx, None, None, None, None, None, None, *grads)
+
+
+def deconf_heads_loss(features, n_conf, cat_heads, cat_targets, cont_head, cont_target, conf_mult=1.0):
+    """``(cat_loss | None, cont_loss | None)`` of the default linear confounder heads on
+    ``features[:, :n_conf]``, read in place: ``cat_heads`` a list of ``(W [K, n_conf], b [K])``,
+    ``cat_targets`` ONE int64 ``[n_heads, B]`` device table, ``cont_head`` ``(W [n_cont, n_conf],
+    b)`` with ``cont_target`` [B, n_cont]; either kind may be absent (empty list / None).
+    ``cat_loss = conf_mult * sum_h CE_h / n_heads`` (mean cross entropy per head), ``cont_loss =
+    conf_mult * mse``. A label outside ``[0, K)`` is never used as an index: the loss is NaN.
+    Fused route (``deconf_route``): one launch forward, two backward (d features, every dW and db).
+    Beyond its limits the same values come from ``split_columns``, ``linear``, ``cross_entropy`` and
+    ``mse_loss``."""
+    cat_heads = list(cat_heads or [])
+    if not cat_heads and cont_head is None:
+        return None, None
+    n_conf = int(n_conf)
+    if features.dim() != 2 or not 0 < n_conf < features.shape[1]:
+        raise ValueError(f"deconf_heads_loss: features [B, F] and n_conf in (0, F) expected, got "
+                         f"{tuple(features.shape)} and n_conf {n_conf}")
+    n_cont = int(cont_head[0].shape[0]) if cont_head is not None else 0
+    if deconf_route(n_conf, [int(W.shape[0]) for W, _ in cat_heads], n_cont) == "composed":
+        conf, _ = split_columns(features, n_conf)
+        cat_loss = cont_loss = None
+        if cat_heads:
+            cat_loss = sum(cross_entropy(linear(conf, W, b), cat_targets[h]) / len(cat_heads)
+                           for h, (W, b) in enumerate(cat_heads)) * conf_mult
+        if cont_head is not None:
+            pred = linear(conf, cont_head[0], cont_head[1])
+            cont_loss = mse_loss(pred, cont_target.to(pred)) * conf_mult
+        return cat_loss, cont_loss
+    params = [t for pair in cat_heads for t in pair] + (list(cont_head) if cont_head is not None else [])
+    if cont_head is not None:
+        cont_target = cont_target.detach().to(device=features.device, dtype=torch.float32).contiguous()
+    cat, cont = _DeconfHeadsFn.apply(features.contiguous(), n_conf, len(cat_heads),
+                                     cont_head is not None,
+                                     None if not cat_heads else cat_targets,
+                                     cont_target if cont_head is not None else None,
+                                     float(conf_mult), *params)
+    return (cat if cat_heads else None), (cont if cont_head is not None else None)

@@ -19,6 +19,9 @@ weight decay and the normal group, or the head / body split when ``weight_decay`
 ``on_train_end``, ``predict_step_gp``), and ``optimizer_groups`` puts the trainable parameters of
 any ``GaussianProcessLayer`` into the no-decay group.
 
+``DeconfoundedNetPL`` (:2275-2573) wraps ``DeconfoundedNetGeneric``: its four loss terms, Adam over
+the confounder / classifier groups (see the class).
+
 Not mirrored: ``calibrate`` / ``predict_calibrated_step`` (conformal calibration), ``on_train_end``
 and ``predict_step_gp`` of the single-network wrappers (their Gaussian-process head is not built),
 and the hyper-parameter logging of ``on_train_start``.
@@ -30,10 +33,12 @@ from typing import Callable
 import torch
 
 from ... import classification_metrics as CM
-from ...optim import FusedAdamW
+from ... import functional as HF
+from ...optim import FusedAdam, FusedAdamW
 from ..learning_rate import CosineAnnealingWithWarmupLR
 from ..layers.gaussian_process import GaussianProcessLayer
 from .classification import CatNet, OrdNet, ViTClassifier, ordinal_prediction_to_class
+from .deconfounded_classification import DeconfoundedNetGeneric
 from .ensemble import AveragingEnsemble, GenericEnsemble
 from .losses import BCEWithLogitsLoss
 from .multiple_instance_learning import MultipleInstanceClassifier, TransformableTransformer
@@ -553,3 +558,188 @@ class AveragingEnsemblePL(AveragingEnsemble, _EnsemblePL):
                  *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._setup_wrapper(locals())
+
+
+class DeconfoundedNetPL(DeconfoundedNetGeneric, ClassPLABC):
+    """pl.py:2275-2573: the feature deconfounder's training wrapper. The network IS the module (its
+    parameters carry no ``network.`` prefix). ``step`` returns the reference's 6-tuple
+    ``(classification loss, cat_conf_loss | None, cont_conf_loss | None, feature_loss | None,
+    classification, y)``; the training and validation steps return the sum of the terms present.
+
+    On the device: ``correlation_loss`` is ``functional.deconf_correlation_loss``; with the default
+    linear heads (empty ``deconfounder_structure``) inside the fused limits and the features on the
+    GPU, ``step`` skips the heads' own forward and takes both confounder losses from
+    ``functional.deconf_heads_loss``, which reads the feature rows in place
+    (``heads_route`` names the route). Otherwise the heads run and ``loss_cat_confounder`` /
+    ``loss_cont_confounder`` compose the same values. The embedder runs on the host; its integer
+    tensors are stacked and uploaded once as an int64 ``[n_heads, B]`` table. A batch entry that is
+    already such a table (a tensor) is taken as it is.
+
+    ``configure_optimizers`` is Adam, not AdamW, as in the reference: ``FusedAdam`` over two groups,
+    the parameters whose name contains "confound" at weight decay 0 and the rest at
+    ``weight_decay``. The reference's default ``loss_fn`` is ``F.binary_cross_entropy`` on logits,
+    which no caller keeps; the default here is ``BCEWithLogitsLoss()``, as for ``ClassNetPL``.
+    ``cosine_loss`` is kept as written (torch's ``cosine_similarity`` along axis 1 of the broadcast
+    pair); no step calls it."""
+
+    def __init__(self, image_key: str = "image", label_key: str = "label",
+                 embedder: torch.nn.Module = None, cat_confounder_key: str = None,
+                 cont_confounder_key: str = None, learning_rate: float = 0.001, batch_size: int = 4,
+                 weight_decay: float = 0.0, training_dataloader_call: Callable = None,
+                 loss_fn: Callable = None, loss_params: dict = {}, n_epochs: int = 100,
+                 warmup_steps: int = 0, start_decay: int = None,
+                 training_batch_preproc: Callable = None,
+                 optimizer_eps: float = OPTIMIZER_EPS_DEFAULT, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        loss_fn = BCEWithLogitsLoss() if loss_fn is None else loss_fn
+        _store(self, locals(), _HYPERPARAMETERS)
+        self.embedder = embedder
+        self.cat_confounder_key = cat_confounder_key
+        self.cont_confounder_key = cont_confounder_key
+        self.loss_str = ["loss", "cat_loss", "cont_loss", "feat_loss"]
+        self.conf_mult = 1.0
+        self.save_hyperparameters(ignore=_IGNORED)
+        self.setup_metrics()
+
+    # ---- the confounder targets -------------------------------------------------------------------
+    def cat_confounder_table(self, y, device):
+        """The int64 ``[n_heads, B]`` device table of the categorical confounders: a tensor is taken
+        as that table, anything else goes through the embedder on the host and is uploaded once."""
+        if torch.is_tensor(y):
+            return y.to(device=device, dtype=torch.int64)
+        table = torch.stack([t.to(torch.int64) for t in self.embedder(y)])
+        if torch.device(device).type == "cuda":
+            return table.pin_memory().to(device, non_blocking=True)
+        return table.to(device)
+
+    # ---- losses -------------------------------------------------------------------------------------
+    def loss_cat_confounder(self, pred, y):
+        table = self.cat_confounder_table(y, pred[0].device)
+        return sum(HF.cross_entropy(p, y_) / len(pred) for p, y_ in zip(pred, table)) * self.conf_mult
+
+    def loss_cont_confounder(self, pred, y):
+        return HF.mse_loss(pred, torch.as_tensor(y).to(pred)) * self.conf_mult
+
+    def correlation_loss(self, features):
+        return HF.deconf_correlation_loss(features, self.n_features_deconfounder)
+
+    def cosine_loss(self, features):
+        conf_f = features[:, :self.n_features_deconfounder, None]
+        deconf_f = features[:, None, self.n_features_deconfounder:]
+        return torch.nn.functional.cosine_similarity(conf_f, deconf_f).mean()
+
+    def loss_features(self, features):
+        if self.n_features_deconfounder > 0:
+            return self.correlation_loss(features)
+
+    def heads_route(self, device=None):
+        """ "fused" when ``step`` takes the confounder losses from ``deconf_heads_loss`` for tensors
+        on ``device`` (default: the parameters'), else "composed"."""
+        device = next(self.parameters()).device if device is None else torch.device(device)
+        heads = self.linear_heads()
+        want_cat = self.cat_confounder_key is not None and len(self.n_cat_deconfounder) > 0
+        want_cont = self.cont_confounder_key is not None and self.n_cont_deconfounder > 0
+        if heads is None or device.type != "cuda" or not (want_cat or want_cont):
+            return "composed"
+        return HF.deconf_route(self.n_features_deconfounder,
+                               self.n_cat_deconfounder if want_cat else [],
+                               self.n_cont_deconfounder if want_cont else 0)
+
+    def fused_confounder_losses(self, batch, features):
+        """``(cat_conf_loss | None, cont_conf_loss | None)`` of the linear heads from the feature rows
+        in place (``functional.deconf_heads_loss``): the heads whose key is set."""
+        cat_heads, cont_head = self.linear_heads()
+        table = cont_target = None
+        if self.cat_confounder_key is not None and cat_heads:
+            table = self.cat_confounder_table(batch[self.cat_confounder_key], features.device)
+        else:
+            cat_heads = []
+        if self.cont_confounder_key is not None and cont_head is not None:
+            cont_target = torch.as_tensor(batch[self.cont_confounder_key]).to(features)
+        else:
+            cont_head = None
+        return HF.deconf_heads_loss(features, self.n_features_deconfounder, cat_heads, table,
+                                    cont_head, cont_target, self.conf_mult)
+
+    def step(self, batch, with_loss_params: bool):
+        x, y = batch[self.image_key], batch[self.label_key]
+        if getattr(self, "training_batch_preproc", None) is not None:
+            x, y = self.training_batch_preproc(x, y)
+        fused = self.heads_route(x.device) == "fused"
+        classification, confounder_classification, confounder_regression, features = self.forward(
+            x, heads=not fused)
+        cat_conf_loss = cont_conf_loss = feature_loss = None
+        if fused:
+            cat_conf_loss, cont_conf_loss = self.fused_confounder_losses(batch, features)
+        else:
+            if self.cat_confounder_key is not None:
+                cat_conf_loss = self.loss_cat_confounder(confounder_classification,
+                                                         batch[self.cat_confounder_key])
+            if self.cont_confounder_key is not None:
+                cont_conf_loss = self.loss_cont_confounder(confounder_regression,
+                                                           batch[self.cont_confounder_key])
+        if self.cat_confounder_key or self.cont_confounder_key:
+            feature_loss = self.loss_features(features)
+        classification_loss = self.calculate_loss(classification.squeeze(1), y,
+                                                  with_loss_params=with_loss_params)
+        return (classification_loss, cat_conf_loss, cont_conf_loss, feature_loss, classification, y)
+
+    def log_losses(self, losses, prefix: str):
+        for loss_val, s in zip(losses, self.loss_str):
+            if loss_val is not None:
+                self.log(f"{prefix}_{s}", loss_val.detach(), prog_bar=True)
+
+    def _losses(self, batch, with_loss_params, prefix):
+        output = self.step(batch, with_loss_params=with_loss_params)
+        losses = [loss_val.mean() if loss_val is not None else None for loss_val in output[:4]]
+        self.log_losses(losses, prefix)
+        return sum(loss_val for loss_val in losses if loss_val is not None), output[4:]
+
+    def training_step(self, batch, batch_idx):
+        return self._losses(batch, True, "tr")[0]
+
+    def validation_step(self, batch, batch_idx):
+        total, (prediction, y) = self._losses(batch, False, "val")
+        self.update_metrics(prediction, y, self.val_metrics, on_epoch=True, prog_bar=True)
+        return total
+
+    def test_step(self, batch, batch_idx):
+        total, (prediction, y) = self._losses(batch, False, "test")
+        self.update_metrics(prediction, y, self.test_metrics, log=False, on_epoch=True, prog_bar=True)
+        return total
+
+    def update_metrics(self, prediction, y, metrics, log=True, **kwargs):
+        y = y.to(prediction.device).long()
+        if self.n_classes == 2:
+            prediction = torch.sigmoid(prediction.detach()).squeeze(1)
+        else:
+            prediction = torch.softmax(prediction.detach(), -1)
+        if len(y.shape) > 1:
+            y = y.squeeze(1)
+        CM.update_many(metrics.values(), prediction, y)
+        if log is True:
+            for k in metrics:
+                self.log(k, metrics[k], **kwargs)
+
+    def confounder_groups(self):
+        """pl.py:2531-2547: the parameters whose name contains "confound" at weight decay 0, the
+        rest at ``weight_decay``."""
+        params_confounder, params_classifier = [], []
+        for n, p in self.named_parameters():
+            (params_confounder if "confound" in n else params_classifier).append(p)
+        return [{"params": params_confounder, "weight_decay": 0},
+                {"params": params_classifier, "weight_decay": self.weight_decay}]
+
+    def configure_optimizers(self) -> dict:
+        optimizer = FusedAdam(self.confounder_groups(), lr=self.learning_rate, eps=self.optimizer_eps)
+        lr_schedulers = CosineAnnealingWithWarmupLR(
+            optimizer, T_max=self.n_epochs, start_decay=self.start_decay,
+            n_warmup_steps=self.warmup_steps)
+        return {"optimizer": optimizer, "lr_scheduler": lr_schedulers, "monitor": "val_loss"}
+
+    def predict_step(self, batch, batch_idx, dataloader_idx=0, *args, **kwargs):
+        x = batch[self.image_key]
+        prediction = self.forward(x, *args, **kwargs)
+        if kwargs.get("return_features", False):
+            return {"features": prediction}
+        return {"prediction": torch.squeeze(prediction[0], 1)}

@@ -4763,3 +4763,175 @@ def be_tgrad(p, q, n, m0=0, m1=0, scale=1.0, table=None, idx=None, need_x=False,
     check(_lib.lib().adell_be_tgrad(_ptr(p), _ptr(q), _ptr(table), _ptr(idx), int(m0), K, n,
                                     float(scale), _ptr(dx), _ptr(dt), _ptr(part), B, V, C, _stream()))
     return dx, dt
+
+
+# ---- deconfounded classification (csrc/deconfound.hip) ---------------------------------------------------
+DECONF_ROUTES = {0: "fused", 1: "composed"}
+DECONF_MAX_HEADS = _lib.DECONF_MAX_HEADS   # ADELL_DECONF_MAX_HEADS
+DECONF_MAX_CLASSES = 64                    # ADELL_DECONF_MAX_CLASSES
+DECONF_MAX_CONT = 64                       # ADELL_DECONF_MAX_CONT
+DECONF_MAX_CONF = 1024                     # ADELL_DECONF_MAX_CONF
+
+
+def _deconf_features(what, features, n_conf):
+    """(B, F) of the dense fp32 device rows [B, F] the kernels read in place, 0 < n_conf < F."""
+    if features.dim() != 2:
+        raise ValueError(f"{what}: features [B, F] expected, got {tuple(features.shape)}")
+    B, F = (int(v) for v in features.shape)
+    n_conf = int(n_conf)
+    if not 0 < n_conf < F:
+        raise ValueError(f"{what}: n_conf must lie in (0, {F}), got {n_conf}")
+    if B < 1:
+        raise ValueError(f"{what}: empty batch {tuple(features.shape)}")
+    _ens_rows(what, features)
+    return B, F
+
+
+def deconf_route(n_conf, cat_classes=(), n_cont=0):
+    """The route of the confounder heads over ``n_conf`` columns with categorical heads of
+    ``cat_classes`` classes and ``n_cont`` regression outputs, by the library's own host function (no
+    device needed): "fused" (deconf_heads_fwd / _bwd) or "composed"."""
+    K = [int(k) for k in cat_classes]
+    arr = (ctypes.c_int * max(1, len(K)))(*K)
+    rc = _lib.lib().adell_deconf_route(int(n_conf), len(K), arr, int(n_cont or 0))
+    check(min(rc, 0))
+    return DECONF_ROUTES[rc]
+
+
+def deconf_split_fwd(features, n_conf):
+    """The dense halves [B, n_conf] and [B, F - n_conf] of the rows; one launch."""
+    what = "split_columns"
+    B, F = _deconf_features(what, features, n_conf)
+    a = torch.empty((B, n_conf), device=features.device, dtype=torch.float32)
+    b = torch.empty((B, F - n_conf), device=features.device, dtype=torch.float32)
+    check(_lib.lib().adell_deconf_split_fwd(_ptr(features), _ptr(a), _ptr(b), B, F, int(n_conf),
+                                            _stream()))
+    return a, b
+
+
+def deconf_split_bwd(da, db, B, F, n_conf, device):
+    """The whole [B, F] gradient from the halves' (None: zeros); one launch."""
+    what = "split_columns backward"
+    for g, w in ((da, n_conf), (db, F - n_conf)):
+        if g is not None and tuple(g.shape) != (B, w):
+            raise ValueError(f"{what}: a gradient [{B}, {w}] expected, got {tuple(g.shape)}")
+    _ens_rows(what, da, db)
+    dx = torch.empty((B, F), device=device, dtype=torch.float32)
+    check(_lib.lib().adell_deconf_split_bwd(_ptr(da), _ptr(db), _ptr(dx), B, F, int(n_conf),
+                                            _stream()))
+    return dx
+
+
+def deconf_corr_fwd(features, n_conf):
+    """(loss [1], saved): the mean squared clamped correlation of the pairs (confounded column,
+    other column); ``saved`` holds the per-column means and centred norms and the ratio of every
+    pair before the clamp, in fp64. One launch (and its counter's memset)."""
+    what = "deconf_correlation_loss"
+    B, F = _deconf_features(what, features, n_conf)
+    h = _lib.lib()
+    words = h.adell_deconf_corr_workspace_doubles(B, F, int(n_conf))
+    keep = h.adell_deconf_corr_saved_doubles(B, F, int(n_conf))
+    check(min(words, keep, 0))
+    ws = torch.empty(words, device=features.device, dtype=torch.float64)
+    saved = torch.empty(keep, device=features.device, dtype=torch.float64)
+    loss = torch.empty(1, device=features.device, dtype=torch.float32)
+    check(h.adell_deconf_corr_fwd(_ptr(features), B, F, int(n_conf), _ptr(ws), _ptr(saved), _ptr(loss),
+                                  _stream()))
+    return loss, saved
+
+
+def deconf_corr_bwd(features, n_conf, saved, g):
+    """g times the gradient of the loss, the whole [B, F]; one launch."""
+    what = "deconf_correlation_loss backward"
+    B, F = _deconf_features(what, features, n_conf)
+    _ens_rows(what, g)
+    if g.numel() != 1 or saved.dtype != torch.float64 or not saved.is_cuda \
+            or saved.numel() != 2 * F + n_conf * (F - n_conf):
+        raise ValueError(f"{what}: a one-element gradient and the forward's statistics expected")
+    dx = torch.empty_like(features)
+    check(_lib.lib().adell_deconf_corr_bwd(_ptr(features), _ptr(saved), _ptr(g), B, F, int(n_conf),
+                                           _ptr(dx), _stream()))
+    return dx
+
+
+def _deconf_heads(what, features, n_conf, cat_heads, cat_targets, cont_head, cont_target):
+    """(B, F, O, adell_deconf_heads) after the argument checks of the fused heads."""
+    B, F = _deconf_features(what, features, n_conf)
+    cat_heads = list(cat_heads or [])
+    if not cat_heads and cont_head is None:
+        raise ValueError(f"{what}: no head")
+    if len(cat_heads) > DECONF_MAX_HEADS:
+        raise NotImplementedError(f"{what}: {len(cat_heads)} heads, the fused route takes "
+                                  f"{DECONF_MAX_HEADS}")
+    hd = _lib.DeconfHeads()
+    hd.n_heads, hd.n_cont = len(cat_heads), 0
+    O = 0
+    for h, (W, b) in enumerate(cat_heads):
+        if W.dim() != 2 or W.shape[1] != n_conf or b is None or tuple(b.shape) != (W.shape[0],):
+            raise ValueError(f"{what}: head {h}: W [K, {n_conf}] and b [K] expected, got "
+                             f"{tuple(W.shape)} and {None if b is None else tuple(b.shape)}")
+        _ens_rows(what, W, b)
+        hd.K[h], hd.W[h], hd.b[h] = int(W.shape[0]), W.data_ptr(), b.data_ptr()
+        O += int(W.shape[0])
+    if cat_heads:
+        if (cat_targets is None or not cat_targets.is_cuda or cat_targets.dtype != torch.int64
+                or tuple(cat_targets.shape) != (len(cat_heads), B) or not cat_targets.is_contiguous()):
+            raise ValueError(f"{what}: the labels are one dense int64 [{len(cat_heads)}, {B}] device "
+                             f"table, got {None if cat_targets is None else (cat_targets.dtype, tuple(cat_targets.shape), cat_targets.device)}")
+    if cont_head is not None:
+        W, b = cont_head
+        if W.dim() != 2 or W.shape[1] != n_conf or b is None or tuple(b.shape) != (W.shape[0],):
+            raise ValueError(f"{what}: regression head: W [n_cont, {n_conf}] and b [n_cont] expected")
+        if cont_target is None or tuple(cont_target.shape) != (B, W.shape[0]):
+            raise ValueError(f"{what}: a regression target [{B}, {W.shape[0]}] expected, got "
+                             f"{None if cont_target is None else tuple(cont_target.shape)}")
+        _ens_rows(what, W, b, cont_target)
+        hd.n_cont, hd.Wc, hd.bc = int(W.shape[0]), W.data_ptr(), b.data_ptr()
+        O += int(W.shape[0])
+    if deconf_route(n_conf, [int(W.shape[0]) for W, _ in cat_heads], hd.n_cont) != "fused":
+        raise NotImplementedError(
+            f"{what}: beyond the fused route (n_conf <= {DECONF_MAX_CONF}, heads of <= "
+            f"{DECONF_MAX_CLASSES} classes, <= {DECONF_MAX_CONT} regression outputs)")
+    return B, F, O, hd
+
+
+def deconf_heads_fwd(features, n_conf, cat_heads, cat_targets, cont_head, cont_target, conf_mult=1.0):
+    """out [2] = (cat_loss, cont_loss) of the linear heads on features[:, :n_conf] read in place; one
+    launch (and its counter's memset)."""
+    what = "deconf_heads_loss"
+    B, F, _, hd = _deconf_heads(what, features, n_conf, cat_heads, cat_targets, cont_head, cont_target)
+    h = _lib.lib()
+    ws = torch.empty(h.adell_deconf_heads_workspace_doubles(B), device=features.device,
+                     dtype=torch.float64)
+    out = torch.empty(2, device=features.device, dtype=torch.float32)
+    check(h.adell_deconf_heads_fwd(ctypes.byref(hd), _ptr(features), _ptr(cat_targets),
+                                   _ptr(cont_target if cont_head is not None else None), B, F,
+                                   int(n_conf), float(conf_mult), _ptr(ws), _ptr(out), _stream()))
+    return out
+
+
+def deconf_heads_bwd(features, n_conf, cat_heads, cat_targets, cont_head, cont_target, conf_mult,
+                     g_cat, g_cont, need_x=True, need_w=True):
+    """(dx [B, F] or None, [(dW, db) per categorical head], (dWc, dbc) or None); two launches, one
+    without the heads' gradients. ``g_cat`` / ``g_cont``: one-element device gradients or None."""
+    what = "deconf_heads_loss backward"
+    B, F, O, hd = _deconf_heads(what, features, n_conf, cat_heads, cat_targets, cont_head, cont_target)
+    _ens_rows(what, g_cat, g_cont)
+    dev = features.device
+    dz = torch.empty((B, O), device=dev, dtype=torch.float64)
+    dx = torch.empty_like(features) if need_x else None
+    gr, cat_grads, cont_grads = None, [], None
+    if need_w:
+        gr = _lib.DeconfHeadGrads()
+        for h, (W, b) in enumerate(cat_heads or []):
+            dW, db = torch.empty_like(W), torch.empty_like(b)
+            gr.dW[h], gr.db[h] = dW.data_ptr(), db.data_ptr()
+            cat_grads.append((dW, db))
+        if cont_head is not None:
+            cont_grads = (torch.empty_like(cont_head[0]), torch.empty_like(cont_head[1]))
+            gr.dWc, gr.dbc = cont_grads[0].data_ptr(), cont_grads[1].data_ptr()
+    check(_lib.lib().adell_deconf_heads_bwd(
+        ctypes.byref(hd), ctypes.byref(gr) if gr is not None else None, _ptr(features),
+        _ptr(cat_targets), _ptr(cont_target if cont_head is not None else None), _ptr(g_cat),
+        _ptr(g_cont), B, F, int(n_conf), float(conf_mult), _ptr(dz), _ptr(dx), _stream()))
+    return dx, cat_grads, cont_grads

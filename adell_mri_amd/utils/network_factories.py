@@ -1,5 +1,6 @@
 """Network factories of the hot path: ``get_classification_network``
-(adell_mri/utils/network_factories.py:136-305), ``get_segmentation_network`` (:493-701) and
+(adell_mri/utils/network_factories.py:136-305), ``get_deconfounded_classification_network``
+(:309-402), ``get_segmentation_network`` (:493-701) and
 ``get_ssl_network`` (:705-1028) on this
 package's HIP-backed modules. Same argument lists, same keyword plumbing into the ``*PL``
 constructors, same ``ValueError`` for an unknown ``net_type``. ``ssl_method="dino"`` builds
@@ -88,6 +89,47 @@ def get_classification_network(
     for k in ["in_channels", "n_classes", "adn_fn"]:
         network_config.pop(k, None)
     return ClassNetPL(net_type=net_type, adn_fn=adn_fn, **boilerplate_args, **network_config)
+
+
+def get_deconfounded_classification_network(
+        network_config: dict[str, Any], dropout_param: float, seed: int, n_classes: int,
+        keys: list[str], cat_confounder_key: list[str], cont_confounder_key: list[str],
+        cat_vars: list[list[str]], cont_vars: int, train_loader_call: Callable, max_epochs: int,
+        warmup_steps: int, start_decay: int, n_features_deconfounder: int = 64,
+        exclude_surrogate_variables: bool = False, label_smoothing: float | None = None,
+        mixup_alpha: float | None = None, partial_mixup: float | None = None,
+        optimizer_eps: float = OPTIMIZER_EPS_DEFAULT):
+    """network_factories.py:309-402: ``DeconfoundedNetPL`` with the reference's keyword plumbing
+    (``act_fn``, default "relu", and ``norm_fn`` popped from a copy of ``network_config`` into the
+    3-D ``adn_fn``, the ``BatchPreprocessing`` of the three mixup arguments, a
+    ``CategoricalConversion`` of ``cat_vars`` as the embedder and its level counts as
+    ``n_cat_deconfounder``). ``network_config`` names the feature extractor
+    (``feature_extraction_module="cat"``); without it the reference's default "vgg" raises
+    ``NotImplementedError``."""
+    from ..modules.classification.deconfounded_classification import CategoricalConversion
+    from ..modules.classification.pl import DeconfoundedNetPL
+    from .batch_preprocessing import BatchPreprocessing
+
+    network_config = dict(network_config)
+    act_fn = network_config.pop("act_fn", "relu")
+    norm_fn = network_config.pop("norm_fn", "batch")
+    adn_fn = get_adn_fn(3, norm_fn, act_fn=act_fn, dropout_param=dropout_param)
+    batch_preprocessing = BatchPreprocessing(label_smoothing, mixup_alpha, partial_mixup, seed)
+    cat_conv = CategoricalConversion(cat_vars) if cat_vars is not None else None
+    boilerplate_args = {
+        "in_channels": len(keys), "n_classes": n_classes,
+        "training_dataloader_call": train_loader_call, "image_key": "image", "label_key": "label",
+        "n_epochs": max_epochs, "warmup_steps": warmup_steps,
+        "training_batch_preproc": batch_preprocessing, "start_decay": start_decay,
+        "optimizer_eps": optimizer_eps,
+    }
+    n_cat_deconfounder = [len(x) for x in cat_vars] if cat_vars is not None else None
+    return DeconfoundedNetPL(
+        adn_fn=adn_fn, embedder=cat_conv, n_features_deconfounder=n_features_deconfounder,
+        n_cat_deconfounder=n_cat_deconfounder, n_cont_deconfounder=cont_vars,
+        cat_confounder_key=cat_confounder_key, cont_confounder_key=cont_confounder_key,
+        exclude_surrogate_variables=exclude_surrogate_variables, **boilerplate_args,
+        **network_config)
 
 
 def get_detection_network(

@@ -1795,6 +1795,68 @@ int adell_be_tgrad(const float* p, const float* q, const float* table, const int
                    int n, float scale, float* dx, float* dtable, double* part, int B, long V, int C,
                    void* stream);
 
+/* ------------------------------------------------------------------------
+ * Deconfounded classification (csrc/deconfound.hip; the reference's DeconfoundedNetPL,
+ * modules/classification/pl.py). The pooled features x [B][F] are read in place: columns [0, n) are
+ * the confounded ones, [n, F) the others, 0 < n < F. fp32, every sum in a fixed order in fp64, no float
+ * atomics: bit-reproducible.
+ * ---------------------------------------------------------------------- */
+/* One launch each: a [B][n] and b [B][F - n] from x; dx [B][F] from da and db (NULL: zeros). */
+int adell_deconf_split_fwd(const float* x, float* a, float* b, int B, int F, int n, void* stream);
+int adell_deconf_split_bwd(const float* da, const float* db, float* dx, int B, int F, int n, void* stream);
+/* Doubles of the forward's workspace (16 bytes of ticket counter and a partial per block) and of what it
+ * keeps for the backward: mean [F], centred norm [F], the ratio before the clamp [n][F - n]. */
+long adell_deconf_corr_workspace_doubles(int B, int F, int n);
+long adell_deconf_corr_saved_doubles(int B, int F, int n);
+/* One launch (and the counter's memset): loss[0] = the mean over the n (F - n) pairs of
+ * clamp(<a', b'> / max(|a'| |b'|, 1e-8), -1, 1)^2, a' and b' the columns centred over the batch. */
+int adell_deconf_corr_fwd(const float* x, int B, int F, int n, double* ws, double* saved, float* loss,
+                          void* stream);
+/* One launch: dx [B][F] = g[0] * the gradient, clamp gradients passed on their closed intervals; the
+ * gradient of sqrt at an exactly zero centred norm is 0 (such a column gets an exact 0). */
+int adell_deconf_corr_bwd(const float* x, const double* saved, const float* g, int B, int F, int n,
+                          float* dx, void* stream);
+#define ADELL_DECONF_MAX_HEADS 8    /* categorical heads of one launch */
+#define ADELL_DECONF_MAX_CLASSES 64 /* classes of one head */
+#define ADELL_DECONF_MAX_CONT 64    /* outputs of the regression head */
+#define ADELL_DECONF_MAX_CONF 1024  /* confounded columns (kept in LDS) */
+#define ADELL_DECONF_FUSED 0
+#define ADELL_DECONF_COMPOSED 1
+/* The linear confounder heads: W[h] [K[h]][n] and b[h] [K[h]] per categorical head, Wc [n_cont][n] and
+ * bc [n_cont] of the regression head (device pointers, the struct itself on the host). */
+typedef struct adell_deconf_heads {
+  int32_t n_heads, n_cont;
+  int32_t K[ADELL_DECONF_MAX_HEADS];
+  const float* W[ADELL_DECONF_MAX_HEADS];
+  const float* b[ADELL_DECONF_MAX_HEADS];
+  const float* Wc;
+  const float* bc;
+} adell_deconf_heads;
+typedef struct adell_deconf_head_grads { /* NULL: not wanted */
+  float* dW[ADELL_DECONF_MAX_HEADS];
+  float* db[ADELL_DECONF_MAX_HEADS];
+  float* dWc;
+  float* dbc;
+} adell_deconf_head_grads;
+/* Host only: ADELL_DECONF_FUSED when the kernels below take n confounded columns, n_heads heads of K[h]
+ * classes and n_cont regression outputs, ADELL_DECONF_COMPOSED beyond a limit above, or ADELL_E_BADARG. */
+int adell_deconf_route(int n, int n_heads, const int* K, int n_cont);
+long adell_deconf_heads_workspace_doubles(int B);
+/* One launch (and the counter's memset): out[0] = conf_mult * sum_h mean_b CE(x[b][:n] W[h]^T + b[h],
+ * cat_t[h][b]) / n_heads, out[1] = conf_mult * the mean squared error of the regression head against
+ * cont_t [B][n_cont]; 0 for a kind without heads. cat_t: int64 [n_heads][B]; a label outside [0, K[h])
+ * is never used as an index and makes the loss NaN. */
+int adell_deconf_heads_fwd(const adell_deconf_heads* hd, const float* x, const long long* cat_t,
+                           const float* cont_t, int B, int F, int n, float conf_mult, double* ws,
+                           float* out, void* stream);
+/* Two launches: dz [B][sum K + n_cont] doubles (workspace) and dx [B][F] (zeros past n; NULL: skipped)
+ * per item, then every dW and db of gr (NULL: one launch) over the items in order. g_cat / g_cont: the
+ * one-element gradients of out[0] / out[1] (NULL: none). */
+int adell_deconf_heads_bwd(const adell_deconf_heads* hd, const adell_deconf_head_grads* gr, const float* x,
+                           const long long* cat_t, const float* cont_t, const float* g_cat,
+                           const float* g_cont, int B, int F, int n, float conf_mult, double* dz,
+                           float* dx, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
