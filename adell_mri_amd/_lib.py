@@ -323,6 +323,9 @@ SIGNATURES = {
                                     _vp, _vp]),
     "adell_deconf_heads_bwd": (_i, [ctypes.POINTER(DeconfHeads), ctypes.POINTER(DeconfHeadGrads), _vp,
                                     _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "adell_boot_auroc_route": (_i, [_i]),
+    "adell_boot_auroc_pairs": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "adell_aps_cumulative": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "adell_convt_k2_applicable": (_i, [_i] * 6),
     "adell_convt_k2_fwd": (_i, [_i] * 6 + [_vp] * 5),
     "adell_convt_k2_bwd_data": (_i, [_i] * 6 + [_vp] * 4),

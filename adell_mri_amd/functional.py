@@ -3482,3 +3482,54 @@ def deconf_heads_loss(features, n_conf, cat_heads, cat_targets, cont_head, cont_
                                      cont_target if cont_head is not None else None,
                                      float(conf_mult), *params)
     return (cat if cat_heads else None), (cont if cont_head is not None else None)
+
+
+# ---- adaptive prediction sets (modules/conformal_prediction/conformal.py; csrc/bootstrap.hip) ------------
+def aps_route(pred):
+    """ "kernel" for probabilities [N, C] on the GPU with C <= ``ops.APS_MAX_CLASSES``, otherwise
+    "composite" (CPU tensors, wider rows): the same rule in torch ops."""
+    return ops.aps_route(pred.shape[1]) if pred.is_cuda else "composite"
+
+
+def _aps_cumulative_composite(pred):
+    order = torch.sort(pred, dim=1, descending=True, stable=True).indices
+    prefix = torch.take_along_dim(pred, order, dim=1).double().cumsum(1).float()
+    return torch.empty_like(prefix).scatter_(1, order, prefix)
+
+
+def aps_cumulative(pred, labels=None):
+    """``(cum [N, C], scores [N] | None)``: ``cum[i, c]`` is the cumulative probability of row i at
+    the rank of class c in the stable descending order (of equal probabilities the lower index
+    first); every prefix is summed in fp64 and rounded to fp32, which is what the reference's CPU
+    ``cumsum`` does -- ``qhat`` is frequently exactly 1.0 and the sets test ``cum <= qhat``, so a
+    plain fp32 running sum gives other sets. ``scores[i] = cum[i, labels[i]]``. No gradient."""
+    pred = pred.detach().float()
+    if pred.dim() != 2:
+        raise ValueError(f"aps_cumulative: probabilities [N, C] expected, got {tuple(pred.shape)}")
+    if labels is not None:
+        labels = labels.detach().reshape(-1).to(device=pred.device, dtype=torch.int64)
+        if labels.shape[0] != pred.shape[0]:
+            raise ValueError(f"aps_cumulative: {labels.shape[0]} labels for {pred.shape[0]} rows")
+    if aps_route(pred) == "kernel":
+        return ops.aps_cumulative(pred.contiguous(), labels)
+    cum = _aps_cumulative_composite(pred)
+    if labels is None:
+        return cum, None
+    ok = (labels >= 0) & (labels < pred.shape[1])
+    picked = torch.take_along_dim(cum, torch.where(ok, labels, torch.zeros_like(labels))[:, None], 1)
+    return cum, torch.where(ok, picked[:, 0], torch.full_like(picked[:, 0], float("nan")))
+
+
+def aps_scores(pred, labels):
+    """The conformal score of every calibration row: the cumulative probability down to, and
+    including, its own label (``AdaptivePredictionSets.calculate``)."""
+    return aps_cumulative(pred, labels)[1]
+
+
+def aps_sets(pred, qhat):
+    """bool [N, C]: the classes whose cumulative probability is at most ``qhat`` (a float or a
+    one-element tensor), and always the argmax class (the first maximal index)."""
+    cum, _ = aps_cumulative(pred)
+    sets = cum <= torch.as_tensor(qhat, dtype=torch.float32, device=cum.device)
+    sets.scatter_(1, torch.argmax(pred.detach(), 1, keepdim=True), True)
+    return sets

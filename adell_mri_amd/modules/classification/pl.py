@@ -22,9 +22,18 @@ any ``GaussianProcessLayer`` into the no-decay group.
 ``DeconfoundedNetPL`` (:2275-2573) wraps ``DeconfoundedNetGeneric``: its four loss terms, Adam over
 the confounder / classifier groups (see the class).
 
-Not mirrored: ``calibrate`` / ``predict_calibrated_step`` (conformal calibration), ``on_train_end``
-and ``predict_step_gp`` of the single-network wrappers (their Gaussian-process head is not built),
-and the hyper-parameter logging of ``on_train_start``.
+``calibrate(dataloader, alpha=0.2)`` and ``predict_calibrated_step`` (:460-479, :597-618) fit and apply
+``conformal_prediction.AdaptivePredictionSets`` for every wrapper whose ``predict_step`` returns
+``{"prediction": ...}``; ``OrdNetPL`` raises ``NotImplementedError`` (ordinal logits are no class
+probabilities). ``calibrate`` runs under ``no_grad``. Deviations from the reference: (a) for two
+classes the ``[B, 1]`` probability p is laid out as ``[1 - p, p]`` (the reference indexes a one-column
+matrix with label 1 and fails); (b) both methods take ``predict_step(batch, 0)["prediction"]`` and
+apply the same activation, sigmoid for two classes and softmax otherwise (the reference hands the
+whole dict to the module and fails); (c) there is no tqdm; (d) the labels are flattened and cast to
+int64.
+
+Not mirrored: ``on_train_end`` and ``predict_step_gp`` of the single-network wrappers (their
+Gaussian-process head is not built), and the hyper-parameter logging of ``on_train_start``.
 Lightning is optional as in ``self_supervised/pl.py``.
 """
 from abc import ABC
@@ -36,6 +45,7 @@ from ... import classification_metrics as CM
 from ... import functional as HF
 from ...optim import FusedAdam, FusedAdamW
 from ..learning_rate import CosineAnnealingWithWarmupLR
+from ..conformal_prediction import AdaptivePredictionSets
 from ..layers.gaussian_process import GaussianProcessLayer
 from .classification import CatNet, OrdNet, ViTClassifier, ordinal_prediction_to_class
 from .deconfounded_classification import DeconfoundedNetGeneric
@@ -135,6 +145,40 @@ class ClassPLABC(_Base, ABC):
         if "return_features" in kwargs:
             return {"features": prediction}
         return {"prediction": prediction}
+
+    def calibration_probabilities(self, batch):
+        """Class probabilities [B, C] of a batch for the conformal calibration, from
+        ``predict_step(batch, 0)["prediction"]``: softmax over the last axis, or for two classes the
+        sigmoid p laid out as ``[1 - p, p]``."""
+        if self.net_type == "ord":
+            raise NotImplementedError(
+                "conformal calibration of an ordinal network: its logits are no class probabilities")
+        prediction = self.predict_step(batch, 0)["prediction"]
+        if self.n_classes == 2:
+            p = torch.sigmoid(prediction).reshape(-1, 1)
+            return torch.cat([1 - p, p], 1)
+        return torch.softmax(prediction, -1)
+
+    def calibrate(self, dataloader, alpha: float = 0.2):
+        """Calibrates adaptive prediction sets at miscoverage ``alpha`` on the batches of
+        ``dataloader`` (pl.py:460-479; see the module docstring for the deviations)."""
+        self.calibration = AdaptivePredictionSets(alpha)
+        with torch.no_grad():
+            for batch in dataloader:
+                prediction = self.calibration_probabilities(batch)
+                y = batch[self.label_key].reshape(-1).to(device=prediction.device, dtype=torch.int64)
+                self.calibration.update(y, prediction)
+            self.calibration.calculate()
+        self.calibrated = True
+
+    def predict_calibrated_step(self, batch, batch_idx, *args, **kwargs):
+        """``[B, 2 C]``: the prediction set of every item as 0 / 1 floats, then the class
+        probabilities (pl.py:597-618). The wrapper must be calibrated."""
+        if self.calibrated is not True:
+            raise RuntimeError(
+                "Model needs to be calibrated before calibrated prediction"
+            )
+        return self.calibration(self.calibration_probabilities(batch))
 
     def train_dataloader(self):
         return self.training_dataloader_call()

@@ -4935,3 +4935,105 @@ def deconf_heads_bwd(features, n_conf, cat_heads, cat_targets, cont_head, cont_t
         _ptr(cat_targets), _ptr(cont_target if cont_head is not None else None), _ptr(g_cat),
         _ptr(g_cont), B, F, int(n_conf), float(conf_mult), _ptr(dz), _ptr(dx), _stream()))
     return dx, cat_grads, cont_grads
+
+
+# ---- evaluation with uncertainty (csrc/bootstrap.hip) ---------------------------------------------------
+BOOT_ROUTES = {0: "bitmask", 1: "loop"}
+BOOT_MAX_N = 196608          # ADELL_BOOT_MAX_N: 3 n / 8 bytes of LDS = 72 KiB, two blocks per CU of 160 KiB
+APS_MAX_CLASSES = 64         # ADELL_APS_MAX_CLASSES
+
+
+def boot_auroc_route(n):
+    """The route of the bootstrap AUC over ``n`` stored samples, by the library's own host function (no
+    device needed): "bitmask" (``boot_auroc_pairs``, n <= BOOT_MAX_N) or "loop" (one
+    ``cls_auroc_pairs`` per resample)."""
+    rc = _lib.lib().adell_boot_auroc_route(int(n))
+    check(min(rc, 0))
+    return BOOT_ROUTES[rc]
+
+
+def boot_auroc_tables(scores, labels):
+    """(pos, gstart, gend, lab), int32 [n] each, of fp32 scores [n] and 0 / 1 / -1 labels [n]: the
+    once-per-class preparation of ``boot_auroc_pairs`` in torch, without a host synchronisation.
+    A stable ascending sort; ``pos[i]`` the sorted position of sample i; ``[gstart[p], gend[p])`` the
+    run of equal scores around sorted position p (a NaN score gets the empty run [0, 0): it counts 0
+    against every negative, as in ``cls_auroc_pairs``); ``lab`` the labels in sorted order."""
+    n = int(scores.shape[0])
+    dev = scores.device
+    vals, perm = torch.sort(scores, stable=True)
+    ar = torch.arange(n, device=dev, dtype=torch.int64)
+    pos = torch.empty(n, device=dev, dtype=torch.int64)
+    pos[perm] = ar
+    change = vals[1:] != vals[:-1]
+    one = torch.ones(1, device=dev, dtype=torch.bool)
+    first = torch.cat([one, change])          # p starts a run
+    last = torch.cat([change, one])           # p ends a run
+    gstart = torch.cummax(torch.where(first, ar, torch.zeros_like(ar)), 0).values
+    gend = torch.cummin(torch.where(last, ar + 1, torch.full_like(ar, n)).flip(0), 0).values.flip(0)
+    nan = torch.isnan(vals)
+    gstart = torch.where(nan, torch.zeros_like(ar), gstart)
+    gend = torch.where(nan, torch.zeros_like(ar), gend)
+    i32 = torch.int32
+    return (pos.to(i32), gstart.to(i32), gend.to(i32), labels[perm].to(i32).contiguous())
+
+
+def boot_auroc_pairs(sample_idxs, pos, gstart, gend, lab):
+    """int64 [R, 4] on the device: per row of ``sample_idxs`` (int32 [R, m], distinct values in
+    [0, n)) the exact (2 #{pos > neg} + #{pos == neg}, positives, negatives, bad indices) over the
+    selected samples, from ONE launch (a block per row) and the tables of ``boot_auroc_tables``.
+    n <= BOOT_MAX_N (``boot_auroc_route``). Raises ``ValueError`` when a row holds an index twice or
+    one outside [0, n) (one host read of the counts)."""
+    what = "boot_auroc_pairs"
+    ts = (sample_idxs, pos, gstart, gend, lab)
+    _cls_on_device(*ts)
+    if any(t.dtype != torch.int32 for t in ts):
+        raise ValueError(f"{what}: int32 tensors expected, got {[str(t.dtype) for t in ts]}")
+    n = int(pos.shape[0])
+    if sample_idxs.dim() != 2 or any(tuple(t.shape) != (n,) for t in ts[1:]):
+        raise ValueError(f"{what}: indices [R, m] and four tables [n] expected, got "
+                         f"{[tuple(t.shape) for t in ts]}")
+    if n < 1 or boot_auroc_route(n) != "bitmask":
+        raise ValueError(f"{what}: n = {n} is outside [1, {BOOT_MAX_N}]")
+    R, m = (int(v) for v in sample_idxs.shape)
+    out = torch.zeros((R, 4), device=pos.device, dtype=torch.int64)
+    if R == 0 or m == 0:
+        return out
+    check(_lib.lib().adell_boot_auroc_pairs(
+        _ptr(sample_idxs.contiguous()), R, m, _ptr(pos.contiguous()), _ptr(gstart.contiguous()),
+        _ptr(gend.contiguous()), _ptr(lab.contiguous()), n, _ptr(out), _stream()))
+    bad = out[:, 3] != 0
+    if bool(bad.any()):
+        rows = torch.nonzero(bad).reshape(-1)[:8].tolist()
+        raise ValueError(f"{what}: a resample holds an index twice or one outside [0, {n}): rows {rows}")
+    return out
+
+
+def aps_route(n_classes):
+    """ "kernel" (``aps_cumulative``, at most APS_MAX_CLASSES classes) or "composite" (torch)."""
+    return "kernel" if 1 <= int(n_classes) <= APS_MAX_CLASSES else "composite"
+
+
+def aps_cumulative(pred, labels=None):
+    """(cum [N, C], scores [N] or None) of fp32 probabilities [N, C], C <= APS_MAX_CLASSES, one
+    launch: ``cum[i, c]`` is the cumulative probability of row i at the rank of class c in the
+    stable descending order (of equal probabilities the lower index first), each prefix an fp64 sum
+    in rank order rounded to fp32; ``scores[i] = cum[i, labels[i]]`` (int64 labels; NaN outside
+    [0, C))."""
+    what = "aps_cumulative"
+    _cls_on_device(pred, labels)
+    if pred.dtype != torch.float32 or pred.dim() != 2:
+        raise ValueError(f"{what}: fp32 probabilities [N, C] expected, got {pred.dtype} "
+                         f"{tuple(pred.shape)}")
+    N, C = (int(v) for v in pred.shape)
+    if aps_route(C) != "kernel":
+        raise ValueError(f"{what}: {C} classes, the kernel takes 1 to {APS_MAX_CLASSES}")
+    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (N,)):
+        raise ValueError(f"{what}: int64 labels [{N}] expected, got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    cum = torch.empty((N, C), device=pred.device, dtype=torch.float32)
+    scores = None if labels is None else torch.empty((N,), device=pred.device, dtype=torch.float32)
+    if N:
+        check(_lib.lib().adell_aps_cumulative(
+            _ptr(pred.contiguous()), _ptr(None if labels is None else labels.contiguous()), N, C,
+            _ptr(cum), _ptr(scores), _stream()))
+    return cum, scores

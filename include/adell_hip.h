@@ -1857,6 +1857,33 @@ int adell_deconf_heads_bwd(const adell_deconf_heads* hd, const adell_deconf_head
                            const float* g_cont, int B, int F, int n, float conf_mult, double* dz,
                            float* dx, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Evaluation with uncertainty (csrc/bootstrap.hip; the reference's utils/bootstrap_metrics.py and
+ * modules/conformal_prediction/conformal.py). Integer or fixed-order fp64 arithmetic: bit-reproducible.
+ * ---------------------------------------------------------------------- */
+#define ADELL_BOOT_MAX_N 196608 /* samples of the bitmask route: 72 KiB of LDS, two blocks per CU */
+#define ADELL_BOOT_BITMASK 0
+#define ADELL_BOOT_LOOP 1
+/* Host only: ADELL_BOOT_BITMASK when adell_boot_auroc_pairs takes n samples, ADELL_BOOT_LOOP beyond
+ * ADELL_BOOT_MAX_N (the caller loops over adell_cls_auroc_pairs), or ADELL_E_BADARG. */
+int adell_boot_auroc_route(int n);
+/* One launch, a block per resample: out[r] = (2 #{pos > neg} + #{pos == neg}, positives, negatives, bad
+ * indices) over the samples idx[r][0 .. m) (int32 [R][m], distinct values in [0, n)), every element
+ * written. The caller sorts the n scores once, stable and ascending: pos[i] is the sorted position of
+ * sample i, [gstart[p], gend[p]) the run of equal scores around sorted position p, lab[p] the label at p
+ * (1 positive, 0 negative, anything else skipped). Bad indices: a value outside [0, n), or one that a row
+ * holds twice (of a sample that is not skipped); a row with any has unspecified counts. LDS: 3 n / 8
+ * bytes, n <= ADELL_BOOT_MAX_N. */
+int adell_boot_auroc_pairs(const int* idx, int R, int m, const int* pos, const int* gstart, const int* gend,
+                           const int* lab, int n, long long* out, void* stream);
+#define ADELL_APS_MAX_CLASSES 64
+/* One launch: cum[i][c] = the cumulative probability of row i of p [N][C] at the rank of class c in the
+ * stable descending order (of equal probabilities the lower index first), every prefix summed in fp64 in
+ * rank order and rounded to fp32. With y (int64 [N]) and score [N]: score[i] = cum[i][y[i]], NaN for a
+ * label outside [0, C), which is never used as an index; both NULL: skipped. C <= ADELL_APS_MAX_CLASSES. */
+int adell_aps_cumulative(const float* p, const long long* y, int N, int C, float* cum, float* score,
+                         void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
