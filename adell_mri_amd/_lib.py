@@ -417,6 +417,19 @@ SIGNATURES = {
     "adell_gemm_f32_workspace_floats": (_l, [_i, _i, _i]),
     "adell_gemm_f32": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp, _vp]),
     "adell_absmax_f32": (_i, [_vp, _l, _vp, _vp]),
+    "adell_semisl_route": (_i, [_i, _i, _i]),
+    "adell_loco_anchor_workspace_doubles": (_l, [_i, _l, _i]),
+    "adell_loco_anchor_fwd": (_i, [_vp, _vp, _vp, _i, _l, _i, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "adell_loco_anchor_bwd": (_i, [_vp] * 7 + [_i, _l, _i, _f, _vp, _vp, _vp, _vp]),
+    "adell_nn_queue_normalize": (_i, [_vp, _i, _i, _vp, _vp]),
+    "adell_nn_queue_workspace_doubles": (_l, [_i, _l]),
+    "adell_nn_queue_loss_fwd": (_i, [_vp] * 4 + [_i, _l, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "adell_nn_queue_loss_bwd": (_i, [_vp] * 8 + [_i, _l, _i, _i, _i, _f, _vp, _vp]),
+    "adell_nn_queue_count": (_i, [_vp, _i, _i, _l, _vp, _vp]),
+    "adell_nn_queue_gather": (_i, [_vp] * 5 + [_i, _i, _i, _l, _i, _l, _l, _l, _vp, _vp]),
+    "adell_pseudo_label_ce_workspace_doubles": (_l, [_i, _l]),
+    "adell_pseudo_label_ce_fwd": (_i, [_vp, _vp, _vp, _i, _i, _l, _f, _f, _i, _vp, _vp, _l, _vp]),
+    "adell_pseudo_label_ce_bwd": (_i, [_vp] * 4 + [_i, _i, _l, _f, _f, _i, _vp, _vp]),
     "adell_gemm_plan": (_i, [_i] * 6 + [_l, _l, _i, _i, _vp]),
     "adell_gemm_f16x3_workspace_floats": (_l, [_i, _i, _i]),
     "adell_gemm_f16x3": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp, _vp,

@@ -3533,3 +3533,182 @@ def aps_sets(pred, qhat):
     sets = cum <= torch.as_tensor(qhat, dtype=torch.float32, device=cum.device)
     sets.scatter_(1, torch.argmax(pred.detach(), 1, keepdim=True), True)
     return sets
+
+
+# ---- semi-supervised U-Net losses beyond the local contrastive one (csrc/semisl.hip) ---------------------
+def semisl_route(kind, C=1, K=1, reduction="mean", ignore_index=-100):
+    """The route of a semi-supervised loss, "fused" (csrc/semisl.hip) or "composed" (the same rule in
+    torch ops; CPU tensors and tensors that are not fp32 always take it). Limits of the fused routes:
+
+    * ``"anchor"`` (``loco_anchor_loss``): ``C % 4 == 0`` and ``C <= 1024`` (the kernels loop over
+      channel quads, so no width spills);
+    * ``"nn"`` (``nn_queue_loss``): ``C % 4 == 0``, ``C <= 64`` (two blocks per CU's LDS) and ``K <= 64``;
+    * ``"pseudo_label"`` (``pseudo_label_ce``): ``K <= 64``, ``reduction`` "mean" or "sum" and the default
+      ``ignore_index`` (probability targets never read it); ``weight`` and ``label_smoothing`` are fused.
+    """
+    if kind == "pseudo_label" and (reduction not in ("mean", "sum") or ignore_index != -100):
+        return "composed"
+    return ops.semisl_route(kind, C, K)
+
+
+def _semisl_rows(x):
+    """Dense NDHWC rows [B, V, C] of features [B, C, *spatial] (a view of channels-last memory)."""
+    B, C = x.shape[0], x.shape[1]
+    if x.dim() == 5:
+        return ops.ndhwc(x).permute(0, 2, 3, 4, 1).reshape(B, -1, C)
+    return x.flatten(2).transpose(1, 2).contiguous()
+
+
+def _semisl_unrows(rows, shape):
+    """The gradient rows [B, V, C] under the logical shape [B, C, *spatial]."""
+    return rows.reshape(shape[0], *shape[2:], shape[1]).movedim(-1, 1)
+
+
+def loco_anchor_loss_composite(x, a1, a2, temperature=0.1):
+    """``LocalContrastiveLossWithAnchors.forward`` as the reference writes it
+    (semi_supervised_segmentation/losses.py:576-585), in torch ops."""
+    F = torch.nn.functional
+    x, a1, a2 = x.flatten(start_dim=2), a1.flatten(start_dim=2), a2.flatten(start_dim=2)
+    sim_1 = F.cosine_similarity(x, a1, dim=1) / temperature
+    sim_2 = F.cosine_similarity(x, a2, dim=1) / temperature
+    return F.kl_div(F.softmax(sim_1, dim=1), F.softmax(sim_2, dim=1), reduction="none").sum(-1)
+
+
+class _LocoAnchorFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, a1, a2, temperature):
+        shape = x.shape
+        x, a1, a2 = _semisl_rows(x), _semisl_rows(a1), _semisl_rows(a2)
+        loss, sim1, sim2, stats = ops.loco_anchor_fwd(x, a1, a2, temperature)
+        ctx.save_for_backward(x, a1, a2, sim1, sim2, stats)
+        ctx.conf = (temperature, shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        temperature, shape = ctx.conf
+        dx, da1, da2 = ops.loco_anchor_bwd(*ctx.saved_tensors, g, temperature,
+                                           ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return (_semisl_unrows(dx, shape) if ctx.needs_input_grad[0] else None,
+                None if da1 is None else _semisl_unrows(da1, shape),
+                None if da2 is None else _semisl_unrows(da2, shape), None)
+
+
+def loco_anchor_loss(x, a1, a2, temperature=0.1):
+    """Per-item anchor loss [B] of features and two anchor maps [B, C, *spatial]
+    (``LocalContrastiveLossWithAnchors.forward``, semi_supervised_segmentation/losses.py:547-585):
+    ``sim_k[b, v] = cos(x[b, :, v], a_k[b, :, v]) / temperature``, ``p = softmax_v(sim_1)``,
+    ``q = softmax_v(sim_2)`` over the voxels of an item, ``loss[b] = sum_v (xlogy(q, q) - q p)`` --
+    ``F.kl_div`` with a probability, not a log-probability, as its input, as the reference calls it.
+    Differentiable in all three inputs; the fused route writes two floats per voxel."""
+    if tuple(a1.shape) != tuple(x.shape) or tuple(a2.shape) != tuple(x.shape) or x.dim() < 3:
+        raise ValueError(f"loco_anchor_loss: features and anchors [B, C, *spatial] of one shape expected, "
+                         f"got {tuple(x.shape)}, {tuple(a1.shape)}, {tuple(a2.shape)}")
+    if not x.is_cuda or x.dtype != torch.float32 or semisl_route("anchor", C=x.shape[1]) == "composed":
+        return loco_anchor_loss_composite(x, a1, a2, temperature)
+    return _LocoAnchorFn.apply(x, a1, a2, float(temperature))
+
+
+def nn_queue_loss_composite(x, y, past, past_labels, temperature=0.1):
+    """``NearestNeighbourLoss.forward`` past the queue (semi_supervised_segmentation/losses.py:425-444)
+    in torch ops: ``past_labels`` is the one-hot [Q, K]; writes the [B, V, Q] tensors."""
+    F = torch.nn.functional
+    x = x.flatten(start_dim=2).permute(0, 2, 1)
+    y = y.flatten(start_dim=2).permute(0, 2, 1)
+    distances = 1 - F.cosine_similarity(x[:, :, None], past[None, None, :], -1)
+    is_same = torch.sum(y[:, :, None] * past_labels[None, None, :], -1)
+    same = torch.exp(-distances * is_same / temperature)
+    other = torch.exp(-distances * (1 - is_same) / temperature)
+    return torch.nanmean(same.nansum(-1) / other.nansum(-1))
+
+
+class _NNQueueFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, past, past_class, temperature):
+        shape = x.shape
+        x = _semisl_rows(x)
+        y = y.reshape(y.shape[0], y.shape[1], -1).contiguous().float()
+        pastn = ops.nn_queue_normalize(past.contiguous())
+        loss, S, O, stats = ops.nn_queue_loss_fwd(x, y, pastn, past_class, temperature)
+        ctx.save_for_backward(x, y, pastn, past_class, S, O, stats)
+        ctx.conf = (temperature, shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        temperature, shape = ctx.conf
+        dx = ops.nn_queue_loss_bwd(*ctx.saved_tensors, g, temperature)
+        return _semisl_unrows(dx, shape), None, None, None, None
+
+
+def nn_queue_loss(x, y, past, past_class, temperature=0.1):
+    """Nearest-neighbour loss (0-d) of features ``x`` [B, C, *spatial] and labels ``y``
+    [B, K, *spatial] (any float data) against the queued rows ``past`` [Q, C] of classes ``past_class``
+    (integers [Q]): per voxel ``d_q = 1 - cos(x_v, past_q)``, ``m_q = y[b, past_class[q], v]``,
+    ``S = sum_q exp(-d_q m_q / T)``, ``O = sum_q exp(-d_q (1 - m_q) / T)``; the mean of ``S / O`` over
+    the voxels whose ratio is not NaN, a NaN term counting 0 in either sum
+    (``NearestNeighbourLoss.forward``, semi_supervised_segmentation/losses.py:425-444). Differentiable
+    in ``x``. The fused route keeps two floats per voxel and never writes a [B, V, Q] tensor. One
+    deviation: the gradient at a voxel whose ratio is NaN is an exact 0 (torch gives 0 * NaN there)."""
+    if x.dim() < 3 or y.dim() != x.dim() or y.shape[0] != x.shape[0] \
+            or tuple(y.shape[2:]) != tuple(x.shape[2:]):
+        raise ValueError(f"nn_queue_loss: x [B, C, *spatial] and y [B, K, *spatial] expected, got "
+                         f"{tuple(x.shape)} and {tuple(y.shape)}")
+    if past.dim() != 2 or past.shape[1] != x.shape[1] or past_class.shape != past.shape[:1]:
+        raise ValueError(f"nn_queue_loss: past [Q, {x.shape[1]}] and past_class [Q] expected, got "
+                         f"{tuple(past.shape)} and {tuple(past_class.shape)}")
+    if past.shape[0] == 0:
+        return torch.zeros([], device=x.device)
+    K = y.shape[1]
+    if not x.is_cuda or x.dtype != torch.float32 or semisl_route("nn", C=x.shape[1], K=K) == "composed":
+        labels = torch.nn.functional.one_hot(past_class.to(device=x.device, dtype=torch.int64), K)
+        return nn_queue_loss_composite(x, y, past.to(x.device), labels, temperature)
+    past_class = past_class.to(device=x.device, dtype=torch.int32).contiguous()
+    return _NNQueueFn.apply(x, y, past.detach(), past_class, float(temperature))
+
+
+class _PseudoLabelCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, proba, threshold, weight, label_smoothing, mean):
+        shape = pred.shape
+        pred = pred.reshape(shape[0], shape[1], -1).contiguous()
+        proba = proba.reshape(shape[0], shape[1], -1).contiguous()
+        weight = None if weight is None else weight.contiguous()
+        loss = ops.pseudo_label_ce_fwd(pred, proba, threshold, weight, label_smoothing, mean)
+        ctx.save_for_backward(pred, proba, weight)
+        ctx.conf = (threshold, label_smoothing, mean, shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        pred, proba, weight = ctx.saved_tensors
+        threshold, label_smoothing, mean, shape = ctx.conf
+        d = ops.pseudo_label_ce_bwd(pred, proba, threshold, weight, label_smoothing, mean, g)
+        return (d.reshape(shape),) + (None,) * 5
+
+
+def pseudo_label_ce(pred, proba, threshold, weight=None, label_smoothing=0.0, reduction="mean"):
+    """Cross entropy of the logits ``pred`` [B, K, *spatial] against the 0/1 pseudo-labels
+    ``proba > threshold`` (strict, compared in fp32 as torch compares a tensor with a number) taken as
+    PROBABILITY targets -- zero, one or several hot classes per voxel -- which is
+    ``F.cross_entropy(pred, (proba > threshold).float(), weight, label_smoothing=..., reduction=...)``
+    (``PseudoLabelCrossEntropy.forward``, semi_supervised_segmentation/losses.py:465-477). "mean"
+    divides the sum by B V, with or without ``weight``. Differentiable in ``pred``. The fused route
+    forms the log-softmax and the targets in registers: one launch each way."""
+    if tuple(proba.shape) != tuple(pred.shape) or pred.dim() < 2:
+        raise ValueError(f"pseudo_label_ce: logits and probabilities [B, K, *spatial] of one shape "
+                         f"expected, got {tuple(pred.shape)} and {tuple(proba.shape)}")
+    fused = pred.is_cuda and pred.dtype == torch.float32 and pred.numel() > 0 \
+        and semisl_route("pseudo_label", K=pred.shape[1], reduction=reduction) == "fused"
+    if not fused:
+        return torch.nn.functional.cross_entropy(pred, (proba > threshold).float(), weight,
+                                                 reduction=reduction,
+                                                 label_smoothing=float(label_smoothing))
+    if weight is not None:
+        weight = weight.detach().to(device=pred.device, dtype=torch.float32)
+    return _PseudoLabelCEFn.apply(pred, proba.detach().float(), float(threshold), weight,
+                                  float(label_smoothing), reduction == "mean")

@@ -107,8 +107,10 @@ class UNetContrastiveSemiSL(UNetSemiSL, UNetBasePL):
         return self.loss_fn_semi_sl(features_1, features_2, *args, **kwargs).mean() * self.ssl_weight
 
     def step_semi_sl_anchors(self, x, x_1, x_2, x_cond, x_fc, *args, **kwargs):
-        """pl.py:283-337: anchors from the two views, features from the annotated image; needs a
-        three-argument loss (LocalContrastiveLossWithAnchors in the reference)."""
+        """pl.py:283-337: anchors from the two views (without gradient), features from the annotated
+        image; takes a three-argument loss, ``LocalContrastiveLossWithAnchors`` (an anchor that is
+        None is drawn there by derangement of the features). As in the reference, ``training_step``
+        passes ``x=None`` and so never comes here: call ``step_semi_sl`` with the annotated image."""
         x, x_1, x_2, x_cond, x_fc = self.coerce_batch_size(x, x_1, x_2, x_cond, x_fc)
         with torch.no_grad():
             anchor_1 = (self.forward_features(X=x_1, X_skip_layer=x_cond,

@@ -5037,3 +5037,239 @@ def aps_cumulative(pred, labels=None):
             _ptr(pred.contiguous()), _ptr(None if labels is None else labels.contiguous()), N, C,
             _ptr(cum), _ptr(scores), _stream()))
     return cum, scores
+
+
+# ---- semi-supervised U-Net losses beyond the local contrastive one (csrc/semisl.hip) ---------------------
+SEMISL_KINDS = {"anchor": 0, "nn": 1, "pseudo_label": 2}   # ADELL_SEMISL_ANCHOR / _NN / _PSEUDO_LABEL
+SEMISL_ROUTES = {0: "fused", 1: "composed"}
+SEMISL_ANCHOR_MAX_C = 1024    # ADELL_SEMISL_ANCHOR_MAX_C
+SEMISL_NN_MAX_C = 64          # ADELL_SEMISL_NN_MAX_C
+SEMISL_MAX_CLASSES = 64       # ADELL_SEMISL_MAX_CLASSES
+SEMISL_PUT_CHUNK = 4096       # ADELL_SEMISL_PUT_CHUNK
+
+
+def semisl_route(kind, C=1, K=1):
+    """The route of one of the semi-supervised losses by the library's own host function (no device
+    needed): "fused" or "composed". ``kind``: "anchor" (C channels), "nn" (C channels, K classes),
+    "pseudo_label" (K classes)."""
+    if kind not in SEMISL_KINDS:
+        raise ValueError(f"semisl_route: kind {kind!r}, expected one of {sorted(SEMISL_KINDS)}")
+    rc = _lib.lib().adell_semisl_route(SEMISL_KINDS[kind], int(C), int(K))
+    check(min(rc, 0))
+    return SEMISL_ROUTES[rc]
+
+
+def _semisl_rows(what, *ts):
+    """(B, V, C) of dense fp32 device rows [B, V, C] of one shape."""
+    _ens_rows(what, *ts)
+    shape = tuple(ts[0].shape)
+    if len(shape) != 3 or any(tuple(t.shape) != shape for t in ts) or 0 in shape:
+        raise ValueError(f"{what}: non-empty rows [B, V, C] of one shape expected, got "
+                         f"{[tuple(t.shape) for t in ts]}")
+    return shape
+
+
+def loco_anchor_fwd(x, a1, a2, temperature):
+    """(loss [B], sim1 [B, V], sim2 [B, V], stats [B, 6] fp64) of feature rows [B, V, C]; four launches."""
+    what = "loco_anchor_loss"
+    B, V, C = _semisl_rows(what, x, a1, a2)
+    h = _lib.lib()
+    words = h.adell_loco_anchor_workspace_doubles(B, V, C)
+    check(min(words, 0))
+    dev = x.device
+    ws = torch.empty(words, device=dev, dtype=torch.float64)
+    sim1 = torch.empty((B, V), device=dev, dtype=torch.float32)
+    sim2 = torch.empty((B, V), device=dev, dtype=torch.float32)
+    stats = torch.empty((B, 6), device=dev, dtype=torch.float64)
+    loss = torch.empty(B, device=dev, dtype=torch.float32)
+    check(h.adell_loco_anchor_fwd(_ptr(x), _ptr(a1), _ptr(a2), B, V, C, float(temperature), _ptr(sim1),
+                                  _ptr(sim2), _ptr(stats), _ptr(loss), _ptr(ws), words, _stream()))
+    return loss, sim1, sim2, stats
+
+
+def loco_anchor_bwd(x, a1, a2, sim1, sim2, stats, gloss, temperature, need1, need2):
+    """(dx, da1 or None, da2 or None) as rows [B, V, C]; one launch."""
+    what = "loco_anchor_loss backward"
+    B, V, C = _semisl_rows(what, x, a1, a2)
+    gloss = gloss.contiguous().float()
+    _ens_rows(what, sim1, sim2, gloss)
+    if tuple(sim1.shape) != (B, V) or tuple(sim2.shape) != (B, V) or gloss.numel() != B \
+            or stats.dtype != torch.float64 or tuple(stats.shape) != (B, 6) or not stats.is_cuda:
+        raise ValueError(f"{what}: the forward's rows and statistics and a gradient [{B}] expected")
+    dx = torch.empty_like(x)
+    da1 = torch.empty_like(x) if need1 else None
+    da2 = torch.empty_like(x) if need2 else None
+    check(_lib.lib().adell_loco_anchor_bwd(_ptr(x), _ptr(a1), _ptr(a2), _ptr(sim1), _ptr(sim2),
+                                           _ptr(stats), _ptr(gloss), B, V, C, float(temperature),
+                                           _ptr(dx), _ptr(da1), _ptr(da2), _stream()))
+    return dx, da1, da2
+
+
+def _nn_queue_args(what, x, y, pastn, past_class):
+    B, V, C = _semisl_rows(what, x)
+    _ens_rows(what, y, pastn)
+    if y.dim() != 3 or y.shape[0] != B or y.shape[2] != V:
+        raise ValueError(f"{what}: labels [{B}, K, {V}] expected, got {tuple(y.shape)}")
+    if pastn.dim() != 2 or pastn.shape[1] != C or pastn.shape[0] < 1:
+        raise ValueError(f"{what}: past samples [Q, {C}] expected, got {tuple(pastn.shape)}")
+    Q = int(pastn.shape[0])
+    if not past_class.is_cuda or past_class.dtype != torch.int32 or tuple(past_class.shape) != (Q,) \
+            or not past_class.is_contiguous():
+        raise ValueError(f"{what}: int32 device classes [{Q}] expected")
+    return B, V, C, int(y.shape[1]), Q
+
+
+def nn_queue_normalize(past):
+    """The rows of ``past`` [Q, C] divided by max(their norm, 1e-8); one launch."""
+    what = "nn_queue_normalize"
+    _ens_rows(what, past)
+    if past.dim() != 2 or 0 in past.shape:
+        raise ValueError(f"{what}: non-empty rows [Q, C] expected, got {tuple(past.shape)}")
+    out = torch.empty_like(past)
+    check(_lib.lib().adell_nn_queue_normalize(_ptr(past), int(past.shape[0]), int(past.shape[1]),
+                                              _ptr(out), _stream()))
+    return out
+
+
+def nn_queue_loss_fwd(x, y, pastn, past_class, temperature):
+    """(loss [1], S [B V], O [B V], stats [2] fp64) of rows x [B, V, C], labels y [B, K, V], the
+    normalised past rows [Q, C] and their int32 classes [Q]; two launches."""
+    what = "nn_queue_loss"
+    B, V, C, K, Q = _nn_queue_args(what, x, y, pastn, past_class)
+    h = _lib.lib()
+    words = h.adell_nn_queue_workspace_doubles(B, V)
+    check(min(words, 0))
+    dev = x.device
+    ws = torch.empty(words, device=dev, dtype=torch.float64)
+    S = torch.empty(B * V, device=dev, dtype=torch.float32)
+    O = torch.empty(B * V, device=dev, dtype=torch.float32)
+    stats = torch.empty(2, device=dev, dtype=torch.float64)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    check(h.adell_nn_queue_loss_fwd(_ptr(x), _ptr(y), _ptr(pastn), _ptr(past_class), B, V, C, K, Q,
+                                    float(temperature), _ptr(S), _ptr(O), _ptr(stats), _ptr(loss),
+                                    _ptr(ws), words, _stream()))
+    return loss, S, O, stats
+
+
+def nn_queue_loss_bwd(x, y, pastn, past_class, S, O, stats, g, temperature):
+    """dx [B, V, C]; one launch."""
+    what = "nn_queue_loss backward"
+    B, V, C, K, Q = _nn_queue_args(what, x, y, pastn, past_class)
+    g = g.reshape(1).contiguous().float()
+    _ens_rows(what, S, O, g)
+    if S.numel() != B * V or O.numel() != B * V or stats.dtype != torch.float64 or stats.numel() != 2 \
+            or not stats.is_cuda:
+        raise ValueError(f"{what}: the forward's sums and statistics expected")
+    dx = torch.empty_like(x)
+    check(_lib.lib().adell_nn_queue_loss_bwd(_ptr(x), _ptr(y), _ptr(pastn), _ptr(past_class), _ptr(S),
+                                             _ptr(O), _ptr(stats), _ptr(g), B, V, C, K, Q,
+                                             float(temperature), _ptr(dx), _stream()))
+    return dx
+
+
+def nn_queue_count(y):
+    """int32 [B, K, chunks]: the positives (y > 0) of labels [B, K, V] per chunk of SEMISL_PUT_CHUNK
+    voxels; one launch."""
+    what = "nn_queue_count"
+    _ens_rows(what, y)
+    if y.dim() != 3 or 0 in y.shape:
+        raise ValueError(f"{what}: non-empty labels [B, K, V] expected, got {tuple(y.shape)}")
+    B, K, V = (int(v) for v in y.shape)
+    chunks = (V + SEMISL_PUT_CHUNK - 1) // SEMISL_PUT_CHUNK
+    cc = torch.empty((B, K, chunks), device=y.device, dtype=torch.int32)
+    check(_lib.lib().adell_nn_queue_count(_ptr(y), B, K, V, _ptr(cc), _stream()))
+    return cc
+
+
+def nn_queue_put(x, y, select):
+    """The gather behind ``NearestNeighbourLoss.put``. ``x`` [B, C, *spatial] (dense, channel-major or
+    channels-last) and ``y`` [B, K, *spatial]; ``select(counts)`` receives the int64 numpy table [B, K]
+    of positives (y > 0) -- the one host read -- and returns, per class, None or the int64 ranks to
+    keep among the positives of that class in the order of ``torch.where(y > 0)`` (item-major, then
+    voxel). Returns a list with, per class, None or the gathered rows [n, C]: bit-equal to
+    ``x.flatten(2)[b[idx], :, v[idx]][ranks]``. Neither the index triples nor the rows of all
+    positives are materialised: a count launch, a scan of the small table, one gather launch."""
+    what = "nn_queue_put"
+    _require_cuda(x, y)
+    if x.dim() < 3 or y.dim() != x.dim() or x.shape[0] != y.shape[0] \
+            or tuple(x.shape[2:]) != tuple(y.shape[2:]) or 0 in x.shape or 0 in y.shape:
+        raise ValueError(f"{what}: x [B, C, *spatial] and y [B, K, *spatial] expected, got "
+                         f"{tuple(x.shape)} and {tuple(y.shape)}")
+    B, C, K = int(x.shape[0]), int(x.shape[1]), int(y.shape[1])
+    V = x.numel() // (B * C)
+    x = x.detach()
+    rows = x.dim() == 5 and x.is_contiguous(memory_format=torch.channels_last_3d) \
+        and not x.is_contiguous()
+    if rows:
+        strides = (V * C, 1, C)
+    else:
+        x = x.contiguous()
+        strides = (C * V, V, 1)
+    y3 = y.detach().reshape(B, K, V).contiguous()
+    cc = nn_queue_count(y3)
+    counts = cc.sum(-1, dtype=torch.int64).cpu().numpy()
+    ranks = select(counts)
+    picked = [(cl, np.asarray(r, dtype=np.int64).reshape(-1)) for cl, r in enumerate(ranks)
+              if r is not None and len(r) > 0]
+    out = [None] * K
+    if not picked:
+        return out
+    for cl, r in picked:
+        if r.min() < 0 or r.max() >= counts[:, cl].sum():
+            raise ValueError(f"{what}: a rank outside the {int(counts[:, cl].sum())} positives of "
+                             f"class {cl}")
+    incl = cc.permute(1, 0, 2).reshape(K, -1).cumsum(-1, dtype=torch.int64).contiguous()
+    sel = np.concatenate([r for _, r in picked])
+    cls = np.concatenate([np.full(len(r), cl, dtype=np.int32) for cl, r in picked])
+    n = int(sel.shape[0])
+    sel_d = torch.from_numpy(sel).to(x.device)
+    cls_d = torch.from_numpy(cls).to(x.device)
+    rows_out = torch.empty((n, C), device=x.device, dtype=torch.float32)
+    xp = ctypes.c_void_p(x.data_ptr())   # dense in one of the two layouts checked above
+    check(_lib.lib().adell_nn_queue_gather(xp, _ptr(y3), _ptr(incl), _ptr(cls_d), _ptr(sel_d), n, B, K,
+                                           V, C, *strides, _ptr(rows_out), _stream()))
+    at = 0
+    for cl, r in picked:
+        out[cl] = rows_out[at:at + len(r)]
+        at += len(r)
+    return out
+
+
+def _pl_ce_args(what, pred, proba, weight):
+    _ens_rows(what, pred, proba, weight)
+    if pred.dim() != 3 or tuple(proba.shape) != tuple(pred.shape) or 0 in pred.shape:
+        raise ValueError(f"{what}: logits and probabilities [B, K, V] of one shape expected, got "
+                         f"{tuple(pred.shape)} and {tuple(proba.shape)}")
+    B, K, V = (int(v) for v in pred.shape)
+    if weight is not None and tuple(weight.shape) != (K,):
+        raise ValueError(f"{what}: a weight [{K}] expected, got {tuple(weight.shape)}")
+    return B, K, V
+
+
+def pseudo_label_ce_fwd(pred, proba, threshold, weight, label_smoothing, mean):
+    """loss [1] of logits and probabilities [B, K, V]; one launch (and the clearing of its ticket)."""
+    what = "pseudo_label_ce"
+    B, K, V = _pl_ce_args(what, pred, proba, weight)
+    h = _lib.lib()
+    words = h.adell_pseudo_label_ce_workspace_doubles(B, V)
+    check(min(words, 0))
+    ws = torch.empty(words, device=pred.device, dtype=torch.float64)
+    ws[:1].zero_()
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    check(h.adell_pseudo_label_ce_fwd(_ptr(pred), _ptr(proba), _ptr(weight), B, K, V, float(threshold),
+                                      float(label_smoothing), int(bool(mean)), _ptr(loss), _ptr(ws),
+                                      words, _stream()))
+    return loss
+
+
+def pseudo_label_ce_bwd(pred, proba, threshold, weight, label_smoothing, mean, g):
+    """d pred [B, K, V]; one launch."""
+    what = "pseudo_label_ce backward"
+    B, K, V = _pl_ce_args(what, pred, proba, weight)
+    g = g.reshape(1).contiguous().float()
+    _ens_rows(what, g)
+    dpred = torch.empty_like(pred)
+    check(_lib.lib().adell_pseudo_label_ce_bwd(_ptr(pred), _ptr(proba), _ptr(weight), _ptr(g), B, K, V,
+                                               float(threshold), float(label_smoothing),
+                                               int(bool(mean)), _ptr(dpred), _stream()))
+    return dpred

@@ -1884,6 +1884,77 @@ int adell_boot_auroc_pairs(const int* idx, int R, int m, const int* pos, const i
 int adell_aps_cumulative(const float* p, const long long* y, int N, int C, float* cum, float* score,
                          void* stream);
 
+/* ------------------------------------------------------------------------
+ * Losses of the semi-supervised U-Net beyond LocalContrastiveLoss (csrc/semisl.hip; the reference's
+ * LocalContrastiveLossWithAnchors, NearestNeighbourLoss and PseudoLabelCrossEntropy,
+ * semi_supervised_segmentation/losses.py). fp32 data, fixed-order fp64 sums, no float atomics:
+ * bit-reproducible. Feature rows are NDHWC, [B][V][C]; label and logit planes channel-major, [B][K][V].
+ * ---------------------------------------------------------------------- */
+#define ADELL_SEMISL_ANCHOR 0
+#define ADELL_SEMISL_NN 1
+#define ADELL_SEMISL_PSEUDO_LABEL 2
+#define ADELL_SEMISL_FUSED 0
+#define ADELL_SEMISL_COMPOSED 1
+#define ADELL_SEMISL_ANCHOR_MAX_C 1024 /* the anchor kernels loop over channel quads: no register limit */
+#define ADELL_SEMISL_NN_MAX_C 64       /* two blocks of the nearest-neighbour kernels per CU's LDS */
+#define ADELL_SEMISL_MAX_CLASSES 64
+#define ADELL_SEMISL_PUT_CHUNK 4096    /* voxels per entry of the adell_nn_queue_count table */
+/* Host only: ADELL_SEMISL_FUSED when the kernels of `kind` take C channels (anchor, nn: C % 4 == 0 and
+ * C <= the kind's maximum) and K classes (nn, pseudo-label: K <= ADELL_SEMISL_MAX_CLASSES),
+ * ADELL_SEMISL_COMPOSED beyond, or ADELL_E_BADARG. An argument the kind does not use is ignored. */
+int adell_semisl_route(int kind, int C, int K);
+/* loss[b] = sum_v (xlogy(q_v, q_v) - q_v p_v), p = softmax_v(cos(x, a1) / T), q = softmax_v(cos(x, a2) / T),
+ * the softmax over the V voxels of item b: F.kl_div(p, q, reduction="none").sum(-1) with a probability
+ * (not a log-probability) as its input. Four launches. Kept for the backward: sim1, sim2 [B][V] (the
+ * cosines / T) and stats [B][6] = (max_1, log sum_1, max_2, log sum_2, sum q log q, sum p q).
+ * Workspace: adell_loco_anchor_workspace_doubles(B, V, C) doubles. */
+long adell_loco_anchor_workspace_doubles(int B, long V, int C);
+int adell_loco_anchor_fwd(const float* x, const float* a1, const float* a2, int B, long V, int C,
+                          float temperature, float* sim1, float* sim2, double* stats, float* loss,
+                          double* workspace, long workspace_doubles, void* stream);
+/* One launch: dx (always), da1 and da2 (NULL: not wanted) for the loss gradient gloss [B]. */
+int adell_loco_anchor_bwd(const float* x, const float* a1, const float* a2, const float* sim1,
+                          const float* sim2, const double* stats, const float* gloss, int B, long V, int C,
+                          float temperature, float* dx, float* da1, float* da2, void* stream);
+/* out[q] = past[q] / max(|past[q]|, 1e-8), [Q][C]; one launch. */
+int adell_nn_queue_normalize(const float* past, int Q, int C, float* out, void* stream);
+/* loss = the mean over the voxels whose ratio is not NaN of S / O, S = sum_q exp(-d_q m_q / T),
+ * O = sum_q exp(-d_q (1 - m_q) / T), d_q = 1 - cos(x[b][v], past_q), m_q = y[b][past_class[q]][v] (0 for a
+ * class outside [0, K), which is never used as an index); a NaN term counts 0. pastn: the rows of
+ * adell_nn_queue_normalize. Two launches. Kept for the backward: S, O [B V] and stats = (sum, count).
+ * Workspace: adell_nn_queue_workspace_doubles(B, V) doubles. The [B][V][Q] products are never written. */
+long adell_nn_queue_workspace_doubles(int B, long V);
+int adell_nn_queue_loss_fwd(const float* x, const float* y, const float* pastn, const int* past_class, int B,
+                            long V, int C, int K, int Q, float temperature, float* S, float* O,
+                            double* stats, float* loss, double* workspace, long workspace_doubles,
+                            void* stream);
+/* One launch: dx [B][V][C] for the gradient g [1]; an exact 0 at a voxel whose ratio is NaN. */
+int adell_nn_queue_loss_bwd(const float* x, const float* y, const float* pastn, const int* past_class,
+                            const float* S, const float* O, const double* stats, const float* g, int B,
+                            long V, int C, int K, int Q, float temperature, float* dx, void* stream);
+/* cc[b][k][chunk] = #{v in the chunk of ADELL_SEMISL_PUT_CHUNK voxels: y[b][k][v] > 0}, int32, every
+ * entry written; one launch. */
+int adell_nn_queue_count(const float* y, int B, int K, long V, int* cc, void* stream);
+/* out[r] = the row x[b][:][v] of the sel_rank[r]-th positive (y > 0; item-major, then voxel) of class
+ * sel_class[r]; incl [K][B chunks] int64: the inclusive scan of cc over (item, chunk) per class. x is
+ * read through the element strides (sb, sc, sv) of its [B][C][V] view, channel-major or channels-last.
+ * A rank beyond the positives of its class writes zeros. One launch, a wave per row. */
+int adell_nn_queue_gather(const float* x, const float* y, const long long* incl, const int* sel_class,
+                          const long long* sel_rank, int n_sel, int B, int K, long V, int C, long sb, long sc,
+                          long sv, float* out, void* stream);
+/* Cross entropy of the logits pred [B][K][V] against the probability targets
+ * t_k = (proba_k > threshold) (1 - label_smoothing) + label_smoothing / K, weighted per class (weight
+ * NULL: ones): the sum over voxels and classes of -w_k t_k log_softmax_k, divided by B V when `mean`.
+ * One launch each way. workspace: adell_pseudo_label_ce_workspace_doubles(B, V) doubles whose first
+ * word is zero on entry (and left zero). */
+long adell_pseudo_label_ce_workspace_doubles(int B, long V);
+int adell_pseudo_label_ce_fwd(const float* pred, const float* proba, const float* weight, int B, int K,
+                              long V, float threshold, float label_smoothing, int mean, float* loss,
+                              double* workspace, long workspace_doubles, void* stream);
+int adell_pseudo_label_ce_bwd(const float* pred, const float* proba, const float* weight, const float* g,
+                              int B, int K, long V, float threshold, float label_smoothing, int mean,
+                              float* dpred, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
