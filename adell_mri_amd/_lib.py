@@ -50,6 +50,7 @@ class AdnSite(ctypes.Structure):
 
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_d = ctypes.c_double
 
 DECONF_MAX_HEADS = 8     # ADELL_DECONF_MAX_HEADS
 
@@ -156,8 +157,8 @@ SIGNATURES = {
     "adell_class_sums_fwd": (_i, [_vp, _vp, _i, _l, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "adell_class_sums_bwd": (_i, [_vp, _vp, _i, _l, _i, _vp, _vp]),
     "adell_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _i, _f, _vp]),
-    "adell_adamw_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _l, _f, _vp]),
-    "adell_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _l, _f, _vp]),
+    "adell_adamw_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _d, _d, _f, _f, _l, _f, _vp]),
+    "adell_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _d, _d, _f, _f, _l, _f, _vp]),
     "adell_ema_update": (_i, [_vp, _vp, _l, _f, _vp]),
     "adell_layernorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
     "adell_layernorm_bwd_workspace": (_l, [_l, _i]),
@@ -285,7 +286,7 @@ SIGNATURES = {
     "adell_det_decode": (_i, [_vp] * 4 + [_i] + [_vp] * 3 + [_f] * 3 + [_i] * 6 + [_vp] * 5),
     "adell_det_match": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "adell_det_encode": (_i, [_vp] * 4 + [ctypes.c_double] * 4 + [_i] * 6 + [_vp, _vp]),
-    "adell_adamw_amsgrad_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _l, _f, _vp]),
+    "adell_adamw_amsgrad_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _f, _d, _d, _f, _f, _l, _f, _vp]),
     "adell_eca_gates_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _vp]),
     "adell_eca_gates_bwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "adell_eca_apply_fwd": (_i, [_vp, _vp, _i, _vp, _i, _l, _i, _vp]),
@@ -436,7 +437,7 @@ SIGNATURES = {
                               _vp, _vp]),
     "adell_gemm_f16x3_act": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp,
                                   _vp, _vp, _i, _f, _vp, _vp, _vp]),
-    "adell_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _l, _f, _f, _f, ctypes.POINTER(ctypes.c_float),
+    "adell_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _l, _f, _f, _f, ctypes.POINTER(_d),
                               _vp]),
     "adell_seg_loss_workspace": (_l, [_i, _l, _i]),
     "adell_seg_loss_fwd": (_i, [_i, _vp, _vp, _vp, _i, _l, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp,

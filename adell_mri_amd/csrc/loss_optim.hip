@@ -98,7 +98,9 @@ __global__ __launch_bounds__(256) void adell_dice_focal_bwd_kernel(LossArgs a) {
   const float wf = a.gfocal_dev ? a.gfocal_dev[b] : a.gfocal;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < a.S; i += (long)gridDim.x * 256L) {
     const float pi = p[i], ti = t[i];
-    const float dnum = (ti * pi > 0.f) ? ti : 0.f;
+    // (>=: torch.clip passes the gradient at the bound itself, and t p == 0 is where a saturated
+    // head puts a positive voxel: the right-hand derivative, not a dead zone)
+    const float dnum = (ti * pi >= 0.f) ? ti : 0.f;
     const float dden = (ti + pi + a.smooth > a.dice_eps) ? 1.f : 0.f;
     const float gd = -2.0f * (dnum * den - num * dden) * inv_den2;
     const float tb = ti > 0.5f ? 1.f : 0.f;
@@ -355,7 +357,8 @@ __global__ __launch_bounds__(256) void adell_adamw_kernel(float* __restrict__ p,
                                                           const float* __restrict__ g,
                                                           float* __restrict__ m,
                                                           float* __restrict__ v, long n, float lr,
-                                                          float b1, float b2, float eps, float wd,
+                                                          float b1, float b2, float omb1,
+                                                          float omb2, float eps, float wd,
                                                           float bc1, float bc2_sqrt,
                                                           float grad_scale) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
@@ -365,8 +368,8 @@ __global__ __launch_bounds__(256) void adell_adamw_kernel(float* __restrict__ p,
       pi *= 1.0f - lr * wd;
     else
       gi += wd * pi;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -375,31 +378,47 @@ __global__ __launch_bounds__(256) void adell_adamw_kernel(float* __restrict__ p,
   }
 }
 
+// The scalars that depend on the betas are formed in double from the betas as given, as torch.optim
+// forms them, and rounded once: 1 - (float)0.999 is 1.3e-5 off 0.001, which exp_avg_sq would carry.
+struct AdamScalars {
+  float b1, b2, omb1, omb2, bc1, bc2s;
+};
+
+static AdamScalars adell_adam_scalars(double beta1, double beta2, long step) {
+  AdamScalars s;
+  s.b1 = (float)beta1;
+  s.b2 = (float)beta2;
+  s.omb1 = (float)(1.0 - beta1);
+  s.omb2 = (float)(1.0 - beta2);
+  s.bc1 = (float)(1.0 - pow(beta1, (double)step));
+  s.bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+  return s;
+}
+
 static int adell_adam_launch(bool decoupled, float* param, const float* grad, float* exp_avg,
-                             float* exp_avg_sq, long n, float lr, float beta1, float beta2,
+                             float* exp_avg_sq, long n, float lr, double beta1, double beta2,
                              float eps, float weight_decay, long step, float grad_scale,
                              void* stream) {
   ADELL_REQUIRE(param && grad && exp_avg && exp_avg_sq, "adam(w)_step: null pointer");
   ADELL_REQUIRE(n > 0 && step >= 1, "adam(w)_step: bad n / step");
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  const AdamScalars c = adell_adam_scalars(beta1, beta2, step);
   long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (decoupled)
     hipLaunchKernelGGL(adell_adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
-                       eps, weight_decay, bc1, bc2s, grad_scale);
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, c.b1, c.b2,
+                       c.omb1, c.omb2, eps, weight_decay, c.bc1, c.bc2s, grad_scale);
   else
     hipLaunchKernelGGL(adell_adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
-                       eps, weight_decay, bc1, bc2s, grad_scale);
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, c.b1, c.b2,
+                       c.omb1, c.omb2, eps, weight_decay, c.bc1, c.bc2s, grad_scale);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
 
 // torch.optim.AdamW (amsgrad off), step = 1-based step count.
 extern "C" int adell_adamw_step(float* param, const float* grad, float* exp_avg,
-                                float* exp_avg_sq, long n, float lr, float beta1, float beta2,
+                                float* exp_avg_sq, long n, float lr, double beta1, double beta2,
                                 float eps, float weight_decay, long step, float grad_scale,
                                 void* stream) {
   return adell_adam_launch(true, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
@@ -408,7 +427,7 @@ extern "C" int adell_adamw_step(float* param, const float* grad, float* exp_avg,
 
 // torch.optim.Adam (amsgrad off): L2 weight decay added to the gradient.
 extern "C" int adell_adam_step(float* param, const float* grad, float* exp_avg,
-                               float* exp_avg_sq, long n, float lr, float beta1, float beta2,
+                               float* exp_avg_sq, long n, float lr, double beta1, double beta2,
                                float eps, float weight_decay, long step, float grad_scale,
                                void* stream) {
   return adell_adam_launch(false, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
@@ -418,13 +437,13 @@ extern "C" int adell_adam_step(float* param, const float* grad, float* exp_avg,
 // torch.optim.AdamW(amsgrad=True): vmax = max(vmax, v) kept beside v, the denominator from vmax.
 __global__ __launch_bounds__(256) void adell_adamw_amsgrad_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-    float* __restrict__ vmax, long n, float lr, float b1, float b2, float eps, float wd, float bc1,
-    float bc2_sqrt, float grad_scale) {
+    float* __restrict__ vmax, long n, float lr, float b1, float b2, float omb1, float omb2, float eps,
+    float wd, float bc1, float bc2_sqrt, float grad_scale) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
     const float gi = g[i] * grad_scale;
     float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     const float vm = fmaxf(vmax[i], vi);
     m[i] = mi;
     v[i] = vi;
@@ -437,18 +456,17 @@ __global__ __launch_bounds__(256) void adell_adamw_amsgrad_kernel(
 
 extern "C" int adell_adamw_amsgrad_step(float* param, const float* grad, float* exp_avg,
                                         float* exp_avg_sq, float* max_exp_avg_sq, long n, float lr,
-                                        float beta1, float beta2, float eps, float weight_decay,
+                                        double beta1, double beta2, float eps, float weight_decay,
                                         long step, float grad_scale, void* stream) {
   ADELL_REQUIRE(param && grad && exp_avg && exp_avg_sq && max_exp_avg_sq,
                 "adamw_amsgrad_step: null pointer");
   ADELL_REQUIRE(n > 0 && step >= 1, "adamw_amsgrad_step: bad n / step");
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  const AdamScalars c = adell_adam_scalars(beta1, beta2, step);
   long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(adell_adamw_amsgrad_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, lr,
-                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
+                     c.b1, c.b2, c.omb1, c.omb2, eps, weight_decay, c.bc1, c.bc2s, grad_scale);
   ADELL_CHECK_HIP(hipGetLastError());
   return ADELL_OK;
 }
@@ -642,7 +660,8 @@ __global__ __launch_bounds__(256) void adell_segloss_bwd_kernel(SegLossArgs a) {
         break;
       }
       default: {
-        const float dnum = (te * pe * a.scale > 0.f) ? a.cw[c] * te * a.scale : 0.f;
+        // (>= as in adell_dice_focal_bwd_kernel: the gradient passes at t p == 0)
+        const float dnum = (te * pe * a.scale >= 0.f) ? a.cw[c] * te * a.scale : 0.f;
         const float dden = ((te + pe + a.smooth) * a.scale > a.eps) ? a.cw[c] * a.scale : 0.f;
         d = -2.0f * (dnum * den - num * dden) * inv_den2;
         break;
@@ -732,6 +751,7 @@ struct OptimArgs {
   int kind;
   float wd, eps, grad_scale;
   float c[5];
+  float om0, om1;   // 1 - c[0], 1 - c[1] formed in double on the host (1 - beta as torch.optim has it)
 };
 
 __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
@@ -740,10 +760,14 @@ __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
     const float gi = a.g[i] * a.grad_scale + a.wd * pi;
     switch (a.kind) {
       case 0: {
-        const float m = a.c[0] * a.s1[i] + (1.f - a.c[0]) * gi;
-        const float u = fmaxf(a.c[1] * a.s2[i], fabsf(gi) + a.eps);
+        const float m = a.c[0] * a.s1[i] + a.om0 * gi;
+        const float u0 = a.s2[i];
+        const float u = fmaxf(a.c[1] * u0, fabsf(gi) + a.eps);
         a.s1[i] = m;
-        a.s2[i] = u;
+        // An element that has never seen a gradient (the padding between the slices of the flat
+        // buffer) keeps exp_inf = 0, so that padding stays zero in every buffer. torch would store eps
+        // there; no later step can tell the two apart, since beta2 * eps < |g| + eps for every g.
+        a.s2[i] = (gi == 0.f && u0 == 0.f) ? 0.f : u;
         pi -= a.c[2] * m / u;
         break;
       }
@@ -754,8 +778,8 @@ __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
         break;
       }
       case 2: {
-        const float m = a.c[0] * a.s1[i] + (1.f - a.c[0]) * gi;
-        const float v = a.c[1] * a.s2[i] + (1.f - a.c[1]) * gi * gi;
+        const float m = a.c[0] * a.s1[i] + a.om0 * gi;
+        const float v = a.c[1] * a.s2[i] + a.om1 * gi * gi;
         a.s1[i] = m;
         a.s2[i] = v;
         const float denom = sqrtf(v / a.c[2]) + a.eps;
@@ -764,8 +788,8 @@ __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
         break;
       }
       case 3: {
-        const float m = a.c[0] * a.s1[i] + (1.f - a.c[0]) * gi;
-        const float v = a.c[1] * a.s2[i] + (1.f - a.c[1]) * gi * gi;
+        const float m = a.c[0] * a.s1[i] + a.om0 * gi;
+        const float v = a.c[1] * a.s2[i] + a.om1 * gi * gi;
         a.s1[i] = m;
         a.s2[i] = v;
         if (a.c[3] >= 0.f)
@@ -775,7 +799,7 @@ __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
         break;
       }
       default: {
-        const float s = a.c[0] * a.s1[i] + (1.f - a.c[0]) * gi * gi;
+        const float s = a.c[0] * a.s1[i] + a.om0 * gi * gi;
         a.s1[i] = s;
         pi -= a.c[1] * gi / (sqrtf(s) + a.eps);
         break;
@@ -787,14 +811,16 @@ __global__ __launch_bounds__(256) void adell_optim_kernel(OptimArgs a) {
 
 extern "C" int adell_optim_step(int kind, float* param, const float* grad, float* state1,
                                 float* state2, long n, float weight_decay, float eps,
-                                float grad_scale, const float* c5, void* stream) {
+                                float grad_scale, const double* c5, void* stream) {
   ADELL_REQUIRE(kind >= 0 && kind <= 4, "optim_step: kind must be 0..4");
   ADELL_REQUIRE(param && grad && state1 && c5 && n > 0, "optim_step: bad arguments");
   ADELL_REQUIRE(state2 || kind == 1 || kind == 4, "optim_step: this optimiser needs two state buffers");
   OptimArgs a;
   a.p = param; a.g = grad; a.s1 = state1; a.s2 = state2; a.n = n; a.kind = kind;
   a.wd = weight_decay; a.eps = eps; a.grad_scale = grad_scale;
-  for (int i = 0; i < 5; ++i) a.c[i] = c5[i];   // host array
+  for (int i = 0; i < 5; ++i) a.c[i] = (float)c5[i];   // host array
+  a.om0 = (float)(1.0 - c5[0]);
+  a.om1 = (float)(1.0 - c5[1]);
   long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(adell_optim_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);

@@ -3830,7 +3830,8 @@ OPTIM_KINDS = {"adamax": 0, "adagrad": 1, "nadam": 2, "radam": 3, "rmsprop": 4}
 def optim_step(kind, param, grad, s1, s2, weight_decay, eps, grad_scale, c5):
     """One fused step of adamax / adagrad / nadam / radam / rmsprop on flat fp32 buffers."""
     _require_cuda(param, grad, s1, s2)
-    arr = (ctypes.c_float * 5)(*[float(v) for v in (list(c5) + [0.0] * 5)[:5]])
+    # doubles: the kernel's 1 - beta comes from the betas as given, not from their fp32 roundings
+    arr = (ctypes.c_double * 5)(*[float(v) for v in (list(c5) + [0.0] * 5)[:5]])
     check(_lib.lib().adell_optim_step(OPTIM_KINDS[kind], _ptr(param), _ptr(grad), _ptr(s1),
                                       _ptr(s2), param.numel(), weight_decay, eps, grad_scale, arr,
                                       _stream()))

@@ -590,18 +590,19 @@ int adell_class_sums_bwd(const float* t, const float* gsums, int B, long V, int 
  * adell_adamw_step: torch.optim.AdamW (self_supervised/pl.py:245-250);
  * adell_ema_update: ExponentialMovingAverage.update (utils/utils.py:447-493).
  * grad_scale multiplies the gradient first (1/world_size after a sum
- * all-reduce, 1/accumulate_grad_batches).
+ * all-reduce, 1/accumulate_grad_batches). The betas (and c5 below) are doubles: 1 - beta and
+ * the bias corrections are formed from them in double, as torch.optim forms them, and rounded once.
  * ---------------------------------------------------------------------- */
 int adell_sgd_step(float* param, const float* grad, float* momentum_buf, long n, float lr,
                    float momentum, float weight_decay, int nesterov, int first_step,
                    float grad_scale, void* stream);
 int adell_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                     long n, float lr, float beta1, float beta2, float eps,
+                     long n, float lr, double beta1, double beta2, float eps,
                      float weight_decay, long step, float grad_scale, void* stream);
 /* torch.optim.Adam ("adam" of optimizer_factory.py:5-14): as above with the weight decay added
  * to the gradient instead of decoupled. */
 int adell_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n,
-                    float lr, float beta1, float beta2, float eps, float weight_decay, long step,
+                    float lr, double beta1, double beta2, float eps, float weight_decay, long step,
                     float grad_scale, void* stream);
 
 /* The other optimisers of the reference's factory (utils/optimizer_factory.py:5-14), torch.optim
@@ -610,7 +611,7 @@ int adell_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
  * 4 RMSprop (square_avg; momentum 0, not centered). c5: HOST array of the five per-step scalars
  * documented at adell_optim_kernel (csrc/loss_optim.hip). */
 int adell_optim_step(int kind, float* param, const float* grad, float* state1, float* state2,
-                     long n, float weight_decay, float eps, float grad_scale, const float* c5,
+                     long n, float weight_decay, float eps, float grad_scale, const double* c5,
                      void* stream);
 int adell_ema_update(float* shadow, const float* param, long n, float decay, void* stream);
 
@@ -1136,7 +1137,7 @@ int adell_det_encode(const double* boxes, const double* classes, const int* coun
                      int W, int D, double* out, void* stream);
 /* torch.optim.AdamW(amsgrad=True): adell_adamw_step with max_exp_avg_sq kept and used in the denominator. */
 int adell_adamw_amsgrad_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                             float* max_exp_avg_sq, long n, float lr, float beta1, float beta2, float eps,
+                             float* max_exp_avg_sq, long n, float lr, double beta1, double beta2, float eps,
                              float weight_decay, long step, float grad_scale, void* stream);
 
 /* DDPM diffusion (modules/diffusion/unet.py, diffusion_process.py, modules/layers/class_attention.py;

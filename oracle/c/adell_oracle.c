@@ -303,7 +303,8 @@ void oracle_dice_focal(const float* p, const float* t, int B, long S, float smoo
       for (long i = 0; i < S; ++i) {
         const double pi = pp[i], ti = tt[i];
         /* dice: d/dp [1 - 2 num/den] */
-        const double dnum = (ti * pi > 0) ? ti : 0.0;
+        /* (>=: torch.clip(t p, 0) passes the gradient at the bound itself, i.e. at p == 0) */
+        const double dnum = (ti * pi >= 0) ? ti : 0.0;
         const double dden = (ti + pi + (double)smooth > dice_eps) ? 1.0 : 0.0;
         const double gd = -2.0 * (dnum * den - num * dden) / (den * den);
         /* focal */
