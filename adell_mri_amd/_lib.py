@@ -68,6 +68,15 @@ class DeconfHeadGrads(ctypes.Structure):
                 ("dbc", _vp)]
 
 
+class AttentionDesc(ctypes.Structure):
+    """adell_attention_desc (include/adell_hip.h): everything of an attention call but its tensors."""
+    _fields_ = [("BH", ctypes.c_int32), ("H", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("A", ctypes.c_int32), ("Dv", ctypes.c_int32), ("scale", _f), ("drop_p", _f),
+                ("rng_offset", ctypes.c_uint32), ("seed", ctypes.c_uint64), ("bias", _vp),
+                ("labels", _vp), ("nbias", ctypes.c_int32), ("nlab", ctypes.c_int32),
+                ("strided", ctypes.c_int32), ("stride", ctypes.c_int64 * 3 * 8)]
+
+
 # name -> (restype, argtypes); every symbol include/adell_hip.h declares.
 SIGNATURES = {
     "adell_abi_version": (_i, []),
@@ -165,32 +174,11 @@ SIGNATURES = {
     "adell_layernorm_bwd": (_i, [_vp] * 8 + [_l, _i, _vp, ctypes.c_size_t, _vp]),
     "adell_add_bcast": (_i, [_vp, _vp, _vp, _l, _l, _vp]),
     "adell_sum_bcast": (_i, [_vp, _vp, _l, _l, _vp]),
-    "adell_attention_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, ctypes.c_ulonglong,
-                                 ctypes.c_uint, _vp, _vp, _vp]),
-    "adell_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f,
-                                 ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp]),
-    "adell_attention_strided_ok": (_i, [_i, _i, _i]),
+    "adell_attention_fwd": (_i, [ctypes.POINTER(AttentionDesc)] + [_vp] * 6),
+    "adell_attention_bwd": (_i, [ctypes.POINTER(AttentionDesc)] + [_vp] * 10),
     "adell_attention_plan": (_i, [_i] * 5 + [_vp]),
-    "adell_attention_fwd_strided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _f,
-                                         ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp]),
-    "adell_attention_bwd_strided": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                                         _vp, _f, _f, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp,
-                                         _vp, _vp]),
-    "adell_attention_fwd_labels": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f,
-                                        ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp]),
-    "adell_attention_bwd_labels": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i,
-                                        _i, _i, _f, _f, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp,
-                                        _vp, _vp]),
-    "adell_attention_fwd_strided_labels": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i,
-                                                _vp, _f, _f, ctypes.c_ulonglong, ctypes.c_uint, _vp,
-                                                _vp, _vp]),
-    "adell_attention_bwd_strided_labels": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i,
-                                                _i, _i, _i, _i, _vp, _f, _f, ctypes.c_ulonglong,
-                                                ctypes.c_uint, _vp, _vp, _vp, _vp]),
     "adell_attention_bias_grad_workspace_floats": (_l, [_i, _i]),
-    "adell_attention_bias_grad": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i,
-                                       _i, _i, _vp, _f, _f, ctypes.c_ulonglong, ctypes.c_uint, _vp,
-                                       _vp, _l, _vp]),
+    "adell_attention_bias_grad": (_i, [ctypes.POINTER(AttentionDesc)] + [_vp] * 8 + [_l, _vp]),
     "adell_copy_channels": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _vp]),
     "adell_interp_nearest_fwd": (_i, [_vp, _vp] + [_i] * 8 + [_vp]),
     "adell_interp_nearest_bwd": (_i, [_vp, _vp] + [_i] * 8 + [_vp]),

@@ -8,8 +8,6 @@
 // the token axis). Sequences are short (216 tokens at config 3): these kernels
 // are latency/HBM-bound fp32 VALU code, one wave per row, wavefront-shuffle
 // reductions, fixed summation order.
-#include <initializer_list>
-
 #include "common.h"
 
 ADELL_RNG_STEP_DEFINE(tokens)
@@ -1030,7 +1028,7 @@ __global__ __launch_bounds__(256) void adell_attn_mfma_bwd_kv_kernel(AttArgs a) 
 // j's sequences (grid z), walks the chunk in ascending bh and accumulates in registers. With one
 // chunk the tile goes straight to dbias; otherwise to partial slice z of the workspace, and
 // adell_attn_dbias_fold_kernel adds the partial slices in chunk order: no atomics, the same bits on
-// every run. Operands by (item, head, row) strides as in adell_attention_bwd_strided.
+// every run. Operands by (item, head, row) strides as in adell_attention_bwd.
 // ---------------------------------------------------------------------------------------------
 struct AttBiasGrad {
   float* dst;    // dbias, or the workspace [chunks][nbias][T][T]
@@ -1311,207 +1309,119 @@ static int adell_att_launch(int which, const AttArgs& a, int BH, const AdellAttP
                             : adell_att_valu_launch<adell_attention_bwd_kv_kernel<ATT_ROWS / 2>>(a, BH, p, st);
 }
 
-static int adell_att_check(int BH, int T, int A, int Dv, int nbias, const float* bias) {
-  ADELL_REQUIRE(BH > 0 && T > 0 && A > 0 && Dv > 0, "attention: bad dims");
-  ADELL_REQUIRE(A <= 256 && Dv <= 256, "attention: head dims up to 256 supported");
-  ADELL_REQUIRE(bias == nullptr || nbias > 0, "attention: bias needs nbias > 0");
+// The three launching entries. Each uses the first `nops` operands of the order of
+// adell_attention_desc::stride (q, k, v, out, dout, dq, dk, dv). Stride policy of strided operands:
+// strict entries refuse what the MFMA kernels cannot stage with 16-byte loads (and shapes without an
+// MFMA instance); the lenient one plans the vector-ALU form for it.
+enum AttEntry { ATT_FWD, ATT_BWD, ATT_DBIAS };
+static const struct { const char* name; int nops; bool strict; } ATT_ENTRY[] = {
+    {"attention_fwd", 4, true}, {"attention_bwd", 8, true}, {"attention_bias_grad", 5, false}};
+static const char* const ATT_OPERAND[8] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
+
+static bool adell_att_is_mfma(const AdellAttPlan& p) {
+  return p.path == ADELL_ATT_MFMA_RESIDENT || p.path == ADELL_ATT_MFMA_STREAMED;
+}
+
+// Element strides of operand `i` (`C` values per row) of entry `e`, checked by the entry's policy.
+// *aligned: what adell_att_plan is to be asked with.
+static int adell_att_stride(AttEntry e, const adell_attention_desc* d, int i, const void* p, int C,
+                            AttStride* out, bool* aligned) {
+  const char* who = ATT_ENTRY[e].name;
+  const bool a16 = (((uintptr_t)p) & 15) == 0;
+  if (!d->strided) {   // contiguous [BH][T][C], any alignment
+    *out = {(long)d->T * C, 0, C};
+    *aligned = *aligned && a16;
+    return ADELL_OK;
+  }
+  const int64_t* s = d->stride[i];
+  const bool mult4 = s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0;
+  ADELL_REQUIRE(s[0] >= 0 && s[1] >= 0 && s[2] >= C,
+                "%s (strided): bad %s strides (%ld, %ld, %ld): none negative, rows at least %d apart", who,
+                ATT_OPERAND[i], (long)s[0], (long)s[1], (long)s[2], C);
+  if (ATT_ENTRY[e].strict) {
+    ADELL_REQUIRE(a16, "%s (strided): %s must be 16-byte aligned", who, ATT_OPERAND[i]);
+    ADELL_REQUIRE(mult4, "%s (strided): %s strides (%ld, %ld, %ld) must be multiples of 4 elements", who,
+                  ATT_OPERAND[i], (long)s[0], (long)s[1], (long)s[2]);
+  }
+  *out = {(long)s[0], (long)s[1], (long)s[2]};
+  *aligned = *aligned && a16 && mult4;
   return ADELL_OK;
 }
 
-// region labels [nlab][T] of items of H sequences each (null: none)
-static int adell_att_set_labels(AttArgs* a, const int* labels, int nlab, int H) {
-  ADELL_REQUIRE(labels == nullptr || (nlab > 0 && H > 0), "attention: labels need nlab > 0 and H > 0");
-  a->labels = labels;
-  a->nlab = nlab > 0 ? nlab : 1;
-  a->labH = H > 0 ? H : 1;
-  return ADELL_OK;
-}
-
-static bool adell_att_aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (((uintptr_t)p) & 15) return false;
-  return true;
-}
-
-// contiguous [BH][T][A | Dv] operands as strides
-static void adell_att_contiguous(AttArgs* a) {
-  const AttStride sa = {(long)a->T * a->A, 0, a->A}, sd = {(long)a->T * a->Dv, 0, a->Dv};
-  a->H = 1;
-  a->sq = a->sk = a->sdq = a->sdk = sa;
-  a->sv = a->so = a->sg = a->sdv = sd;
-}
-
-static int adell_att_stride(const char* what, const void* p, const long* s, int C, AttStride* out) {
-  ADELL_REQUIRE(p && (((uintptr_t)p) & 15) == 0, "attention (strided): %s must be 16-byte aligned", what);
-  ADELL_REQUIRE(s[0] >= 0 && s[1] >= 0 && s[2] >= C && s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0,
-                "attention (strided): %s strides (%ld, %ld, %ld) must be multiples of 4 elements, "
-                "rows at least %d apart", what, s[0], s[1], s[2], C);
-  out->b = s[0]; out->h = s[1]; out->r = s[2];
-  return ADELL_OK;
-}
-
-extern "C" int adell_attention_fwd_labels(const float* q, const float* k, const float* v,
-                                          const float* bias, int nbias, const int* labels, int nlab,
-                                          int H, int BH, int T, int A, int Dv, float scale,
-                                          float drop_p, unsigned long long seed,
-                                          unsigned int rng_offset, float* out, float* lse,
-                                          void* stream) {
-  int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(q && k && v && out && lse, "attention_fwd: null pointer");
+// The kernels' arguments of entry `e` from its descriptor and tensors (op: the 8 operands in
+// descriptor order, those past the entry's own null): every check that needs no plan, in one place.
+static int adell_att_fill(AttEntry e, const adell_attention_desc* d, const float* const op[8],
+                          const float* lse, AttArgs* out, bool* aligned) {
+  const char* who = ATT_ENTRY[e].name;
+  ADELL_REQUIRE(d, "%s: null descriptor", who);
+  const int BH = d->BH, T = d->T, A = d->A, Dv = d->Dv;
+  ADELL_REQUIRE(BH > 0 && T > 0 && A > 0 && Dv > 0, "%s: bad dims", who);
+  ADELL_REQUIRE(A <= 256 && Dv <= 256, "%s: head dims up to 256 supported", who);
+  ADELL_REQUIRE(!d->strided || (d->H > 0 && BH % d->H == 0),
+                "%s (strided): %d sequences are not items of %d heads", who, BH, d->H);
+  ADELL_REQUIRE(d->bias == nullptr || d->nbias > 0, "%s: bias needs nbias > 0", who);
+  if (e == ATT_DBIAS) {
+    ADELL_REQUIRE(d->nbias > 0 && d->nbias <= BH, "%s: nbias must be in [1, BH]", who);
+    ADELL_REQUIRE(d->nbias <= 65535, "%s: at most 65535 bias slices (grid y), got %d", who, d->nbias);
+  }
+  ADELL_REQUIRE(!(d->strided && ATT_ENTRY[e].strict) || adell_att_is_mfma(adell_att_plan(0, T, A, Dv, true)),
+                "%s (strided): head dims (%d, %d) at %d tokens have no MFMA instance", who, A, Dv, T);
+  for (int i = 0; i < ATT_ENTRY[e].nops; ++i) ADELL_REQUIRE(op[i], "%s: null pointer (%s)", who, ATT_OPERAND[i]);
+  ADELL_REQUIRE(lse, "%s: null pointer (lse)", who);
+  ADELL_REQUIRE(d->labels == nullptr || (d->nlab > 0 && d->H > 0), "%s: labels need nlab > 0 and H > 0", who);
+  ADELL_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "%s: bad dropout probability", who);
   AttArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out; a.lse_out = lse;
-  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale;
-  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
-  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
-  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  a.rng_offset = rng_offset;
-  // the MFMA kernels stage with 16-byte loads: unaligned operands take the vector-ALU kernels
-  const AdellAttPlan p = adell_att_plan(0, T, A, Dv, adell_att_aligned16({q, k, v, out}));
-  adell_att_contiguous(&a);
-  return adell_att_launch(0, a, BH, p, (hipStream_t)stream);
+  a.q = op[0]; a.k = op[1]; a.v = op[2]; a.bias = d->bias; a.labels = d->labels;
+  if (e == ATT_FWD) {
+    a.out = (float*)op[3]; a.lse_out = (float*)lse;
+  } else {
+    a.o = op[3]; a.dout = op[4]; a.lse = lse;
+    a.dq = (float*)op[5]; a.dk = (float*)op[6]; a.dv = (float*)op[7];
+  }
+  a.T = T; a.A = A; a.Dv = Dv; a.nbias = d->nbias > 0 ? d->nbias : 1;
+  a.nlab = d->nlab > 0 ? d->nlab : 1; a.labH = d->H > 0 ? d->H : 1;
+  a.scale = d->scale; a.drop_p = d->drop_p;
+  a.seed_lo = (uint32_t)d->seed; a.seed_hi = (uint32_t)(d->seed >> 32); a.rng_offset = d->rng_offset;
+  a.H = d->strided ? d->H : 1;
+  AttStride* const st[8] = {&a.sq, &a.sk, &a.sv, &a.so, &a.sg, &a.sdq, &a.sdk, &a.sdv};
+  const int width[8] = {A, A, Dv, Dv, Dv, A, A, Dv};
+  *aligned = true;   // the MFMA kernels stage with 16-byte loads: other operands take the vector-ALU kernels
+  for (int i = 0; i < ATT_ENTRY[e].nops; ++i) {
+    const int rc = adell_att_stride(e, d, i, op[i], width[i], st[i], aligned);
+    if (rc != ADELL_OK) return rc;
+  }
+  *out = a;
+  return ADELL_OK;
 }
 
-extern "C" int adell_attention_fwd(const float* q, const float* k, const float* v,
-                                   const float* bias, int nbias, int BH, int T, int A, int Dv,
-                                   float scale, float drop_p, unsigned long long seed,
-                                   unsigned int rng_offset, float* out, float* lse,
-                                   void* stream) {
-  return adell_attention_fwd_labels(q, k, v, bias, nbias, nullptr, 0, 1, BH, T, A, Dv, scale, drop_p,
-                                    seed, rng_offset, out, lse, stream);
-}
-
-extern "C" int adell_attention_bwd_labels(const float* q, const float* k, const float* v,
-                                          const float* bias, int nbias, const int* labels, int nlab,
-                                          int H, const float* out, const float* dout,
-                                          const float* lse, int BH, int T, int A, int Dv, float scale,
-                                          float drop_p, unsigned long long seed,
-                                          unsigned int rng_offset, float* dq, float* dk, float* dv,
-                                          void* stream) {
-  int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
+// With strided operands (sequence bh = b * H + h) Q / K / V can stay inside the packed
+// [B][T][H][q | k | v] projection output, O / dO are read and written as [B][T][H * Dv] token rows,
+// dQ / dK / dV land where the caller's next kernel wants them -- none of the permute / slice copies
+// of linear_blocks.py:372-417 exist as launches.
+extern "C" int adell_attention_fwd(const adell_attention_desc* d, const float* q, const float* k,
+                                   const float* v, float* out, float* lse, void* stream) {
+  const float* const op[8] = {q, k, v, out};
+  AttArgs a;
+  bool aligned;
+  const int rc = adell_att_fill(ATT_FWD, d, op, lse, &a, &aligned);
   if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(q && k && v && out && dout && lse && dq && dk && dv, "attention_bwd: null pointer");
-  AttArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
-  a.dq = dq; a.dk = dk; a.dv = dv;
-  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale;
-  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
-  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
-  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  a.rng_offset = rng_offset;
-  const bool aligned = adell_att_aligned16({q, k, v, out, dout, dq, dk, dv});
-  const AdellAttPlan pq = adell_att_plan(1, T, A, Dv, aligned), pkv = adell_att_plan(2, T, A, Dv, aligned);
+  return adell_att_launch(0, a, d->BH, adell_att_plan(0, a.T, a.A, a.Dv, aligned), (hipStream_t)stream);
+}
+
+extern "C" int adell_attention_bwd(const adell_attention_desc* d, const float* q, const float* k,
+                                   const float* v, const float* out, const float* dout,
+                                   const float* lse, float* dq, float* dk, float* dv, void* stream) {
+  const float* const op[8] = {q, k, v, out, dout, dq, dk, dv};
+  AttArgs a;
+  bool aligned;
+  int rc = adell_att_fill(ATT_BWD, d, op, lse, &a, &aligned);
+  if (rc != ADELL_OK) return rc;
+  const AdellAttPlan pq = adell_att_plan(1, a.T, a.A, a.Dv, aligned), pkv = adell_att_plan(2, a.T, a.A, a.Dv, aligned);
   ADELL_REQUIRE(pq.path != ADELL_ATT_REFUSED && pkv.path != ADELL_ATT_REFUSED,
-                "attention_bwd: no kernel for head dims (%d, %d)", A, Dv);   // before the first launch
-  adell_att_contiguous(&a);
-  rc = adell_att_launch(1, a, BH, pq, (hipStream_t)stream);
+                "attention_bwd: no kernel for head dims (%d, %d)", a.A, a.Dv);   // before the first launch
+  rc = adell_att_launch(1, a, d->BH, pq, (hipStream_t)stream);
   if (rc != ADELL_OK) return rc;
-  return adell_att_launch(2, a, BH, pkv, (hipStream_t)stream);
-}
-
-extern "C" int adell_attention_bwd(const float* q, const float* k, const float* v,
-                                   const float* bias, int nbias, const float* out,
-                                   const float* dout, const float* lse, int BH, int T, int A,
-                                   int Dv, float scale, float drop_p, unsigned long long seed,
-                                   unsigned int rng_offset, float* dq, float* dk, float* dv,
-                                   void* stream) {
-  return adell_attention_bwd_labels(q, k, v, bias, nbias, nullptr, 0, 1, out, dout, lse, BH, T, A, Dv,
-                                    scale, drop_p, seed, rng_offset, dq, dk, dv, stream);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same attention with every operand addressed by (item, head, token row) element strides:
-// sequence bh = b * H + h. Q / K / V can stay inside the packed [B][T][H][q | k | v] projection
-// output, O / dO are read and written as [B][T][H * Dv] token rows, dQ / dK / dV land where the
-// caller's next kernel wants them -- none of the permute / slice copies of
-// linear_blocks.py:372-417 exist as launches. MFMA-shaped heads only (adell_attention_strided_ok).
-// ---------------------------------------------------------------------------------------------
-extern "C" int adell_attention_strided_ok(int T, int A, int Dv) {
-  const int path = adell_att_plan(0, T, A, Dv, true).path;
-  return path == ADELL_ATT_MFMA_RESIDENT || path == ADELL_ATT_MFMA_STREAMED ? 1 : 0;
-}
-
-extern "C" int adell_attention_fwd_strided_labels(const float* q, const float* k, const float* v,
-                                                  const float* bias, int nbias, const int* labels,
-                                                  int nlab, int B, int H, int T, int A, int Dv,
-                                                  const long* strides, float scale, float drop_p,
-                                                  unsigned long long seed, unsigned int rng_offset,
-                                                  float* out, float* lse, void* stream) {
-  ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_fwd_strided: bad dims");
-  int rc = adell_att_check(B * H, T, A, Dv, nbias, bias);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(adell_attention_strided_ok(T, A, Dv),
-                "attention_fwd_strided: head dims (%d, %d) at %d tokens have no MFMA instance", A, Dv, T);
-  ADELL_REQUIRE(lse, "attention_fwd_strided: null pointer");
-  AttArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out; a.lse_out = lse;
-  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale; a.H = H;
-  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
-  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
-  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  a.rng_offset = rng_offset;
-  if ((rc = adell_att_stride("q", q, strides, A, &a.sq)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("k", k, strides + 3, A, &a.sk)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("v", v, strides + 6, Dv, &a.sv)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("out", out, strides + 9, Dv, &a.so)) != ADELL_OK) return rc;
-  return adell_att_launch(0, a, B * H, adell_att_plan(0, T, A, Dv, true), (hipStream_t)stream);
-}
-
-extern "C" int adell_attention_fwd_strided(const float* q, const float* k, const float* v,
-                                           const float* bias, int nbias, int B, int H, int T,
-                                           int A, int Dv, const long* strides, float scale,
-                                           float drop_p, unsigned long long seed,
-                                           unsigned int rng_offset, float* out, float* lse,
-                                           void* stream) {
-  return adell_attention_fwd_strided_labels(q, k, v, bias, nbias, nullptr, 0, B, H, T, A, Dv, strides,
-                                            scale, drop_p, seed, rng_offset, out, lse, stream);
-}
-
-extern "C" int adell_attention_bwd_strided_labels(const float* q, const float* k, const float* v,
-                                                  const float* bias, int nbias, const int* labels,
-                                                  int nlab, const float* out, const float* dout,
-                                                  const float* lse, int B, int H, int T, int A,
-                                                  int Dv, const long* strides, float scale,
-                                                  float drop_p, unsigned long long seed,
-                                                  unsigned int rng_offset, float* dq, float* dk,
-                                                  float* dv, void* stream) {
-  ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_bwd_strided: bad dims");
-  int rc = adell_att_check(B * H, T, A, Dv, nbias, bias);
-  if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(adell_attention_strided_ok(T, A, Dv),
-                "attention_bwd_strided: head dims (%d, %d) at %d tokens have no MFMA instance", A, Dv, T);
-  ADELL_REQUIRE(lse, "attention_bwd_strided: null pointer");
-  AttArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
-  a.dq = dq; a.dk = dk; a.dv = dv;
-  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias > 0 ? nbias : 1; a.scale = scale; a.H = H;
-  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
-  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
-  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  a.rng_offset = rng_offset;
-  if ((rc = adell_att_stride("q", q, strides, A, &a.sq)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("k", k, strides + 3, A, &a.sk)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("v", v, strides + 6, Dv, &a.sv)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("out", out, strides + 9, Dv, &a.so)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("dout", dout, strides + 12, Dv, &a.sg)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("dq", dq, strides + 15, A, &a.sdq)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("dk", dk, strides + 18, A, &a.sdk)) != ADELL_OK) return rc;
-  if ((rc = adell_att_stride("dv", dv, strides + 21, Dv, &a.sdv)) != ADELL_OK) return rc;
-  rc = adell_att_launch(1, a, B * H, adell_att_plan(1, T, A, Dv, true), (hipStream_t)stream);
-  if (rc != ADELL_OK) return rc;
-  return adell_att_launch(2, a, B * H, adell_att_plan(2, T, A, Dv, true), (hipStream_t)stream);
-}
-
-extern "C" int adell_attention_bwd_strided(const float* q, const float* k, const float* v,
-                                           const float* bias, int nbias, const float* out,
-                                           const float* dout, const float* lse, int B, int H,
-                                           int T, int A, int Dv, const long* strides, float scale,
-                                           float drop_p, unsigned long long seed,
-                                           unsigned int rng_offset, float* dq, float* dk,
-                                           float* dv, void* stream) {
-  return adell_attention_bwd_strided_labels(q, k, v, bias, nbias, nullptr, 0, out, dout, lse, B, H, T,
-                                            A, Dv, strides, scale, drop_p, seed, rng_offset, dq, dk,
-                                            dv, stream);
+  return adell_att_launch(2, a, d->BH, pkv, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1551,36 +1461,17 @@ static int adell_att_dbias_mfma1(const AttArgs& a, const AttBiasGrad& g, dim3 gr
   }
 }
 
-extern "C" int adell_attention_bias_grad(const float* q, const float* k, const float* v,
-                                         const float* bias, int nbias, const int* labels, int nlab,
-                                         const float* out, const float* dout, const float* lse,
-                                         int B, int H, int T, int A, int Dv, const long* strides,
-                                         float scale, float drop_p, unsigned long long seed,
-                                         unsigned int rng_offset, float* dbias, float* workspace,
+extern "C" int adell_attention_bias_grad(const adell_attention_desc* d, const float* q, const float* k,
+                                         const float* v, const float* out, const float* dout,
+                                         const float* lse, float* dbias, float* workspace,
                                          long workspace_floats, void* stream) {
-  ADELL_REQUIRE(B > 0 && H > 0 && strides, "attention_bias_grad: bad dims");
-  const int BH = B * H;
-  int rc = adell_att_check(BH, T, A, Dv, nbias, bias);
+  const float* const op[8] = {q, k, v, out, dout};
+  AttArgs a;
+  bool aligned;
+  int rc = adell_att_fill(ATT_DBIAS, d, op, lse, &a, &aligned);
   if (rc != ADELL_OK) return rc;
-  ADELL_REQUIRE(nbias > 0 && nbias <= BH, "attention_bias_grad: nbias must be in [1, B * H]");
-  ADELL_REQUIRE(nbias <= 65535, "attention_bias_grad: at most 65535 bias slices (grid y), got %d", nbias);
-  ADELL_REQUIRE(q && k && v && out && dout && lse && dbias, "attention_bias_grad: null pointer");
-  AttArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = out; a.dout = dout; a.lse = lse;
-  a.T = T; a.A = A; a.Dv = Dv; a.nbias = nbias; a.scale = scale; a.H = H;
-  if ((rc = adell_att_set_labels(&a, labels, nlab, H)) != ADELL_OK) return rc;
-  ADELL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attention: bad dropout probability");
-  a.drop_p = drop_p; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-  a.rng_offset = rng_offset;
-  AttStride* dst[5] = {&a.sq, &a.sk, &a.sv, &a.so, &a.sg};
-  const int width[5] = {A, A, Dv, Dv, Dv};
-  bool aligned = adell_att_aligned16({q, k, v, out, dout});
-  for (int i = 0; i < 5; ++i) {
-    const long* s = strides + 3 * i;
-    ADELL_REQUIRE(s[0] >= 0 && s[1] >= 0 && s[2] >= width[i], "attention_bias_grad: bad strides");
-    dst[i]->b = s[0]; dst[i]->h = s[1]; dst[i]->r = s[2];
-    aligned = aligned && s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0;
-  }
+  ADELL_REQUIRE(dbias, "attention_bias_grad: null pointer (dbias)");
+  const int BH = d->BH, T = a.T, A = a.A, Dv = a.Dv, nbias = a.nbias;
   const AdellAttPlan p = adell_att_plan(1, T, A, Dv, aligned);   // the dQ kernel's choice of form
   ADELL_REQUIRE(p.path != ADELL_ATT_REFUSED, "attention_bias_grad: no kernel for head dims (%d, %d)", A, Dv);
   const bool mfma = p.path != ADELL_ATT_VALU;
@@ -1617,8 +1508,8 @@ extern "C" int adell_attention_bias_grad(const float* q, const float* k, const f
                                                     (const float*)workspace, dbias, n, chunks);
 }
 
-// Host-only launch plan of one pass of adell_attention_fwd / _bwd (and, with aligned = 1, of the
-// strided entries): the adell_att_plan call the launch makes (include/adell_hip.h: out[4]).
+// Host-only launch plan of one pass of adell_attention_fwd / _bwd (strided operands: aligned = 1):
+// the adell_att_plan call the launch makes (include/adell_hip.h: out[4]).
 extern "C" int adell_attention_plan(int pass, int T, int A, int Dv, int aligned, int* out) {
   ADELL_REQUIRE(out && pass >= 0 && pass <= 2, "attention_plan: bad arguments");
   const AdellAttPlan p = adell_att_plan(pass, T, A, Dv, aligned != 0);

@@ -1555,16 +1555,30 @@ def sum_bcast(g, period_shape):
     return db
 
 
-def _att_labels(labels, T):
-    """(labels, nlab) of an int32 [nlab, T] region-label operand, or (None, 0)."""
-    if labels is None:
-        return None, 0
-    if not labels.is_cuda:
-        raise AdellHipError("adell_mri_amd kernels run on MI355X only: got CPU labels")
-    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[1] != T:
-        raise AdellHipError(f"attention: labels must be int32 [nlab, {T}], got "
-                            f"{labels.dtype} {tuple(labels.shape)}")
-    return labels.contiguous(), int(labels.shape[0])
+def _att_desc(BH, H, T, A, Dv, scale, drop_p, seed, offset, bias, labels, strides=None):
+    """adell_attention_desc of one call. bias: [nbias,T,T] or None; labels: int32 [nlab,T] or None;
+    strides: (item, head, row) element strides of the operands in the order q, k, v, out, dout, dq,
+    dk, dv (as many triples as the entry reads), None for contiguous operands."""
+    d = _lib.AttentionDesc(BH=int(BH), H=int(H), T=int(T), A=int(A), Dv=int(Dv), scale=float(scale),
+                           drop_p=float(drop_p), rng_offset=int(offset) & 0xFFFFFFFF,
+                           seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    if bias is not None:
+        bias = bias.contiguous()
+        d.bias, d.nbias = _ptr(bias), bias.numel() // (T * T)
+    if labels is not None:
+        if not labels.is_cuda:
+            raise AdellHipError("adell_mri_amd kernels run on MI355X only: got CPU labels")
+        if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[1] != T:
+            raise AdellHipError(f"attention: labels must be int32 [nlab, {T}], got "
+                                f"{labels.dtype} {tuple(labels.shape)}")
+        labels = labels.contiguous()
+        d.labels, d.nlab = _ptr(labels), int(labels.shape[0])
+    if strides is not None:
+        d.strided = 1
+        flat = (ctypes.c_int64 * len(strides)).from_buffer(d, _lib.AttentionDesc.stride.offset)
+        flat[:] = [int(s) for s in strides]
+    d.keep = (bias, labels)     # the descriptor holds their addresses
+    return d
 
 
 def attention_fwd(q, k, v, bias, scale, drop_p=0.0, seed=0, offset=0, labels=None, heads=1):
@@ -1577,15 +1591,9 @@ def attention_fwd(q, k, v, bias, scale, drop_p=0.0, seed=0, offset=0, labels=Non
     Dv = v.shape[-1]
     out = torch.empty((BH, T, Dv), device=q.device, dtype=torch.float32)
     lse = torch.empty((BH, T), device=q.device, dtype=torch.float32)
-    nb = 0
-    if bias is not None:
-        bias = bias.contiguous()
-        nb = bias.numel() // (T * T)
-    labels, nlab = _att_labels(labels, T)
-    check(_lib.lib().adell_attention_fwd_labels(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, int(heads), BH, T, A, Dv,
-        float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF,
-        _ptr(out), _ptr(lse), _stream()))
+    d = _att_desc(BH, heads, T, A, Dv, scale, drop_p, seed, offset, bias, labels)
+    check(_lib.lib().adell_attention_fwd(ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                         _ptr(lse), _stream()))
     return out, lse
 
 
@@ -1595,15 +1603,10 @@ def attention_bwd(q, k, v, bias, out, dout, lse, scale, drop_p=0.0, seed=0, offs
     Dv = v.shape[-1]
     dout = dout.contiguous()
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    if bias is not None:
-        bias = bias.contiguous()
-    nb = 0 if bias is None else bias.numel() // (T * T)
-    labels, nlab = _att_labels(labels, T)
-    check(_lib.lib().adell_attention_bwd_labels(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, int(heads), _ptr(out),
-        _ptr(dout), _ptr(lse), BH, T, A, Dv, float(scale), float(drop_p),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF, _ptr(dq), _ptr(dk), _ptr(dv),
-        _stream()))
+    d = _att_desc(BH, heads, T, A, Dv, scale, drop_p, seed, offset, bias, labels)
+    check(_lib.lib().adell_attention_bwd(ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                         _ptr(dout), _ptr(lse), _ptr(dq), _ptr(dk), _ptr(dv),
+                                         _stream()))
     return dq, dk, dv
 
 
@@ -1624,23 +1627,20 @@ def attention_bias_grad(q, k, v, bias, out, dout, lse, scale, nbias, drop_p=0.0,
         H = int(heads)
         if BH % H:
             raise AdellHipError(f"attention_bias_grad: {BH} sequences are not items of {H} heads")
-        B = BH // H
-        strides = (H * T * A, T * A, A) * 2 + (H * T * Dv, T * Dv, Dv) * 3
     else:
         B, H, T, A, Dv = (int(x) for x in dims)
+        BH = B * H
     nbias = int(nbias)
-    bias = None if bias is None else bias.contiguous()
     if bias is not None and bias.numel() != nbias * T * T:
         raise AdellHipError("attention_bias_grad: bias is not [nbias, T, T]")
-    labels, nlab = _att_labels(labels, T)
+    d = _att_desc(BH, H, T, A, Dv, scale, drop_p, seed, offset, bias, labels, strides)
+    d.nbias = nbias     # the number of result slices, with or without a bias
     dbias = torch.empty((nbias, T, T), device=q.device, dtype=torch.float32)
     nws = _lib.lib().adell_attention_bias_grad_workspace_floats(nbias, T)
     ws = _workspace(nws * 4, q.device) if nws else None
-    st = (ctypes.c_long * 15)(*[int(x) for x in strides])
-    check(_lib.lib().adell_attention_bias_grad(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nbias, _ptr(labels), nlab, _ptr(out), _ptr(dout),
-        _ptr(lse), B, H, T, A, Dv, st, float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-        int(offset) & 0xFFFFFFFF, _ptr(dbias), _ptr(ws), nws, _stream()))
+    check(_lib.lib().adell_attention_bias_grad(ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                               _ptr(dout), _ptr(lse), _ptr(dbias), _ptr(ws), nws,
+                                               _stream()))
     return dbias
 
 
@@ -2211,7 +2211,8 @@ def gather_nd(x, dims, axes, out=None):
 
 
 def attention_strided_ok(T, A, Dv):
-    return bool(_lib.lib().adell_attention_strided_ok(int(T), int(A), int(Dv)))
+    """Whether the strided forms run (T, A, Dv): the forward plan of aligned operands is an MFMA path."""
+    return attention_plan(T, A, Dv, "fwd", aligned=True).path in ("mfma_resident", "mfma_streamed")
 
 
 def attention_fwd_strided(q, k, v, out, strides, bias, B, H, T, A, Dv, scale, drop_p=0.0, seed=0,
@@ -2220,14 +2221,10 @@ def attention_fwd_strided(q, k, v, out, strides, bias, B, H, T, A, Dv, scale, dr
     into packed buffers are fine); strides: 12 element strides, (item, head, row) for each of
     q, k, v, out. Writes ``out``; returns lse [B*H, T]."""
     _require_cuda(q, k, v, out, bias)
-    bias = None if bias is None else bias.contiguous()
     lse = torch.empty((B * H, T), device=q.device, dtype=torch.float32)
-    nb = 0 if bias is None else bias.numel() // (T * T)
-    st = (ctypes.c_long * 12)(*[int(x) for x in strides])
-    labels, nlab = _att_labels(labels, T)
-    check(_lib.lib().adell_attention_fwd_strided_labels(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, B, H, T, A, Dv, st, float(scale), float(drop_p),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF, _ptr(out), _ptr(lse), _stream()))
+    d = _att_desc(B * H, H, T, A, Dv, scale, drop_p, seed, offset, bias, labels, strides)
+    check(_lib.lib().adell_attention_fwd(ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                         _ptr(lse), _stream()))
     return lse
 
 
@@ -2235,15 +2232,10 @@ def attention_bwd_strided(q, k, v, out, dout, lse, dq, dk, dv, strides, bias, B,
                           drop_p=0.0, seed=0, offset=0, labels=None):
     """strides: 24 element strides, (item, head, row) for q, k, v, out, dout, dq, dk, dv."""
     _require_cuda(q, k, v, out, dout, lse, dq, dk, dv, bias)
-    bias = None if bias is None else bias.contiguous()
-    nb = 0 if bias is None else bias.numel() // (T * T)
-    st = (ctypes.c_long * 24)(*[int(x) for x in strides])
-    labels, nlab = _att_labels(labels, T)
-    check(_lib.lib().adell_attention_bwd_strided_labels(
-        _ptr(q), _ptr(k), _ptr(v), _ptr(bias), nb, _ptr(labels), nlab, _ptr(out), _ptr(dout),
-        _ptr(lse), B, H, T, A, Dv,
-        st, float(scale), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF,
-        _ptr(dq), _ptr(dk), _ptr(dv), _stream()))
+    d = _att_desc(B * H, H, T, A, Dv, scale, drop_p, seed, offset, bias, labels, strides)
+    check(_lib.lib().adell_attention_bwd(ctypes.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                         _ptr(dout), _ptr(lse), _ptr(dq), _ptr(dk), _ptr(dv),
+                                         _stream()))
 
 
 def layernorm_rows_fwd(x, rows, C, inner, so, si, gamma, beta, eps):

@@ -634,21 +634,52 @@ int adell_layernorm_bwd(const float* x, const float* dy, const float* gamma,
 int adell_add_bcast(const float* a, const float* b, float* out, long n, long period,
                     void* stream);
 int adell_sum_bcast(const float* g, float* db, long n, long period, void* stream);
-/* softmax(q k^T * scale + bias) v per sequence: q,k [BH][T][A]; v,out [BH][T][Dv];
- * bias [nbias][T][T] or NULL (sequence bh uses bias[bh % nbias]); lse [BH][T]. Head dims A, Dv up
- * to 256, in the forward and the backward alike (adell_attention_plan below).
+/* softmax(q k^T * scale + bias) v per sequence, F.scaled_dot_product_attention as called at
+ * linear_blocks.py:407-414. adell_attention_desc holds everything of a call that is not one of its
+ * tensors; the three entries below take it and their tensors.
+ *
+ * Contiguous operands (strided = 0): q,k [BH][T][A]; v,out [BH][T][Dv]; lse [BH][T]. Head dims A, Dv
+ * up to 256, in the forward and the backward alike, any alignment (adell_attention_plan below).
+ * bias [nbias][T][T] or NULL: sequence bh uses bias[bh % nbias].
  * drop_p > 0 drops attention probabilities (dropout_p of the same call): the mask of entry
  * (bh, query, key) is a Philox function of (seed, rng_offset), regenerated by the backward.
- * F.scaled_dot_product_attention as called at linear_blocks.py:407-414. */
-int adell_attention_fwd(const float* q, const float* k, const float* v, const float* bias,
-                        int nbias, int BH, int T, int A, int Dv, float scale, float drop_p,
-                        unsigned long long seed, unsigned int rng_offset, float* out,
-                        float* lse, void* stream);
-int adell_attention_bwd(const float* q, const float* k, const float* v, const float* bias,
-                        int nbias, const float* out, const float* dout, const float* lse,
-                        int BH, int T, int A, int Dv, float scale, float drop_p,
-                        unsigned long long seed, unsigned int rng_offset, float* dq, float* dk,
-                        float* dv, void* stream);
+ *
+ * Region labels: labels int32 [nlab][T] or NULL. Item b (sequences b * H .. b * H + H - 1; contiguous
+ * calls take H for this alone) reads row b % nlab, and the score of query i and key j gains -100
+ * where labels[i] != labels[j], after scale and bias: the shifted-window mask of SWIN
+ * (vit.py:132-207) without its [n_windows][T][T] expansion. NULL labels run the same kernels with the
+ * term left out: the results without labels are the same bit for bit whatever nlab and H say.
+ *
+ * Strided operands (strided != 0): every operand is addressed by element strides, sequence
+ * bh = b * H + h (BH a multiple of H), stride[i] = (item b, head h, token row) of operand i in the
+ * order q, k, v, out, dout, dq, dk, dv -- the forward reads the first 4, the bias gradient the
+ * first 5, the backward all 8. Q / K / V may stay inside the packed [B][T][H][q | k | v] projection
+ * output of linear_blocks.py:372-385, O / dO are [B][T][H * Dv] token rows, dV can land inside the
+ * packed gradient: the slice / permute copies around F.scaled_dot_product_attention
+ * (linear_blocks.py:380-417) are not launches. In the forward and the backward the strides are
+ * multiples of 4 elements with rows at least the head width apart, the pointers 16-byte aligned, and
+ * the heads MFMA-shaped (A, Dv in {32, 64, 128}, T >= 16: the forward plan with aligned = 1 is an
+ * MFMA path); anything else is ADELL_E_BADARG before any launch, and the backward refuses before
+ * its first launch whichever of its two passes has no kernel. */
+typedef struct adell_attention_desc {
+  int32_t BH;           /* sequences */
+  int32_t H;            /* sequences per item: label rows, strided addressing */
+  int32_t T, A, Dv;     /* tokens, q / k head dim, v / out head dim */
+  float scale;          /* of q k^T */
+  float drop_p;         /* attention-probability dropout, 0 = off */
+  uint32_t rng_offset;  /* distinguishes the calls that share one seed */
+  uint64_t seed;        /* Philox key */
+  const float* bias;    /* [nbias][T][T] or NULL */
+  const int32_t* labels; /* [nlab][T] or NULL */
+  int32_t nbias, nlab;
+  int32_t strided;      /* 0: contiguous operands, `stride` is not read */
+  int64_t stride[8][3]; /* (item, head, row) of q, k, v, out, dout, dq, dk, dv */
+} adell_attention_desc;
+int adell_attention_fwd(const adell_attention_desc* d, const float* q, const float* k,
+                        const float* v, float* out, float* lse, void* stream);
+int adell_attention_bwd(const adell_attention_desc* d, const float* q, const float* k,
+                        const float* v, const float* out, const float* dout, const float* lse,
+                        float* dq, float* dk, float* dv, void* stream);
 /* Launch plan of one attention pass, host only (no launch, no tensor read, no device needed): what
  * adell_attention_fwd (pass 0) or the dQ (pass 1) and dK/dV (pass 2) kernels of adell_attention_bwd
  * would run under the current tuning switches, decided by the same function the launches call.
@@ -667,73 +698,25 @@ int adell_attention_bwd(const float* q, const float* k, const float* v, const fl
 #define ADELL_ATT_MFMA_STREAMED 2
 #define ADELL_ATT_REFUSED 3
 int adell_attention_plan(int pass, int T, int A, int Dv, int aligned, int* out);
-/* The same attention with every operand addressed by element strides: sequence bh = b * H + h,
- * `strides` holds (item b, head h, token row) triples in the order q, k, v, out (forward: 12
- * values) and q, k, v, out, dout, dq, dk, dv (backward: 24). Q / K / V may stay inside the packed
- * [B][T][H][q | k | v] projection output of linear_blocks.py:372-385, O / dO are [B][T][H * Dv]
- * token rows, dV can land inside the packed gradient: the slice / permute copies around
- * F.scaled_dot_product_attention (linear_blocks.py:380-417) are not launches. Strides are
- * multiples of 4 elements, pointers 16-byte aligned; MFMA-shaped heads only
- * (adell_attention_strided_ok: A, Dv in {32, 64, 128}, T >= 16), ADELL_E_BADARG otherwise. */
-int adell_attention_strided_ok(int T, int A, int Dv);
-int adell_attention_fwd_strided(const float* q, const float* k, const float* v, const float* bias,
-                                int nbias, int B, int H, int T, int A, int Dv, const long* strides,
-                                float scale, float drop_p, unsigned long long seed,
-                                unsigned int rng_offset, float* out, float* lse, void* stream);
-int adell_attention_bwd_strided(const float* q, const float* k, const float* v, const float* bias,
-                                int nbias, const float* out, const float* dout, const float* lse,
-                                int B, int H, int T, int A, int Dv, const long* strides,
-                                float scale, float drop_p, unsigned long long seed,
-                                unsigned int rng_offset, float* dq, float* dk, float* dv,
-                                void* stream);
-/* The four entries above with region labels: labels int32 [nlab][T] or NULL. Item b (sequences
- * b * H .. b * H + H - 1; the contiguous entries take H for this alone) reads row b % nlab, and the
- * score of query i and key j gains -100 where labels[i] != labels[j], after scale and bias: the
- * shifted-window mask of SWIN (vit.py:132-207) without its [n_windows][T][T] expansion. NULL labels
- * are the entries above, bit for bit (they call these). */
-int adell_attention_fwd_labels(const float* q, const float* k, const float* v, const float* bias,
-                               int nbias, const int* labels, int nlab, int H, int BH, int T, int A,
-                               int Dv, float scale, float drop_p, unsigned long long seed,
-                               unsigned int rng_offset, float* out, float* lse, void* stream);
-int adell_attention_bwd_labels(const float* q, const float* k, const float* v, const float* bias,
-                               int nbias, const int* labels, int nlab, int H, const float* out,
-                               const float* dout, const float* lse, int BH, int T, int A, int Dv,
-                               float scale, float drop_p, unsigned long long seed,
-                               unsigned int rng_offset, float* dq, float* dk, float* dv,
-                               void* stream);
-int adell_attention_fwd_strided_labels(const float* q, const float* k, const float* v,
-                                       const float* bias, int nbias, const int* labels, int nlab,
-                                       int B, int H, int T, int A, int Dv, const long* strides,
-                                       float scale, float drop_p, unsigned long long seed,
-                                       unsigned int rng_offset, float* out, float* lse,
-                                       void* stream);
-int adell_attention_bwd_strided_labels(const float* q, const float* k, const float* v,
-                                       const float* bias, int nbias, const int* labels, int nlab,
-                                       const float* out, const float* dout, const float* lse, int B,
-                                       int H, int T, int A, int Dv, const long* strides, float scale,
-                                       float drop_p, unsigned long long seed,
-                                       unsigned int rng_offset, float* dq, float* dk, float* dv,
-                                       void* stream);
 /* Gradient of the additive bias: dbias[j] = sum over sequences bh % nbias == j of
  * dS[bh] = P o (keep dP / (1 - drop_p) - rowsum(dO o O)), [nbias][T][T], no `scale` factor (the bias
- * is added after it). nbias in [1, B * H] is the number of result slices whether or not `bias` is
- * NULL: H gives the gradient of a per-head bias, B * H the plain dS. Scores, labels and the dropout
- * mask are rebuilt as the backward kernels build them. `strides`: 15 element strides, (item, head,
- * row) for q, k, v, out, dout; head dims 32 / 64 / 128 at T >= 16 with 16-byte aligned pointers and
- * strides that are multiples of 4 run on the MFMA, everything else up to head dims of 256 on the
- * vector ALU. No atomics: the sequences of a slice are summed in ascending order within a chunk, the
- * chunks in order by a second pass through `workspace`, whose size
+ * is added after it). d->nbias in [1, BH] is the number of result slices whether or not d->bias is
+ * NULL: H gives the gradient of a per-head bias, BH the plain dS. Scores, labels and the dropout
+ * mask are rebuilt as the backward kernels build them. Operands as in adell_attention_bwd, but
+ * strided ones need only rows at least the head width apart and non-negative strides: head dims
+ * 32 / 64 / 128 at T >= 16 with 16-byte aligned pointers and strides that are multiples of 4 run on
+ * the MFMA, everything else up to head dims of 256 on the vector ALU (the form is the one the dQ pass
+ * of the same operands plans). No atomics: the sequences of a slice are summed in ascending order
+ * within a chunk, the chunks in order by a second pass through `workspace`, whose size
  * (adell_attention_bias_grad_workspace_floats: at most 16 partial results, and at most 512 tiles of
- * 128 x 128 floats) does not depend on the number of sequences. Nothing of B * H * T * T elements
+ * 128 x 128 floats) does not depend on the number of sequences. Nothing of BH * T * T elements
  * is ever written. The slices are the y dimension of the grid: nbias above 65535 is refused with
- * ADELL_E_BADARG (the attention entries above put B * H there and fail at the launch beyond it). */
+ * ADELL_E_BADARG (the attention entries above put BH there and fail at the launch beyond it). */
 long adell_attention_bias_grad_workspace_floats(int nbias, int T);
-int adell_attention_bias_grad(const float* q, const float* k, const float* v, const float* bias,
-                              int nbias, const int* labels, int nlab, const float* out,
-                              const float* dout, const float* lse, int B, int H, int T, int A, int Dv,
-                              const long* strides, float scale, float drop_p,
-                              unsigned long long seed, unsigned int rng_offset, float* dbias,
-                              float* workspace, long workspace_floats, void* stream);
+int adell_attention_bias_grad(const adell_attention_desc* d, const float* q, const float* k,
+                              const float* v, const float* out, const float* dout,
+                              const float* lse, float* dbias, float* workspace,
+                              long workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------
  * Data movement for the U-Net++ dense links (standard_blocks.py:365-371):
