@@ -184,7 +184,12 @@ def _packed(w, mode):
     """Repacked copy of a weight (see _tensor_pack_cache; the f16x3 conv operands of modes 0 / 1
     live in _PACK_REG instead, for the one-launch repack)."""
     split = CONV_PRECISION == "f16x3" and mode in (0, 1, 2, 3)
-    if split and mode in (0, 1) and w.dim() == 5 and w.is_contiguous():
+    # the value of a parametrised weight is a fresh tensor on every access: registered under its id it
+    # would leave a dead entry, and the packs it holds, behind per step -- its packs live on the tensor
+    # (a view of it, Conv2d's unsqueeze, under no_grad: its base carries the mark)
+    transient = w.grad_fn is not None or getattr(w, "_adell_transient", False) \
+        or (w._base is not None and getattr(w._base, "_adell_transient", False))
+    if split and mode in (0, 1) and w.dim() == 5 and w.is_contiguous() and not transient:
         key = (id(w), mode)
         ent = _PACK_REG.get(key)
         if ent is not None and ent[0]() is not w:
@@ -3712,3 +3717,67 @@ def pseudo_label_ce(pred, proba, threshold, weight=None, label_smoothing=0.0, re
         weight = weight.detach().to(device=pred.device, dtype=torch.float32)
     return _PseudoLabelCEFn.apply(pred, proba.detach().float(), float(threshold), weight,
                                   float(label_smoothing), reduction == "mean")
+
+
+# ---- spectral normalisation (modules.layers.spectral_norm._SpectralNorm) -----------------------------------
+def spectral_norm_route(h, w):
+    """The route of ``spectral_normalize`` for an ``h x w`` matrix: "block" (one workgroup keeps the
+    matrix, both vectors and the fp64 products in LDS: one launch each way whatever n is), "grid" (rows
+    over workgroups, the last ticket folds: 2 n + 1 launches forward, 2 backward; up to 32768 rows and
+    columns) or "composed" (torch operators) beyond."""
+    return ops.spectral_norm_route(h, w)
+
+
+class _SpectralNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, u, v, n_iter, eps, dim):
+        out, sigma, u_used, v_used = ops.spectral_norm_fwd(weight, u, v, n_iter, eps, dim)
+        # the output itself, sigma on the device and the vectors THIS access used: a later access
+        # advances the buffers without changing this one's gradient
+        ctx.save_for_backward(out, sigma, u_used, v_used)
+        ctx.dim = dim
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        out, sigma, u_used, v_used = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        return (ops.spectral_norm_bwd(g, out, u_used, v_used, sigma, ctx.dim),) + (None,) * 5
+
+
+def spectral_normalize(weight, u, v, n_power_iterations=1, eps=1e-12, dim=0, training=True):
+    """``W / sigma`` of torch's ``_SpectralNorm.forward``: when ``training``, ``n_power_iterations``
+    times ``u <- normalize(W v, eps)``, ``v <- normalize(W^T u, eps)`` written IN PLACE into the given
+    buffers (same storage), then ``sigma = u^T W v`` with ``u`` and ``v`` as constants. The matrix is
+    the weight with ``dim`` in front, read in place; the result has the weight's layout. Backward:
+    ``dL/dW = (G - <G, W_sn> u v^T) / sigma`` with the vectors of THIS access. A zero weight gives NaN,
+    as torch does. Routes: ``spectral_norm_route``; CPU tensors, other dtypes and "composed" shapes
+    run torch's own operators."""
+    dim = dim if dim >= 0 else dim + weight.dim()
+    outer, h, inner = ops.spectral_norm_matrix(weight.shape, dim)
+    fused = weight.is_cuda and weight.dtype == torch.float32 and u.dtype == torch.float32 \
+        and spectral_norm_route(h, outer * inner) != "composed"
+    if not fused:
+        mat = weight if dim == 0 else weight.permute(dim, *(d for d in range(weight.dim()) if d != dim))
+        mat = mat.flatten(1)
+        # on the device the products are summed in fp64 here too (and rounded where torch stores or
+        # returns them); on the CPU this is torch's own arithmetic, bit for bit
+        wide = weight.is_cuda and weight.dtype == torch.float32
+        up = (lambda t: t.double()) if wide else (lambda t: t)
+        if training:
+            with torch.no_grad():
+                big = up(mat)
+                for _ in range(int(n_power_iterations)):
+                    u.copy_(torch.nn.functional.normalize(torch.mv(big, up(v)), dim=0, eps=eps))
+                    v.copy_(torch.nn.functional.normalize(torch.mv(big.H, up(u)), dim=0, eps=eps))
+        uc, vc = u.clone(), v.clone()
+        sigma = torch.vdot(up(uc), torch.mv(up(mat), up(vc)))
+        return (weight / sigma).to(weight.dtype)
+    n_iter = int(n_power_iterations) if training else 0
+    if training and n_iter < 1:
+        raise ValueError(f"Expected n_power_iterations to be positive, but got "
+                         f"n_power_iterations={n_power_iterations}")
+    return _SpectralNormFn.apply(weight.contiguous(), u, v, n_iter, float(eps), int(dim))

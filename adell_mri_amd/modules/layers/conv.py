@@ -21,6 +21,24 @@ def _resolve_padding(padding, kernel_size, stride, dilation):
     return tuple(padding)
 
 
+def weight_meta(module):
+    """The tensor that carries the shape, dtype and ``requires_grad`` of ``module.weight`` WITHOUT
+    evaluating a parametrization of it (a spectral-norm read runs a power iteration and advances its
+    buffers): the ``original`` parameter of a parametrised weight, else the weight itself."""
+    par = module._modules.get("parametrizations")
+    if par is not None and "weight" in par:
+        return par["weight"].original
+    return module.weight
+
+
+def is_exactly(module, cls):
+    """``type(module) is cls``, looking through the subclass ``torch.nn.utils.parametrize`` puts in
+    front of a parametrised module's class (same ``forward``, same signature)."""
+    t = type(module)
+    return t is cls or (t.__bases__ == (cls,) and t.__name__ == "Parametrized" + cls.__name__
+                        and "parametrizations" in module._modules)
+
+
 class Conv3d(torch.nn.Conv3d):
     def _dilated(self):
         """kernel 3, stride 1, padding "same", dilation > 1 (the atrous pyramid's convs)."""
@@ -47,7 +65,7 @@ class Conv3d(torch.nn.Conv3d):
                 or tuple(self.kernel_size) != (3, 3, 3) or tuple(self.stride) != (1, 1, 1)):
             return None
         pad = _resolve_padding(self.padding, self.kernel_size, self.stride, self.dilation)
-        return (self.weight, (1, 1, 1), tuple(pad))
+        return (weight_meta(self), (1, 1, 1), tuple(pad))
 
     def forward(self, X, X_cat=None, residual=None, carry_in=None, carry_out=None,
                 carry_x0=None, carry_cat=None):

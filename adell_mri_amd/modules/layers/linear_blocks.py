@@ -109,9 +109,13 @@ class MLP(torch.nn.Module):
                 and hasattr(mods[1], "pure_activation")):
             # Linear -> activation -> Linear: the activation and its backward inside GEMM epilogues
             spec = mods[1].pure_activation()
-            if spec is not None and HF.mlp_ok(X, mods[0].weight, mods[2].weight):
-                return HF.mlp(X, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias,
-                              act=spec[0], act_p=spec[1], residual=residual)
+            if spec is not None and not HF.FLAGS["no_mlp_fuse"]:
+                w0, w2 = mods[0].weight, mods[2].weight   # ONE read each (a parametrised weight)
+                if HF.mlp_ok(X, w0, w2):
+                    return HF.mlp(X, w0, mods[0].bias, w2, mods[2].bias, act=spec[0], act_p=spec[1],
+                                  residual=residual)
+                h = mods[1](HF.linear(X, w0, mods[0].bias))
+                return HF.linear(h, w2, mods[2].bias, residual=residual)
         for mod in mods[:-1]:
             X = mod(X)
         return mods[-1](X, residual=residual) if residual is not None else mods[-1](X)

@@ -10,7 +10,7 @@ import torch
 from ... import functional as HF
 from ... import ops
 from .adn_fn import ActDropNorm
-from .conv import Conv2d, Conv3d
+from .conv import Conv2d, Conv3d, is_exactly, weight_meta
 from .linear_blocks import LayerNorm as RowLayerNorm
 from .linear_blocks import Linear
 
@@ -60,7 +60,7 @@ class ResidualBlock3d(torch.nn.Module):
         for i, mod in enumerate(mods[1:-1], 1):
             # an ADN output read by the next conv only (functional.single_use; it may be written
             # as split rows: functional.expect_rows)
-            only_reader = isinstance(mod, ActDropNorm) and type(mods[i + 1]) is self._conv and h.dim() == 5
+            only_reader = isinstance(mod, ActDropNorm) and is_exactly(mods[i + 1], self._conv) and h.dim() == 5
             if only_reader and self._conv is Conv3d:
                 HF.expect_rows(mod, mods[i + 1])
             h = mod(h)
@@ -209,17 +209,19 @@ class ConvNeXtBlock3d(torch.nn.Module):
         else:
             w2, b2 = HF.rowscale(self.gamma, self.pwconv2.weight, self.pwconv2.bias)
         res = inp.permute(0, 2, 3, 4, 1)
-        if HF.mlp_ok(rows, self.pwconv1.weight, w2):
+        # ONE read of pwconv1's weight per forward: a parametrised weight is evaluated per access
+        w1 = None if HF.FLAGS["no_mlp_fuse"] else self.pwconv1.weight
+        if w1 is not None and HF.mlp_ok(rows, w1, w2):
             # GELU inside the epilogues of pwconv1 (forward) and of the dY W2 GEMM (backward): no
             # element-wise pass over the 4 C-wide hidden layer
-            rows = HF.mlp(rows, self.pwconv1.weight, self.pwconv1.bias, w2, b2, act="gelu",
-                          residual=res)
+            rows = HF.mlp(rows, w1, self.pwconv1.bias, w2, b2, act="gelu", residual=res)
         else:
-            rows = HF.linear(HF.elementwise(self.pwconv1(rows), act="gelu"), w2, b2, residual=res)
+            hid = self.pwconv1(rows) if w1 is None else HF.linear(rows, w1, self.pwconv1.bias)
+            rows = HF.linear(HF.elementwise(hid, act="gelu"), w2, b2, residual=res)
         out = rows.permute(0, 4, 1, 2, 3)
         if self.out_layer is not None:
             proj = self.out_layer[0]
-            y = proj(out.squeeze(2)).unsqueeze(2) if proj.weight.dim() == 4 else proj(out)
+            y = proj(out.squeeze(2)).unsqueeze(2) if weight_meta(proj).dim() == 4 else proj(out)
             out = HF.norm_drop_act(y, act="gelu")
         return out
 

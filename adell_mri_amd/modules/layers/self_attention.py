@@ -19,7 +19,8 @@ def _like(Y, X):
 def _spatial_gate(op, X5):
     """sigmoid(pointwise conv C -> 1) of a [N, C, D, H, W] tensor: [N, 1, D, H, W]."""
     conv = op[0]
-    w = conv.weight if conv.weight.dim() == 5 else conv.weight.unsqueeze(2)
+    w = conv.weight
+    w = w if w.dim() == 5 else w.unsqueeze(2)
     return HF.norm_drop_act(HF.conv3d(X5, w, conv.bias, 1, 0, want_stats=False), act="sigmoid")
 
 

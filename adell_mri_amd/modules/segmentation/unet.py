@@ -24,7 +24,7 @@ from ... import ops
 from ..._lib import AdellHipError
 from ..layers.adn_fn import ActDropNorm, get_adn_fn, norm_fn_dict
 from ..layers.conv import (Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d, MaxPool2d,
-                           MaxPool3d, Upsample)
+                           MaxPool3d, Upsample, is_exactly)
 from ..layers.linear_blocks import Linear
 from ..layers.regularization import UOut
 from ..layers.res_blocks import (DepthwiseConv2dStrided, DepthwiseConv3dStrided, ResidualBlock2d,
@@ -56,7 +56,7 @@ def _run_rest(mods, h):
     kernel take over half of the site's backward."""
     for i, mod in enumerate(mods):
         only_reader = (isinstance(mod, ActDropNorm) and i + 1 < len(mods)
-                       and type(mods[i + 1]) is Conv3d)
+                       and is_exactly(mods[i + 1], Conv3d))
         if only_reader:
             HF.expect_rows(mod, mods[i + 1])     # ... which may take its input as split rows
         h = mod(h)
@@ -80,11 +80,11 @@ def _first_conv(module):
     """The Conv3d that reads the input of ``module`` first (through nested Sequentials), or None."""
     while isinstance(module, torch.nn.Sequential) and len(module) > 0:
         module = module[0]
-    return module if type(module) is Conv3d else None
+    return module if is_exactly(module, Conv3d) else None
 
 
 def _takes_carry(module):
-    return type(module) is Conv3d and module.takes_carry()
+    return is_exactly(module, Conv3d) and module.takes_carry()
 
 
 def _head_with_carry(module, X, **carries):

@@ -5266,3 +5266,76 @@ def pseudo_label_ce_bwd(pred, proba, threshold, weight, label_smoothing, mean, g
                                                float(threshold), float(label_smoothing),
                                                int(bool(mean)), _ptr(dpred), _stream()))
     return dpred
+
+
+# ---- spectral normalisation of a weight (csrc/spectral_norm.hip) -------------------------------------------
+SN_ROUTES = {0: "block", 1: "grid", 2: "composed"}   # ADELL_SN_BLOCK / _GRID / _COMPOSED
+SN_MAX_DIM = 32768                                    # ADELL_SN_MAX_DIM
+
+
+def spectral_norm_route(h, w):
+    """The route of the spectral normalisation of an ``h x w`` matrix by the library's own host
+    function (no device needed): "block", "grid" or "composed"."""
+    rc = _lib.lib().adell_spectral_norm_route(int(h), int(w))
+    check(min(rc, 0))
+    return SN_ROUTES[rc]
+
+
+def spectral_norm_matrix(shape, dim):
+    """(outer, h, inner) of a weight of this shape read as the matrix ``[h, outer * inner]`` with
+    ``dim`` in front (torch's ``_reshape_weight_to_matrix`` without the permuted copy)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 2 or not 0 <= dim < len(shape) or 0 in shape:
+        raise ValueError(f"spectral_normalize: a non-empty weight of rank >= 2 and 0 <= dim < rank "
+                         f"expected, got shape {shape}, dim {dim}")
+    outer = inner = 1
+    for s in shape[:dim]:
+        outer *= s
+    for s in shape[dim + 1:]:
+        inner *= s
+    return outer, shape[dim], inner
+
+
+def _sn_workspace(h, w, device):
+    words = _lib.lib().adell_spectral_norm_workspace_doubles(h, w)
+    check(min(words, 0))
+    return torch.empty(words, device=device, dtype=torch.float64), words
+
+
+def spectral_norm_fwd(weight, u, v, n_iter, eps, dim):
+    """(W_sn, sigma [1] fp64, u_used, v_used). ``n_iter`` power iterations update ``u`` [h] and ``v``
+    [w] IN PLACE (0: eval mode, both only read); ``u_used`` / ``v_used`` are the copies sigma was
+    taken with. Block route: one launch; grid route: 2 n_iter + 1 (2 in eval mode)."""
+    what = "spectral_normalize"
+    outer, h, inner = spectral_norm_matrix(weight.shape, dim)
+    w = outer * inner
+    _ens_rows(what, weight, u, v)
+    if weight.dtype != torch.float32 or u.dtype != torch.float32 or v.dtype != torch.float32 \
+            or u.numel() != h or v.numel() != w:
+        raise ValueError(f"{what}: fp32 weight, u [{h}] and v [{w}] expected, got "
+                         f"{tuple(u.shape)} {u.dtype} and {tuple(v.shape)} {v.dtype}")
+    dev = weight.device
+    ws, words = _sn_workspace(h, w, dev)
+    out = torch.empty_like(weight)
+    u_used, v_used = torch.empty_like(u), torch.empty_like(v)
+    sigma = torch.empty(1, device=dev, dtype=torch.float64)
+    check(_lib.lib().adell_spectral_norm_fwd(_ptr(weight), _ptr(u), _ptr(v), outer, h, inner,
+                                             int(n_iter), float(eps), _ptr(ws), words, _ptr(u_used),
+                                             _ptr(v_used), _ptr(sigma), _ptr(out), _stream()))
+    return out, sigma, u_used, v_used
+
+
+def spectral_norm_bwd(g, w_sn, u, v, sigma, dim):
+    """dW = (g - <g, W_sn> u v^T) / sigma in the weight's layout; one launch (block) or two (grid)."""
+    what = "spectral_normalize backward"
+    outer, h, inner = spectral_norm_matrix(w_sn.shape, dim)
+    _ens_rows(what, g, w_sn, u, v)
+    if tuple(g.shape) != tuple(w_sn.shape) or sigma.dtype != torch.float64 or not sigma.is_cuda \
+            or sigma.numel() != 1 or u.numel() != h or v.numel() != outer * inner:
+        raise ValueError(f"{what}: an fp32 gradient of the weight's shape and the forward's u, v and "
+                         f"sigma expected")
+    ws, words = _sn_workspace(h, outer * inner, g.device)
+    dw = torch.empty_like(w_sn)
+    check(_lib.lib().adell_spectral_norm_bwd(_ptr(g), _ptr(w_sn), _ptr(u), _ptr(v), _ptr(sigma), outer, h,
+                                             inner, _ptr(ws), words, _ptr(dw), _stream()))
+    return dw

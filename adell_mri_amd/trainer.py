@@ -42,11 +42,19 @@ class StepRunner:
       that already holds ``torch.nn.SyncBatchNorm`` modules (torch's converter) is synchronised either
       way; its batch-norm group is created here.
 
+    * ``spectral_norm`` (None: off): an int ``n`` stands for ``utils.pl_callbacks.SpectralNorm(
+      n_power_iterations=n)`` (the entry points' ``--spectral_norm_power_iterations``), a
+      ``SpectralNorm`` instance is used as given. Its ``setup(None, module, "fit")`` runs BEFORE
+      ``configure_optimizers()``, so that the ``parametrizations.<name>.original`` parameters are the
+      ones the optimiser's flat buffers hold; an explicit ``optimizer`` that still holds a replaced
+      plain weight is refused.
+
     ``step_idx`` counts micro-batches (the ``batch_idx`` of ``training_step``), ``optimizer_steps``
     the optimiser steps, ``last_grad_norm`` is the device tensor of the last clip."""
 
     def __init__(self, module, optimizer=None, sync=None, gradient_clip_val=None,
-                 gradient_clip_algorithm="norm", accumulate_grad_batches=1, sync_batchnorm=False):
+                 gradient_clip_algorithm="norm", accumulate_grad_batches=1, sync_batchnorm=False,
+                 spectral_norm=None):
         if gradient_clip_val is not None and float(gradient_clip_val) < 0:
             raise ValueError(f"gradient_clip_val should be >= 0, got {gradient_clip_val}")
         if gradient_clip_algorithm == "value":
@@ -70,6 +78,7 @@ class StepRunner:
         elif _has_sync_bn(module):
             sync_bn_group()      # collective: the dedicated batch-norm group, on every rank here
         self.sync_batchnorm = sync_batchnorm
+        self.spectral_norm = _apply_spectral_norm(module, spectral_norm, optimizer)
         self.module = module
         if optimizer is None:
             # a dict with "optimizer", or the bare optimiser (ViTMaskedAutoEncoderPL without warm-up)
@@ -282,11 +291,35 @@ class StepRunner:
         return self._graph_loss
 
 
+def _apply_spectral_norm(module, spectral_norm, optimizer):
+    """The ``SpectralNorm`` callback of a ``spectral_norm`` argument (None: nothing), set up on
+    ``module``; raises for an optimiser built over the plain weights it has replaced."""
+    if spectral_norm is None:
+        return None
+    from .utils.pl_callbacks import SpectralNorm
+
+    if isinstance(spectral_norm, bool) or not isinstance(spectral_norm, (int, SpectralNorm)):
+        raise TypeError(f"spectral_norm must be None, a number of power iterations or a SpectralNorm "
+                        f"callback, got {spectral_norm!r}")
+    callback = spectral_norm if isinstance(spectral_norm, SpectralNorm) \
+        else SpectralNorm(n_power_iterations=spectral_norm)
+    callback.setup(None, module, "fit")
+    if optimizer is not None:
+        live = {id(p) for p in module.parameters()}
+        stale = [p for g in optimizer.param_groups for p in g["params"] if id(p) not in live]
+        if stale:
+            raise ValueError(f"StepRunner(spectral_norm=...): the optimiser holds {len(stale)} parameters "
+                             "that are no longer the module's: spectral normalisation replaced the "
+                             "plain weights by parametrizations.<name>.original -- build the optimiser "
+                             "after the callback's setup, or leave optimizer=None")
+    return callback
+
+
 def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulate_grad_batches=1,
-              sync_batchnorm=False):
+              sync_batchnorm=False, spectral_norm=None):
     runner = StepRunner(module, optimizer, gradient_clip_val=gradient_clip_val,
                         accumulate_grad_batches=accumulate_grad_batches,
-                        sync_batchnorm=sync_batchnorm)
+                        sync_batchnorm=sync_batchnorm, spectral_norm=spectral_norm)
     module.train()
     losses = [runner.train_step(b).detach() for b in batches]
     runner.flush()

@@ -1939,6 +1939,38 @@ int adell_pseudo_label_ce_bwd(const float* pred, const float* proba, const float
                               int B, int K, long V, float threshold, float label_smoothing, int mean,
                               float* dpred, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Spectral normalisation of a weight (csrc/spectral_norm.hip; torch's _SpectralNorm parametrization,
+ * which the reference's utils/pl_callbacks.SpectralNorm applies). fp32 data, fixed-order fp64 sums, no
+ * float atomics: bit-reproducible. The weight is read in place as the matrix [h][w], w = outer * inner,
+ * element (r, c = o * inner + t) at (o * h + r) * inner + t: dim = 0 is outer = 1, a transposed-conv
+ * weight [Cin][Cout][k...] is outer = Cin, h = Cout, inner = prod(k).
+ * ---------------------------------------------------------------------- */
+#define ADELL_SN_BLOCK 0
+#define ADELL_SN_GRID 1
+#define ADELL_SN_COMPOSED 2
+#define ADELL_SN_MAX_DIM 32768 /* rows and columns of the grid route */
+/* Host only: ADELL_SN_BLOCK when one workgroup keeps the matrix, both vectors and the fp64 products in
+ * LDS (4 (h w + h + w) + 8 (max(h, w) + 1040) <= 158 KiB), ADELL_SN_GRID up to ADELL_SN_MAX_DIM rows and
+ * columns, ADELL_SN_COMPOSED beyond (the caller composes torch operators), or ADELL_E_BADARG. */
+int adell_spectral_norm_route(long h, long w);
+/* Doubles of workspace of both directions (the ticket counter's 16 bytes first), or ADELL_E_BADARG. */
+long adell_spectral_norm_workspace_doubles(long h, long w);
+/* n_iter times u <- normalize(W v), v <- normalize(W^T u) IN PLACE in u [h] and v [w] (normalize(x) =
+ * x / max(|x|, eps), rounded to fp32), then sigma[0] = u^T W v (fp64; with n_iter > 0 taken as
+ * (W^T u) . v of the last half-iteration), out = W / sigma in the weight's layout, and u_used / v_used =
+ * the vectors sigma was taken with. n_iter = 0 (eval mode): u and v are only read. A zero weight gives
+ * sigma = 0 and NaN in out. Block route: one launch; grid route: 2 n_iter + 1 launches (2 for n_iter = 0)
+ * and the counter's memset. */
+int adell_spectral_norm_fwd(const float* W, float* u, float* v, int outer, int h, int inner, int n_iter,
+                            double eps, double* ws, long ws_doubles, float* u_used, float* v_used,
+                            double* sigma, float* out, void* stream);
+/* dW = (G - <G, Wsn> u v^T) / sigma in the weight's layout, u and v constants (the forward's u_used /
+ * v_used). Block route: one launch; grid route: two and the counter's memset. */
+int adell_spectral_norm_bwd(const float* G, const float* Wsn, const float* u, const float* v,
+                            const double* sigma, int outer, int h, int inner, double* ws, long ws_doubles,
+                            float* dW, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
