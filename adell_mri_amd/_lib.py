@@ -423,6 +423,11 @@ SIGNATURES = {
     "adell_spectral_norm_workspace_doubles": (_l, [_l, _l]),
     "adell_spectral_norm_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _l, _vp, _vp, _vp, _vp, _vp]),
     "adell_spectral_norm_bwd": (_i, [_vp] * 5 + [_i, _i, _i, _vp, _l, _vp, _vp]),
+    "adell_ewc_chunk": (_i, []),
+    "adell_ewc_workspace_doubles": (_l, [_i, _i]),
+    "adell_ewc_partials": (_i, [_vp, _i, _d, _vp, _vp]),
+    "adell_ewc_finalize": (_i, [_vp, _i, _i, _d, _vp, _vp, _vp, _vp]),
+    "adell_ewc_grad": (_i, [_vp, _i, _d, _vp, _f, _vp, _i, _vp, _vp]),
     "adell_gemm_plan": (_i, [_i] * 6 + [_l, _l, _i, _i, _vp]),
     "adell_gemm_f16x3_workspace_floats": (_l, [_i, _i, _i]),
     "adell_gemm_f16x3": (_i, [_i, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp, _l, _vp, _vp, _l, _vp, _vp,

@@ -1952,6 +1952,63 @@ def grad_scale_by(g, coef):
     check(_lib.lib().adell_grad_scale_by(_ptr(g), g.numel(), _ptr(coef), _stream()))
 
 
+# ---- elastic-weight-consolidation penalty (csrc/ewc.hip) ----------------------------------------
+EWC_COLS = 5     # longs per chunk row: parameter, anchor, count, tensor index, destination offset
+
+
+def ewc_chunk():
+    """Elements per chunk row of the penalty's tables (the library's compile-time constant)."""
+    return int(_lib.lib().adell_ewc_chunk())
+
+
+def ewc_workspace(chunks, tensors, device):
+    """The fp64 workspace of ``ewc_partials`` / ``ewc_finalize``: allocate once per table."""
+    n = int(_lib.lib().adell_ewc_workspace_doubles(int(chunks), int(tensors)))
+    if n <= 0:
+        raise _lib.AdellHipError(f"ewc_workspace: bad table extents ({chunks} chunks, {tensors} tensors)")
+    return torch.empty(n, dtype=torch.float64, device=device)
+
+
+def _ewc_table(table, chunks, what):
+    if not table.is_cuda or table.dtype != torch.int64 or table.numel() < int(chunks) * EWC_COLS:
+        raise _lib.AdellHipError(f"{what}: the table must be an int64 CUDA tensor of {EWC_COLS} "
+                                 "columns per chunk")
+
+
+def ewc_partials(table, chunks, p, workspace):
+    """workspace[r] = sum |param - anchor|^p over chunk row ``r`` of ``table``."""
+    _ewc_table(table, chunks, "ewc_partials")
+    if workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < chunks:
+        raise _lib.AdellHipError("ewc_partials: the workspace is too small (ewc_workspace)")
+    check(_lib.lib().adell_ewc_partials(_ptr(table), int(chunks), float(p), _ptr(workspace), _stream()))
+
+
+def ewc_finalize(tensor_first, tensors, chunks, p, workspace, norms, total):
+    """norms[k] = ||param_k - anchor_k||_p (fp32), total[0] = their sum."""
+    _require_cuda(norms, total)
+    if not tensor_first.is_cuda or tensor_first.dtype != torch.int64 or tensor_first.numel() < tensors + 1:
+        raise _lib.AdellHipError("ewc_finalize: tensor_first must be an int64 CUDA tensor of tensors + 1")
+    if workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < chunks + tensors:
+        raise _lib.AdellHipError("ewc_finalize: the workspace is too small (ewc_workspace)")
+    if norms.numel() < tensors or total.numel() < 1:
+        raise _lib.AdellHipError("ewc_finalize: norms needs one element per tensor, total one")
+    check(_lib.lib().adell_ewc_finalize(_ptr(tensor_first), int(tensors), int(chunks), float(p),
+                                        _ptr(workspace), _ptr(norms), _ptr(total), _stream()))
+
+
+def ewc_grad(table, chunks, p, norms, c, c_dev, add, base):
+    """The penalty's gradient times ``c * c_dev[0]`` (``c_dev``: a device scalar or None), written to
+    (``add`` false) or added into ``base`` at every chunk's destination offset. The table lives on
+    the device: its pointers, counts and offsets are the caller's word (whoever builds a table keeps
+    ``offset + count <= base.numel()``), they cannot be checked here without a host read."""
+    _ewc_table(table, chunks, "ewc_grad")
+    _require_cuda(norms, c_dev, base)
+    if c_dev is not None and c_dev.numel() < 1:
+        raise _lib.AdellHipError("ewc_grad: empty device scalar")
+    check(_lib.lib().adell_ewc_grad(_ptr(table), int(chunks), float(p), _ptr(norms), float(c),
+                                    _ptr(c_dev), int(bool(add)), _ptr(base), _stream()))
+
+
 # ---- segmentation metrics (csrc/seg_metrics.hip) ------------------------------------------------
 SEG_METRIC_KINDS = {"iou": 0, "precision": 1, "fbeta": 2, "dice": 3}
 SEG_MAX_CLASSES = 32

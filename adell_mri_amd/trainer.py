@@ -49,12 +49,28 @@ class StepRunner:
       ones the optimiser's flat buffers hold; an explicit ``optimizer`` that still holds a replaced
       plain weight is refused.
 
+    * ``ewc`` (None: off): a ``modules.continuous_learning.ElasticWeightConsolidation`` over
+      ``module``; every optimiser step applies ``ewc_weight * d penalty`` on top of the task gradient
+      without autograd seeing the term. After the gradient exchange and before clipping the penalty is
+      evaluated and its gradient ADDED into the optimiser's flat gradient slots, scaled by
+      ``ewc_weight / grad_scale`` as in force at that moment (one launch per parameter group), so the
+      amount applied does not depend on the world size or on ``accumulate_grad_batches``. For full
+      accumulation windows that is what ``loss + ewc_weight * ewc(module)`` in every micro-batch gives
+      (the parameters do not move inside a window); ``flush()`` of a partial window applies the same
+      ``ewc_weight * d penalty``, where the loss route would apply it scaled by the window's share.
+      Clipping sees task plus penalty gradient. ``train_step`` returns
+      ``loss + ewc_weight * penalty`` for the micro-batch that steps (a device-side add; the other
+      micro-batches of a window return the plain loss) and ``last_ewc_penalty`` holds the ``[1]``
+      penalty.
+
     ``step_idx`` counts micro-batches (the ``batch_idx`` of ``training_step``), ``optimizer_steps``
-    the optimiser steps, ``last_grad_norm`` is the device tensor of the last clip."""
+    the optimiser steps, ``last_grad_norm`` is the device tensor of the last clip. ``current_epoch``,
+    ``callback_metrics`` and ``should_stop`` are plain attributes kept by whoever owns the epoch loop:
+    with them a StepRunner is the ``trainer`` of ``MultiPhaseTraining.on_validation_epoch_end``."""
 
     def __init__(self, module, optimizer=None, sync=None, gradient_clip_val=None,
                  gradient_clip_algorithm="norm", accumulate_grad_batches=1, sync_batchnorm=False,
-                 spectral_norm=None):
+                 spectral_norm=None, ewc=None, ewc_weight=1.0):
         if gradient_clip_val is not None and float(gradient_clip_val) < 0:
             raise ValueError(f"gradient_clip_val should be >= 0, got {gradient_clip_val}")
         if gradient_clip_algorithm == "value":
@@ -90,11 +106,17 @@ class StepRunner:
                 hasattr(optimizer, "clip_grad_norm_") and hasattr(optimizer, "fold_grads")):
             raise TypeError("StepRunner: gradient clipping / accumulation need a fused optimiser "
                             "(adell_mri_amd.optim)")
+        self.ewc, self.ewc_weight = _check_ewc(module, optimizer, ewc), float(ewc_weight)
+        self.last_ewc_penalty = None
         self.sync = sync if sync is not None else GradSync(optimizer)
         self.sync.broadcast_parameters(module=module)
         self.step_idx = 0
         self.optimizer_steps = 0
         self.last_grad_norm = None
+        # the epoch loop's state, as a Lightning Trainer names it (MultiPhaseTraining reads and sets it)
+        self.current_epoch = 0
+        self.callback_metrics = {}
+        self.should_stop = False
         self._micro = 0                  # micro-batches of the current accumulation window so far
         self._graph = None
 
@@ -225,7 +247,7 @@ class StepRunner:
         loss.backward()
         self._exchange_and_step()
         self.step_idx += 1
-        return loss
+        return self._with_penalty(loss)
 
     def _micro_step(self, batch):
         if self._micro == 0:
@@ -239,14 +261,28 @@ class StepRunner:
         else:
             loss.backward()
             self._exchange_and_step()
+            loss = self._with_penalty(loss)
         self.step_idx += 1
         return loss
 
+    def _with_penalty(self, loss):
+        """``loss + ewc_weight * penalty`` of the step just taken (the loss itself without ``ewc``)."""
+        if self.ewc is None:
+            return loss
+        return loss.detach() + (self.ewc_weight * self.last_ewc_penalty).reshape(loss.shape)
+
+    def _add_penalty(self):
+        """The penalty's gradient into the flat gradient slots, under the grad_scale now in force."""
+        self.last_ewc_penalty = self.ewc.add_to_optimizer(self.module, self.optimizer, self.ewc_weight)
+
     def _exchange_and_step(self):
-        """all-reduce -> clip -> step of the current window (1/N folded into grad_scale)."""
+        """all-reduce -> penalty gradient -> clip -> step of the current window (1/N folded into
+        grad_scale)."""
         self.sync.all_reduce()
         n = self.accumulate_grad_batches
         if n == 1 and not self.gradient_clip_val:
+            if self.ewc is not None:
+                self._add_penalty()
             self.optimizer.step()
         else:
             groups = self.optimizer.param_groups
@@ -254,6 +290,8 @@ class StepRunner:
             try:
                 for g, s in zip(groups, kept):
                     g["grad_scale"] = s / n
+                if self.ewc is not None:
+                    self._add_penalty()
                 if self.gradient_clip_val:
                     self.last_grad_norm = self.optimizer.clip_grad_norm_(self.gradient_clip_val, 2.0)
                 self.optimizer.step()
@@ -288,7 +326,7 @@ class StepRunner:
             HF._dropout_counter = itertools.count(_offsets_drawn() + self._graph_draws)
         self._exchange_and_step()
         self.step_idx += 1
-        return self._graph_loss
+        return self._with_penalty(self._graph_loss)
 
 
 def _apply_spectral_norm(module, spectral_norm, optimizer):
@@ -315,11 +353,35 @@ def _apply_spectral_norm(module, spectral_norm, optimizer):
     return callback
 
 
+def _check_ewc(module, optimizer, ewc):
+    """``ewc`` as given (None: off), refused unless it is a penalty over ``module``'s parameters and
+    the optimiser keeps flat gradient slots."""
+    if ewc is None:
+        return None
+    from .modules.continuous_learning import ElasticWeightConsolidation
+
+    if not isinstance(ewc, ElasticWeightConsolidation):
+        raise TypeError(f"StepRunner: ewc must be an ElasticWeightConsolidation, got {type(ewc).__name__}")
+    if not hasattr(optimizer, "flat_groups"):
+        raise TypeError("StepRunner(ewc=...): the fused route needs a fused optimiser "
+                        "(adell_mri_amd.optim); add ewc(module) to the loss instead")
+    own = {k: p.shape for k, p in module.named_parameters()}
+    keys = set(ewc.keys)
+    selected = [k for k in ewc.anchor_parameters if k in keys]
+    wrong = [k for k in selected if k not in own or own[k] != ewc.anchor_parameters[k].shape]
+    if wrong or not selected:
+        raise ValueError(f"StepRunner(ewc=...): the penalty's selected parameters are not the module's "
+                         f"({len(wrong)} of {len(selected)} missing or of another shape, e.g. "
+                         f"{wrong[:3]}): build it with ElasticWeightConsolidation(module, ...)")
+    return ewc
+
+
 def fit_steps(module, batches, optimizer=None, gradient_clip_val=None, accumulate_grad_batches=1,
-              sync_batchnorm=False, spectral_norm=None):
+              sync_batchnorm=False, spectral_norm=None, ewc=None, ewc_weight=1.0):
     runner = StepRunner(module, optimizer, gradient_clip_val=gradient_clip_val,
                         accumulate_grad_batches=accumulate_grad_batches,
-                        sync_batchnorm=sync_batchnorm, spectral_norm=spectral_norm)
+                        sync_batchnorm=sync_batchnorm, spectral_norm=spectral_norm, ewc=ewc,
+                        ewc_weight=ewc_weight)
     module.train()
     losses = [runner.train_step(b).detach() for b in batches]
     runner.flush()

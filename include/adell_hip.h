@@ -1971,6 +1971,35 @@ int adell_spectral_norm_bwd(const float* G, const float* Wsn, const float* u, co
                             const double* sigma, int outer, int h, int inner, double* ws, long ws_doubles,
                             float* dW, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Elastic-weight-consolidation penalty (csrc/ewc.hip): sum_k ||p_k - p0_k||_p over any number of
+ * parameter tensors, the reference's ElasticWeightConsolidation.__call__
+ * (continuous_learning/regularization.py:38-45), value and gradient in three launches. fp32 data (the
+ * difference is taken in fp32 as the reference takes it), fp64 sums in a fixed order, no float
+ * atomics: bit-reproducible. p is any finite number >= 1; 1 and 2 have instances without pow.
+ * `table` is a DEVICE array of `chunks` rows of 5 longs: parameter pointer, anchor pointer, element
+ * count (1 .. adell_ewc_chunk()), tensor index, destination offset in elements (read by
+ * adell_ewc_grad only). The chunks of a tensor are consecutive rows; `tensor_first` is a DEVICE array of
+ * tensors + 1 longs, the rows of tensor k being tensor_first[k] .. tensor_first[k + 1] - 1. Null
+ * pointers, counts < 1 and a p that is not a finite number >= 1 are refused before any HIP call.
+ * ---------------------------------------------------------------------- */
+/* continuous_learning/regularization.py:38-45: elements per chunk (a compile-time constant). */
+int adell_ewc_chunk(void);
+/* continuous_learning/regularization.py:38-45: doubles of workspace of the partials and finalize
+ * passes (0: bad arguments). */
+long adell_ewc_workspace_doubles(int chunks, int tensors);
+/* continuous_learning/regularization.py:38-45: workspace[r] = sum |p - p0|^p over chunk r. */
+int adell_ewc_partials(const long* table, int chunks, double p, double* workspace, void* stream);
+/* continuous_learning/regularization.py:38-45: norms[k] = (sum of tensor k's partials)^(1/p) in fp32
+ * (kept for adell_ewc_grad), total[0] = sum_k norm_k (fp64, stored as fp32). */
+int adell_ewc_finalize(const long* tensor_first, int tensors, int chunks, double p, double* workspace,
+                       float* norms, float* total, void* stream);
+/* continuous_learning/regularization.py:38-45 (its gradient): g = C sgn(d) |d|^(p-1) / norm_k^(p-1),
+ * d = p - p0 in fp32, C = c * c_dev[0] (c_dev may be NULL: C = c), exactly 0 where d == 0 or
+ * norm_k == 0 (torch's masked forms). add == 0: base[offset + i] = g; add != 0: base[offset + i] += g. */
+int adell_ewc_grad(const long* table, int chunks, double p, const float* norms, float c,
+                   const float* c_dev, int add, float* base, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
